@@ -19,11 +19,14 @@ the solver's own phase 1 run on the GPU beforehand (untimed): --phase1Tol 1e-2 a
 Everything is resident in HBM when the timed region starts.
 """
 import argparse
+import atexit
 import ctypes as C
 import json
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -32,6 +35,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 64 << 20  # --dump-outputs: the most all .npy files together may take
 
 
 def traffic_from_profiles(workload):
@@ -138,6 +142,21 @@ def replicate_blocks(path, nblk, out):
                 f.write("%d %d %s %s %s\n" % (mat if mat == 0 else mat + k * m, k + 1, e[2], e[3], e[4]))
     os.replace(out + ".tmp", out)
     return out
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64.  When all of them together would exceed DUMP_BYTES (with
+    room for the .npy headers), every array of more than 16 values keeps the same seeded sample of its rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    big = [k for k, v in arrays.items() if v.size > 16]
+    small = sum(v.nbytes for k, v in arrays.items() if k not in big)
+    keep = min(1.0, (DUMP_BYTES - 4096 * len(arrays) - small) / max(1, sum(arrays[k].nbytes for k in big)))
+    for k, v in arrays.items():
+        if k in big and keep < 1.0:
+            rows = np.random.default_rng(0).choice(v.shape[0], int(v.shape[0] * keep), replace=False)
+            v = v[np.sort(rows)]
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def admm_steps(be, host, rho, err1, steps, session=None):
@@ -514,18 +533,16 @@ def profile_stamp_ok(relpath):
     return st.get("hip_source_sha256") == hip_source_hash(), st.get("git_head")
 
 
-def run_workload(a, workload, torch, dist, device, world, rank, host, with_cpu, tlr=None):
+def run_workload(a, workload, torch, dist, device, world, rank, host, with_cpu, workdir, tlr=None, dump=None):
+    """One workload: untimed phase 1, then the timed ADMM steps.  Every rank writes its own copy of the seeded instance into
+    `workdir` (this process's own directory), so the input depends on the arguments alone.  With `dump` (a dict) rank 0 adds
+    what the timed path computed in its last step."""
     tlr = a.times_log_rank if tlr is None else tlr
     strong = a.scaling == "strong"
-    base = build_instance(workload, "/tmp/lorads_bench_%s.dat-s" % workload) if rank == 0 else None
-    if dist:
-        dist.barrier()
-    base = "/tmp/lorads_bench_%s.dat-s" % workload
-    path = base
+    path = build_instance(workload, os.path.join(workdir, "%s.dat-s" % workload))
     if world > 1 and not strong:
-        path = "/tmp/lorads_bench_%s_x%d.dat-s" % (workload, world)
-        if rank == 0:
-            replicate_blocks(base, world, path)
+        path = replicate_blocks(path, world, os.path.join(workdir, "%s_x%d.dat-s" % (workload, world)))
+    if dist:
         dist.barrier()
 
     t_setup0 = time.time()
@@ -575,7 +592,7 @@ def run_workload(a, workload, torch, dist, device, world, rank, host, with_cpu, 
     info = s.block_info(0)   # (phase 1 may have grown the rank)
     log("rank %d: phase 1 took %.2fs (%d inner its), rho=%.4g err1=%.3e, %d local cone(s), n=%d r=%d" %
         (rank, time.time() - t0, int(res["alm_inner"]), rho, err1, nloc, info["n"], info["rank"]))
-    state_file = "/tmp/lorads_bench_state_%d.bin" % os.getpid()
+    state_file = os.path.join(workdir, "state_%s.bin" % workload)
     # (the state the CPU reference and the full-size parity check start from is taken AFTER the timed region and its untimed passes:
     # fetching the factors and writing them out idles the GPU for tens of milliseconds, and taken here -- right in front of the warm-up
     # -- that idle time showed in the timed steps as a clock ramp: 0.127 against 0.124 ms per step)
@@ -610,6 +627,13 @@ def run_workload(a, workload, torch, dist, device, world, rank, host, with_cpu, 
         c = torch.tensor([float(cg_iters)], dtype=torch.float64, device=device)
         dist.all_reduce(c)
         cg_iters = int(c.item())
+    if dump is not None and rank == 0:
+        # the state the timed steps leave (rank 0's cones and multipliers) and the last step's scalars, before anything else runs
+        for k in range(nloc):
+            dump["%s_U%d" % (workload, k)] = be.get_mat(host.MAT_U, k)
+            dump["%s_V%d" % (workload, k)] = be.get_mat(host.MAT_V, k)
+        dump["%s_lambda" % workload] = be.get_vec(host.VEC_LAMBDA)
+        dump["%s_scalars" % workload] = np.array([pobj, dobj, err1, cg_iters], dtype=np.float64)  # pObj, dObj, err1, CG its of the timed steps
     # ---- further windows of K steps each (outside the contract's timed region): spread of ms_per_step
     win_ms = [1e3 * elapsed / a.steps]
     for _ in range(max(0, a.windows - 1)):
@@ -958,7 +982,12 @@ def main():
                     "steps (reported as ms_per_step_windows / _median; the headline value is the FIRST window)")
     ap.add_argument("--roofline-samples", type=int, default=200, help="untimed pass after the timed region: every operator "
                     "application timed with HIP events until this many samples exist")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed in the last "
+                    "step as DIR/<workload>_<name>.npy (float64, at most 64 MB in all; rank 0's cones): U<k>, V<k>, lambda and "
+                    "scalars = [pObj, dObj, err1, CG iterations of the timed steps]")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     explicit_workload = a.workload is not None or a.scaling == "strong"
     if a.workload is None:
         a.workload = "blk16x4000" if a.scaling == "strong" else "rand20000"
@@ -999,7 +1028,10 @@ def main():
         dist.barrier()
     from lorads_amd import host
 
-    out = run_workload(a, a.workload, torch, dist, device, world, rank, host, not a.no_cpu)
+    workdir = tempfile.mkdtemp(prefix="lorads_bench_")
+    atexit.register(shutil.rmtree, workdir, True)
+    dump = {} if a.dump_outputs else None
+    out = run_workload(a, a.workload, torch, dist, device, world, rank, host, not a.no_cpu, workdir, dump=dump)
     if world > 1 and not a.no_extra and not explicit_workload:
         # N > 1 as the driver calls it (no --workload / --scaling): the weak replica line above AND BASELINE config 4 -- the 16 cones of
         # ONE blk16x4000 problem dealt over the N ranks (strong scaling) -- as `extra`, each with ranks_seen, the exchange and a sharded
@@ -1007,7 +1039,7 @@ def main():
         import copy
         a2 = copy.copy(a)
         a2.scaling = "strong"
-        ex = run_workload(a2, "blk16x4000", torch, dist, device, world, rank, host, False, tlr=2.0)
+        ex = run_workload(a2, "blk16x4000", torch, dist, device, world, rank, host, False, workdir, tlr=2.0, dump=dump)
         if rank == 0:
             keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_median", "scaling", "ranks_seen",
                     "scalar_exchange", "cg_iters_per_s", "cg_iters_per_admm_iter", "config", "roofline", "state", "parity_sharded",
@@ -1018,13 +1050,15 @@ def main():
         keys = ("value", "unit", "ms_per_step", "ms_per_step_median", "cg_iters_per_s", "cg_iters_per_admm_iter", "config", "roofline",
                 "cpu_baseline", "state", "parity_full_size", "speedup_vs_cpu_1core", "speedup_vs_cpu_1core_cg_normalised", "phase1",
                 "one_launch_iteration", "launches_per_step")
-        ex = run_workload(a, "maxcut20000", torch, dist, device, world, rank, host, not a.no_cpu, tlr=4.0)
+        ex = run_workload(a, "maxcut20000", torch, dist, device, world, rank, host, not a.no_cpu, workdir, tlr=4.0, dump=dump)
         out["extra"] = [{k: ex[k] for k in keys if k in ex}]
     if dist:
         dist.barrier()
         dist.destroy_process_group()
     rc = 0
     if rank == 0:
+        if dump is not None:
+            write_outputs(a.dump_outputs, dump)
         print(json.dumps(out), flush=True)
         # a run that silently had fewer ranks than --gpus, or whose sharded iterations differ from the single-rank ones, must not pass
         for line in [out] + list(out.get("extra") or []):

@@ -13,7 +13,7 @@
  * LORADSInitFuncSet and an `if (use_hip)` at the call sites listed below; the functions to call are the ones in this file.)
  *
  * Built only in the build container, against the reference's headers where they lie (oracle/Makefile, target ref_hip ->
- * oracle/_ref_hip/, git-ignored); tests/test_reference_shim.py runs the reference's own loops through it on the GPU.
+ * oracle/_ref/hip/, git-ignored); tests/test_reference_shim.py runs the reference's own loops through it on the GPU.
  * This file is ours; it includes the reference's headers and copies none of its code.
  *
  * Symbols taken over (each keeps the reference's signature; "orig" = the reference's definition, reached with

@@ -1,10 +1,13 @@
 """Shared helpers of the parity tests: oracle loading, golden loading and the scripted call
 sequence that oracle/ref_driver.c (mode `trace`) ran against the REFERENCE, replayed against any
 operator table (CPU oracle or HIP)."""
+import atexit
 import ctypes as C
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -61,6 +64,24 @@ def golden_solves():
 
 def instance_path(name):
     return os.path.join(GOLD, name + ".dat-s")
+
+
+_gen_dir = None
+
+
+def generated_instance(name, make=None):
+    """Path of instance `name` from the seeded generators (lorads_amd/instances.py; `make`: a generator call of its own),
+    written once per test process into a private temporary directory that is removed at exit: a test reads no file
+    that another run, user or version of the generators left behind."""
+    global _gen_dir
+    if _gen_dir is None:
+        _gen_dir = tempfile.mkdtemp(prefix="lorads_test_")
+        atexit.register(shutil.rmtree, _gen_dir, True)
+    path = os.path.join(_gen_dir, name + ".dat-s")
+    if not os.path.exists(path):
+        from lorads_amd import instances
+        instances.write_sdpa((make or instances.NAMED[name])(), path)
+    return path
 
 
 def linesearch_tau(coef):

@@ -33,6 +33,30 @@ def test_replicate_blocks_is_block_separable(tmp_path):
     assert len(ents) == 3 * len([ln for ln in a[4:] if ln.strip()])
 
 
+def test_dumped_outputs_are_float64_and_sampled_to_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: all arrays whole while they fit; beyond the cap the large ones keep the same seeded rows, run after run"""
+    rng = np.random.default_rng(1)
+    arrays = {"w_U0": rng.standard_normal((3000, 40)), "w_V0": rng.standard_normal((3000, 40)),
+              "w_lambda": rng.standard_normal(500).astype(np.float32), "w_scalars": np.array([1.0, -2.0, 3e-7, 41.0])}
+    bench.write_outputs(str(tmp_path / "all"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 1 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b)
+    u = np.load(tmp_path / "a" / "w_U0.npy")
+    assert 0 < u.shape[0] < 3000 and u.shape[1] == 40
+    assert all(any(np.array_equal(r, s) for s in arrays["w_U0"]) for r in u[:5])   # rows of the original, not new values
+    assert np.array_equal(np.load(tmp_path / "a" / "w_scalars.npy"), arrays["w_scalars"])
+
+
 def test_profile_stamp_gates_the_replay(tmp_path, monkeypatch):
     h = bench.hip_source_hash()
     assert len(h) == 64 and h == bench.hip_source_hash()
@@ -98,6 +122,37 @@ def test_bench_line_keeps_the_contract_end_to_end():
     p1 = d["phase1"]
     assert p1["inner_iters"] > 0 and p1["us_per_inner_iter"] > 0 and p1["launches_per_inner_iter"] < 12
     assert p1["again_in_a_warm_process"]["inner_iters"] == p1["inner_iters"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_dumps_what_the_timed_steps_computed(tmp_path):
+    """`bench.py --dump-outputs DIR`: the factors, multipliers and scalars the last timed step left, as float64 .npy files -- the
+    scalars are the line's `state` -- and the same arrays from a second run with the same arguments"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", "maxcut800",
+                            "--times-log-rank", "2.0", "--no-cpu", "--no-extra", "--roofline-samples", "0", "--windows", "1",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=280, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines.append(json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1]))
+    d = lines[0]
+    assert d["steps"] == 7
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["maxcut800_U0.npy", "maxcut800_V0.npy", "maxcut800_lambda.npy", "maxcut800_scalars.npy"], files
+    out = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 and np.all(np.isfinite(v)) for v in out.values())
+    assert out["maxcut800_U0"].shape == out["maxcut800_V0"].shape == (800, d["config"]["r"])
+    assert out["maxcut800_lambda"].shape == (d["config"]["m_per_block"],)
+    pobj, dobj, err1, cg = out["maxcut800_scalars"]
+    assert (pobj, dobj, err1) == (d["state"]["pObj"], d["state"]["dObj"], d["state"]["err1_end"])
+    assert cg == round(d["cg_iters_per_admm_iter"] * 7)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), out[f[:-4]]), f
 
 
 @pytest.mark.gpu

@@ -3,7 +3,6 @@ cone's own rank, which the caller never sees) so that cones of unequal rank run 
 single-cone forms of phase 1 -- instead of cone by cone.  Against per-cone ranks (LORADS_COMMON_RANK=0).  Reference: the ranks are per cone
 (src_semi/data/lorads_solver.c:290-319, AUG_RANK :806-906); what is computed on the extra columns is exact zeros."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -21,12 +20,7 @@ def built():
 
 
 def _gen(name):
-    path = os.path.join("/tmp", "lorads_test_%s.dat-s" % name)
-    if not os.path.exists(path):
-        sys.path.insert(0, os.path.join(common.ROOT, "oracle"))
-        import gen_instances
-        gen_instances.write_sdpa(gen_instances.NAMED[name](), path)
-    return path
+    return common.generated_instance(name)
 
 
 def _session(path, on, **kw):

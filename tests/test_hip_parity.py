@@ -2,7 +2,6 @@
 REFERENCE and (b) the CPU oracle on larger seeded inputs.  Run on a real MI355X (-m gpu)."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -67,12 +66,7 @@ def _pair(path, **params):
 
 
 def _gen(name):
-    path = os.path.join("/tmp", "lorads_test_%s.dat-s" % name)
-    if not os.path.exists(path):
-        sys.path.insert(0, os.path.join(common.ROOT, "oracle"))
-        import gen_instances
-        gen_instances.write_sdpa(gen_instances.NAMED[name](), path)
-    return path
+    return common.generated_instance(name)
 
 
 @pytest.mark.parametrize("name,tlr", [("maxcut800", 2.0), ("maxcut4000", 3.0), ("rand4000", 3.0), ("densec300", 2.0),
@@ -878,10 +872,7 @@ def test_lockstep_convergence_test_on_the_last_workgroup_is_bitwise_its_own_laun
     keeps its name.)  Same sums in the same order: iterates, iteration counts and evaluations must be bit-for-bit equal -- also on
     cfg4 at full size (16 cones of n = 4000: 544 workgroups per update, every XCD involved)."""
     if name == "blk16x4000":
-        path = os.path.join("/tmp", "lorads_test_blk16x4000.dat-s")
-        if not os.path.exists(path):
-            from lorads_amd import instances
-            instances.write_sdpa(instances.NAMED["blk16x4000"](), path)
+        path = common.generated_instance("blk16x4000")
     else:
         path = common.instance_path(name)
     res = []
@@ -1047,10 +1038,7 @@ def test_carried_scalar_steps_on_a_grid_larger_than_the_device(built):
     workgroups) late workgroups start after early ones have finished, so the two sets of partials must never share a
     slot -- they once did (start of a solve / restart residual vs the operator's p.Q partials), which showed up as a
     one-in-eight flake on a two-workgroup cone.  Bit-for-bit against the separate launches at n = 48000."""
-    path = os.path.join("/tmp", "lorads_test_maxcut48000.dat-s")
-    if not os.path.exists(path):
-        from lorads_amd import instances
-        instances.write_sdpa(instances.maxcut(48000, 200000, 48001), path)
+    path = common.generated_instance("maxcut48000", lambda: instances.maxcut(48000, 200000, 48001))
     res = []
     for lazy in ("1", "0"):
         os.environ["LORADS_LAZY_SCALARS"] = lazy

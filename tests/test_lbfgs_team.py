@@ -2,7 +2,6 @@
 the launch-by-launch form of the same library (LORADS_LBFGS_TEAM=0: k_his_two_dot, 2 nn + 1 k_lbfgs_stage, k_use_grad_p).  Reference:
 setlbfgsHisTwo, LBFGSDirection, LBFGSDirectionUseGrad (src_semi/lorads_alg/lorads_alm.c:230-391,469-489,540-560)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -20,12 +19,7 @@ def built():
 
 
 def _gen(name):
-    path = os.path.join("/tmp", "lorads_test_%s.dat-s" % name)
-    if not os.path.exists(path):
-        sys.path.insert(0, os.path.join(common.ROOT, "oracle"))
-        import gen_instances
-        gen_instances.write_sdpa(gen_instances.NAMED[name](), path)
-    return path
+    return common.generated_instance(name)
 
 
 def _session(path, team, **kw):

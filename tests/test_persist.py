@@ -2,7 +2,6 @@
 registers, in-kernel all-reduces) against the launch-by-launch form of the same library (LORADS_PERSIST=0) and, at full size,
 against the compiled reference.  Reference loops: lorads_alg/lorads_alg_common.c:187-215, linalg/lorads_cgs.c:174-234."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -20,12 +19,7 @@ def built():
 
 
 def _gen(name):
-    path = os.path.join("/tmp", "lorads_test_%s.dat-s" % name)
-    if not os.path.exists(path):
-        sys.path.insert(0, os.path.join(common.ROOT, "oracle"))
-        import gen_instances
-        gen_instances.write_sdpa(gen_instances.NAMED[name](), path)
-    return path
+    return common.generated_instance(name)
 
 
 def _session(path, persist, **kw):

@@ -1,7 +1,7 @@
 """The literal drop-in boundary: the REFERENCE'S OWN outer loops (LORADS_ALMOptimize, LORADSADMMOptimize, reopt, unmodified,
 compiled from /root/reference where it lies) drive liblorads_hip.so through the operator table that
-integration/lorads_func_hip.c installs by symbol interposition (oracle/Makefile ref_hip -> oracle/_ref_hip/, built in the build
-container and shipped to the GPU box like oracle/_ref/).  The results are compared with the reference's CPU runs of the same
+integration/lorads_func_hip.c installs by symbol interposition (oracle/Makefile ref_hip -> oracle/_ref/hip/, built where the
+reference's sources are and carried with the rest of oracle/_ref/).  The results are compared with the reference's CPU runs of the same
 command (tests/golden/solve.json)."""
 import os
 import subprocess
@@ -11,7 +11,7 @@ import torch
 
 from tests import common
 
-SHIM_DIR = os.path.join(common.ROOT, "oracle", "_ref_hip")
+SHIM_DIR = os.path.join(common.ROOT, "oracle", "_ref", "hip")
 DRV = os.path.join(SHIM_DIR, "ref_driver_hip")
 LIB = os.path.join(SHIM_DIR, "liblorads_func_hip.so")
 
@@ -21,7 +21,7 @@ TAKEN_OVER = ["LORADSInitFuncSet", "LORADSInitConstrValAll", "LORADSInitConstrVa
 
 def _need_shim():
     if not (os.path.exists(DRV) and os.path.exists(LIB)):
-        pytest.skip("oracle/_ref_hip not built (compiled against /root/reference in the build container)")
+        pytest.skip("oracle/_ref/hip not built (oracle/Makefile ref_hip: needs the reference's sources)")
 
 
 def test_shim_defines_the_reference_symbols_it_takes_over(built):
