@@ -740,16 +740,61 @@ __global__ __launch_bounds__(TPB) void k_spmm2(int n, const int *__restrict__ ad
 // their way: the dependent-load chain is index -> (weight | neighbour rows) for every row, whatever its slot count.
 // Padding slots name the row itself (an L1 hit) with coefficient 0.  Slots are accumulated in list order, exactly as
 // k_spmm<CW> does.  mode = OP_CG or OP_RES.
-template <int LG, bool V2, int NS, int EW>
+//
+// CG0 = true: CG iteration 0 of a cone on the one-kernel-front path (Cg0Args), the update that k_cg_update would run next is
+// done here, row by row.  alpha = rr / (p.Q) needs the global dot p.Q, but with p_0 = r_0 it is known before this kernel starts:
+// k_wsum forms w_i = sum over the slots s of constraint i of a_s (p_row(s) . V_col(s)), this kernel forms
+// Q_p = p_p + sum over the slots s of row p of a_s w_con(s) V_col(s), and regrouping the slots of sum_p p_p . Q_p by constraint gives
+//   p.Q = ||p||^2 + ||w||^2 = rr + ||w||^2          (cg0_alpha; k_wsum leaves the partials of ||w||^2)
+// So Q stays in registers: x_p += alpha p_p, the partials of ||r_0 - alpha Q||^2 go to `part` (r stored when store_r), the kept
+// constraint values follow x (w_acc += alpha w_p, on the low thread ids), R = (U + V) / 2 when asked for -- also in the gated-off
+// "solve already over" case, as k_cg_update does -- and workgroup 0 writes the shadow state.  The kernel gathers rows of the
+// fixed factor X only and reads and writes its own rows of p (= r) and x: no workgroup reads what another one writes.
+struct Cg0Args {
+    const CGState *st;            // the solve's state (rr)
+    const double *part_ww;        // k_wsum's partials of ||w||^2
+    int nww;
+    double *x, *r;                // the solve variable, the residual (= p_0, the kernel's xin)
+    int store_r;
+    double *w_acc;                // null: no recurrence of the constraint values
+    const double *w_p;
+    int nw;
+    CGState *shadow;
+    const double *avg_other;      // avg_out != null: R = (avg_other + x) / 2
+    double *avg_out;
+};
+// the update of one element, shared by k_cg_update and the CG0 form of k_spmm_ell (same arithmetic, same bits)
+struct CgElem { double x, r; };
+__device__ __forceinline__ CgElem cg_elem(double alpha, double p, double q, double x, double r) {
+    return CgElem{x + alpha * p, r - alpha * q};
+}
+__device__ __forceinline__ double cg_avg(double other, double x) { return (other + x) / 2; }
+__device__ __forceinline__ double cg_wacc(double wa, double alpha, double wp) { return wa + alpha * wp; }
+// alpha of CG iteration 0 from ||r_0||^2 and the ||w||^2 partials (see Cg0Args): every kernel that forms it sums the same
+// partials in the same order
+__device__ __forceinline__ double cg0_alpha(double rr, double ww) { return rr / (rr + ww); }
+
+template <int LG, bool V2, int NS, int EW, bool CG0 = false>
 __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,
                                                   const int *__restrict__ adj_con, const double *__restrict__ adj_a,
                                                   const int *__restrict__ ell_col, const int *__restrict__ ell_con,
                                                   const double *__restrict__ ell_a, const double *__restrict__ wgt,
                                                   const double *__restrict__ X, int r, int mode,
-                                                  const double *__restrict__ xin, const double *__restrict__ rhs,
-                                                  double *__restrict__ out, double *__restrict__ part, Guard g) {
+                                                  const double *xin, const double *__restrict__ rhs,
+                                                  double *__restrict__ out, double *__restrict__ part, Guard g,
+                                                  Cg0Args u = Cg0Args{}) {
+    // (xin is not __restrict__: in the CG0 form the kernel writes its rows back through u.r, after it has read them)
     __shared__ double sh[4];
     const Gate gt = gate_load(g); // (both gate words requested now, looked at where GATE_OPEN first appears)
+    // CG0: the state's rr and this thread's share of the ||w||^2 partials travel with the gate words; so do the kept constraint
+    // value and its increment of thread id `gid` (the first of the m-vector slice this thread updates)
+    double rr = 0.0, ww = 0.0, wa0 = 0.0, wp0 = 0.0;
+    const int gid = blockIdx.x * TPB + threadIdx.x;
+    if (CG0) {
+        rr = u.st->rr;
+        ww = private_partials(u.part_ww, u.nww);
+        if (u.w_acc) { const int iw = gid < u.nw ? gid : 0; wa0 = u.w_acc[iw]; wp0 = u.w_p[iw]; }
+    }
     constexpr int W = V2 ? 2 : 1;
     constexpr int NH = EW / 8;             // index words per lane
     constexpr int CH = NS <= 5 ? 4 : 2; // neighbour rows gathered per step (a step is skipped when the group has no such slots: 4.5 slots per row on average at the headline; 8 per step was 10.1 us, 4: 9.1 us, 2: 9.4 us)
@@ -765,7 +810,8 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__
     const int t0 = adj_ptr[rowc], t1 = adj_ptr[rowc + 1]; // (both words exist for every clamped row: no predicated load)
     double xi[NS][W], rh[NS][W], acc[NS][W];
     Slice<LG, V2, NS>::load(xin + base, r, lane, xi);
-    Slice<LG, V2, NS>::load((mode == OP_RES ? rhs : xin) + base, r, lane, rh); // (OP_CG: an L1 hit, never used)
+    // (OP_CG: an L1 hit, never used; CG0: the row of x)
+    Slice<LG, V2, NS>::load((CG0 ? (const double *)u.x : mode == OP_RES ? rhs : xin) + base, r, lane, rh);
 #pragma unroll
     for (int c = 0; c < NS; ++c)
 #pragma unroll
@@ -824,6 +870,53 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__
 #pragma unroll
                 for (int w = 0; w < W; ++w) acc[c][w] += su * v[u][c][w];
         }
+    }
+    if (CG0) {
+        const double alpha = cg0_alpha(rr, block_sum(ww, sh));
+        const bool open = GATE_OPEN;
+        // gated off with the solve already over and the stage reached: the average alone, from the x that is there
+        const bool avg_only = !open && gt.vs != 0 && !(g.need && gt.vn == 0);
+        if (open && blockIdx.x == 0 && threadIdx.x == 0 && u.shadow) *u.shadow = *u.st; // the state the convergence test starts from
+        if (open && u.w_acc && gid < u.nw) {
+            u.w_acc[gid] = cg_wacc(wa0, alpha, wp0);
+            for (int i = gid + gridDim.x * TPB; i < u.nw; i += gridDim.x * TPB) u.w_acc[i] = cg_wacc(u.w_acc[i], alpha, u.w_p[i]);
+        }
+        double local = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {
+            const int j0 = (lane + c * LG) * W;
+            double xo[W], ro[W];
+#pragma unroll
+            for (int w = 0; w < W; ++w) { // p_0 = r_0: xi is both p and r, rh is x, Q = p + acc
+                const CgElem e = cg_elem(alpha, xi[c][w], xi[c][w] + acc[c][w], rh[c][w], xi[c][w]);
+                xo[w] = e.x; ro[w] = e.r;
+                local += e.r * e.r;
+            }
+            if (act && j0 < r) {
+                if (open) {
+                    if (V2) *(double2 *)(u.x + base + j0) = make_double2(xo[0], xo[W - 1]);
+                    else u.x[base + j0] = xo[0];
+                    if (u.store_r) {
+                        if (V2) *(double2 *)(u.r + base + j0) = make_double2(ro[0], ro[W - 1]);
+                        else u.r[base + j0] = ro[0];
+                    }
+                }
+                if (u.avg_out && (open || avg_only)) {
+                    double ao[W];
+#pragma unroll
+                    for (int w = 0; w < W; ++w) ao[w] = open ? xo[w] : rh[c][w];
+                    if (V2) {
+                        const double2 o = *(const double2 *)(u.avg_other + base + j0);
+                        *(double2 *)(u.avg_out + base + j0) = make_double2(cg_avg(o.x, ao[0]), cg_avg(o.y, ao[W - 1]));
+                    } else {
+                        u.avg_out[base + j0] = cg_avg(u.avg_other[base + j0], ao[0]);
+                    }
+                }
+            }
+        }
+        const double t = block_sum(act ? local : 0.0, sh);
+        if (open && threadIdx.x == 0) part[blockIdx.x] = t;
+        return;
     }
     double local = 0.0;
 #pragma unroll
@@ -1082,10 +1175,11 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const do
 // 8 lanes per constraint, lane l adds entries l, l + 8, ... in that order and the lanes are combined by the same butterfly
 // every time (deterministic).  The first kernel of iteration 0: the solve's start rides on it (InitArgs, as on k_cw), and --
 // first solve of a sweep -- it stores the multipliers of the dual update the front has already used (rho_dual != 0): all m_all of them.
+// part_ww != null: workgroup b also writes part_ww[b] = sum of w_i^2 over its constraints (fixed order), see Cg0Args.
 __global__ __launch_bounds__(TPB) void k_wsum(int nrow, int cw, const double *__restrict__ contrib, double *__restrict__ w_out, Guard g,
                                               InitArgs ia, int dual_on, DS rho_dual_s, int m_all,
                                               const double *__restrict__ b, const double *__restrict__ csum,
-                                              double *__restrict__ lambda) {
+                                              double *__restrict__ lambda, double *__restrict__ part_ww = nullptr) {
     __shared__ double sh[8];
     const Gate gt = gate_load(ia.st ? Guard{nullptr, g.need} : g);
     double iv[2] = {0.0, 0.0};
@@ -1113,6 +1207,10 @@ __global__ __launch_bounds__(TPB) void k_wsum(int nrow, int cw, const double *__
     }
     const bool live = ia.st ? finish_init(ia, !(g.need && gt.vn == 0), iv, sh) == 0 : GATE_OPEN;
     if (live && act && lane == 0) w_out[i] = s;
+    if (part_ww) { // this workgroup's constraints' share of ||w||^2, for alpha of iteration 0 (cg0_alpha)
+        const double t = block_sum(act && lane == 0 ? s * s : 0.0, sh);
+        if (live && threadIdx.x == 0) part_ww[blockIdx.x] = t;
+    }
 }
 
 // Max-Cut-type cones (every A_i = a_i e_p e_p^T): the whole operator is row-local,
@@ -1697,7 +1795,8 @@ __global__ __launch_bounds__(TPB) void k_cg_update(size_t len, const CGState *st
                                                    double *__restrict__ w_acc, const double *__restrict__ w_p, int nw,
                                                    CGState *shadow = nullptr, int store_r = 1,
                                                    const double *__restrict__ avg_other = nullptr, double *__restrict__ avg_out = nullptr,
-                                                   int tile = 0, int tile_w = 0) {
+                                                   int tile = 0, int tile_w = 0, const double *__restrict__ part_ww = nullptr,
+                                                   int nww = 0) {
     // tile > 0 (row-local operators: Max-Cut-type cones): workgroup b owns elements [b tile, (b + 1) tile) -- the rows of k_op_diag's
     // (and the front's, and k_eval_diag's) workgroup b, tile_w of them.  Workgroups go to the eight XCDs round robin by number, so
     // what this kernel reads (p, Q, r, x) was written by the same-numbered workgroup of the kernel before it ON THE SAME XCD, and
@@ -1732,45 +1831,43 @@ __global__ __launch_bounds__(TPB) void k_cg_update(size_t len, const CGState *st
     const bool hasw = w_acc && iw0 < (size_t)nw && (!tile || (int)threadIdx.x < tile_w);
     const size_t iw = hasw ? iw0 : 0;
     const double wa0 = w_acc ? w_acc[iw] : 0.0, wp0 = w_acc ? w_p[iw] : 0.0;
-    const double pq = sum_partials(part_pq, npq, sh);
-    const double alpha = rr / pq;
+    // part_ww != null: iteration 0 of a cone whose k_wsum has left the partials of ||w||^2 -- alpha by the rule of the CG0 form of
+    // k_spmm_ell (cg0_alpha), whichever of the two kernels runs the update
+    const double alpha = part_ww ? cg0_alpha(rr, sum_partials(part_ww, nww, sh)) : rr / sum_partials(part_pq, npq, sh);
     if (!GATE_OPEN) {
         if (avg_out && gt.vs != 0 && !(g.need && gt.vn == 0)) { // solve over before this update, stage reached: the average alone
             for (size_t i = i0; i < ne; i += stride) {
                 const T a = ((const T *)avg_other)[i], b = ((const T *)x)[i];
-                if constexpr (VEC) ((double2 *)avg_out)[i] = make_double2((a.x + b.x) / 2, (a.y + b.y) / 2);
-                else avg_out[i] = (a + b) / 2;
+                if constexpr (VEC) ((double2 *)avg_out)[i] = make_double2(cg_avg(a.x, b.x), cg_avg(a.y, b.y));
+                else avg_out[i] = cg_avg(a, b);
             }
         }
         return;
     }
     if (shadow && blockIdx.x == 0 && threadIdx.x == 0) *shadow = *st; // the state the convergence test will start from
     if (hasw) {
-        w_acc[iw0] = wa0 + alpha * wp0;
+        w_acc[iw0] = cg_wacc(wa0, alpha, wp0);
         if (!tile)
-            for (size_t i = i0 + stride; i < (size_t)nw; i += stride) w_acc[i] += alpha * w_p[i];
+            for (size_t i = i0 + stride; i < (size_t)nw; i += stride) w_acc[i] = cg_wacc(w_acc[i], alpha, w_p[i]);
     }
     double local = 0.0;
     auto one = [&](size_t i, const T &pe, const T &qe, const T &xe, const T &re) { // p may alias r (iteration 0): read before written
         if constexpr (VEC) {
-            double2 xo, ro;
-            xo.x = xe.x + alpha * pe.x; xo.y = xe.y + alpha * pe.y;
-            ro.x = re.x - alpha * qe.x; ro.y = re.y - alpha * qe.y;
-            ((double2 *)x)[i] = xo;
-            if (store_r) ((double2 *)r)[i] = ro;
-            local += ro.x * ro.x;
-            local += ro.y * ro.y;
+            const CgElem ex = cg_elem(alpha, pe.x, qe.x, xe.x, re.x), ey = cg_elem(alpha, pe.y, qe.y, xe.y, re.y);
+            ((double2 *)x)[i] = make_double2(ex.x, ey.x);
+            if (store_r) ((double2 *)r)[i] = make_double2(ex.r, ey.r);
+            local += ex.r * ex.r;
+            local += ey.r * ey.r;
             if (avg_out) {
                 const double2 o = ((const double2 *)avg_other)[i];
-                ((double2 *)avg_out)[i] = make_double2((o.x + xo.x) / 2, (o.y + xo.y) / 2);
+                ((double2 *)avg_out)[i] = make_double2(cg_avg(o.x, ex.x), cg_avg(o.y, ey.x));
             }
         } else {
-            const double xo = xe + alpha * pe;
-            x[i] = xo;
-            const double t = re - alpha * qe;
-            if (store_r) r[i] = t;
-            local += t * t;
-            if (avg_out) avg_out[i] = (avg_other[i] + xo) / 2;
+            const CgElem e = cg_elem(alpha, pe, qe, xe, re);
+            x[i] = e.x;
+            if (store_r) r[i] = e.r;
+            local += e.r * e.r;
+            if (avg_out) avg_out[i] = cg_avg(avg_other[i], e.x);
         }
     };
 #pragma unroll

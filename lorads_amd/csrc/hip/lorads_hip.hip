@@ -81,7 +81,8 @@ namespace {
 constexpr int TPB = 256;
 constexpr int MINPART = 4096; // least capacity of one partial-sum slot; a context sizes its slots to its largest cone (lorads_hip_ctx::maxpart)
 constexpr int SX_WORD = 56; // control-block words [56, 60): a rank's local sums of an evaluation on their way to its host (lorads_hip_set_scalar_exchange)
-constexpr int NSLOT = 20; // (18, 19: start-of-solve and restart residual partials of the ADMM sweep, see solve_front)
+constexpr int NSLOT = 21; // (18, 19: start-of-solve and restart residual partials of the ADMM sweep, see solve_front; 20: ||w||^2
+                          // partials of iteration 0's k_wsum, see Cg0Args)
 
 thread_local std::string g_err;
 int fail(const char *what, hipError_t e) {
@@ -573,6 +574,7 @@ struct lorads_hip_ctx {
     bool avg_folded = false;  // ... and has done so for the evaluation that is enqueued next
     bool opt_front_lds = true; // k_front_cw parks the first four slot rows in LDS for its second visit (LORADS_FRONT_LDS=0: gathered again)
     bool opt_front_cw = true; // k_front_cw + k_wsum instead of k_sval + k_spmm2<FRONT> + iteration 0's k_cw (LORADS_FRONT_CW=0: the latter)
+    bool opt_fuse_cg0 = true; // CG iteration 0 of a front_cw_ok cone: the update inside k_spmm_ell (LORADS_FUSE_CG0=0: k_cg_update)
     bool pend_dual_virtual = false; // the pending dual update has already been USED (formed on the fly by k_front_cw) but not stored
     bool opt_exact_refresh = false, opt_split_front = false; // test knobs (read at creation): see constr_by_recurrence, fused_front
     bool final_pending = false;              // an evaluation's closing sums wait for the next hand-over (k_publish_final)
@@ -745,6 +747,7 @@ int lorads_hip_create(const lorads_hip_problem *prob, lorads_hip_ctx **out) {
     c->opt_seg_carry_restart = !(getenv("LORADS_SEG_CARRY_RESTART") && getenv("LORADS_SEG_CARRY_RESTART")[0] == '0');
     c->opt_cw_quad = !(getenv("LORADS_CW_QUAD") && getenv("LORADS_CW_QUAD")[0] == '0');
     c->opt_front_cw = !(getenv("LORADS_FRONT_CW") && getenv("LORADS_FRONT_CW")[0] == '0');
+    c->opt_fuse_cg0 = !(getenv("LORADS_FUSE_CG0") && getenv("LORADS_FUSE_CG0")[0] == '0');
     c->opt_front_lds = !(getenv("LORADS_FRONT_LDS") && getenv("LORADS_FRONT_LDS")[0] == '0');
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
     c->opt_fold_avg = !(getenv("LORADS_FOLD_AVG") && getenv("LORADS_FOLD_AVG")[0] == '0');

@@ -103,10 +103,23 @@ int spmm_front(lorads_hip_ctx *c, const Block &B, const Pattern &P, const double
 }
 // epilogue(x + sum over (neighbour, constraint) slots of a w_i V_q): the operator's SpMM with the coefficients formed
 // from the constraint weights w
+// cg0 != null: CG iteration 0's update folded in (the CG0 form of k_spmm_ell: 16-byte rows, mode OP_CG, out unused, `part`
+// receives the partials of the new residual's norm)
 int spmm_cw(lorads_hip_ctx *c, const Block &B, const double *w, const double *X, int mode, const double *xin, const double *rhs,
-            double *out, double *part, Guard g) {
+            double *out, double *part, Guard g, const Cg0Args *cg0 = nullptr) {
     const Shape sh = shape_for(B.r);
     const int grid = nblocks_for((size_t)B.n, TPB / sh.lg);
+    if (cg0) {
+        if (!B.cell_w || !sh.v2 || mode != OP_CG) { c->launch_err = "CG iteration 0 in the operator: no kernel form for this cone"; return 0; }
+        if (B.cell_w == 8) {
+            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
+                                             B.cell_col, B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, (double *)nullptr, part, g, *cg0))
+        } else {
+            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
+                                             B.cell_col, B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, (double *)nullptr, part, g, *cg0))
+        }
+        return grid;
+    }
     if (B.cell_w && (mode == OP_CG || mode == OP_RES)) {
         if (B.cell_w == 8)
             SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
@@ -345,7 +358,8 @@ void sval(lorads_hip_ctx *c, const Pattern &P, bool with_c, int mode, const WArg
 }
 
 // the constraint weights of iteration 0's operator application from the contributions k_front_cw has left (see there)
-int wsum(lorads_hip_ctx *c, Block &B, Guard g) {
+// (part_ww != null: also the partials of ||w||^2, one per workgroup, see Cg0Args)
+int wsum(lorads_hip_ctx *c, Block &B, Guard g, double *part_ww = nullptr) {
     InitArgs ia{};
     if (c->pend_init.st && !c->pend_chk.st && g.skip == &c->pend_init.st->done && g.need == c->pend_init_g.need) ia = take_init(c);
     double rho_dual = 0.0;
@@ -353,14 +367,16 @@ int wsum(lorads_hip_ctx *c, Block &B, Guard g) {
     if (c->pend_dual_virtual) { c->pend_dual_virtual = false; rho_dual = c->pend_dual_rho; dual_on = 1; } // this kernel stores the multipliers
     const int grid = nblocks_for((size_t)B.nrow, TPB / 8);
     LAUNCH(k_wsum, grid, B.nrow, B.cs_w, (const double *)B.w_contrib, B.w_op, g, ia, dual_on, ds_rho_dual(c, rho_dual), c->m, (const double *)c->b,
-           (const double *)c->csum, c->lambda);
+           (const double *)c->csum, c->lambda, part_ww);
     return grid;
 }
 
 // one application of the CG operator  out = epilogue(x + (sum_i <A_i, sym(x V^T)> A_i) V)
 // (linSysProduct, lorads_admm.c:376-391); returns #partials in `part`
+// (iteration 0 of a cone on the one-kernel-front path, see solve_iter_body: part_ww receives k_wsum's partials of ||w||^2,
+// cg0 != null folds the iteration's update into the operator kernel)
 int apply_operator(lorads_hip_ctx *c, Block &B, const double *V, const double *x, int mode, const double *rhs, double *out,
-                   double *part, Guard g) {
+                   double *part, Guard g, double *part_ww = nullptr, const Cg0Args *cg0 = nullptr) {
     // (prof_every >= 2^20: count applications, time none -- such a window is replayed like any other, see graph_ok)
     // A timed application runs exactly what an untimed one runs (iteration 0 of a k_cw cone: k_wsum + k_spmm_ell with the solve's
     // start on board; a fused direction update stays fused): the events bracket the launches, they do not change them.
@@ -387,7 +403,7 @@ int apply_operator(lorads_hip_ctx *c, Block &B, const double *V, const double *x
         if (B.w0_ready && mode == OP_CG && x == c->cr + B.off) {
             // iteration 0 (p_0 = r_0) right behind k_front_cw: the constraint values of (r_0, V) are the sums of the
             // contributions the front has left -- no gather pass
-            wsum(c, B, g);
+            wsum(c, B, g, part_ww);
             w = B.w_op;
             B.t_uv_valid = false;
         } else if (!(is_uv && B.t_uv_valid)) {
@@ -398,7 +414,7 @@ int apply_operator(lorads_hip_ctx *c, Block &B, const double *V, const double *x
         B.w0_ready = false;
         // (no event between the two kernels of an application: a marker there would keep them from running back to back,
         // which is how they run when nobody is watching)
-        grid = spmm_cw(c, B, w, V, mode, x, rhs, out, part, g);
+        grid = spmm_cw(c, B, w, V, mode, x, rhs, out, part, g, cg0);
     } else {
         // x and V are this cone's (U,V) in either order and B.T already holds their pair dots
         const bool is_uv = (x == c->U + B.off && V == c->V + B.off) || (x == c->V + B.off && V == c->U + B.off);
@@ -678,6 +694,13 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         LAUNCH(k_cg_init, 1, s.st, pA, na, pB, nb1, ds_tol(c, tol), s.front, shadow_of(c, s.st));
     }
 }
+// CG iteration 0 of this cone takes alpha = rr / (rr + ||w||^2) (cg0_alpha, see Cg0Args) when its operator application runs
+// k_wsum: the w that k_wsum leaves must be exactly the w that k_spmm_ell applies -- one cone on the k_front_cw path (not the
+// merged lockstep cone, no dense constraint part, fixed-width slot list), its k_wsum grid within one partial-sum slot.  A sharded
+// cone qualifies as well: its solve's operator is built from the rank's own slot lists alone, which k_wsum and k_spmm_ell share.
+bool cg0_rule(lorads_hip_ctx *c, const Block &B) {
+    return front_cw_ok(c, B) && B.nrow > 0 && nblocks_for((size_t)B.nrow, TPB / 8) <= c->maxpart;
+}
 // body of CG iteration k up to and including the convergence test (lorads_cgs.c:180-194)
 void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int maxit, bool fold_avg = false) {
     Block &B = *s.B;
@@ -685,8 +708,7 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     double *pA = part_slot(c, 0), *pC = part_slot(c, 2);
     const Guard g{&s.st->done, s.front.need};
     const bool rec = constr_by_recurrence(c, B) && B.t_uv_valid; // (valid since the front's initial residual)
-    const int npq = apply_operator(c, B, s.V, p, OP_CG, nullptr, Q, pA, g);
-    // the operator has just left w_op = A(sym(p V^T)); x += alpha p  =>  A(sym(x V^T)) += alpha w_op
+    // the update below moves x by alpha p: w_op = A(sym(p V^T)) from the operator  =>  A(sym(x V^T)) += alpha w_op
     const int nw = !rec ? 0 : B.diag_only ? B.n : B.nrow; // (row dots for Max-Cut-type cones, constraint values otherwise)
     const bool v2 = (s.len & 1) == 0 && (((uintptr_t)s.x | (uintptr_t)r | (uintptr_t)p | (uintptr_t)Q) & 15) == 0;
     // the residual of an iteration whose tail is a restart is recomputed there: summed here, not stored
@@ -695,20 +717,39 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     const double *avg_other = fold_avg ? s.V : (const double *)nullptr;
     double *avg_out = fold_avg ? c->R + B.off : (double *)nullptr;
     if (fold_avg) c->avg_folded = true;
-    if (v2 && (!fold_avg || (((uintptr_t)avg_other | (uintptr_t)avg_out) & 15) == 0))
-        LAUNCH(k_cg_update<true>, s.gv, s.len, s.st, pA, npq, s.x, r, p, Q, pC, g, rec ? B.w_uv : (double *)nullptr,
-               (const double *)B.w_op, nw, shadow_of(c, s.st), store_r, avg_other, avg_out, s.tile, s.tile_w);
-    else
-        LAUNCH(k_cg_update<false>, s.gv, s.len, s.st, pA, npq, s.x, r, p, Q, pC, g, rec ? B.w_uv : (double *)nullptr,
-               (const double *)B.w_op, nw, shadow_of(c, s.st), store_r, avg_other, avg_out, s.tile, s.tile_w);
+    const bool v2_avg = v2 && (!fold_avg || (((uintptr_t)avg_other | (uintptr_t)avg_out) & 15) == 0);
+    // iteration 0 right behind the one-kernel front (its weights come out of k_wsum, see apply_operator): alpha from ||w||^2, and
+    // the update inside k_spmm_ell (LORADS_FUSE_CG0=0: k_cg_update with the same alpha)
+    const bool rule0 = k == 0 && B.w0_ready && cg0_rule(c, B);
+    double *pW = rule0 ? part_slot(c, 20) : (double *)nullptr;
+    const int nww = rule0 ? nblocks_for((size_t)B.nrow, TPB / 8) : 0;
+    const bool fuse0 = rule0 && c->opt_fuse_cg0 && v2_avg;
+    Cg0Args u{};
+    if (fuse0) {
+        u.st = s.st; u.part_ww = pW; u.nww = nww; u.x = s.x; u.r = r; u.store_r = store_r;
+        u.w_acc = rec ? B.w_uv : (double *)nullptr; u.w_p = B.w_op; u.nw = nw; u.shadow = shadow_of(c, s.st);
+        u.avg_other = avg_other; u.avg_out = avg_out;
+    }
+    // (fused: the operator kernel leaves the partials of the new residual's norm in pC, there are as many as it has workgroups)
+    const int npq = apply_operator(c, B, s.V, p, OP_CG, nullptr, Q, fuse0 ? pC : pA, g, pW, fuse0 ? &u : (const Cg0Args *)nullptr);
+    int nrr = npq;
+    if (!fuse0) {
+        if (v2_avg)
+            LAUNCH(k_cg_update<true>, s.gv, s.len, s.st, pA, npq, s.x, r, p, Q, pC, g, rec ? B.w_uv : (double *)nullptr,
+                   (const double *)B.w_op, nw, shadow_of(c, s.st), store_r, avg_other, avg_out, s.tile, s.tile_w, (const double *)pW, nww);
+        else
+            LAUNCH(k_cg_update<false>, s.gv, s.len, s.st, pA, npq, s.x, r, p, Q, pC, g, rec ? B.w_uv : (double *)nullptr,
+                   (const double *)B.w_op, nw, shadow_of(c, s.st), store_r, avg_other, avg_out, s.tile, s.tile_w, (const double *)pW, nww);
+        nrr = s.gv;
+    }
     B.t_uv_valid = rec; // x (= U or V) moved: the kept values moved with it, or are stale
     if (B.wj_for == s.x) B.wj_for = nullptr; // (... and so are products kept for x as a fixed factor)
     c->merged.t_uv_valid = false;
     if (c->opt_lazy_scalars) { // the convergence test rides on the next kernel if that kernel can carry it
-        c->pend_chk = Deferred{s.st, shadow_of(c, s.st), pC, s.gv, ds_maxit(c, maxit), ds_tol(c, tol), s.front.need};
+        c->pend_chk = Deferred{s.st, shadow_of(c, s.st), pC, nrr, ds_maxit(c, maxit), ds_tol(c, tol), s.front.need};
         c->pend_chk_g = g;
     } else {
-        LAUNCH(k_cg_check, 1, s.st, (int)CHK_ITER, pC, s.gv, ds_tol(c, tol), ds_maxit(c, maxit), g);
+        LAUNCH(k_cg_check, 1, s.st, (int)CHK_ITER, pC, nrr, ds_tol(c, tol), ds_maxit(c, maxit), g);
     }
 }
 // tail of CG iteration k: restart with the true residual when k % 20 == 0 (incl. k = 0), new direction (:195-228)
