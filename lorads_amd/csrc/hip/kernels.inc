@@ -1120,8 +1120,9 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const do
     }
     // ---- second visit of the row's slots: contributions of the constraint values of (r0, X)
     // (A.contrib == null -- measurement only, lorads_hip_ubench -- leaves the visit out: what it costs is the difference)
+    // (rows past n are clamped to row 0: their lanes must not write row 0's tail contributions, which row 0's own lanes write)
     const int cnt2 = A.contrib ? cnt : 0;
-    const int a1b = A.contrib ? a1 : a0;
+    const int a1b = A.contrib && act ? a1 : a0;
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
         if ((h == 0 && cnt2 > 0) || cnt2 > 8 * h) {

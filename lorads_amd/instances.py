@@ -167,6 +167,37 @@ def with_dense_constraints(prob, n_dense, seed, r0=2):
     return dict(m=m0 + n_dense, blocks=[n], b=np.array(b), entries=ent)
 
 
+def with_hub_rows(prob, n_hub, per_hub, seed, r0=2):
+    """gives rows 0 .. n_hub-1 `per_hub` more operator slots each, far more than the fixed-width slot list of k_spmm_ell holds, so
+    that its adjacency tail runs: per_hub / 2 appended constraints per hub row, each with two off-diagonal entries (p, q1), (p, q2)
+    (N(0,1)) -- small constraints, so the one-kernel front stays eligible.  The partner rows q are drawn among rows with at most 6
+    slots, so that the other rows keep at most 8.  b_i = <A_i, R0 R0^T>."""
+    (n,) = prob["blocks"]
+    rng = np.random.default_rng(seed)
+    R0 = rng.standard_normal((n, r0)) / math.sqrt(n)
+    deg = np.zeros(n, dtype=np.int64)
+    for mat, blk, i, j, v in prob["entries"]:
+        if mat > 0:
+            deg[i - 1] += 1
+            deg[j - 1] += i != j
+    ent = list(prob["entries"])
+    b = list(prob["b"])
+    m = prob["m"]
+    for h in range(n_hub):
+        pool = np.array([q for q in range(n_hub, n) if deg[q] <= 6])
+        cols = rng.choice(pool, size=per_hub, replace=False)
+        vals = rng.standard_normal(per_hub)
+        for t in range(0, per_hub - 1, 2):
+            m += 1
+            acc = 0.0
+            for q, v in sorted(zip(cols[t:t + 2].tolist(), vals[t:t + 2].tolist())):
+                ent.append((m, 1, q + 1, h + 1, v))
+                acc += 2.0 * v * float(R0[h] @ R0[q])
+                deg[q] += 1
+            b.append(acc)
+    return dict(m=m, blocks=[n], b=np.array(b), entries=ent)
+
+
 def blockdiag_maxcut(nblk, n_k, edges_k, seed0):
     """cfg4: nblk independent max-cut blocks, block-separable constraints, m = nblk * n_k."""
     ent = []
@@ -316,6 +347,12 @@ NAMED = {
     # separable cones of different size and kind, equal rank 9: the lockstep (batched) sweep with row padding
     "mix4": lambda: block_diag([maxcut(60, 90, 61), randsparse(70, 45, 62, c_edges=90, n_diag=2, n_off=3, r0=3),
                                 maxcut(66, 100, 63), matcomp(35, 33, 220, 3, 64)]),
+    # one-kernel-front cones (LORADS_OP_CW=1) with hub rows 0..2: slot width 8 (<= 0.5 % of the rows over 8 slots) and 16; 810 rows,
+    # so that the front's last workgroup holds rows past n (clamped to row 0)
+    "hub8": lambda: with_hub_rows(randsparse(810, 200, 2101, c_edges=1600, n_diag=2, n_off=3, r0=3), 3, 40, 2102),
+    "hub16": lambda: with_hub_rows(randsparse(810, 400, 2103, c_edges=1600, n_diag=2, n_off=8, r0=3), 3, 60, 2104),
+    # ... and one with ten times as many constraints as rows: the constraint values outnumber the operator kernel's threads
+    "wide60": lambda: randsparse(60, 600, 2105, c_edges=120, n_diag=1, n_off=2, r0=2),
     # Max-Cut cones of unequal size (and therefore unequal rank, data/lorads_solver.c:290-319), separable: one team of workgroups each
     "blkmix5": lambda: block_diag([maxcut(90, 140, 71), maxcut(120, 250, 72), maxcut(150, 400, 73), maxcut(260, 900, 74), maxcut(200, 500, 75)]),
     "densec300": lambda: randsparse(300, 60, 778, n_diag=2, n_off=4, r0=3, dense_c=True),  # dense C -> MFMA C.X path

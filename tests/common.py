@@ -228,6 +228,37 @@ def replay_trace(sess, g, rtol=1e-9, atol=1e-13, resync=True):
     return log
 
 
+def random_uv_state(sess, seed):
+    """seeded U, V, lambda of the session's shapes (rows of U, V of norm ~1, as the Max-Cut constraints X_ii = 1 ask)"""
+    rng = np.random.default_rng(seed)
+    U, V = [], []
+    for k in range(sess.nblk):
+        n, r = sess.block_shape(k)
+        U.append(rng.standard_normal((n, r)) / np.sqrt(r))
+        V.append(rng.standard_normal((n, r)) / np.sqrt(r))
+    return U, V, rng.standard_normal(sess.m)
+
+
+def load_uv_state(be, U, V, lam):
+    """an ADMM state into a table: R = U, alm_to_admm, then U, V, lambda and the constraint sums of (U, V)"""
+    for k, u in enumerate(U):
+        be.set_mat(host.MAT_R, k, u)
+    be.alm_to_admm()
+    for k, (u, v) in enumerate(zip(U, V)):
+        be.set_mat(host.MAT_U, k, u)
+        be.set_mat(host.MAT_V, k, v)
+    be.set_vec(host.VEC_LAMBDA, lam)
+    be.init_constr(host.PAIR_UV)
+
+
+def rel_to_scale(got, want):
+    """max |got - want| over max |want|"""
+    got = np.asarray(got, dtype=np.float64).ravel()
+    want = np.asarray(want, dtype=np.float64).ravel()
+    scale = max(float(np.max(np.abs(want))), 1e-300) if want.size else 1.0
+    return float(np.max(np.abs(got - want))) / scale if want.size else 0.0
+
+
 def trace_worst(log):
     """worst rel-to-scale error of a replay, by group: phase 1, ADMM factors, ADMM m-vectors, ADMM objectives, err1"""
     def worst(pred):
