@@ -129,6 +129,27 @@ int lorads_hip_cal_dual_obj(lorads_hip_ctx *ctx, double *dobj);
 int lorads_hip_dual_infeasibility(lorads_hip_ctx *ctx, double tol, int32_t ncv, int32_t max_restarts, double *sum_neg,
                                   double *lam_min, int32_t *matvecs);
 
+/* Solution export (DESIGN.md "Exporting a solution"; no reference counterpart).  The exported point is X_k = R_k R_k^T per SDP cone
+ * (x_j = r_j^2 on the LP block), the multipliers lambda -- with a dual update that still waits for a carrier applied to a copy -- and
+ * the slack S_k = C_k - sum_i lambda_i A_ik.  src = LORADS_HIP_PAIR_UV takes R = (U + V) / 2 (phase 2), LORADS_HIP_PAIR_RR takes R
+ * itself (phase 1).  Neither call writes any state of the solve: the next iteration computes what it would have computed.
+ * Values are in device terms like the neighbouring entries (objective, multipliers and slack scaled by scaleObjHis; the caller
+ * divides).  Sharded contexts (an all-reduce hook, a separable shard) are refused.
+ *   out[0] ||A(X) - b||_2 / (1 + ||b||_1)        out[1] ||A(X) - b||_inf / (1 + ||b||_inf)
+ *   out[2] <C, X> (+ c_lp . x)                    out[3] b . lambda
+ *   out[4] <X, S> (+ x . s_lp)                    out[5] min over cones of lambda_min(S_k) (LP block: min_j s_j)
+ *   out[6] Lanczos matvecs                        out[7] ||A(X) - b||_2   out[8] ||A(X) - b||_inf   out[9] ||b||_inf
+ * lam_min ([nblocks], may be NULL) gets the per-cone eigenvalue, residual ([m], may be NULL) A(X) - b.  tol, ncv, max_restarts are
+ * the Lanczos parameters of lorads_hip_dual_infeasibility; tol <= 0 skips the eigen-solves (out[5] and lam_min are NaN).
+ * lambda ([m], may be NULL) receives the multipliers of the certificate: lorads_hip_get_vec would first store a waiting dual update. */
+#define LORADS_HIP_CERT_N 10
+int lorads_hip_certificate(lorads_hip_ctx *ctx, int32_t src, double tol, int32_t ncv, int32_t max_restarts,
+                           double out[LORADS_HIP_CERT_N], double *lam_min, double *residual, double *lambda);
+/* S of cone blk as lower-triangle triplets (row >= col) in device terms: the union pattern's entries (ordered by column, then row);
+ * the whole lower triangle on a cone with dense storage; one (j, j) entry per column on the LP block.  NULL arrays: *nnz = the count
+ * and nothing else. */
+int lorads_hip_get_slack(lorads_hip_ctx *ctx, int32_t blk, int64_t *nnz, int32_t *row, int32_t *col, double *val);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

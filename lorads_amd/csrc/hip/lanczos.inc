@@ -166,17 +166,19 @@ struct LanczosBufs {
 // lorads_hip_dual_infeasibility), so everything here is launched on an explicit stream.
 #define LAUNCH_ON(st, kern, grid, ...) hipLaunchKernelGGL(kern, dim3(grid), dim3(TPB), 0, st, __VA_ARGS__)
 
-// y = (C - sum_i lambda_i A_i) x of cone B; the pattern values B.pu.S must hold the W_DUAL assembly
-void slack_matvec(hipStream_t st, Block &B, const double *x, double *y, double *dtmp) {
-    // (dense constraint matrices: B.Sfull holds [C] - sum_j lambda_j A_j, formed once before the iterations)
+// y = (C - sum_i lambda_i A_i) x of cone B; S holds the W_DUAL assembly on the union pattern and Sd (dense-storage cones) the dense
+// share of the slack, npad x npad
+void slack_matvec(hipStream_t st, Block &B, const double *x, double *y, double *dtmp, const double *S, const double *Sd) {
     const bool dn = B.dense_c || B.dense_a;
-    if (dn) LAUNCH_ON(st, k_dense_mv, nblocks_for((size_t)B.n, TPB / 64), B.n, B.npad, B.dense_a ? B.Sfull : B.Cfull, x, dtmp);
-    LAUNCH_ON(st, k_spmv, nblocks_for((size_t)B.n, TPB / 8), B.n, B.pu.adj_ptr, B.pu.adj_col, B.pu.adj_e, B.pu.S, x, y,
+    if (dn) LAUNCH_ON(st, k_dense_mv, nblocks_for((size_t)B.n, TPB / 64), B.n, B.npad, Sd, x, dtmp);
+    LAUNCH_ON(st, k_spmv, nblocks_for((size_t)B.n, TPB / 8), B.n, B.pu.adj_ptr, B.pu.adj_col, B.pu.adj_e, S, x, y,
               dn ? dtmp : (const double *)nullptr);
 }
 
+// S_given / Sd_given null: the slack of the context's multipliers is assembled into B.pu.S (and B.Sfull); otherwise the caller has
+// assembled it there (the solution export's own scratch, solution.inc) and nothing of the cone is written
 int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B, double tol, int ncv, int max_restart,
-                    double *theta_out, int *matvecs) {
+                    double *theta_out, int *matvecs, const double *S_given = nullptr, const double *Sd_given = nullptr) {
     const int n = B.n, m = std::max(1, std::min(ncv, n)), keep_max = 8;
     LanczosBufs lb;
     if (dalloc(&lb.V, (size_t)n * (m + 1)) || dalloc(&lb.V2, (size_t)n * (keep_max + 1)) || dalloc(&lb.w, (size_t)n) ||
@@ -185,10 +187,13 @@ int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B,
     // S on the union pattern: C_e - sum_i lambda_i a  (data/lorads_solver.c:1027-1029)
     WArgs wa{};
     wa.lambda = c->lambda; wa.row_idx = B.row_idx;
-    if (B.pu.ne > 0)
+    const double *Smv = S_given ? S_given : B.pu.S;
+    // (dense constraint matrices: the dense share [C] - sum_j lambda_j A_j, formed once before the iterations)
+    const double *Sdmv = S_given ? Sd_given : B.dense_a ? B.Sfull : B.Cfull;
+    if (!S_given && B.pu.ne > 0)
         LAUNCH_ON(st, k_sval, nblocks_for((size_t)B.pu.ne, TPB), B.pu.ne, B.pu.e_ptr, B.pu.e_con, B.pu.e_val, B.pu.cbase, (int)W_DUAL, wa,
                   B.pu.S, NOGUARD, (CGState *)nullptr, 0);
-    if (B.dense_a) { // the dense constraints' share of the slack: [C_dense] - sum_j lambda_j A_j
+    if (!S_given && B.dense_a) { // the dense constraints' share of the slack: [C_dense] - sum_j lambda_j A_j
         const size_t msz = (size_t)B.npad * B.npad;
         hipLaunchKernelGGL(k_dense_mu, dim3(nblocks_for((size_t)B.nd, TPB)), dim3(TPB), 0, st, B.nd, (const int *)B.d_con, (int)W_DUAL, wa, 1.0,
                            B.d_mu, NOGUARD);
@@ -235,7 +240,7 @@ int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B,
         // the whole sweep j = k .. m - 1 goes to the stream; ONE read-back at its end
         for (int j = k; j < m; ++j) {
             const double *vj = lb.V + (size_t)j * n;
-            slack_matvec(st, B, vj, lb.w, lb.dtmp);
+            slack_matvec(st, B, vj, lb.w, lb.dtmp, Smv, Sdmv);
             double *h1 = lb.h, *h2 = lb.h + (m + 1), *nr2 = lb.h + 2 * (m + 1);
             LAUNCH_ON(st, k_basis_dots, j + 1, n, lb.V, lb.w, h1);
             LAUNCH_ON(st, k_basis_sub, gn, n, lb.V, j + 1, h1, lb.w);

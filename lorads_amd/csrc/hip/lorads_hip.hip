@@ -486,12 +486,28 @@ struct LzWorker {
     double *pinned = nullptr;
 };
 
+// scratch of the solution export (solution.inc): allocated on its first call, never read by the solve
+struct CertScratch {
+    bool ready = false;
+    double *lam = nullptr, *ax = nullptr; // [m] multipliers with a waiting dual update applied; A(X), then A(X) - b
+    double *S = nullptr;                  // slack on every cone's union pattern (cone k at s_off[k])
+    double *d = nullptr, *dA = nullptr;   // pair values R_p.R_q on the union / A-pattern of the cone at hand
+    double *G = nullptr, *Sd = nullptr;   // dense-storage cones: R R^T (npad x npad) and the dense share of S (cone k at sd_off[k])
+    double *mu = nullptr, *part = nullptr, *acc = nullptr;
+    std::vector<size_t> s_off, sd_off;
+    void release() {
+        hipFree(lam); hipFree(ax); hipFree(S); hipFree(d); hipFree(dA); hipFree(G); hipFree(Sd); hipFree(mu); hipFree(part); hipFree(acc);
+        *this = CertScratch{};
+    }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
     hipStream_t stream = nullptr;
     std::vector<Block> blk;
     std::vector<LzWorker> lz_workers; // dual-infeasibility eigen-solves (lanczos.inc)
+    CertScratch cert;                 // solution export (solution.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -817,6 +833,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) {
     hipFree(c->cstage); hipFree(c->sepbuf); hipFree(c->gram);
     hipFree(c->b); hipFree(c->lambda); hipFree(c->lambda_alt); hipFree(c->csum); hipFree(c->q12); hipFree(c->part); hipFree(c->ctrl); hipFree(c->st_shadow); hipFree(c->seg_tile_cone); hipFree(c->seg_rr_alt); hipFree(c->seg_tile_info);
     hipFree(c->ring_ab); hipFree(c->par); hipFree(c->seq_dev);
+    c->cert.release();
     graph_cache_free(c);
     if (c->persist) { c->persist->release(); delete c->persist; c->persist = nullptr; }
     if (c->lteam) { c->lteam->release(); delete c->lteam; c->lteam = nullptr; }
@@ -1631,3 +1648,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 } // extern "C"
 
 #include "lanczos.inc"
+#include "solution.inc"

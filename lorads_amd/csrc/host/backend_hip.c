@@ -45,6 +45,8 @@ typedef struct {
     int (*dual_infeasibility)(lorads_hip_ctx *, double, int32_t, int32_t, double *, double *, int32_t *);
     int (*alm_front)(lorads_hip_ctx *, double, int32_t, double *);
     int (*alm_step)(lorads_hip_ctx *, double, double, int32_t, double *);
+    int (*certificate)(lorads_hip_ctx *, int32_t, double, int32_t, int32_t, double *, double *, double *, double *); /* optional */
+    int (*get_slack)(lorads_hip_ctx *, int32_t, int64_t *, int32_t *, int32_t *, double *);                /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -75,6 +77,13 @@ static int b_step(void *cx, double rho, double tol, int mx, double o[4]) { retur
 static int b_afront(void *cx, double rho, int inner, double o[6]) { return report(H, H->alm_front(H->ctx, rho, inner, o), "alm_front"); }
 static int b_astep(void *cx, double rho, double tau, int nx, double o[8]) { return report(H, H->alm_step(H->ctx, rho, tau, nx, o), "alm_step"); }
 static int b_dinf(void *cx, double *v) { return report(H, H->dual_infeasibility(H->ctx, 1e-2, 40, 600, v, NULL, NULL), "dual_infeasibility"); }
+/* solution export: Lanczos subspace and restart budget of dual_infeasibility, at the caller's tolerance */
+static int b_cert(void *cx, int src, double tol, double *o, double *lm, double *res, double *y) {
+    return report(H, H->certificate(H->ctx, src, tol, 40, 600, o, lm, res, y), "certificate");
+}
+static int b_slack(void *cx, int k, int64_t *nnz, int *row, int *col, double *val) {
+    return report(H, H->get_slack(H->ctx, k, nnz, (int32_t *)row, (int32_t *)col, val), "get_slack");
+}
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
 static int b_a2a(void *cx) { return report(H, H->alm_to_admm(H->ctx), "alm_to_admm"); }
@@ -131,6 +140,10 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     SYM(set_vec, "set_vec"); SYM(get_vec, "get_vec"); SYM(set_allreduce, "set_allreduce"); SYM(admm_step, "admm_step");
     SYM(dual_infeasibility, "dual_infeasibility"); SYM(alm_front, "alm_front"); SYM(alm_step, "alm_step");
 #undef SYM
+    /* optional entry points: a library without them leaves the slots NULL */
+    *(void **)(&h->certificate) = dlsym(h->dl, "lorads_hip_certificate");
+    *(void **)(&h->get_slack) = dlsym(h->dl, "lorads_hip_get_slack");
+    if (!h->get_slack) h->certificate = NULL;
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -174,5 +187,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     out->dual_infeasibility = b_dinf;
     out->alm_front = b_afront;
     out->alm_step = b_astep;
+    if (h->certificate) { out->certificate = b_cert; out->get_slack = b_slack; }
     return 0;
 }

@@ -156,7 +156,15 @@ typedef struct lrd_backend {
      * out = {lagNormSq, err1, p1, p2, a, b, c, d}.  Same results as the separate slots. */
     int (*alm_front)(void *ctx, double rho, int inner, double out[6]);
     int (*alm_step)(void *ctx, double rho, double tau, int next_inner, double out[8]);
+    /* OPTIONAL pair (both or neither): solution export, read-only on the state (include/lorads_hip.h: lorads_hip_certificate,
+     * lorads_hip_get_slack).  certificate: src = LRD_PAIR_UV (R = (U+V)/2) or LRD_PAIR_RR, Lanczos tol (<= 0: no eigen-solves),
+     * out[LRD_CERT_N] in the backend's terms (scaled by scaleObjHis); lam_min [nblk], residual [m] and y [m] (the multipliers the
+     * certificate used: a dual update still waiting inside the backend applied, not stored) may be NULL.
+     * get_slack: S of block blk as lower-triangle triplets; NULL arrays return the count alone. */
+    int (*certificate)(void *ctx, int src, double tol, double *out, double *lam_min, double *residual, double *y);
+    int (*get_slack)(void *ctx, int blk, int64_t *nnz, int *row, int *col, double *val);
 } lrd_backend;
+#define LRD_CERT_N 10
 
 /* iteration states, as the reference's lorads_alm_state / lorads_admm_state
  * (data/def_lorads_solver.h:130-161) */
@@ -194,6 +202,7 @@ typedef struct {
     int use_fused_step; /* 1: use lrd_backend.admm_step when the table has it */
     int be_fail;        /* a table slot returned non-zero (device error, refused resize, failed all-reduce): the loops
                          * stop with LRD_RET_NUM_ERR instead of steering on numbers nobody produced */
+    int in_admm;        /* phase 2 has begun (lrd_alm_to_admm) and no phase-1 round has followed: the point is R = (U+V)/2 */
 } lrd_solver;
 
 /* ---- params / problem ---- */
@@ -247,6 +256,41 @@ double lrd_reopt(lrd_params *par, lrd_solver *s, double reopt_param, int reopt_a
  * and are "next") */
 int lrd_solve(lrd_params *par, lrd_solver *s);
 int lrd_dual_infeasibility(lrd_solver *s); /* data/lorads_solver.c:1007-1037 through the table's optional slot */
+
+/* ---- solution export (session.c, solution.c; DESIGN.md "Exporting a solution").  Everything in the file's units (divided by
+ * scaleObjHis) and numbering.  Problem: min <C, X> s.t. <A_i, X> = b_i, X psd, C = -F0, A_i = F_i (SDPA: Y_sdpa = X, x_sdpa = -y,
+ * X_sdpa = S). */
+typedef struct {
+    int n, rank;     /* rank: the cone's current rank (LP block: 1) */
+    int is_lp;
+    double *R, *U, *V; /* column-major n x rank; R = (U+V)/2 in phase 2, the phase-1 R otherwise; X = R R^T */
+    double *x;         /* LP block: x_j = r_j^2 (NULL on SDP cones) */
+    int64_t s_nnz;     /* S = C - sum_i y_i A_i, lower-triangle triplets (LP block: one (j, j) entry per column) */
+    int *s_row, *s_col;
+    double *s_val;
+    double lam_min;    /* lambda_min(S) (LP block: min_j s_j) */
+} lrd_solution_cone;
+typedef struct {
+    int m, nblk, status;
+    int src;           /* LRD_PAIR_UV or LRD_PAIR_RR: where R came from */
+    double scale;      /* scaleObjHis the backend's values were divided by */
+    double pobj, dobj; /* <C, X> + c_lp . x,  b . y */
+    /* DIMACS errors of (X, y, S): err1 = ||A(X) - b||_2 / (1 + ||b||_1), err1_inf = ||.||_inf / (1 + ||b||_inf), err2 = err3 = 0 by
+     * construction, err4 = max(0, -min_k lambda_min(S_k)) / (1 + ||C||_1), err5 = (p - d) / (1 + |p| + |d|), err6 = <X, S> / (same) */
+    double err1, err1_inf, err2, err3, err4, err5, err6;
+    double xs;         /* <X, S> */
+    int matvecs;       /* Lanczos S x products */
+    double *y;         /* [m] */
+    lrd_solution_cone *cone; /* [nblk], file order */
+} lrd_solution;
+/* fill *out from the session's current state (tol: Lanczos tolerance of lambda_min); refuses (non-zero) when the table lacks the
+ * export slots or the session holds a sharded deal.  lrd_solution_free releases what it allocated. */
+typedef struct lrd_session lrd_session;
+int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out);
+void lrd_solution_free(lrd_solution *sol);
+/* plain-text file of a solution (a pure function of the struct): "lorads-solution 1", status, pobj, dobj, the certificate, "y m" and
+ * m values, then per cone "sdp k n r" and n rows of R, or "lp k n" and n values of x (k: 1-based block of the file); every double %.17g */
+int lrd_solution_write(const char *path, const lrd_solution *sol);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -28,10 +28,15 @@ int main(int argc, char **argv) {
     }
     lrd_session *s = lrd_session_open(argv[1]);
     if (!s) return 1;
+    const char *solution_file = NULL; /* ours, not the reference's: taken before the parameter block sees the options */
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
             return 2;
+        }
+        if (!strcmp(argv[i], "--solutionFile")) {
+            solution_file = argv[i + 1];
+            continue;
         }
         if (strncmp(argv[i], "--", 2) || lrd_session_set_param(s, argv[i] + 2, argv[i + 1])) {
             fprintf(stderr, "unknown option %s\n", argv[i]);
@@ -73,6 +78,22 @@ int main(int argc, char **argv) {
     printf("-----------------------------------------------------------------------\n");
     printf("phase 1: %f s, phase 2: %f s (%d ADMM iterations, %d CG iterations), dual infeasibility: %f s\n", r[10], r[11],
            (int)r[13], (int)r[14], r2[2]);
+    if (solution_file) {
+        lrd_solution *x = NULL;
+        if (lrd_session_solution(s, 1e-8, &x) || lrd_solution_write(solution_file, x)) {
+            fprintf(stderr, "lorads: cannot write the solution file %s\n", solution_file);
+            lrd_solution_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Certificate of the exported solution (%s):\n", solution_file);
+        printf("\t primal objective <C, X>         : %.10e\n\t dual objective b.y               : %.10e\n", x->pobj, x->dobj);
+        printf("\t err1 ||A(X) - b||_2 rel.        : %.6e\n\t err1 ||A(X) - b||_inf rel.      : %.6e\n", x->err1, x->err1_inf);
+        printf("\t err2 (X = R R^T psd)            : %.6e\n\t err3 (S = C - A*(y))            : %.6e\n", x->err2, x->err3);
+        printf("\t err4 lambda_min(S) rel.         : %.6e\n\t err5 gap rel.                   : %.6e\n", x->err4, x->err5);
+        printf("\t err6 <X, S> rel.                : %.6e\n", x->err6);
+        lrd_solution_free(x);
+    }
     lrd_session_close(s);
     return 0;
 }

@@ -3,6 +3,7 @@
  * backend table has been attached, the solver state. */
 #include "lorads_host.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -202,6 +203,71 @@ int lrd_session_results(lrd_session *s, double out[16]) {
     out[10] = v->t_alm; out[11] = v->t_admm; out[12] = v->status;
     out[13] = v->admm_iters_first; out[14] = v->cg_iters_first;
     out[15] = v->err_constr_l1 * (1 + s->prob->bNrm1) / (1 + s->prob->bNrmInf);
+    return 0;
+}
+
+/* the current point with its certificate, in the file's units (lorads_host.h: lrd_solution) */
+int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out) {
+    *out = NULL;
+    if (!s->have_sol) return 1;
+    lrd_backend *be = &s->be;
+    const lrd_problem *p = s->prob;
+    if (!be->certificate || !be->get_slack) {
+        fprintf(stderr, "lorads: the %s backend cannot export a solution\n", be->name ? be->name : "attached");
+        return 2;
+    }
+    if (p->separable || p->nblk != s->nblk_all || s->sol.allreduce) {
+        fprintf(stderr, "lorads: exporting the solution of a sharded deal (world > 1) is not supported\n");
+        return 3;
+    }
+    const double sc = s->sol.scaleObjHis;
+    const int src = s->sol.in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    double c[LRD_CERT_N];
+    double *lm = (double *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(double));
+    lrd_solution *x = (lrd_solution *)calloc(1, sizeof *x);
+    x->m = p->m; x->nblk = p->nblk; x->status = s->sol.status; x->src = src; x->scale = sc;
+    x->y = (double *)calloc((size_t)(p->m > 0 ? p->m : 1), sizeof(double));
+    x->cone = (lrd_solution_cone *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(lrd_solution_cone));
+    /* (y from the certificate, not get_vec: get_vec would store a dual update that waits inside the backend) */
+    int rc = be->certificate(be->ctx, src, tol, c, lm, NULL, x->y);
+    for (int i = 0; i < p->m && !rc; ++i) x->y[i] /= sc;
+    double minlam = INFINITY;
+    for (int k = 0; k < p->nblk && !rc; ++k) {
+        const lrd_block *b = &p->blk[k];
+        lrd_solution_cone *q = &x->cone[k];
+        const int n = b->n, r = s->sol.rank[k];
+        const size_t len = (size_t)n * (size_t)r;
+        q->n = n; q->rank = r; q->is_lp = b->is_lp;
+        q->R = (double *)calloc(len ? len : 1, sizeof(double));
+        q->U = (double *)calloc(len ? len : 1, sizeof(double));
+        q->V = (double *)calloc(len ? len : 1, sizeof(double));
+        if (be->get_mat(be->ctx, LRD_MAT_U, k, q->U) || be->get_mat(be->ctx, LRD_MAT_V, k, q->V)) { rc = 1; break; }
+        if (src == LRD_PAIR_UV) for (size_t t = 0; t < len; ++t) q->R[t] = (q->U[t] + q->V[t]) / 2;
+        else if (be->get_mat(be->ctx, LRD_MAT_R, k, q->R)) { rc = 1; break; }
+        if (b->is_lp) {
+            q->x = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof(double));
+            for (int j = 0; j < n; ++j) q->x[j] = q->R[j] * q->R[j];
+        }
+        if (be->get_slack(be->ctx, k, &q->s_nnz, NULL, NULL, NULL)) { rc = 1; break; }
+        const size_t nz = q->s_nnz > 0 ? (size_t)q->s_nnz : 1;
+        q->s_row = (int *)calloc(nz, sizeof(int));
+        q->s_col = (int *)calloc(nz, sizeof(int));
+        q->s_val = (double *)calloc(nz, sizeof(double));
+        if (be->get_slack(be->ctx, k, &q->s_nnz, q->s_row, q->s_col, q->s_val)) { rc = 1; break; }
+        for (int64_t t = 0; t < q->s_nnz; ++t) q->s_val[t] /= sc;
+        q->lam_min = lm[k] / sc;
+        if (q->lam_min < minlam) minlam = q->lam_min;
+    }
+    free(lm);
+    if (rc) { lrd_solution_free(x); return 1; }
+    x->pobj = c[2] / sc; x->dobj = c[3] / sc; x->xs = c[4] / sc;
+    x->matvecs = (int)c[6];
+    const double den = 1 + fabs(x->pobj) + fabs(x->dobj);
+    x->err1 = c[0]; x->err1_inf = c[1]; x->err2 = 0.0; x->err3 = 0.0;
+    x->err4 = tol > 0 ? (minlam < 0 ? -minlam : 0.0) / (1 + p->cObjNrm1) : NAN;
+    x->err5 = (x->pobj - x->dobj) / den;
+    x->err6 = x->xs / den;
+    *out = x;
     return 0;
 }
 

@@ -245,6 +245,7 @@ int lrd_alm_optimize(lrd_params *par, lrd_solver *s, int reopt, int early_stop, 
     void *cx = be->ctx;
     lrd_alm_state *st = &s->alm;
     const double t_ori = lrd_time();
+    s->in_admm = 0;
     int ret = LRD_RET_OK;
     if (!reopt) s->max_alm_sub_iter = 5000; /* lorads_alm.c:993 (the reopt variant keeps the global) */
     int is_rank_max = all_rank_max(s, 1.0);
@@ -554,6 +555,7 @@ int lrd_admm_optimize(lrd_params *par, lrd_solver *s, int reopt, int iter_ceilin
 /* LORADS_ALMtoADMM, data/lorads_solver.c:968-1004 */
 void lrd_alm_to_admm(lrd_params *par, lrd_solver *s) {
     BE(s->be->alm_to_admm(s->be->ctx));
+    s->in_admm = 1;
     lrd_alm_state *a = &s->alm;
     lrd_admm_state *d = &s->admm;
     d->l_1_dual_infeasibility = a->l_1_dual_infeasibility;

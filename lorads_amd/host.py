@@ -58,6 +58,8 @@ class BackendStruct(C.Structure):
         ("dual_infeasibility", C.CFUNCTYPE(C.c_int, C.c_void_p, _dp)),
         ("alm_front", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_int, _dp)),
         ("alm_step", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, _dp)),
+        ("certificate", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp)),
+        ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
     ]
 
 
@@ -601,6 +603,41 @@ class Session:
         _check(self.lib.lrd_session_results2(self.h, o2), "results2")
         res.update(dual_infeas_l1=o2[0], dual_infeas_inf=o2[1], t_dual_infeas=o2[2], scale_obj_his=o2[3])
         return res
+
+    def _solution_ptr(self, tol):
+        from .solution import SolutionStruct
+        ptr = C.POINTER(SolutionStruct)()
+        self.lib.lrd_session_solution.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.POINTER(SolutionStruct))]
+        self.lib.lrd_solution_free.argtypes = [C.POINTER(SolutionStruct)]
+        rc = self.lib.lrd_session_solution(self.h, float(tol), C.byref(ptr))
+        if rc == 2:
+            raise NotImplementedError("the attached backend (%s) cannot export a solution: only the HIP backend computes the "
+                                      "certificate" % (self.be.name if self.be else "none"))
+        if rc == 3:
+            raise NotImplementedError("exporting the solution of a sharded deal (world > 1) is not supported")
+        _check(rc, "solution")
+        return ptr
+
+    def solution(self, tol=1e-8):
+        """The current primal-dual point and its DIMACS certificate in the file's units (lorads_amd.solution.Solution): per cone
+        R, U, V (X = R R^T) or x (LP block), y, the slack S = C - sum_i y_i A_i and the certificate.  Read-only: the next
+        iteration computes what it would have computed without the call."""
+        from .solution import Solution
+        ptr = self._solution_ptr(tol)
+        try:
+            return Solution.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_solution_free(ptr)
+
+    def write_solution(self, path, tol=1e-8):
+        """the solution file of the command line's --solutionFile (the same C writer: the same bytes)"""
+        from .solution import SolutionStruct
+        ptr = self._solution_ptr(tol)
+        try:
+            self.lib.lrd_solution_write.argtypes = [C.c_char_p, C.POINTER(SolutionStruct)]
+            _check(self.lib.lrd_solution_write(os.fsencode(path), ptr), "solution_write")
+        finally:
+            self.lib.lrd_solution_free(ptr)
 
     def dual_infeasibility(self):
         """DIMACS error 2 of the current multipliers, data/lorads_solver.c:1007-1037 (-1: slot missing)"""
