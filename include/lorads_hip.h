@@ -150,6 +150,22 @@ int lorads_hip_certificate(lorads_hip_ctx *ctx, int32_t src, double tol, int32_t
  * and nothing else. */
 int lorads_hip_get_slack(lorads_hip_ctx *ctx, int32_t blk, int64_t *nnz, int32_t *row, int32_t *col, double *val);
 
+/* Hyperplane rounding of a +-1-structured context (no reference counterpart).  Qualifies: no LP block, every
+ * constraint one stored entry a_i X_k[p,p] = b_i with b_i / a_i > 0, every diagonal of every cone fixed by exactly one; then
+ * x = sigma o t with t_p = sqrt(b_i / a_i) is feasible for every sigma in {+-1}^n.  Per cone k and trial t a Gaussian g_{k,t} of the
+ * cone's own rank (counter-based on (seed, k, t, column)), sigma_p = sign(R_p . g) with R as lorads_hip_certificate takes it (src),
+ * f_t = x^T C x, then at most max_rounds rounds of the 1-flip local search by colour classes (0: none).  Values in device terms
+ * (C scaled by scaleObjHis).  Read-only on the solver's state; the same state and arguments give the same bits.
+ *   obj [trials]            f after the local search        obj0 [trials] (may be NULL)  f before it
+ *   best / best0            argmin of obj / obj0 (lowest index on ties; may be NULL)
+ *   sign [sum_k n_k]        the best trial's signs (+1 / -1), cone after cone (may be NULL)
+ *   rounds                  local-search rounds run (may be NULL)
+ *   hyperplanes             per cone rank_k x trials (row-major: column j of cone k, then trial), cone after cone (may be NULL)
+ * trials = 0 checks applicability only.  1 <= trials <= 65536.  Returns 2 when the context does not qualify (lorads_hip_last_error
+ * names the first offending constraint or cone), 3 when it is sharded. */
+int lorads_hip_round_pm1(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
+                         double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds, double *hyperplanes);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

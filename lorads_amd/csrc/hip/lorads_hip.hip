@@ -501,6 +501,24 @@ struct CertScratch {
     }
 };
 
+// scratch of the rounding (rounding.inc): allocated on its first call, never read by the solve
+struct RoundScratch {
+    bool checked = false, qualifies = false, coloured = false;
+    std::string why;                          // the first reason the context does not qualify
+    std::vector<int> t_off;                   // [nb + 1] first row of every cone in the stacked row arrays
+    double *t = nullptr;                      // t_p = sqrt(b_i / a_i), cone k at t_off[k]
+    std::vector<std::vector<int>> cls_ptr;    // per cone: colour class -> its range of the class-sorted row list
+    int *cls_rows = nullptr;                  // class-sorted rows, cone k at t_off[k]
+    double *G = nullptr, *part = nullptr, *f = nullptr, *f0 = nullptr; // hyperplanes, field partials, f after / before the search
+    unsigned long long *sgn = nullptr;        // sign words, cone k at t_off[k] * W
+    int *ctl = nullptr;                       // [0] flip flag, [1] best before, [2] best after the search
+    size_t g_cap = 0, sgn_cap = 0, part_cap = 0, f_cap = 0;
+    void release() {
+        hipFree(t); hipFree(cls_rows); hipFree(G); hipFree(part); hipFree(f); hipFree(f0); hipFree(sgn); hipFree(ctl);
+        *this = RoundScratch{};
+    }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -508,6 +526,7 @@ struct lorads_hip_ctx {
     std::vector<Block> blk;
     std::vector<LzWorker> lz_workers; // dual-infeasibility eigen-solves (lanczos.inc)
     CertScratch cert;                 // solution export (solution.inc)
+    RoundScratch rnd;                 // +-1 rounding (rounding.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -834,6 +853,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) {
     hipFree(c->b); hipFree(c->lambda); hipFree(c->lambda_alt); hipFree(c->csum); hipFree(c->q12); hipFree(c->part); hipFree(c->ctrl); hipFree(c->st_shadow); hipFree(c->seg_tile_cone); hipFree(c->seg_rr_alt); hipFree(c->seg_tile_info);
     hipFree(c->ring_ab); hipFree(c->par); hipFree(c->seq_dev);
     c->cert.release();
+    c->rnd.release();
     graph_cache_free(c);
     if (c->persist) { c->persist->release(); delete c->persist; c->persist = nullptr; }
     if (c->lteam) { c->lteam->release(); delete c->lteam; c->lteam = nullptr; }
@@ -1649,3 +1669,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 
 #include "lanczos.inc"
 #include "solution.inc"
+#include "rounding.inc"

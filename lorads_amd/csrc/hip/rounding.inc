@@ -1,0 +1,399 @@
+// rounding.inc -- hyperplane rounding and 1-flip local search of +-1-structured contexts (Max-Cut, weighted Max-Cut, +-1 QUBO
+// relaxations and their scaled forms), included by lorads_hip.hip after solution.inc.  DESIGN.md section 11.
+//
+// A context qualifies when it has no LP block and every constraint is a_i X_k[p,p] = b_i with b_i / a_i > 0, one per diagonal
+// position of every cone.  Then x = sigma o t (t_p = sqrt(b_i / a_i)) is feasible for every sigma in {+-1}^n.  Per cone and trial a
+// Gaussian hyperplane g (counter-based: it depends on (seed, cone, trial, column) alone) gives sigma_p = sign(R_p . g); f = x^T C x;
+// then a deterministic 1-flip local search by colour classes of C's off-diagonal graph.
+//
+// Sign words: bit l of word sgn[w * n + p] is trial 64 w + l of row p (1: sigma = +1).  A wavefront works on one word (lane = trial),
+// so the words of a row's neighbours are wave-uniform loads.  Everything is read-only on the solver's state: R is formed on the fly
+// from U and V as the export forms it, the scratch is the feature's own (RoundScratch), launches go straight to the stream (never
+// through LAUNCH, which would flush a waiting dual update), and every sum is reduced per workgroup and then in a fixed order.
+
+namespace {
+
+constexpr int RND_MAXK = 65536;   // trials per call
+constexpr int RND_STRIPS = 256;   // row strips of the field pass: per-trial partials per cone (fixed: f's summation order is K's own)
+constexpr int RND_RPW = 8;        // rows per wavefront of the sign pass (one load of G's column serves them all)
+
+// splitmix64 of x: the output of the generator whose state was x before its step
+__device__ __host__ __forceinline__ uint64_t rnd_sm(uint64_t x) {
+    uint64_t z = x + 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+// G_k (rk x K, G[j * K + t]) of cone k: c = (k << 32) | (t << 10) | j, a = sm(seed ^ sm(2c)), b = sm(seed ^ sm(2c + 1)),
+// u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = (b >> 11) 2^-53 in [0, 1), g = sqrt(-2 ln u1) cos(2 pi u2)
+__global__ __launch_bounds__(TPB) void k_rnd_hyper(int rk, int K, int cone, uint64_t seed, double *__restrict__ G) {
+    const size_t len = (size_t)rk * K;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
+        const uint64_t j = i / K, t = i % K;
+        const uint64_t ctr = ((uint64_t)cone << 32) | (t << 10) | j;
+        const uint64_t a = rnd_sm(seed ^ rnd_sm(2 * ctr)), b = rnd_sm(seed ^ rnd_sm(2 * ctr + 1));
+        const double u1 = (double)((a >> 11) + 1) * 0x1p-53, u2 = (double)(b >> 11) * 0x1p-53;
+        G[i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    }
+}
+
+// sign words of RND_RPW rows and one word of trials per wavefront: s = R_p . g_t over the cone's own rk columns (R = (U + V) / 2 or R,
+// row stride r), bit = s >= 0; lanes past K give 0 bits.  Wavefronts of one word are neighbours in the grid, so G's 64 columns of
+// the word stay in cache while its rows go by; the rows of R are wave-uniform (scalar) loads.
+__global__ __launch_bounds__(TPB) void k_rnd_sign(int n, int rk, int r, int K, int W, const double *__restrict__ U,
+                                                  const double *__restrict__ V, int uv, const double *__restrict__ G,
+                                                  unsigned long long *__restrict__ sgn) {
+    const int lane = threadIdx.x & 63;
+    const int nch = (n + RND_RPW - 1) / RND_RPW;
+    const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (TPB / 64) + (threadIdx.x >> 6)));
+    if (gw >= nch * W) return;
+    const int w = gw / nch, p0 = (gw % nch) * RND_RPW;
+    const int t = w * 64 + lane;
+    const bool valid = t < K;
+    double s[RND_RPW];
+#pragma unroll
+    for (int i = 0; i < RND_RPW; ++i) s[i] = 0.0;
+    for (int j = 0; j < rk; ++j) {
+        const double g = valid ? G[(size_t)j * K + t] : 0.0;
+#pragma unroll
+        for (int i = 0; i < RND_RPW; ++i) {
+            const int p = p0 + i < n ? p0 + i : n - 1;
+            double a = U[(size_t)p * r + j];
+            if (uv) a = (a + V[(size_t)p * r + j]) / 2;
+            s[i] += a * g;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < RND_RPW; ++i) {
+        const unsigned long long word = __ballot(valid && s[i] >= 0.0);
+        if (lane == 0 && p0 + i < n) sgn[(size_t)w * n + p0 + i] = word;
+    }
+}
+
+// The field pass, one wavefront per (row, word), lane = trial: h_p = sum_{q != p} C_pq x_q over p's row list in its stored order
+// (the union pattern's adjacency; the dense row of a dense-C cone), x = sigma o t.
+//   eval (rows == null): per-workgroup partials of sum_p x_p (h_p + C_pp x_p), part[t * RND_STRIPS + strip]
+//   local search: the rows of one colour class; flip where Delta_p = -4 x_p h_p < -tau_p, tau_p = 2^-40 4 t_p sum_{q != p} |C_pq| t_q,
+//   and raise *flag (every writer writes 1).  No two rows of a class are adjacent: no row reads a word this launch writes.
+// The off-diagonal slots of a qualifying cone are untouched by constraints, so adj_sval holds their C; C_pp comes from cbase.
+__global__ __launch_bounds__(TPB) void k_rnd_field(int nrows, const int *__restrict__ rows, int n, int K, const int *__restrict__ adj_ptr,
+                                                   const int *__restrict__ adj_col, const int *__restrict__ adj_e,
+                                                   const double *__restrict__ adj_sval, const double *__restrict__ cbase,
+                                                   const double *__restrict__ Cfull, int npad, const double *__restrict__ tv,
+                                                   unsigned long long *__restrict__ sgn, double *__restrict__ part, int *__restrict__ flag) {
+    __shared__ double sh[TPB];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int w = blockIdx.y, strip = blockIdx.x;
+    const int t = w * 64 + lane;
+    const bool valid = t < K;
+    unsigned long long *sw = sgn + (size_t)w * n;
+    double acc = 0.0;
+    for (int i = strip * (TPB / 64) + wv; i < nrows; i += gridDim.x * (TPB / 64)) {
+        const int p = __builtin_amdgcn_readfirstlane(rows ? rows[i] : i);
+        double h = 0.0, a = 0.0, cpp = 0.0;
+        if (Cfull) {
+            const double *crow = Cfull + (size_t)p * npad;
+            for (int q = 0; q < n; ++q) {
+                const double cq = crow[q];
+                if (q == p) { cpp = cq; continue; }
+                const double tq = tv[q];
+                h += cq * (((sw[q] >> lane) & 1ull) ? tq : -tq);
+                a += fabs(cq) * tq;
+            }
+        } else {
+            for (int k = adj_ptr[p]; k < adj_ptr[p + 1]; ++k) {
+                const int q = adj_col[k];
+                if (q == p) { cpp = cbase[adj_e[k]]; continue; }
+                const double cq = adj_sval[k], tq = tv[q];
+                h += cq * (((sw[q] >> lane) & 1ull) ? tq : -tq);
+                a += fabs(cq) * tq;
+            }
+        }
+        const unsigned long long wp = sw[p];
+        const double tp = tv[p];
+        const double xp = ((wp >> lane) & 1ull) ? tp : -tp;
+        if (!rows) {
+            acc += xp * (h + cpp * xp);
+        } else {
+            const double delta = -4.0 * xp * h, tau = 0x1p-40 * 4.0 * tp * a;
+            const unsigned long long fl = __ballot(valid && delta < -tau);
+            if (lane == 0 && fl) { sw[p] = wp ^ fl; flag[0] = 1; }
+        }
+    }
+    if (rows) return;
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    if (wv == 0 && valid) part[(size_t)t * RND_STRIPS + strip] = ((sh[lane] + sh[64 + lane]) + sh[128 + lane]) + sh[192 + lane];
+}
+
+// f[t] (= or +=) sum of the strips' partials of trial t, in strip order
+__global__ __launch_bounds__(TPB) void k_rnd_sum(int K, int nstrip, const double *__restrict__ part, double *__restrict__ f, int first) {
+    const int t = blockIdx.x * TPB + threadIdx.x;
+    if (t >= K) return;
+    double s = 0.0;
+    for (int b = 0; b < nstrip; ++b) s += part[(size_t)t * RND_STRIPS + b];
+    f[t] = first ? s : f[t] + s;
+}
+
+// *best = argmin_t f[t], the lowest index on ties (one workgroup)
+__global__ __launch_bounds__(TPB) void k_rnd_best(int K, const double *__restrict__ f, int *__restrict__ best) {
+    __shared__ double sv[TPB];
+    __shared__ int si[TPB];
+    double v = INFINITY;
+    int idx = K;
+    for (int t = threadIdx.x; t < K; t += TPB)
+        if (f[t] < v || idx == K) { v = f[t]; idx = t; }
+    sv[threadIdx.x] = v; si[threadIdx.x] = idx;
+    __syncthreads();
+    for (int o = TPB / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const double v2 = sv[threadIdx.x + o];
+            const int i2 = si[threadIdx.x + o];
+            if (i2 < K && (si[threadIdx.x] == K || v2 < sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x]))) {
+                sv[threadIdx.x] = v2; si[threadIdx.x] = i2;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *best = si[0];
+}
+
+// applicability (once per context: the constraint data never changes); t of every cone to the device
+int rnd_check(lorads_hip_ctx *c) {
+    RoundScratch &X = c->rnd;
+    if (X.checked) return 0;
+    X.qualifies = false;
+    X.why.clear();
+    X.t_off.assign(c->nb + 1, 0);
+    for (int k = 0; k < c->nb; ++k) X.t_off[k + 1] = X.t_off[k] + c->blk[k].n;
+    std::vector<double> b((size_t)c->m), th((size_t)X.t_off[c->nb], 0.0);
+    if (c->m) HC(hipMemcpyAsync(b.data(), c->b, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
+    HC(hipStreamSynchronize(c->stream));
+    std::vector<int> per_con((size_t)c->m, 0);
+    char msg[256];
+    for (int k = 0; k < c->nb && X.why.empty(); ++k)
+        if (c->blk[k].is_lp) { snprintf(msg, sizeof msg, "block %d is an LP block", k + 1); X.why = msg; }
+    for (int k = 0; k < c->nb && X.why.empty(); ++k) {
+        const Block &B = c->blk[k];
+        if (B.dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); X.why = msg; break; }
+        std::vector<int> ri(B.nrow), ap(B.nrow + 1), ae(B.na), er(B.pa.ne), ec(B.pa.ne);
+        std::vector<double> av(B.na);
+        if (B.nrow) {
+            HC(hipMemcpyAsync(ri.data(), B.row_idx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(ap.data(), B.a_ptr, sizeof(int) * ap.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (B.na) {
+            HC(hipMemcpyAsync(ae.data(), B.a_e, sizeof(int) * ae.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(av.data(), B.a_val, sizeof(double) * av.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (B.pa.ne) {
+            HC(hipMemcpyAsync(er.data(), B.pa.erow, sizeof(int) * er.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(ec.data(), B.pa.ecol, sizeof(int) * ec.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        HC(hipStreamSynchronize(c->stream));
+        std::vector<int> cover((size_t)B.n, 0);
+        for (int i = 0; i < B.nrow && X.why.empty(); ++i) {
+            const int gi = ri[i], cnt = ap[i + 1] - ap[i];
+            per_con[gi] += cnt;
+            if (cnt != 1) { snprintf(msg, sizeof msg, "constraint %d has %d entries on cone %d", gi + 1, cnt, k + 1); X.why = msg; break; }
+            const int e = ae[ap[i]], p = er[e];
+            if (er[e] != ec[e]) { snprintf(msg, sizeof msg, "constraint %d is not on a diagonal", gi + 1); X.why = msg; break; }
+            const double ratio = b[gi] / av[ap[i]];
+            if (!(ratio > 0) || !std::isfinite(ratio)) {
+                snprintf(msg, sizeof msg, "constraint %d has b / a = %g (not positive)", gi + 1, ratio);
+                X.why = msg;
+                break;
+            }
+            cover[p]++;
+            th[X.t_off[k] + p] = std::sqrt(ratio);
+        }
+        for (int p = 0; p < B.n && X.why.empty(); ++p)
+            if (cover[p] != 1) {
+                snprintf(msg, sizeof msg, "diagonal %d of cone %d is fixed by %d constraints", p + 1, k + 1, cover[p]);
+                X.why = msg;
+            }
+    }
+    for (int i = 0; i < c->m && X.why.empty(); ++i)
+        if (per_con[i] != 1) { snprintf(msg, sizeof msg, "constraint %d has %d stored entries", i + 1, per_con[i]); X.why = msg; }
+    if (c->nb == 0 && X.why.empty()) X.why = "no cone";
+    X.qualifies = X.why.empty();
+    if (X.qualifies && upload(&X.t, th)) return 1;
+    X.checked = true;
+    return 0;
+}
+
+// greedy colouring of every cone's off-diagonal graph of C in increasing vertex order (a vertex takes the smallest colour that none
+// of its lower-numbered neighbours holds) and the class-sorted row list (class by class, rows ascending within a class)
+int rnd_colour(lorads_hip_ctx *c) {
+    RoundScratch &X = c->rnd;
+    if (X.coloured) return 0;
+    std::vector<int> all((size_t)X.t_off[c->nb]);
+    X.cls_ptr.assign(c->nb, {});
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        const int n = B.n;
+        std::vector<int> ptr, col;
+        if (B.dense_c) {
+            std::vector<double> cf((size_t)B.npad * B.npad);
+            HC(hipMemcpyAsync(cf.data(), B.Cfull, sizeof(double) * cf.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipStreamSynchronize(c->stream));
+            ptr.assign(n + 1, 0);
+            for (int p = 0; p < n; ++p) {
+                for (int q = 0; q < n; ++q)
+                    if (q != p && cf[(size_t)p * B.npad + q] != 0.0) col.push_back(q);
+                ptr[p + 1] = (int)col.size();
+            }
+        } else {
+            ptr.resize(n + 1);
+            col.resize(B.pu.nslot);
+            HC(hipMemcpyAsync(ptr.data(), B.pu.adj_ptr, sizeof(int) * ptr.size(), hipMemcpyDeviceToHost, c->stream));
+            if (B.pu.nslot) HC(hipMemcpyAsync(col.data(), B.pu.adj_col, sizeof(int) * col.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipStreamSynchronize(c->stream));
+        }
+        std::vector<int> colour((size_t)n, 0), seen;
+        int ncol = 0;
+        for (int p = 0; p < n; ++p) {
+            for (int s = ptr[p]; s < ptr[p + 1]; ++s) {
+                const int q = col[s];
+                if (q < p) { if ((int)seen.size() <= colour[q]) seen.resize(colour[q] + 1, -1); seen[colour[q]] = p; }
+            }
+            int cp = 0;
+            while (cp < (int)seen.size() && seen[cp] == p) ++cp;
+            colour[p] = cp;
+            ncol = std::max(ncol, cp + 1);
+        }
+        std::vector<int> &cp = X.cls_ptr[k];
+        cp.assign(ncol + 1, 0);
+        for (int p = 0; p < n; ++p) cp[colour[p] + 1]++;
+        for (int i = 0; i < ncol; ++i) cp[i + 1] += cp[i];
+        std::vector<int> fill(cp.begin(), cp.end() - 1);
+        for (int p = 0; p < n; ++p) all[X.t_off[k] + fill[colour[p]]++] = p;
+    }
+    if (upload(&X.cls_rows, all)) return 1;
+    X.coloured = true;
+    return 0;
+}
+
+// buffers for K trials (grown on demand, freed with the context)
+int rnd_reserve(lorads_hip_ctx *c, int K) {
+    RoundScratch &X = c->rnd;
+    const int W = (K + 63) / 64;
+    size_t g = 0;
+    for (auto &B : c->blk) g += (size_t)B.rl * K;
+    const size_t words = (size_t)X.t_off[c->nb] * W, part = (size_t)K * RND_STRIPS;
+    if (g > X.g_cap) { hipFree(X.G); X.G = nullptr; X.g_cap = 0; if (dalloc(&X.G, g)) return 1; X.g_cap = g; }
+    if (words > X.sgn_cap) { hipFree(X.sgn); X.sgn = nullptr; X.sgn_cap = 0; if (dalloc(&X.sgn, words)) return 1; X.sgn_cap = words; }
+    if (part > X.part_cap) { hipFree(X.part); X.part = nullptr; X.part_cap = 0; if (dalloc(&X.part, part)) return 1; X.part_cap = part; }
+    if ((size_t)K > X.f_cap) {
+        hipFree(X.f); hipFree(X.f0); X.f = X.f0 = nullptr; X.f_cap = 0;
+        if (dalloc(&X.f, (size_t)K) || dalloc(&X.f0, (size_t)K)) return 1;
+        X.f_cap = (size_t)K;
+    }
+    if (!X.ctl && dalloc(&X.ctl, 4)) return 1;
+    return 0;
+}
+
+// launch one field pass of cone k over nrows rows (rows == null: all of them, evaluation)
+void rnd_field(lorads_hip_ctx *c, int k, int K, const int *rows, int nrows, unsigned long long *sg) {
+    const Block &B = c->blk[k];
+    RoundScratch &X = c->rnd;
+    const int W = (K + 63) / 64;
+    const int strips = rows ? std::max(1, std::min(RND_STRIPS, nblocks_for((size_t)nrows, TPB / 64))) : RND_STRIPS;
+    hipLaunchKernelGGL(k_rnd_field, dim3(strips, W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, (const int *)B.pu.adj_ptr,
+                       (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.adj_sval, (const double *)B.pu.cbase,
+                       (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad, (const double *)(X.t + X.t_off[k]), sg, X.part, X.ctl);
+}
+
+// f (K values) of the current sign words: every cone's field pass, its strips added per trial in cone order
+void rnd_eval(lorads_hip_ctx *c, int K, double *f) {
+    RoundScratch &X = c->rnd;
+    const int W = (K + 63) / 64;
+    for (int k = 0; k < c->nb; ++k) {
+        rnd_field(c, k, K, nullptr, c->blk[k].n, X.sgn + (size_t)X.t_off[k] * W);
+        hipLaunchKernelGGL(k_rnd_sum, dim3(nblocks_for((size_t)K, TPB)), dim3(TPB), 0, c->stream, K, (int)RND_STRIPS,
+                           (const double *)X.part, f, (int)(k == 0));
+    }
+}
+
+} // namespace
+
+extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
+                                    double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds,
+                                    double *hyperplanes) {
+    if (!c || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) || trials < 0 || trials > RND_MAXK || max_rounds < 0 ||
+        (trials > 0 && !obj))
+        return fail_msg("round_pm1: bad argument");
+    if (c->ar || c->sep || c->sx) {
+        fail_msg("round_pm1: sharded contexts (world > 1) cannot be rounded");
+        return 3;
+    }
+    if (rnd_check(c)) return 1;
+    RoundScratch &X = c->rnd;
+    if (!X.qualifies) {
+        fail_msg("round_pm1: the context is not +-1-structured: " + X.why);
+        return 2;
+    }
+    if (trials == 0) return 0;
+    const int K = trials, W = (K + 63) / 64;
+    if (rnd_reserve(c, K) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    const int uv = src == LORADS_HIP_PAIR_UV;
+    // hyperplanes and sign words
+    size_t goff = 0;
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        double *G = X.G + goff;
+        const size_t glen = (size_t)B.rl * K;
+        if (glen) hipLaunchKernelGGL(k_rnd_hyper, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, B.rl, K, k, seed, G);
+        const double *U = (uv ? c->U : c->R) + B.off, *V = (uv ? c->V : c->R) + B.off;
+        const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
+        hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, U, V, uv,
+                           (const double *)G, X.sgn + (size_t)X.t_off[k] * W);
+        goff += glen;
+    }
+    if (hyperplanes && goff) HC(hipMemcpyAsync(hyperplanes, X.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    rnd_eval(c, K, X.f0);
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0, X.ctl + 1);
+    // local search: one host synchronisation per round (the flag decides whether another round runs)
+    int nr = 0;
+    for (int round = 0; round < max_rounds; ++round) {
+        HC(hipMemsetAsync(X.ctl, 0, sizeof(int), c->stream));
+        for (int k = 0; k < c->nb; ++k) {
+            const std::vector<int> &cp = X.cls_ptr[k];
+            for (size_t cl = 0; cl + 1 < cp.size(); ++cl)
+                rnd_field(c, k, K, X.cls_rows + X.t_off[k] + cp[cl], cp[cl + 1] - cp[cl], X.sgn + (size_t)X.t_off[k] * W);
+        }
+        int flag = 0;
+        HC(hipMemcpyAsync(&flag, X.ctl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HC(hipStreamSynchronize(c->stream));
+        nr = round + 1;
+        if (!flag) break;
+    }
+    double *f = X.f0;
+    if (nr > 0) {
+        rnd_eval(c, K, X.f);
+        f = X.f;
+    }
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, X.ctl + 2);
+    int bb[2] = {0, 0};
+    HC(hipMemcpyAsync(bb, X.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    HC(hipMemcpyAsync(obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (obj0) HC(hipMemcpyAsync(obj0, X.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HC(hipStreamSynchronize(c->stream));
+    if (best) *best = bb[1];
+    if (best0) *best0 = bb[0];
+    if (rounds) *rounds = nr;
+    if (sign) { // the best trial's signs, cone after cone
+        const int w = bb[1] / 64, l = bb[1] % 64;
+        std::vector<unsigned long long> words;
+        for (int k = 0; k < c->nb; ++k) {
+            const int n = c->blk[k].n;
+            words.resize((size_t)n);
+            if (n) HC(hipMemcpyAsync(words.data(), X.sgn + (size_t)X.t_off[k] * W + (size_t)w * n, sizeof(unsigned long long) * n,
+                                     hipMemcpyDeviceToHost, c->stream));
+            HC(hipStreamSynchronize(c->stream));
+            for (int p = 0; p < n; ++p) sign[X.t_off[k] + p] = ((words[p] >> l) & 1ull) ? 1 : -1;
+        }
+    }
+    return 0;
+}

@@ -47,6 +47,8 @@ typedef struct {
     int (*alm_step)(lorads_hip_ctx *, double, double, int32_t, double *);
     int (*certificate)(lorads_hip_ctx *, int32_t, double, int32_t, int32_t, double *, double *, double *, double *); /* optional */
     int (*get_slack)(lorads_hip_ctx *, int32_t, int64_t *, int32_t *, int32_t *, double *);                /* optional */
+    int (*round_pm1)(lorads_hip_ctx *, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, int8_t *,
+                     int32_t *, double *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -83,6 +85,12 @@ static int b_cert(void *cx, int src, double tol, double *o, double *lm, double *
 }
 static int b_slack(void *cx, int k, int64_t *nnz, int *row, int *col, double *val) {
     return report(H, H->get_slack(H->ctx, k, nnz, (int32_t *)row, (int32_t *)col, val), "get_slack");
+}
+/* rounding: codes 2 (not +-1-structured) and 3 (sharded) pass through with the library's reason on stderr */
+static int b_round(void *cx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                   int8_t *sign, int *rounds, double *hyp) {
+    return report(H, H->round_pm1(H->ctx, src, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, sign,
+                                  (int32_t *)rounds, hyp), "round_pm1");
 }
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
@@ -144,6 +152,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->certificate) = dlsym(h->dl, "lorads_hip_certificate");
     *(void **)(&h->get_slack) = dlsym(h->dl, "lorads_hip_get_slack");
     if (!h->get_slack) h->certificate = NULL;
+    *(void **)(&h->round_pm1) = dlsym(h->dl, "lorads_hip_round_pm1");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -188,5 +197,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     out->alm_front = b_afront;
     out->alm_step = b_astep;
     if (h->certificate) { out->certificate = b_cert; out->get_slack = b_slack; }
+    if (h->round_pm1) out->round_pm1 = b_round;
     return 0;
 }

@@ -163,6 +163,10 @@ typedef struct lrd_backend {
      * get_slack: S of block blk as lower-triangle triplets; NULL arrays return the count alone. */
     int (*certificate)(void *ctx, int src, double tol, double *out, double *lam_min, double *residual, double *y);
     int (*get_slack)(void *ctx, int blk, int64_t *nnz, int *row, int *col, double *val);
+    /* OPTIONAL: hyperplane rounding + 1-flip local search of a +-1-structured context, read-only on the state (include/lorads_hip.h:
+     * lorads_hip_round_pm1, the same arguments and return codes; values in the backend's terms) */
+    int (*round_pm1)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                     int8_t *sign, int *rounds, double *hyperplanes);
 } lrd_backend;
 #define LRD_CERT_N 10
 
@@ -291,6 +295,38 @@ void lrd_solution_free(lrd_solution *sol);
 /* plain-text file of a solution (a pure function of the struct): "lorads-solution 1", status, pobj, dobj, the certificate, "y m" and
  * m values, then per cone "sdp k n r" and n rows of R, or "lp k n" and n values of x (k: 1-based block of the file); every double %.17g */
 int lrd_solution_write(const char *path, const lrd_solution *sol);
+
+/* ---- rounding of +-1-structured contexts (session.c, rounding.c).  Everything in the file's units: x = sigma o t
+ * is feasible for every sigma (t_p = sqrt(b_i / a_i) of the one constraint a_i X[p,p] = b_i on the diagonal), f = sum_k x_k^T C_k x_k;
+ * the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) <= every f (T_k = sum_p t_p^2, the trace of every feasible X_k). */
+typedef struct {
+    int n, rank;       /* rank: the cone's own current rank (the hyperplanes' dimension) */
+    int8_t *sigma;     /* [n] the best trial's signs after the local search */
+    double *t, *x;     /* [n] t and x = sigma o t */
+    double T;          /* sum_p t_p^2 */
+    double lam_min;    /* lambda_min(S_k) (NaN without a bound) */
+    double *G;         /* rank x trials (row-major), only when asked for (else NULL) */
+} lrd_rounding_cone;
+typedef struct {
+    int nblk, trials, max_rounds, rounds;
+    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where R came from */
+    uint64_t seed;
+    double scale;       /* scaleObjHis the backend's values were divided by */
+    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
+    double f_best, f_best0;
+    double *obj, *obj0; /* [trials] f after / before the local search */
+    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
+    double tol;         /* Lanczos tolerance of lambda_min */
+    lrd_rounding_cone *cone; /* [nblk], file order */
+} lrd_rounding;
+/* trials = 0: applicability alone (*out stays NULL).  Returns 2 when the context does not qualify or the table lacks the slot, 3 when
+ * it is sharded.  with_hyperplanes: also fill every cone's G. */
+int lrd_session_round(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, lrd_rounding **out);
+int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_hyperplanes,
+                         lrd_rounding **out);
+void lrd_rounding_free(lrd_rounding *r);
+/* plain-text file, a pure function of the struct (rounding.c) */
+int lrd_rounding_write(const char *path, const lrd_rounding *r);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

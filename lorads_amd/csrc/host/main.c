@@ -20,6 +20,7 @@ lrd_problem *lrd_session_problem(lrd_session *s);
 lrd_params *lrd_session_params(lrd_session *s);
 void lrd_session_close(lrd_session *s);
 int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libpath, lrd_backend *out);
+int lrd_session_round(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, lrd_rounding **out);
 
 int main(int argc, char **argv) {
     if (argc < 2) {
@@ -29,6 +30,9 @@ int main(int argc, char **argv) {
     lrd_session *s = lrd_session_open(argv[1]);
     if (!s) return 1;
     const char *solution_file = NULL; /* ours, not the reference's: taken before the parameter block sees the options */
+    const char *round_file = NULL;    /* hyperplane rounding of a +-1-structured problem (ours as well) */
+    int round_trials = 0, round_ls = 100;
+    unsigned long long round_seed = 0;
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -36,6 +40,19 @@ int main(int argc, char **argv) {
         }
         if (!strcmp(argv[i], "--solutionFile")) {
             solution_file = argv[i + 1];
+            continue;
+        }
+        if (!strcmp(argv[i], "--roundFile")) { round_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--roundTrials") || !strcmp(argv[i], "--roundSeed") || !strcmp(argv[i], "--roundLocalSearch")) {
+            char *end = NULL;
+            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
+            if (!end || *end || argv[i + 1][0] == '-' || (argv[i][7] != 'S' && v > 65536)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                return 2;
+            }
+            if (argv[i][7] == 'T') round_trials = (int)v;
+            else if (argv[i][7] == 'S') round_seed = v;
+            else round_ls = (int)v;
             continue;
         }
         if (strncmp(argv[i], "--", 2) || lrd_session_set_param(s, argv[i] + 2, argv[i + 1])) {
@@ -55,6 +72,15 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (lrd_session_attach(s, &be)) return 1;
+    if (round_trials > 0) { /* applicability before any solving */
+        lrd_rounding *none = NULL;
+        const int rrc = lrd_session_round(s, 0, round_seed, round_ls, 0.0, &none);
+        if (rrc) {
+            fprintf(stderr, "lorads: --roundTrials needs a +-1-structured problem (see above); nothing was solved\n");
+            lrd_session_close(s);
+            return 2;
+        }
+    }
     const int rc = lrd_session_solve(s);
     if (rc != 0) {
         fprintf(stderr, "lorads: the solve failed (code %d): a backend call reported an error\n", rc);
@@ -93,6 +119,22 @@ int main(int argc, char **argv) {
         printf("\t err4 lambda_min(S) rel.         : %.6e\n\t err5 gap rel.                   : %.6e\n", x->err4, x->err5);
         printf("\t err6 <X, S> rel.                : %.6e\n", x->err6);
         lrd_solution_free(x);
+    }
+    if (round_trials > 0) {
+        lrd_rounding *x = NULL;
+        if (lrd_session_round(s, round_trials, (uint64_t)round_seed, round_ls, 1e-8, &x) ||
+            (round_file && lrd_rounding_write(round_file, x))) {
+            fprintf(stderr, "lorads: the rounding failed%s%s\n", round_file ? " or cannot write " : "", round_file ? round_file : "");
+            lrd_rounding_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Hyperplane rounding (%d trials, seed %llu, %d local-search rounds%s%s):\n", x->trials, round_seed, x->rounds,
+               round_file ? ", " : "", round_file ? round_file : "");
+        printf("\t best trial                      : %d (before the local search: %d)\n", x->best, x->best0);
+        printf("\t f = x^T C x before local search : %.10e\n\t f = x^T C x after local search  : %.10e\n", x->f_best0, x->f_best);
+        printf("\t dual bound d                    : %.10e\n\t gap (f - d) / max(1, |d|)       : %.6e\n", x->bound, x->gap);
+        lrd_rounding_free(x);
     }
     lrd_session_close(s);
     return 0;

@@ -60,6 +60,8 @@ class BackendStruct(C.Structure):
         ("alm_step", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, _dp)),
         ("certificate", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp)),
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
+        ("round_pm1", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
+                                  C.POINTER(C.c_int8), _ip, _dp)),
     ]
 
 
@@ -638,6 +640,53 @@ class Session:
             _check(self.lib.lrd_solution_write(os.fsencode(path), ptr), "solution_write")
         finally:
             self.lib.lrd_solution_free(ptr)
+
+    def _round_ptr(self, trials, seed, local_search_rounds, tol, hyperplanes):
+        from .rounding import RoundingStruct
+        ptr = C.POINTER(RoundingStruct)()
+        self.lib.lrd_session_round_ex.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
+                                                  C.POINTER(C.POINTER(RoundingStruct))]
+        self.lib.lrd_rounding_free.argtypes = [C.POINTER(RoundingStruct)]
+        rc = self.lib.lrd_session_round_ex(self.h, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds), float(tol),
+                                           1 if hyperplanes else 0, C.byref(ptr))
+        if rc == 2:
+            msg = None
+            if self.be is not None and self.be.name == "hip-gfx950":
+                lib, _ = self._hip()
+                lib.lorads_hip_last_error.restype = C.c_char_p
+                msg = lib.lorads_hip_last_error()
+            raise NotImplementedError("the problem cannot be rounded: it is not +-1-structured (no LP block; every constraint "
+                                      "a_i X[p,p] = b_i with b_i / a_i > 0, one per diagonal) or the %s backend cannot round%s"
+                                      % (self.be.name if self.be else "attached", (": " + msg.decode()) if msg else ""))
+        if rc == 3:
+            raise NotImplementedError("rounding the solution of a sharded deal (world > 1) is not supported")
+        _check(rc, "round")
+        return ptr
+
+    def round_pm1(self, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, hyperplanes=False):
+        """Goemans-Williamson hyperplane rounding of the current point with a 1-flip local search, on the device
+        (lorads_amd.rounding.Rounding, file units): per trial f = x^T C x before and after the search, the best trial's signs and
+        x = sigma o t per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) at Lanczos tolerance tol (tol <= 0:
+        NaN).  trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
+        from .rounding import Rounding
+        if trials == 0:
+            self._round_ptr(0, seed, local_search_rounds, tol, False)
+            return None
+        ptr = self._round_ptr(trials, seed, local_search_rounds, tol, hyperplanes)
+        try:
+            return Rounding.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_rounding_free(ptr)
+
+    def write_rounding(self, path, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
+        """the rounding file of the command line's --roundFile (the same C writer: the same bytes)"""
+        from .rounding import RoundingStruct
+        ptr = self._round_ptr(trials, seed, local_search_rounds, tol, False)
+        try:
+            self.lib.lrd_rounding_write.argtypes = [C.c_char_p, C.POINTER(RoundingStruct)]
+            _check(self.lib.lrd_rounding_write(os.fsencode(path), ptr), "rounding_write")
+        finally:
+            self.lib.lrd_rounding_free(ptr)
 
     def dual_infeasibility(self):
         """DIMACS error 2 of the current multipliers, data/lorads_solver.c:1007-1037 (-1: slot missing)"""

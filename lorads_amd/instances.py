@@ -75,6 +75,51 @@ def maxcut(n, n_edges, seed, weights=None):
     return dict(m=n, blocks=[n], b=np.ones(n), entries=ent)
 
 
+def weighted_maxcut(n, n_edges, seed):
+    """Max-Cut with edge weights drawn from [0.5, 2) (not dyadic: f is compared to a relative bound)"""
+    return maxcut(n, n_edges, seed, weights=lambda rng, k: rng.uniform(0.5, 2.0, k))
+
+
+def scaled_pm1(n, n_edges, seed):
+    """+-1 QUBO relaxation in a scaled form: min <C, X> s.t. a_i X_ii = b_i with a_i, b_i of mixed signs and b_i / a_i > 0 (so
+    X_ii = b_i / a_i, every x = sigma o sqrt(b / a) is feasible); C has off-diagonal entries of both signs and a diagonal."""
+    rng = np.random.default_rng(seed)
+    edges = _rand_edges(n, n_edges, rng)
+    w = rng.uniform(-1.0, 1.0, len(edges))
+    ent = []
+    for i in range(n):
+        ent.append((0, 1, i + 1, i + 1, float(rng.uniform(-0.5, 0.5))))
+    for (i, j), wij in zip(edges.tolist(), w.tolist()):
+        ent.append((0, 1, i + 1, j + 1, wij))
+    sgn = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    a = sgn * rng.uniform(0.5, 2.0, n)
+    b = sgn * rng.uniform(0.5, 2.0, n)
+    for i in range(n):
+        ent.append((i + 1, 1, i + 1, i + 1, float(a[i])))
+    return dict(m=n, blocks=[n], b=b, entries=ent)
+
+
+def dense_maxcut(n, n_edges, seed):
+    """Max-Cut on a dense graph: more than 0.1 n (n + 1) / 2 stored entries of C, so the solver keeps C dense"""
+    assert n_edges + n > 0.1 * n * (n + 1) / 2
+    return maxcut(n, n_edges, seed)
+
+
+def maxcut_uncovered(n, n_edges, seed):
+    """near miss of the +-1 structure: Max-Cut whose last diagonal is fixed by no constraint"""
+    p = maxcut(n, n_edges, seed)
+    ent = [e for e in p["entries"] if e[0] != n]
+    return dict(m=n - 1, blocks=[n], b=np.ones(n - 1), entries=ent)
+
+
+def maxcut_negative_ratio(n, n_edges, seed):
+    """near miss of the +-1 structure: Max-Cut whose first constraint reads X_11 = -1 (b / a < 0)"""
+    p = maxcut(n, n_edges, seed)
+    b = np.ones(n)
+    b[0] = -1.0
+    return dict(m=n, blocks=[n], b=b, entries=p["entries"])
+
+
 def theta(n, n_edges, seed):
     """Lovasz theta: max <J, X> s.t. tr X = 1, X_ij = 0 on edges.  m = n_edges + 1."""
     rng = np.random.default_rng(seed)
@@ -362,6 +407,12 @@ NAMED = {
     "sdplp40": lambda: sdp_lp(40, 90, 12, 4001),
     "sdpslack30": lambda: sdp_lp(30, 60, 0, 4002),
     "coupledlp": lambda: coupled_lp(2, 40, 24, 18, 5100),   # coupled cones + LP columns across rows (general path)         # slacks only: every LP column alone in its row (one level)
+    # +-1-structured contexts of the rounding and two near misses
+    "wmaxcut150": lambda: weighted_maxcut(150, 400, 151),
+    "scaledpm1_120": lambda: scaled_pm1(120, 300, 121),
+    "densemaxcut120": lambda: dense_maxcut(120, 2000, 122),
+    "maxcut_uncovered60": lambda: maxcut_uncovered(60, 120, 123),
+    "maxcut_negratio60": lambda: maxcut_negative_ratio(60, 120, 124),
     # timing / log-level instances
     "maxcut800": lambda: maxcut(800, 19176, 8001),         # cfg2 G1-like
     "maxcut4000": lambda: maxcut(4000, 24000, 4000),       # cfg3a-mini
