@@ -75,6 +75,10 @@ int lorads_hip_lbfgs_team_stats(lorads_hip_ctx *ctx, int64_t stats[4]);
  * per solve -- are not counted): bench.py divides the difference over a timed region by its steps */
 int lorads_hip_launch_count(lorads_hip_ctx *ctx, int64_t *n);
 
+/* device and pinned memory this process's contexts hold now:
+ * stats = {device allocations, device bytes, pinned allocations, pinned bytes} */
+int lorads_hip_memory_stats(int64_t stats[4]);
+
 #ifdef __cplusplus
 }
 #endif

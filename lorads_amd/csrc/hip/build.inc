@@ -75,14 +75,14 @@ void build_transpose(int ne, int nrow, const int *a_ptr, const std::vector<int> 
         }
 }
 
-int upload_pattern(Pattern &P, const HostPattern &hp, const std::vector<double> *cbase) {
+int upload_pattern(DevPool &M, Pattern &P, const HostPattern &hp, const std::vector<double> *cbase) {
     P.ne = (int)hp.erow.size();
-    if (upload(&P.erow, hp.erow) || upload(&P.ecol, hp.ecol) || upload(&P.e_ptr, hp.e_ptr) || upload(&P.e_con, hp.e_con) ||
-        upload(&P.e_val, hp.e_val) || upload(&P.adj_ptr, hp.adj_ptr) || upload(&P.adj_col, hp.adj_col) ||
-        upload(&P.adj_e, hp.adj_e))
+    if (M.upload(&P.erow, hp.erow) || M.upload(&P.ecol, hp.ecol) || M.upload(&P.e_ptr, hp.e_ptr) || M.upload(&P.e_con, hp.e_con) ||
+        M.upload(&P.e_val, hp.e_val) || M.upload(&P.adj_ptr, hp.adj_ptr) || M.upload(&P.adj_col, hp.adj_col) ||
+        M.upload(&P.adj_e, hp.adj_e))
         return 1;
-    if (dalloc(&P.S, (size_t)P.ne)) return 1;
-    if (cbase && upload(&P.cbase, *cbase)) return 1;
+    if (M.alloc(&P.S, (size_t)P.ne)) return 1;
+    if (cbase && M.upload(&P.cbase, *cbase)) return 1;
     { // one (entry, constraint) pair per constraint marked as the constraint's owner (see WArgs::lambda_out)
         int nrow = 0;
         for (int i : hp.e_con) nrow = std::max(nrow, i + 1);
@@ -92,7 +92,7 @@ int upload_pattern(Pattern &P, const HostPattern &hp, const std::vector<double> 
         for (size_t t = 0; t < own.size(); ++t)
             if (!seen[own[t]]) { seen[own[t]] = 1; own[t] |= (int)0x80000000; ++marked; }
         P.n_owned = marked;
-        if (upload(&P.e_con_own, own)) return 1;
+        if (M.upload(&P.e_con_own, own)) return 1;
     }
     // per slot: is the entry's coefficient static (no constraint touches it: C alone) or does it change with the weights
     P.nslot = (int)hp.adj_e.size();
@@ -103,12 +103,12 @@ int upload_pattern(Pattern &P, const HostPattern &hp, const std::vector<double> 
         sval[k] = cbase ? (*cbase)[e] : 0.0; // (the objective's part of every slot: read for static slots, and by the on-the-fly front of Max-Cut-type cones for the others too)
         dyn[k] = hp.e_ptr[e + 1] > hp.e_ptr[e] ? e : -1;
     }
-    if (upload(&P.adj_dyn, dyn) || upload(&P.adj_sval, sval)) return 1;
+    if (M.upload(&P.adj_dyn, dyn) || M.upload(&P.adj_sval, sval)) return 1;
     return 0;
 }
 
 // G = A A^T over pattern entries, when sum_i nnz_i^2 stays small
-int build_gram(Block &B, const lorads_hip_block &hb, const std::vector<int> &a_e, int ne) {
+int build_gram(DevPool &M, Block &B, const lorads_hip_block &hb, const std::vector<int> &a_e, int ne) {
     double tot = 0;
     for (int i = 0; i < hb.nrow; ++i) { double k = hb.a_ptr[i + 1] - hb.a_ptr[i]; tot += k * k; }
     if (tot > std::max(64.0 * B.na, 1.0e6) || tot > 2.0e8) return 0;
@@ -130,7 +130,7 @@ int build_gram(Block &B, const lorads_hip_block &hb, const std::vector<int> &a_e
         g_ptr[(int)(tri[k].first >> 32) + 1]++;
     }
     for (int e = 0; e < ne; ++e) g_ptr[e + 1] += g_ptr[e];
-    if (upload(&B.g_ptr, g_ptr) || upload(&B.g_col, g_col) || upload(&B.g_val, g_val)) return 1;
+    if (M.upload(&B.g_ptr, g_ptr) || M.upload(&B.g_col, g_col) || M.upload(&B.g_val, g_val)) return 1;
     B.has_gram = true;
     return 0;
 }
@@ -189,6 +189,7 @@ int make_pattern(lorads_hip_ctx *c, const std::vector<std::pair<int, int>> &pos,
 }
 int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     StageTimer tm;
+    DevPool &M = c->mem;
     // Dense constraint matrices first (the reference's rule for a dense coefficient, data/lorads_sdp_data.c:820): they leave the
     // sparse structures -- the rest of this function sees their rows of the constraint CSR empty -- and are stored full.
     lorads_hip_block hbf = hb_in;
@@ -229,7 +230,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
             f_ptr.push_back((int)f_row.size());
         }
         hbf.a_ptr = f_ptr.data(); hbf.a_row = f_row.data(); hbf.a_col = f_col.data(); hbf.a_val = f_val.data();
-        if (upload(&B.d_con, dcon) || upload(&B.Adense, ad) || dalloc(&B.Sfull, (size_t)npad * npad) || dalloc(&B.d_mu, dcon.size())) return 1;
+        if (M.upload(&B.d_con, dcon) || M.upload(&B.Adense, ad) || M.alloc(&B.Sfull, (size_t)npad * npad) || M.alloc(&B.d_mu, dcon.size())) return 1;
         B.dense_a = true;
         B.nd = (int)dcon.size();
         B.d_con_h = dcon;
@@ -253,7 +254,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     std::vector<int> a_e;
     HostPattern hpA;
     if (make_pattern(c, posA, B.n, hb.nrow, hb.a_ptr, B.na, hb.a_val, uniqA, a_e, hpA, tm, "A-pattern")) return 1;
-    if (upload_pattern(B.pa, hpA, nullptr)) return 1;
+    if (upload_pattern(M, B.pa, hpA, nullptr)) return 1;
     tm.lap("upload A-pattern");
     // dense objective (the reference's rule for a dense coefficient, lorads_sdp_data.c:818-821)
     B.dense_c = !hb.is_lp && (double)B.nc > 0.1 * (double)((int64_t)B.n * (B.n + 1) / 2);
@@ -272,7 +273,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                 cf[(size_t)hb.c_row[t] * B.npad + hb.c_col[t]] += hb.c_val[t];
                 if (hb.c_row[t] != hb.c_col[t]) cf[(size_t)hb.c_col[t] * B.npad + hb.c_row[t]] += hb.c_val[t];
             }
-            if (upload(&B.Cfull, cf)) return 1;
+            if (M.upload(&B.Cfull, cf)) return 1;
         }
     }
     // union pattern C u A (A only when C is dense: the dense part is added by k_dense_cx)
@@ -284,7 +285,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     if (make_pattern(c, posU, B.n, hb.nrow, hb.a_ptr, B.na, hb.a_val, uniqU, u_idx, hpU, tm, "union pattern")) return 1;
     std::vector<double> cbase(uniqU.size(), 0.0);
     for (int t = 0; t < B.nc && !B.dense_c; ++t) cbase[u_idx[B.na + t]] += hb.c_val[t];
-    if (upload_pattern(B.pu, hpU, &cbase)) return 1;
+    if (upload_pattern(M, B.pu, hpU, &cbase)) return 1;
     tm.lap("upload union pattern");
     { // constraint -> its entries of the union pattern, where every touched entry belongs to one constraint (Block::sv_direct)
         bool direct = hb.nrow > 0 && !B.dense_c && !hpU.e_ptr.empty();
@@ -302,7 +303,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                     se[k] = (int)e;
                     sa[k] = hpU.e_val[t];
                 }
-            if (upload(&B.sv_ptr, cnt) || upload(&B.sv_e, se) || upload(&B.sv_a, sa)) return 1;
+            if (M.upload(&B.sv_ptr, cnt) || M.upload(&B.sv_e, se) || M.upload(&B.sv_a, sa)) return 1;
             // (entries no constraint touches are never written by that path and never read through Pattern::adj_dyn; they hold C all the same)
             HC(hipMemcpy(B.pu.S, B.pu.cbase, sizeof(double) * (size_t)B.pu.ne, hipMemcpyDeviceToDevice));
         }
@@ -314,10 +315,10 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     for (int i = 0; i < hb.nrow && B.row_idx_identity; ++i) B.row_idx_identity = hb.row_idx[i] == i;
     std::vector<double> v_aval(hb.a_val, hb.a_val + B.na), v_cval(hb.c_val, hb.c_val + B.nc);
     std::vector<int> v_crow(hb.c_row, hb.c_row + B.nc), v_ccol(hb.c_col, hb.c_col + B.nc);
-    if (upload(&B.row_idx, v_rowidx) || upload(&B.a_ptr, v_aptr) || upload(&B.a_e, a_e) || upload(&B.a_val, v_aval) ||
-        upload(&B.c_row, v_crow) || upload(&B.c_col, v_ccol) || upload(&B.c_val, v_cval))
+    if (M.upload(&B.row_idx, v_rowidx) || M.upload(&B.a_ptr, v_aptr) || M.upload(&B.a_e, a_e) || M.upload(&B.a_val, v_aval) ||
+        M.upload(&B.c_row, v_crow) || M.upload(&B.c_col, v_ccol) || M.upload(&B.c_val, v_cval))
         return 1;
-    if (dalloc(&B.T, (size_t)B.pa.ne) || dalloc(&B.T2, (size_t)B.pa.ne) || dalloc(&B.cv, (size_t)B.nrow) || dalloc(&B.wtmp, (size_t)B.nrow)) return 1;
+    if (M.alloc(&B.T, (size_t)B.pa.ne) || M.alloc(&B.T2, (size_t)B.pa.ne) || M.alloc(&B.cv, (size_t)B.nrow) || M.alloc(&B.wtmp, (size_t)B.nrow)) return 1;
     HC(hipMemset(B.cv, 0, sizeof(double) * (size_t)std::max(B.nrow, 1)));
     // Max-Cut fast path
     bool diag = B.nrow > 0 && !B.dense_a; // (a cone with dense constraint matrices takes the general path everywhere)
@@ -329,12 +330,12 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
         gd[hb.a_row[t]] += hb.a_val[t] * hb.a_val[t];
     }
     B.diag_only = diag;
-    if (diag && upload(&B.gdiag, gd)) return 1;
+    if (diag && M.upload(&B.gdiag, gd)) return 1;
     if (diag) { // per constraint (row, coefficient) and the two row-dot vectors of constr_by_recurrence
         std::vector<int> drow(hb.nrow);
         std::vector<double> dav(hb.nrow);
         for (int i = 0; i < hb.nrow; ++i) { drow[i] = hb.a_row[hb.a_ptr[i]]; dav[i] = hb.a_val[hb.a_ptr[i]]; }
-        if (upload(&B.diag_row, drow) || upload(&B.diag_a, dav) || dalloc(&B.w_uv, (size_t)B.n) || dalloc(&B.w_op, (size_t)B.n)) return 1;
+        if (M.upload(&B.diag_row, drow) || M.upload(&B.diag_a, dav) || M.alloc(&B.w_uv, (size_t)B.n) || M.alloc(&B.w_op, (size_t)B.n)) return 1;
         { // row -> its constraints in fixed width (k_eval_diag); Max-Cut: exactly one per row
             std::vector<int> cntr(B.n, 0);
             for (int i = 0; i < hb.nrow; ++i) cntr[drow[i]]++;
@@ -343,7 +344,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
             if (w <= 8) {
                 std::vector<int> rc((size_t)B.n * w, -1), fillr(B.n, 0);
                 for (int i = 0; i < hb.nrow; ++i) rc[(size_t)drow[i] * w + fillr[drow[i]]++] = i;
-                if (upload(&B.rc_con, rc)) return 1;
+                if (M.upload(&B.rc_con, rc)) return 1;
                 B.rc_w = w;
             }
         }
@@ -353,7 +354,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     if (single_entry) {
         std::vector<double> gev((size_t)B.pa.ne, 0.0);
         for (int i = 0; i < hb.nrow; ++i) gev[a_e[hb.a_ptr[i]]] += hb.a_val[hb.a_ptr[i]] * hb.a_val[hb.a_ptr[i]];
-        if (upload(&B.gentry, gev)) return 1;
+        if (M.upload(&B.gentry, gev)) return 1;
         B.entry_only = true;
         // two-colouring of the entry graph (matrix completion: left factor rows / right factor rows); colour 0 = the side that forms
         // the pair dots, isolated rows included.  Not bipartite (an odd cycle): the one-kernel form stays.
@@ -378,14 +379,14 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
             std::vector<int> rows[2];
             for (int p = 0; p < B.n; ++p) rows[colour[p]].push_back(p);
             if (!rows[1].empty()) {
-                if (upload(&B.bip_rows[0], rows[0]) || upload(&B.bip_rows[1], rows[1]) || dalloc(&B.bip_we, (size_t)std::max(B.pa.ne, 1))) return 1;
+                if (M.upload(&B.bip_rows[0], rows[0]) || M.upload(&B.bip_rows[1], rows[1]) || M.alloc(&B.bip_we, (size_t)std::max(B.pa.ne, 1))) return 1;
                 B.bip_n[0] = (int)rows[0].size();
                 B.bip_n[1] = (int)rows[1].size();
             }
         }
     }
     tm.lap("operator kind (diag / single entry / colouring)");
-    if (!diag && !B.dense_a && build_gram(B, hb, a_e, B.pa.ne)) return 1;
+    if (!diag && !B.dense_a && build_gram(M, B, hb, a_e, B.pa.ne)) return 1;
     tm.lap("Gram");
     // Constraint-wise operator (k_cw + k_spmm<CW>): worthwhile when there are enough constraints to fill the device
     // with one wavefront each and none of them is so large that a single wavefront would crawl through it.
@@ -445,7 +446,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                         if (k < ptr[i + 1]) { ecol[w] = col[k]; econ[w] = con[k]; eav[w] = av[k]; }
                         else ecol[w] = i; // padding: the row itself, coefficient 0
                     }
-                if (upload(&B.cell_col, ecol) || upload(&B.cell_con, econ) || upload(&B.cell_a, eav)) return 1;
+                if (M.upload(&B.cell_col, ecol) || M.upload(&B.cell_con, econ) || M.upload(&B.cell_a, eav)) return 1;
                 B.cell_w = ew;
             }
             if (B.cell_w && !B.dense_c && !getenv("LORADS_NO_FRONT_CW_DATA")) {
@@ -472,8 +473,8 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                     for (int k = 0; k < ptr[B.n]; ++k) dstc[k] = con[k] * csw + fillc[con[k]]++;
                     for (int i = 0; i < B.n; ++i)
                         for (int sl = 0; sl < B.cell_w && ptr[i] + sl < ptr[i + 1]; ++sl) dste[(size_t)i * B.cell_w + sl] = dstc[ptr[i] + sl];
-                    if (upload(&B.fc_ptr, hpC.adj_ptr) || upload(&B.fc_col, hpC.adj_col) || upload(&B.fc_val, fval) ||
-                        upload(&B.cadj_dst, dstc) || upload(&B.cell_dst, dste) || dalloc(&B.w_contrib, (size_t)hb.nrow * csw))
+                    if (M.upload(&B.fc_ptr, hpC.adj_ptr) || M.upload(&B.fc_col, hpC.adj_col) || M.upload(&B.fc_val, fval) ||
+                        M.upload(&B.cadj_dst, dstc) || M.upload(&B.cell_dst, dste) || M.alloc(&B.w_contrib, (size_t)hb.nrow * csw))
                         return 1;
                     HC(hipMemset(B.w_contrib, 0, sizeof(double) * std::max<size_t>((size_t)hb.nrow * csw, 1)));
                     B.cs_w = csw;
@@ -481,9 +482,9 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                     B.front_cw = true;
                 }
             }
-            if (upload(&B.ca_row, car) || upload(&B.ca_col, cac) || upload(&B.ca_val, cav) ||
-                upload(&B.cadj_ptr, ptr) || upload(&B.cadj_col, col) || upload(&B.cadj_con, con) || upload(&B.cadj_a, av) ||
-                dalloc(&B.w_uv, (size_t)B.nrow) || dalloc(&B.w_op, (size_t)B.nrow) || dalloc(&B.pu.S2, (size_t)2 * B.pu.ne))
+            if (M.upload(&B.ca_row, car) || M.upload(&B.ca_col, cac) || M.upload(&B.ca_val, cav) ||
+                M.upload(&B.cadj_ptr, ptr) || M.upload(&B.cadj_col, col) || M.upload(&B.cadj_con, con) || M.upload(&B.cadj_a, av) ||
+                M.alloc(&B.w_uv, (size_t)B.nrow) || M.alloc(&B.w_op, (size_t)B.nrow) || M.alloc(&B.pu.S2, (size_t)2 * B.pu.ne))
                 return 1;
             B.cadj_ptr_host_n = ptr[B.n];
             B.use_cw = true;
@@ -528,9 +529,9 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
         for (int l = 0; l < nlev; ++l) lptr[l + 1] += lptr[l];
         std::vector<int> lf(lptr.begin(), lptr.end() - 1);
         for (int j = 0; j < n; ++j) lcols[lf[lvl[j]]++] = j;
-        if (upload(&B.lp_ptr, ptr) || upload(&B.lp_grow, grow) || upload(&B.lp_a, av) || upload(&B.lp_nrm2sq, nrm) ||
-            upload(&B.lp_cobj, cobj) || upload(&B.lp_lvl_ptr, lptr) || upload(&B.lp_lvl_cols, lcols) ||
-            dalloc(&B.lp_cv, (size_t)B.na))
+        if (M.upload(&B.lp_ptr, ptr) || M.upload(&B.lp_grow, grow) || M.upload(&B.lp_a, av) || M.upload(&B.lp_nrm2sq, nrm) ||
+            M.upload(&B.lp_cobj, cobj) || M.upload(&B.lp_lvl_ptr, lptr) || M.upload(&B.lp_lvl_cols, lcols) ||
+            M.alloc(&B.lp_cv, (size_t)B.na))
             return 1;
         HC(hipMemset(B.lp_cv, 0, sizeof(double) * (size_t)std::max(B.na, 1)));
         B.is_lp = true;
@@ -553,7 +554,7 @@ inline int pad_rows(int n) { return (n + 31) & ~31; }
 // mechanism of the odd ranks' padding column; the caller sees the cone's own rank: Block::rl).  data/lorads_solver.c:290-319,
 // 806-906 keep per-cone ranks; what is computed on the extra columns is exact zeros.  LORADS_COMMON_RANK=0: each cone its own.
 void common_rank(lorads_hip_ctx *c) {
-    if (!c->merged_ok || c->nb < 2 || (getenv("LORADS_COMMON_RANK") && getenv("LORADS_COMMON_RANK")[0] == '0')) return;
+    if (!c->merged_ok || c->nb < 2 || !env_on("LORADS_COMMON_RANK")) return;
     int rmax = 0;
     for (auto &B : c->blk) rmax = std::max(rmax, B.r);
     for (auto &B : c->blk) B.r = rmax;
@@ -567,20 +568,21 @@ int alloc_factors(lorads_hip_ctx *c) {
         block_bytes(B);
     }
     size_t n = c->all_elem;
+    DevPool &M = c->factor_mem;
     double **arrs[] = {&c->R, &c->U, &c->V, &c->G, &c->cr, &c->cp, &c->cQ, &c->rhs, &c->Dtmp};
     for (auto a : arrs) {
-        if (dalloc(a, n)) return 1;
+        if (M.alloc(a, n)) return 1;
         HC(hipMemset(*a, 0, sizeof(double) * std::max<size_t>(n, 1)));
     }
     for (auto &B : c->blk)
-        if ((B.dense_c || B.dense_a) && (dalloc(&B.Wd, (size_t)B.n * B.r) || dalloc(&B.Wpart, (size_t)std::max(1, B.ksplit_b) * B.n * B.r))) return 1;
+        if ((B.dense_c || B.dense_a) && (M.alloc(&B.Wd, (size_t)B.n * B.r) || M.alloc(&B.Wpart, (size_t)std::max(1, B.ksplit_b) * B.n * B.r))) return 1;
     for (auto &B : c->blk) {
         B.wj_for = nullptr;
-        if (B.dense_a && (double)B.nd * B.n * B.r * 8.0 <= 8e9 && (dalloc(&B.Wj, (size_t)B.nd * B.n * B.r) || (B.dense_c && dalloc(&B.Wc, (size_t)B.n * B.r)))) return 1;
+        if (B.dense_a && (double)B.nd * B.n * B.r * 8.0 <= 8e9 && (M.alloc(&B.Wj, (size_t)B.nd * B.n * B.r) || (B.dense_c && M.alloc(&B.Wc, (size_t)B.n * B.r)))) return 1;
     }
     c->ring.resize(c->L);
     for (auto &nd : c->ring) {
-        if (dalloc(&nd.s, n) || dalloc(&nd.y, n)) return 1;
+        if (M.alloc(&nd.s, n) || M.alloc(&nd.y, n)) return 1;
         HC(hipMemset(nd.s, 0, sizeof(double) * std::max<size_t>(n, 1)));
         HC(hipMemset(nd.y, 0, sizeof(double) * std::max<size_t>(n, 1)));
     }
@@ -649,14 +651,13 @@ int build_merged(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     // one constrVal array: the cones' compact vectors are consecutive pieces of the merged one
     size_t o = 0;
     for (auto &B : c->blk) {
-        hipFree(B.cv);
+        c->mem.free(B.cv);
         B.cv = c->merged.cv + o;
-        B.cv_borrowed = true;
         o += (size_t)B.nrow;
     }
-    if (upload(&c->seg_row0, c->seg_row0_h) || dalloc(&c->phase_done, (size_t)2)) return 1;
+    if (c->mem.upload(&c->seg_row0, c->seg_row0_h) || c->mem.alloc(&c->phase_done, (size_t)2)) return 1;
     HC(hipMemset(c->phase_done, 0, 2 * sizeof(int)));
-    if (dalloc(&c->seg_rr_alt, (size_t)2 * std::max(c->nb, 1))) return 1;
+    if (c->mem.alloc(&c->seg_rr_alt, (size_t)2 * std::max(c->nb, 1))) return 1;
     HC(hipMemset(c->seg_rr_alt, 0, sizeof(double) * 2 * (size_t)std::max(c->nb, 1)));
     c->merged_ok = true;
     return 0;
@@ -680,26 +681,24 @@ void refresh_merged(lorads_hip_ctx *c) {
         vt0.push_back((int)vt_seg.size());
     }
     if (vt_seg.size() > (size_t)c->maxpart) return;
-    hipFree(c->seg_vt0); hipFree(c->seg_vt_seg); hipFree(c->seg_vt_e0);
-    c->seg_vt0 = c->seg_vt_seg = nullptr; c->seg_vt_e0 = nullptr;
-    if (upload(&c->seg_vt0, vt0) || upload(&c->seg_vt_seg, vt_seg) || upload(&c->seg_vt_e0, vt_e0)) return;
+    DevPool &M = c->mem;
+    M.free(c->seg_vt0); M.free(c->seg_vt_seg); M.free(c->seg_vt_e0);
+    if (M.upload(&c->seg_vt0, vt0) || M.upload(&c->seg_vt_seg, vt_seg) || M.upload(&c->seg_vt_e0, vt_e0)) return;
     { // row tile -> cone (cone k owns the tiles [row0[k] / rpw, row0[k+1] / rpw))
         const int rpw = TPB / lg_for(c->merged.r);
         std::vector<int> tc((size_t)nblocks_for((size_t)c->merged.n, rpw), c->nb - 1);
         for (int k = 0; k < c->nb; ++k)
             for (int t = c->seg_row0_h[k] / rpw; t < c->seg_row0_h[k + 1] / rpw && t < (int)tc.size(); ++t) tc[t] = k;
-        hipFree(c->seg_tile_cone);
-        c->seg_tile_cone = nullptr;
-        if (upload(&c->seg_tile_cone, tc)) return;
+        M.free(c->seg_tile_cone);
+        if (M.upload(&c->seg_tile_cone, tc)) return;
         // (what a carried convergence test needs of its row tile, in one 16-byte word: see DirArgs.seg_info)
         std::vector<int> info(4 * tc.size());
         for (size_t t = 0; t < tc.size(); ++t) {
             info[4 * t] = tc[t]; info[4 * t + 1] = vt0[tc[t]]; info[4 * t + 2] = vt0[tc[t] + 1];
             info[4 * t + 3] = (t == 0 || tc[t - 1] != tc[t]) ? 1 : 0;
         }
-        hipFree(c->seg_tile_info);
-        c->seg_tile_info = nullptr;
-        if (upload(&c->seg_tile_info, info)) return;
+        M.free(c->seg_tile_info);
+        if (M.upload(&c->seg_tile_info, info)) return;
     }
     c->seg_nvt = (int)vt_seg.size();
     c->spec_b[0] = c->spec_b[1] = 1;
@@ -708,10 +707,9 @@ void refresh_merged(lorads_hip_ctx *c) {
 void graph_cache_clear(lorads_hip_ctx *c);
 void free_factors(lorads_hip_ctx *c) {
     graph_cache_clear(c); // (captured launch chains name the arrays that go away here)
-    double *arrs[] = {c->R, c->U, c->V, c->G, c->cr, c->cp, c->cQ, c->rhs, c->Dtmp};
-    for (auto a : arrs) hipFree(a);
-    for (auto &B : c->blk) { hipFree(B.Wd); hipFree(B.Wpart); hipFree(B.Wj); hipFree(B.Wc); B.Wd = B.Wpart = B.Wj = B.Wc = nullptr; B.wj_for = nullptr; }
-    for (auto &nd : c->ring) { hipFree(nd.s); hipFree(nd.y); }
+    c->factor_mem.release();
+    c->R = c->U = c->V = c->G = c->cr = c->cp = c->cQ = c->rhs = c->Dtmp = nullptr;
+    for (auto &B : c->blk) { B.Wd = B.Wpart = B.Wj = B.Wc = nullptr; B.wj_for = nullptr; }
     c->ring.clear();
 }
 

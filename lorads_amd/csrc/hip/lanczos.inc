@@ -159,7 +159,6 @@ void small_sym_eig(int m, std::vector<double> &A, std::vector<double> &theta, st
 
 struct LanczosBufs {
     double *V = nullptr, *V2 = nullptr, *w = nullptr, *h = nullptr, *Yd = nullptr, *dtmp = nullptr;
-    ~LanczosBufs() { hipFree(V); hipFree(V2); hipFree(w); hipFree(h); hipFree(Yd); hipFree(dtmp); }
 };
 
 // Every cone's eigen-solve is independent of the others: they run on their own streams (one host thread each, see
@@ -180,9 +179,10 @@ void slack_matvec(hipStream_t st, Block &B, const double *x, double *y, double *
 int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B, double tol, int ncv, int max_restart,
                     double *theta_out, int *matvecs, const double *S_given = nullptr, const double *Sd_given = nullptr) {
     const int n = B.n, m = std::max(1, std::min(ncv, n)), keep_max = 8;
+    DevPool mem; // this solve's scratch (a worker thread's own pool): gone on every way out
     LanczosBufs lb;
-    if (dalloc(&lb.V, (size_t)n * (m + 1)) || dalloc(&lb.V2, (size_t)n * (keep_max + 1)) || dalloc(&lb.w, (size_t)n) ||
-        dalloc(&lb.h, (size_t)2 * (m + 1) + 1) || dalloc(&lb.Yd, (size_t)m * keep_max) || dalloc(&lb.dtmp, (size_t)n))
+    if (mem.alloc(&lb.V, (size_t)n * (m + 1)) || mem.alloc(&lb.V2, (size_t)n * (keep_max + 1)) || mem.alloc(&lb.w, (size_t)n) ||
+        mem.alloc(&lb.h, (size_t)2 * (m + 1) + 1) || mem.alloc(&lb.Yd, (size_t)m * keep_max) || mem.alloc(&lb.dtmp, (size_t)n))
         return 1;
     // S on the union pattern: C_e - sum_i lambda_i a  (data/lorads_solver.c:1027-1029)
     WArgs wa{};
@@ -225,8 +225,7 @@ int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B,
     int k = 0, nmv = 0;
     double tnorm = 0.0;
     double *ab = nullptr; // (device) the sweep's coefficients, see k_lz_close
-    if (dalloc(&ab, (size_t)2 * (m + 1) + 2)) return 1;
-    struct AbFree { double *p; ~AbFree() { hipFree(p); } } ab_free{ab};
+    if (mem.alloc(&ab, (size_t)2 * (m + 1) + 2)) return 1;
     {
         std::vector<double> z((size_t)2 * (m + 1) + 2, 0.0);
         z[(size_t)2 * (m + 1) + 1] = -1.0;
@@ -326,12 +325,11 @@ extern "C" int lorads_hip_dual_infeasibility(lorads_hip_ctx *c, double tol, int3
     if (const char *e = getenv("LORADS_LANCZOS_THREADS")) nthr = std::max(1, std::min(nthr, atoi(e)));
     const bool pin_ok = (size_t)2 * (std::min<int>(ncv, 1 << 20) + 1) + 2 <= LZ_PINNED;
     while ((int)c->lz_workers.size() < nthr) { // worker streams + pinned read-back buffers are created once and kept
-        LzWorker w;
-        if (!c->lz_workers.empty() || nthr > 1) {
-            HC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-        }
-        HC(hipHostMalloc((void **)&w.pinned, sizeof(double) * LZ_PINNED));
-        c->lz_workers.push_back(w);
+        const bool own_stream = !c->lz_workers.empty() || nthr > 1;
+        c->lz_workers.emplace_back(); // (first, so that whatever is created below has its owner)
+        LzWorker &w = c->lz_workers.back();
+        if (own_stream) HC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+        if (c->mem.alloc_pinned(&w.pinned, LZ_PINNED, hipHostMallocDefault)) return 1;
     }
     std::atomic<int> next{0}, failed{0}, nmv_tot{0};
     std::mutex err_mu;

@@ -454,8 +454,9 @@ struct LTeamPlan {
     long long launches = 0;
     double *t0 = nullptr;      // sym-pair(R, R) of the fused iteration's pattern pass (k_pairdots_rrd), t0_len entries
     size_t t0_len = 0;
+    DevPool mem;
     void release() {
-        hipFree(d_map); hipFree(gran); hipFree(abort_flag); hipFree(t0);
+        mem.release();
         d_map = nullptr; gran = nullptr; abort_flag = nullptr; t0 = nullptr; t0_len = 0;
         valid = false;
     }
@@ -519,11 +520,11 @@ int lteam_build(lorads_hip_ctx *c) {
     P.offF = words; words += (size_t)2 * G * PK_SLOTW;
     P.offX = words; words += (size_t)2 * 8 * PK_SLOTW;
     P.offB = words; words += (size_t)2 * 8 * PK_SLOTW;
-    if (dalloc(&P.gran, words) || dalloc(&P.abort_flag, 1)) return 1;
+    if (P.mem.alloc(&P.gran, words) || P.mem.alloc(&P.abort_flag, 1)) return 1;
     P.gran_words = words;
     HC(hipMemset(P.gran, 0, sizeof(unsigned long long) * words));
     HC(hipMemset(P.abort_flag, 0, sizeof(int)));
-    if (upload(&P.d_map, map)) return 1;
+    if (P.mem.upload(&P.d_map, map)) return 1;
     P.tag = 0;
     if (getenv("LORADS_HIP_VERBOSE"))
         fprintf(stderr, "lorads_hip: one-launch L-BFGS direction: %d workgroups, %d pairs of doubles per thread and vector\n", P.grid, P.np);
@@ -534,9 +535,9 @@ int lteam_build(lorads_hip_ctx *c) {
 int lteam_scratch(lorads_hip_ctx *c, size_t ne) {
     LTeamPlan &P = *c->lteam;
     if (P.t0 && P.t0_len >= ne) return 0;
-    hipFree(P.t0);
-    P.t0 = nullptr; P.t0_len = 0;
-    if (dalloc(&P.t0, ne)) return 1;
+    P.mem.free(P.t0);
+    P.t0_len = 0;
+    if (P.mem.alloc(&P.t0, ne)) return 1;
     P.t0_len = ne;
     return 0;
 }

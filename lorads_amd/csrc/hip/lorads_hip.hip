@@ -22,7 +22,8 @@
 // Source layout: this file = context + the C ABI; kernels.inc = every kernel; build.inc = a cone's device image
 // (patterns, adjacency, Gram, operator variants, merged block-diagonal cone, LP block); sweep.inc = launch helpers,
 // the CG operator, speculative solves, the cone-by-cone and lockstep sweeps, the evaluation, result hand-over;
-// lanczos.inc = dual infeasibility.
+// lanczos.inc = dual infeasibility; dev_pool.inc = DevPool, the owner of every device and pinned allocation (the fields that
+// hold the addresses are plain pointers; a pool per context, per plan and per scratch frees what it handed out).
 //
 // Kernels (HBM/L2-bound integer+FP64 gather work; bytes per unit in DESIGN.md):
 //   k_pairdots   T_e = X_p.Y_q + X_q.Y_p on a pattern            (reference LORADSUVt)
@@ -93,6 +94,9 @@ int fail_msg(const std::string &m) {
     g_err = m;
     return 1;
 }
+// switches read from the environment at creation: on unless the value starts with '0' / off unless it starts with '1'
+inline bool env_on(const char *name) { const char *v = getenv(name); return !(v && v[0] == '0'); }
+inline bool env_set(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
 #define HC(call)                                        \
     do {                                                \
         hipError_t e__ = (call);                        \
@@ -346,18 +350,7 @@ enum { CV_SET = 0, CV_ADD = 1, CV_DELTA = 2 };
 #endif
 
 // ------------------------------------------------------------------ host side
-template <typename T>
-int dalloc(T **p, size_t n) {
-    *p = nullptr;
-    HC(hipMalloc((void **)p, sizeof(T) * (n > 0 ? n : 1)));
-    return 0;
-}
-template <typename T>
-int upload(T **p, const std::vector<T> &v) {
-    if (dalloc(p, v.size())) return 1;
-    if (!v.empty()) HC(hipMemcpy(*p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-    return 0;
-}
+#include "dev_pool.inc"
 
 struct Pattern {              // one symmetric sparsity pattern with everything the kernels need
     int ne = 0;               // unique lower-tri entries
@@ -373,10 +366,6 @@ struct Pattern {              // one symmetric sparsity pattern with everything 
     double *S = nullptr;      // values on the pattern
     double *S2 = nullptr;     // 2 ne doubles: {S_e, second image sum_i w_i A_i} side by side for the fused front of a CG solve (one 16-byte gather per slot); union pattern of k_cw cones only
     double *cbase = nullptr;  // C on the pattern (union pattern only)
-    void release() {
-        hipFree(erow); hipFree(ecol); hipFree(e_ptr); hipFree(e_con); hipFree(e_con_own); hipFree(e_val);
-        hipFree(adj_ptr); hipFree(adj_col); hipFree(adj_e); hipFree(adj_dyn); hipFree(adj_sval); hipFree(S); hipFree(S2); hipFree(cbase);
-    }
 };
 
 struct Block {
@@ -402,8 +391,7 @@ struct Block {
     int *g_ptr = nullptr, *g_col = nullptr;
     double *g_val = nullptr;
     double *T = nullptr;      // pair dots on the A-pattern
-    bool cv_borrowed = false; // cv points into the merged cone's array
-    double *cv = nullptr;     // constrVal[k], compact
+    double *cv = nullptr;     // constrVal[k], compact (a piece of the merged cone's array once build_merged has run)
     double *wtmp = nullptr;   // compact weights inside the CG operator
     int *c_row = nullptr, *c_col = nullptr;
     double *c_val = nullptr;
@@ -483,7 +471,7 @@ struct LTeamPlan;   // the one-launch L-BFGS history update + direction of phase
 constexpr size_t LZ_PINNED = 256; // doubles of pinned read-back per Lanczos worker (covers ncv <= 126)
 struct LzWorker {
     hipStream_t stream = nullptr; // nullptr: the context's own stream (the first worker of a one-thread run)
-    double *pinned = nullptr;
+    double *pinned = nullptr;     // (owned by lorads_hip_ctx::mem)
 };
 
 // scratch of the solution export (solution.inc): allocated on its first call, never read by the solve
@@ -495,10 +483,8 @@ struct CertScratch {
     double *G = nullptr, *Sd = nullptr;   // dense-storage cones: R R^T (npad x npad) and the dense share of S (cone k at sd_off[k])
     double *mu = nullptr, *part = nullptr, *acc = nullptr;
     std::vector<size_t> s_off, sd_off;
-    void release() {
-        hipFree(lam); hipFree(ax); hipFree(S); hipFree(d); hipFree(dA); hipFree(G); hipFree(Sd); hipFree(mu); hipFree(part); hipFree(acc);
-        *this = CertScratch{};
-    }
+    DevPool mem;
+    void release() { mem.release(); *this = CertScratch{}; }
 };
 
 // scratch of the rounding (rounding.inc): allocated on its first call, never read by the solve
@@ -513,16 +499,16 @@ struct RoundScratch {
     unsigned long long *sgn = nullptr;        // sign words, cone k at t_off[k] * W
     int *ctl = nullptr;                       // [0] flip flag, [1] best before, [2] best after the search
     size_t g_cap = 0, sgn_cap = 0, part_cap = 0, f_cap = 0;
-    void release() {
-        hipFree(t); hipFree(cls_rows); hipFree(G); hipFree(part); hipFree(f); hipFree(f0); hipFree(sgn); hipFree(ctl);
-        *this = RoundScratch{};
-    }
+    DevPool mem;
+    void release() { mem.release(); *this = RoundScratch{}; }
 };
 
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
     hipStream_t stream = nullptr;
+    DevPool mem;              // everything the context holds for its whole life: the cones' images, the tables, the control blocks
+    DevPool factor_mem;       // what alloc_factors makes (released and made anew by lorads_hip_resize_rank)
     std::vector<Block> blk;
     std::vector<LzWorker> lz_workers; // dual-infeasibility eigen-solves (lanczos.inc)
     CertScratch cert;                 // solution export (solution.inc)
@@ -709,6 +695,112 @@ inline void persist_touch(lorads_hip_ctx *c); // (persist.inc: what the one-laun
 #include "persist.inc"
 #include "lbfgs_team.inc"
 
+// everything lorads_hip_create does to a fresh context; whatever it has made when it fails is released by lorads_hip_destroy
+int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
+    c->m = prob->m; c->nb = prob->nblocks; c->L = std::max(prob->lbfgs_len, 1); c->b_nrm1 = prob->b_nrm1;
+    HC(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    { // partial-sum slots: room for every row kernel's grid at any rank (the merged cone of all blocks included)
+        size_t rows_max = 0, rows_all = 0;
+        for (int k = 0; k < c->nb; ++k) {
+            const size_t nk = (size_t)std::max(prob->blocks[k].n, 0);
+            rows_max = std::max(rows_max, nk);
+            rows_all += (nk + 31) & ~(size_t)31;
+        }
+        const size_t need = (std::max(rows_max, rows_all) + 3) / 4 + 1;
+        if (need > ((size_t)1 << 27)) return fail_msg("cone dimension beyond 2^29 rows");
+        c->maxpart = (int)std::max<size_t>((size_t)MINPART, (need + 255) & ~(size_t)255);
+    }
+    c->opt_pad_rank = env_on("LORADS_PAD_ODD_RANK");
+    c->opt_dev_presolve = env_on("LORADS_DEV_PRESOLVE");
+    c->opt_presolve_check = env_set("LORADS_PRESOLVE_CHECK");
+    if (getenv("LORADS_DEV_PRESOLVE_MIN")) c->dev_presolve_min = (size_t)std::max(0ll, atoll(getenv("LORADS_DEV_PRESOLVE_MIN")));
+    c->blk.resize(c->nb);
+    for (int k = 0; k < c->nb; ++k)
+        if (build_block(c, c->blk[k], prob->blocks[k])) return 1;
+    if (build_merged(c, prob)) return 1;
+    common_rank(c);
+    refresh_merged(c);
+    if (getenv("LORADS_HIP_VERBOSE"))
+        fprintf(stderr, "lorads_hip: %d cone(s), merged view %s\n", c->nb, c->has_merged ? "on" : (c->merged_ok ? "off (ranks differ)" : "not applicable"));
+    if (alloc_factors(c)) return 1;
+    std::vector<double> hb(prob->b, prob->b + c->m);
+    DevPool &M = c->mem;
+    if (M.upload(&c->b, hb) || M.alloc(&c->lambda, (size_t)c->m) || M.alloc(&c->lambda_alt, (size_t)c->m) || M.alloc(&c->csum, (size_t)c->m + 2) ||
+        M.alloc(&c->cstage, (size_t)c->m + 2 + MINPART) || M.alloc(&c->gram, 128) ||
+        M.alloc(&c->q12, (size_t)2 * c->m + 2) || M.alloc(&c->part, (size_t)NSLOT * c->maxpart) ||
+        M.alloc(&c->ctrl, 64 * sizeof(double) + sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)) ||
+        M.alloc(&c->ring_ab, (size_t)2 * c->L) || M.alloc(&c->par, 8) || M.alloc(&c->seq_dev, 2))
+        return 1;
+    HC(hipMemset(c->par, 0, sizeof(double) * 8));
+    HC(hipMemset(c->seq_dev, 0, sizeof(unsigned long long) * 2));
+    c->opt_graph = env_on("LORADS_GRAPH");
+    c->opt_graph_batched = getenv("LORADS_GRAPH") && getenv("LORADS_GRAPH")[0] == '2';
+    c->opt_graph_forced = getenv("LORADS_GRAPH") && (getenv("LORADS_GRAPH")[0] == '1' || getenv("LORADS_GRAPH")[0] == '2');
+    if (M.alloc_pinned(&c->h_ctrl, 64 * sizeof(double) + sizeof(CGState) * (size_t)std::max(2 * c->nb, 1), hipHostMallocMapped) ||
+        M.alloc_pinned(&c->h_flag, 64 / sizeof(*c->h_flag), hipHostMallocMapped))
+        return 1;
+    *c->h_flag = 0;
+    HC(hipHostGetDevicePointer((void **)&c->h_ctrl_dev, c->h_ctrl, 0));
+    HC(hipHostGetDevicePointer((void **)&c->h_flag_dev, c->h_flag, 0));
+    c->use_publish = !getenv("LORADS_NO_PUBLISH");
+    c->opt_lazy_scalars = env_on("LORADS_LAZY_SCALARS");
+    c->opt_ar_fast = !env_set("LORADS_AR_PLAIN");
+    c->opt_gram = env_on("LORADS_LBFGS_GRAM");
+    c->opt_gram_single = getenv("LORADS_LBFGS_GRAM") && getenv("LORADS_LBFGS_GRAM")[0] == '2';
+    c->opt_fuse_dir = env_on("LORADS_FUSE_DIR");
+    c->opt_entry_bip = env_on("LORADS_ENTRY_BIP");
+    c->opt_seg_carry = env_on("LORADS_SEG_CARRY");
+    c->opt_seg_carry_init = env_on("LORADS_SEG_CARRY_INIT");
+    c->opt_seg_virt = env_on("LORADS_SEG_VIRT");
+    c->opt_seg_carry_dual = env_on("LORADS_SEG_CARRY_DUAL");
+    c->opt_seg_carry_restart = env_on("LORADS_SEG_CARRY_RESTART");
+    c->opt_cw_quad = env_on("LORADS_CW_QUAD");
+    c->opt_front_cw = env_on("LORADS_FRONT_CW");
+    c->opt_fuse_cg0 = env_on("LORADS_FUSE_CG0");
+    c->opt_front_lds = env_on("LORADS_FRONT_LDS");
+    if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
+    c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
+    c->opt_tile_update = env_on("LORADS_TILE_UPDATE");
+    c->opt_eval_diag = env_on("LORADS_EVAL_DIAG");
+    c->opt_front_diag = env_on("LORADS_FRONT_DIAG");
+    c->opt_dense_cache = env_on("LORADS_DENSE_CACHE");
+    c->opt_fuse_eval = env_on("LORADS_FUSE_EVAL");
+    c->opt_dense_rem = env_on("LORADS_DENSE_REM");
+    c->opt_exact_refresh = env_set("LORADS_EXACT_REFRESH");
+    c->opt_split_front = env_set("LORADS_SPLIT_FRONT");
+    c->scal = (double *)c->ctrl;
+    c->st = (CGState *)(c->ctrl + 64 * sizeof(double));
+    c->h_scal = (double *)c->h_ctrl;
+    c->h_st = (CGState *)(c->h_ctrl + 64 * sizeof(double));
+    HC(hipMemset(c->lambda, 0, sizeof(double) * (size_t)std::max(c->m, 1)));
+    HC(hipMemset(c->csum, 0, sizeof(double) * (size_t)(c->m + 2)));
+    HC(hipMemset(c->q12, 0, sizeof(double) * (size_t)(2 * c->m + 2)));
+    HC(hipMemset(c->scal, 0, sizeof(double) * 64));
+    HC(hipMemset(c->ring_ab, 0, sizeof(double) * (size_t)2 * c->L));
+    HC(hipMemset(c->st, 0, sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)));
+    if (M.alloc(&c->st_shadow, (size_t)std::max(2 * c->nb, 1))) return 1;
+    HC(hipMemset(c->st_shadow, 0, sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)));
+    c->persist = new PersistPlan();
+    c->opt_persist = env_on("LORADS_PERSIST");
+    c->opt_persist_l2 = env_on("LORADS_PERSIST_L2");
+    c->opt_persist_carry = env_on("LORADS_PERSIST_CARRY");
+    c->lteam = new LTeamPlan();
+    c->opt_lbfgs_team = env_on("LORADS_LBFGS_TEAM");
+    c->opt_alm_fused_tail = env_on("LORADS_ALM_FUSED_TAIL");
+    c->opt_alm_fold_cv = env_on("LORADS_ALM_FOLD_CV");
+    c->opt_alm_sval_direct = env_on("LORADS_ALM_SVAL_DIRECT");
+    if (env_set("LORADS_SHARED_GPU")) {
+        int dev = 0;
+        char bus[64] = "0";
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
+        for (char *q = bus; *q; ++q) if (*q == ':' || *q == '.' || *q == '/') *q = '_';
+        const std::string path = std::string("/tmp/lorads_gpu_") + bus + ".lock";
+        c->shared_gpu_fd = open(path.c_str(), O_CREAT | O_RDWR, 0666);
+    }
+    HC(hipDeviceSynchronize());
+    return 0;
+}
+
 } // namespace
 
 // ================================================================== C ABI
@@ -723,145 +815,25 @@ int lorads_hip_create(const lorads_hip_problem *prob, lorads_hip_ctx **out) {
         return fail_msg("no HIP device: the MI355X backend has no CPU fallback");
     if (prob->device >= 0) HC(hipSetDevice(prob->device));
     lorads_hip_ctx *c = new lorads_hip_ctx();
-    c->m = prob->m; c->nb = prob->nblocks; c->L = std::max(prob->lbfgs_len, 1); c->b_nrm1 = prob->b_nrm1;
-    HC(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    { // partial-sum slots: room for every row kernel's grid at any rank (the merged cone of all blocks included)
-        size_t rows_max = 0, rows_all = 0;
-        for (int k = 0; k < c->nb; ++k) {
-            const size_t nk = (size_t)std::max(prob->blocks[k].n, 0);
-            rows_max = std::max(rows_max, nk);
-            rows_all += (nk + 31) & ~(size_t)31;
-        }
-        const size_t need = (std::max(rows_max, rows_all) + 3) / 4 + 1;
-        if (need > ((size_t)1 << 27)) { delete c; return fail_msg("cone dimension beyond 2^29 rows"); }
-        c->maxpart = (int)std::max<size_t>((size_t)MINPART, (need + 255) & ~(size_t)255);
-    }
-    c->opt_pad_rank = !(getenv("LORADS_PAD_ODD_RANK") && getenv("LORADS_PAD_ODD_RANK")[0] == '0');
-    c->opt_dev_presolve = !(getenv("LORADS_DEV_PRESOLVE") && getenv("LORADS_DEV_PRESOLVE")[0] == '0');
-    c->opt_presolve_check = getenv("LORADS_PRESOLVE_CHECK") && getenv("LORADS_PRESOLVE_CHECK")[0] == '1';
-    if (getenv("LORADS_DEV_PRESOLVE_MIN")) c->dev_presolve_min = (size_t)std::max(0ll, atoll(getenv("LORADS_DEV_PRESOLVE_MIN")));
-    c->blk.resize(c->nb);
-    for (int k = 0; k < c->nb; ++k)
-        if (build_block(c, c->blk[k], prob->blocks[k])) { lorads_hip_destroy(c); return 1; }
-    if (build_merged(c, prob)) { lorads_hip_destroy(c); return 1; }
-    common_rank(c);
-    refresh_merged(c);
-    if (getenv("LORADS_HIP_VERBOSE"))
-        fprintf(stderr, "lorads_hip: %d cone(s), merged view %s\n", c->nb, c->has_merged ? "on" : (c->merged_ok ? "off (ranks differ)" : "not applicable"));
-    if (alloc_factors(c)) { lorads_hip_destroy(c); return 1; }
-    std::vector<double> hb(prob->b, prob->b + c->m);
-    if (upload(&c->b, hb) || dalloc(&c->lambda, (size_t)c->m) || dalloc(&c->lambda_alt, (size_t)c->m) || dalloc(&c->csum, (size_t)c->m + 2) ||
-        dalloc(&c->cstage, (size_t)c->m + 2 + MINPART) || dalloc(&c->gram, 128) ||
-        dalloc(&c->q12, (size_t)2 * c->m + 2) || dalloc(&c->part, (size_t)NSLOT * c->maxpart) ||
-        dalloc(&c->ctrl, 64 * sizeof(double) + sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)) ||
-        dalloc(&c->ring_ab, (size_t)2 * c->L) || dalloc(&c->par, 8) || dalloc(&c->seq_dev, 2)) {
-        lorads_hip_destroy(c);
-        return 1;
-    }
-    HC(hipMemset(c->par, 0, sizeof(double) * 8));
-    HC(hipMemset(c->seq_dev, 0, sizeof(unsigned long long) * 2));
-    c->opt_graph = !(getenv("LORADS_GRAPH") && getenv("LORADS_GRAPH")[0] == '0');
-    c->opt_graph_batched = getenv("LORADS_GRAPH") && getenv("LORADS_GRAPH")[0] == '2';
-    c->opt_graph_forced = getenv("LORADS_GRAPH") && (getenv("LORADS_GRAPH")[0] == '1' || getenv("LORADS_GRAPH")[0] == '2');
-    HC(hipHostMalloc((void **)&c->h_ctrl, 64 * sizeof(double) + sizeof(CGState) * (size_t)std::max(2 * c->nb, 1), hipHostMallocMapped));
-    HC(hipHostMalloc((void **)&c->h_flag, 64, hipHostMallocMapped));
-    *c->h_flag = 0;
-    HC(hipHostGetDevicePointer((void **)&c->h_ctrl_dev, c->h_ctrl, 0));
-    HC(hipHostGetDevicePointer((void **)&c->h_flag_dev, c->h_flag, 0));
-    c->use_publish = !getenv("LORADS_NO_PUBLISH");
-    c->opt_lazy_scalars = !(getenv("LORADS_LAZY_SCALARS") && getenv("LORADS_LAZY_SCALARS")[0] == '0');
-    c->opt_ar_fast = !(getenv("LORADS_AR_PLAIN") && getenv("LORADS_AR_PLAIN")[0] == '1');
-    c->opt_gram = !(getenv("LORADS_LBFGS_GRAM") && getenv("LORADS_LBFGS_GRAM")[0] == '0');
-    c->opt_gram_single = getenv("LORADS_LBFGS_GRAM") && getenv("LORADS_LBFGS_GRAM")[0] == '2';
-    c->opt_fuse_dir = !(getenv("LORADS_FUSE_DIR") && getenv("LORADS_FUSE_DIR")[0] == '0');
-    c->opt_entry_bip = !(getenv("LORADS_ENTRY_BIP") && getenv("LORADS_ENTRY_BIP")[0] == '0');
-    c->opt_seg_carry = !(getenv("LORADS_SEG_CARRY") && getenv("LORADS_SEG_CARRY")[0] == '0');
-    c->opt_seg_carry_init = !(getenv("LORADS_SEG_CARRY_INIT") && getenv("LORADS_SEG_CARRY_INIT")[0] == '0');
-    c->opt_seg_virt = !(getenv("LORADS_SEG_VIRT") && getenv("LORADS_SEG_VIRT")[0] == '0');
-    c->opt_seg_carry_dual = !(getenv("LORADS_SEG_CARRY_DUAL") && getenv("LORADS_SEG_CARRY_DUAL")[0] == '0');
-    c->opt_seg_carry_restart = !(getenv("LORADS_SEG_CARRY_RESTART") && getenv("LORADS_SEG_CARRY_RESTART")[0] == '0');
-    c->opt_cw_quad = !(getenv("LORADS_CW_QUAD") && getenv("LORADS_CW_QUAD")[0] == '0');
-    c->opt_front_cw = !(getenv("LORADS_FRONT_CW") && getenv("LORADS_FRONT_CW")[0] == '0');
-    c->opt_fuse_cg0 = !(getenv("LORADS_FUSE_CG0") && getenv("LORADS_FUSE_CG0")[0] == '0');
-    c->opt_front_lds = !(getenv("LORADS_FRONT_LDS") && getenv("LORADS_FRONT_LDS")[0] == '0');
-    if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
-    c->opt_fold_avg = !(getenv("LORADS_FOLD_AVG") && getenv("LORADS_FOLD_AVG")[0] == '0');
-    c->opt_tile_update = !(getenv("LORADS_TILE_UPDATE") && getenv("LORADS_TILE_UPDATE")[0] == '0');
-    c->opt_eval_diag = !(getenv("LORADS_EVAL_DIAG") && getenv("LORADS_EVAL_DIAG")[0] == '0');
-    c->opt_front_diag = !(getenv("LORADS_FRONT_DIAG") && getenv("LORADS_FRONT_DIAG")[0] == '0');
-    c->opt_dense_cache = !(getenv("LORADS_DENSE_CACHE") && getenv("LORADS_DENSE_CACHE")[0] == '0');
-    c->opt_fuse_eval = !(getenv("LORADS_FUSE_EVAL") && getenv("LORADS_FUSE_EVAL")[0] == '0');
-    c->opt_dense_rem = !(getenv("LORADS_DENSE_REM") && getenv("LORADS_DENSE_REM")[0] == '0');
-    c->opt_exact_refresh = getenv("LORADS_EXACT_REFRESH") && getenv("LORADS_EXACT_REFRESH")[0] == '1';
-    c->opt_split_front = getenv("LORADS_SPLIT_FRONT") && getenv("LORADS_SPLIT_FRONT")[0] == '1';
-    c->scal = (double *)c->ctrl;
-    c->st = (CGState *)(c->ctrl + 64 * sizeof(double));
-    c->h_scal = (double *)c->h_ctrl;
-    c->h_st = (CGState *)(c->h_ctrl + 64 * sizeof(double));
-    HC(hipMemset(c->lambda, 0, sizeof(double) * (size_t)std::max(c->m, 1)));
-    HC(hipMemset(c->csum, 0, sizeof(double) * (size_t)(c->m + 2)));
-    HC(hipMemset(c->q12, 0, sizeof(double) * (size_t)(2 * c->m + 2)));
-    HC(hipMemset(c->scal, 0, sizeof(double) * 64));
-    HC(hipMemset(c->ring_ab, 0, sizeof(double) * (size_t)2 * c->L));
-    HC(hipMemset(c->st, 0, sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)));
-    if (dalloc(&c->st_shadow, (size_t)std::max(2 * c->nb, 1))) return 1;
-    HC(hipMemset(c->st_shadow, 0, sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)));
-    c->persist = new PersistPlan();
-    c->opt_persist = !(getenv("LORADS_PERSIST") && getenv("LORADS_PERSIST")[0] == '0');
-    c->opt_persist_l2 = !(getenv("LORADS_PERSIST_L2") && getenv("LORADS_PERSIST_L2")[0] == '0');
-    c->opt_persist_carry = !(getenv("LORADS_PERSIST_CARRY") && getenv("LORADS_PERSIST_CARRY")[0] == '0');
-    c->lteam = new LTeamPlan();
-    c->opt_lbfgs_team = !(getenv("LORADS_LBFGS_TEAM") && getenv("LORADS_LBFGS_TEAM")[0] == '0');
-    c->opt_alm_fused_tail = !(getenv("LORADS_ALM_FUSED_TAIL") && getenv("LORADS_ALM_FUSED_TAIL")[0] == '0');
-    c->opt_alm_fold_cv = !(getenv("LORADS_ALM_FOLD_CV") && getenv("LORADS_ALM_FOLD_CV")[0] == '0');
-    c->opt_alm_sval_direct = !(getenv("LORADS_ALM_SVAL_DIRECT") && getenv("LORADS_ALM_SVAL_DIRECT")[0] == '0');
-    if (getenv("LORADS_SHARED_GPU") && getenv("LORADS_SHARED_GPU")[0] == '1') {
-        int dev = 0;
-        char bus[64] = "0";
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
-        for (char *q = bus; *q; ++q) if (*q == ':' || *q == '.' || *q == '/') *q = '_';
-        const std::string path = std::string("/tmp/lorads_gpu_") + bus + ".lock";
-        c->shared_gpu_fd = open(path.c_str(), O_CREAT | O_RDWR, 0666);
-    }
-    HC(hipDeviceSynchronize());
+    if (ctx_init(c, prob)) { lorads_hip_destroy(c); return 1; }
     *out = c;
     return 0;
 }
 
-void lorads_hip_destroy(lorads_hip_ctx *c) {
+void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage of ctx_init)
     if (!c) return;
     if (c->stream) hipStreamSynchronize(c->stream);
     drain_events(c);
     for (auto &e : c->ev_pool) hipEventDestroy(e);
-    std::vector<Block *> all;
-    for (auto &B : c->blk) all.push_back(&B);
-    if (c->merged_ok) all.push_back(&c->merged);
-    for (Block *bp : all) {
-        Block &B = *bp;
-        B.pa.release(); B.pu.release();
-        if (!B.cv_borrowed) hipFree(B.cv);
-        hipFree(B.sv_ptr); hipFree(B.sv_e); hipFree(B.sv_a);
-        hipFree(B.row_idx); hipFree(B.a_ptr); hipFree(B.a_e); hipFree(B.a_val); hipFree(B.Cfull); hipFree(B.T); hipFree(B.T2); hipFree(B.wtmp);
-        hipFree(B.c_row); hipFree(B.c_col); hipFree(B.c_val); hipFree(B.gdiag); hipFree(B.diag_row); hipFree(B.diag_a); hipFree(B.rc_con); hipFree(B.gentry); hipFree(B.bip_rows[0]); hipFree(B.bip_rows[1]); hipFree(B.bip_we); hipFree(B.ca_row); hipFree(B.ca_col); hipFree(B.ca_val); hipFree(B.cadj_ptr); hipFree(B.cadj_col); hipFree(B.cadj_con); hipFree(B.cadj_a); hipFree(B.cell_col); hipFree(B.cell_con); hipFree(B.cell_a);
-        hipFree(B.d_con); hipFree(B.Adense); hipFree(B.Sfull); hipFree(B.d_mu); hipFree(B.fc_ptr); hipFree(B.fc_col); hipFree(B.fc_val); hipFree(B.cell_dst); hipFree(B.cadj_dst); hipFree(B.w_contrib);
-        hipFree(B.w_uv); hipFree(B.w_op); hipFree(B.lp_lvl_ptr); hipFree(B.lp_lvl_cols); hipFree(B.lp_ptr); hipFree(B.lp_grow);
-        hipFree(B.lp_a); hipFree(B.lp_nrm2sq); hipFree(B.lp_cobj); hipFree(B.lp_cv); hipFree(B.g_ptr); hipFree(B.g_col);
-        hipFree(B.g_val);
-    }
-    free_factors(c);
-    hipFree(c->cstage); hipFree(c->sepbuf); hipFree(c->gram);
-    hipFree(c->b); hipFree(c->lambda); hipFree(c->lambda_alt); hipFree(c->csum); hipFree(c->q12); hipFree(c->part); hipFree(c->ctrl); hipFree(c->st_shadow); hipFree(c->seg_tile_cone); hipFree(c->seg_rr_alt); hipFree(c->seg_tile_info);
-    hipFree(c->ring_ab); hipFree(c->par); hipFree(c->seq_dev);
+    graph_cache_free(c);
+    if (c->persist) { c->persist->release(); delete c->persist; }
+    if (c->lteam) { c->lteam->release(); delete c->lteam; }
     c->cert.release();
     c->rnd.release();
-    graph_cache_free(c);
-    if (c->persist) { c->persist->release(); delete c->persist; c->persist = nullptr; }
-    if (c->lteam) { c->lteam->release(); delete c->lteam; c->lteam = nullptr; }
+    c->factor_mem.release();
+    c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
-    hipFree(c->seg_row0); hipFree(c->seg_vt0); hipFree(c->seg_vt_seg); hipFree(c->seg_vt_e0); hipFree(c->phase_done);
-    if (c->h_ctrl) hipHostFree(c->h_ctrl);
-    if (c->h_flag) hipHostFree(c->h_flag);
-    for (auto &w : c->lz_workers) { if (w.stream) hipStreamDestroy(w.stream); if (w.pinned) hipHostFree(w.pinned); }
+    for (auto &w : c->lz_workers) if (w.stream) hipStreamDestroy(w.stream);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -890,7 +862,7 @@ int lorads_hip_set_scalar_exchange(lorads_hip_ctx *c, lorads_hip_scalar_exchange
 int lorads_hip_set_separable(lorads_hip_ctx *c, int32_t on) {
     flush_pending(c);
     c->sep = on != 0;
-    if (c->sep && !c->sepbuf && dalloc(&c->sepbuf, 32)) return 1;
+    if (c->sep && !c->sepbuf && c->mem.alloc(&c->sepbuf, 32)) return 1;
     return 0;
 }
 
@@ -1479,13 +1451,14 @@ int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
     std::vector<size_t> off_old(c->nb);
     std::vector<int> r_old(c->nb), rl_old(c->nb);
     for (int k = 0; k < c->nb; ++k) { off_old[k] = c->blk[k].off; r_old[k] = c->blk[k].r; rl_old[k] = c->blk[k].rl; }
-    c->R = c->U = c->V = c->G = nullptr; // (kept alive across free_factors)
+    DevPool old_mem; // the old arrays live until the kernels below have read them, and go on every way out
+    old_mem.swap(c->factor_mem);
     free_factors(c);
     invalidate_t(c);
     for (int k = 0; k < c->nb; ++k) { c->blk[k].rl = nr[k]; c->blk[k].r = dev_rank(c, nr[k], c->blk[k].is_lp); }
     common_rank(c);
     refresh_merged(c);
-    if (alloc_factors(c)) { for (auto p : old) hipFree(p); return 1; }
+    if (alloc_factors(c)) return 1;
     double *now[4] = {c->R, c->U, c->V, c->G};
     for (int a = 0; a < 4; ++a)
         for (int k = 0; k < c->nb; ++k) {
@@ -1497,7 +1470,6 @@ int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
         }
     HC(hipMemsetAsync(c->ring_ab, 0, sizeof(double) * (size_t)2 * c->L, c->stream));
     HC(hipStreamSynchronize(c->stream)); // (the old arrays are read by the kernels above)
-    for (auto p : old) hipFree(p);
     return 0;
 }
 
@@ -1617,6 +1589,11 @@ int lorads_hip_persist_stats(lorads_hip_ctx *c, int64_t stats[6]) {
 
 int lorads_hip_launch_count(lorads_hip_ctx *c, int64_t *n) {
     *n = c->n_launch;
+    return 0;
+}
+
+int lorads_hip_memory_stats(int64_t stats[4]) {
+    for (int i = 0; i < 4; ++i) stats[i] = g_mem_live[i].load();
     return 0;
 }
 

@@ -809,9 +809,9 @@ struct PersistPlan {
     unsigned long long *stamps = nullptr, *h_stamps = nullptr;
     double *cx = nullptr;      // (C V)_p of every row, from one launch's evaluation to the next launch's U front
     bool cx_ok = false;        // ... and whether it still belongs to the V in memory (persist_touch: every writer of V or C clears it)
+    DevPool mem;
     void release() {
-        hipFree(d_cones); hipFree(d_map); hipFree(gran); hipFree(team_out); hipFree(arrive); hipFree(abort_flag); hipFree(stamps); hipFree(cx);
-        if (h_stamps) hipHostFree(h_stamps);
+        mem.release();
         d_cones = nullptr; d_map = nullptr; gran = nullptr; team_out = nullptr; arrive = nullptr; abort_flag = nullptr; stamps = nullptr; h_stamps = nullptr;
         cx = nullptr; cx_ok = false;
         valid = false;
@@ -949,8 +949,8 @@ int persist_build(lorads_hip_ctx *c) {
         offX[k] = words; words += (size_t)2 * 8 * PK_SLOTW;
         offB[k] = words; words += (size_t)2 * 8 * PK_SLOTW;
     }
-    if (dalloc(&P.gran, words) || dalloc(&P.team_out, (size_t)4 * c->nb) || dalloc(&P.arrive, 1) || dalloc(&P.abort_flag, 1) || dalloc(&P.stamps, 16)) return 1;
-    if (c->opt_persist_carry && dalloc(&P.cx, c->all_elem)) return 1;
+    if (P.mem.alloc(&P.gran, words) || P.mem.alloc(&P.team_out, (size_t)4 * c->nb) || P.mem.alloc(&P.arrive, 1) || P.mem.alloc(&P.abort_flag, 1) || P.mem.alloc(&P.stamps, 16)) return 1;
+    if (c->opt_persist_carry && P.mem.alloc(&P.cx, c->all_elem)) return 1;
     P.cx_ok = false;
     P.gran_words = words;
     HC(hipMemset(P.gran, 0, sizeof(unsigned long long) * std::max<size_t>(words, 1)));
@@ -958,9 +958,9 @@ int persist_build(lorads_hip_ctx *c) {
     HC(hipMemset(P.arrive, 0, sizeof(unsigned long long)));
     HC(hipMemset(P.abort_flag, 0, sizeof(int)));
     HC(hipMemset(P.stamps, 0, sizeof(unsigned long long) * 16));
-    HC(hipHostMalloc((void **)&P.h_stamps, sizeof(unsigned long long) * 16, hipHostMallocDefault));
+    if (P.mem.alloc_pinned(&P.h_stamps, 16, hipHostMallocDefault)) return 1;
     for (int k = 0; k < c->nb; ++k) { cones[k].slA = P.gran + offA[k]; cones[k].slF = P.gran + offF[k]; cones[k].slX = P.gran + offX[k]; cones[k].slB = P.gran + offB[k]; }
-    if (upload(&P.d_cones, cones) || upload(&P.d_map, map)) return 1;
+    if (P.mem.upload(&P.d_cones, cones) || P.mem.upload(&P.d_map, map)) return 1;
     P.launches = 0;
     P.tag = 0;
     if (getenv("LORADS_HIP_VERBOSE"))

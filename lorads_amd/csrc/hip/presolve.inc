@@ -150,8 +150,9 @@ struct DevPre { // scratch of one build: one allocation, handed out in 256-byte 
     hipStream_t st = nullptr;
     char *base = nullptr;
     size_t cap = 0, used = 0;
+    DevPool mem;
     int reserve(size_t bytes) {
-        if (hipMalloc((void **)&base, bytes) != hipSuccess) { base = nullptr; return 1; }
+        if (mem.alloc(&base, bytes)) return 1;
         cap = bytes;
         return 0;
     }
@@ -162,7 +163,6 @@ struct DevPre { // scratch of one build: one allocation, handed out in 256-byte 
         used += b;
         return p;
     }
-    ~DevPre() { if (base) hipFree(base); }
 };
 inline int dp_grid(size_t n) { return (int)std::max<size_t>(1, (n + TPB - 1) / TPB); } // (never an empty grid: a kernel over nothing does nothing)
 // exclusive scan in place; *total_dev (may be null) receives the sum

@@ -17,8 +17,10 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <atomic>
 #include <cstring>
 #include <string>
+#include <vector>
 
 namespace {
 
@@ -33,7 +35,14 @@ struct Api {
 
 thread_local std::string g_err;
 
+int fail(const char *what, hipError_t e) {
+    g_err = std::string(what) + ": " + hipGetErrorString(e);
+    return 1;
+}
+#include "dev_pool.inc"
+
 struct Comm {
+    DevPool mem;                  // owns scratch
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr; // the HIP library's own stream: the collective is ordered with its kernels
     double *scratch = nullptr;    // for the few host-buffer sums (rank agreement on a decision: 1-2 doubles)
@@ -88,8 +97,7 @@ void *lorads_rccl_comm_create(const char id_bytes[NCCL_UNIQUE_ID_BYTES], int ran
     ncclResult_t r = api.CommInitRank(&c->comm, world, id, rank);
     if (r != ncclSuccess) { fail("ncclCommInitRank", r); delete c; return nullptr; }
     c->scratch_len = 64;
-    if (hipMalloc((void **)&c->scratch, sizeof(double) * c->scratch_len) != hipSuccess) {
-        g_err = "hipMalloc of the scratch buffer failed";
+    if (c->mem.alloc(&c->scratch, c->scratch_len)) {
         api.CommDestroy(c->comm);
         delete c;
         return nullptr;
@@ -110,8 +118,8 @@ int lorads_rccl_allreduce_hook(void *user, double *buf, int32_t count, int32_t o
     }
     if ((size_t)count > c->scratch_len) {
         double *p = nullptr;
-        if (hipMalloc((void **)&p, sizeof(double) * (size_t)count) != hipSuccess) { g_err = "hipMalloc failed"; return 1; }
-        hipFree(c->scratch);
+        if (c->mem.alloc(&p, (size_t)count)) return 1;
+        c->mem.free(c->scratch);
         c->scratch = p;
         c->scratch_len = (size_t)count;
     }
@@ -133,7 +141,6 @@ void lorads_rccl_comm_destroy(void *h) {
     Comm *c = (Comm *)h;
     if (!c) return;
     if (c->comm) api.CommDestroy(c->comm);
-    hipFree(c->scratch);
     delete c;
 }
 

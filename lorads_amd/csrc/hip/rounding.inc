@@ -218,7 +218,7 @@ int rnd_check(lorads_hip_ctx *c) {
         if (per_con[i] != 1) { snprintf(msg, sizeof msg, "constraint %d has %d stored entries", i + 1, per_con[i]); X.why = msg; }
     if (c->nb == 0 && X.why.empty()) X.why = "no cone";
     X.qualifies = X.why.empty();
-    if (X.qualifies && upload(&X.t, th)) return 1;
+    if (X.qualifies && X.mem.upload(&X.t, th)) return 1;
     X.checked = true;
     return 0;
 }
@@ -270,7 +270,7 @@ int rnd_colour(lorads_hip_ctx *c) {
         std::vector<int> fill(cp.begin(), cp.end() - 1);
         for (int p = 0; p < n; ++p) all[X.t_off[k] + fill[colour[p]]++] = p;
     }
-    if (upload(&X.cls_rows, all)) return 1;
+    if (X.mem.upload(&X.cls_rows, all)) return 1;
     X.coloured = true;
     return 0;
 }
@@ -282,15 +282,15 @@ int rnd_reserve(lorads_hip_ctx *c, int K) {
     size_t g = 0;
     for (auto &B : c->blk) g += (size_t)B.rl * K;
     const size_t words = (size_t)X.t_off[c->nb] * W, part = (size_t)K * RND_STRIPS;
-    if (g > X.g_cap) { hipFree(X.G); X.G = nullptr; X.g_cap = 0; if (dalloc(&X.G, g)) return 1; X.g_cap = g; }
-    if (words > X.sgn_cap) { hipFree(X.sgn); X.sgn = nullptr; X.sgn_cap = 0; if (dalloc(&X.sgn, words)) return 1; X.sgn_cap = words; }
-    if (part > X.part_cap) { hipFree(X.part); X.part = nullptr; X.part_cap = 0; if (dalloc(&X.part, part)) return 1; X.part_cap = part; }
+    if (g > X.g_cap) { X.mem.free(X.G); X.g_cap = 0; if (X.mem.alloc(&X.G, g)) return 1; X.g_cap = g; }
+    if (words > X.sgn_cap) { X.mem.free(X.sgn); X.sgn_cap = 0; if (X.mem.alloc(&X.sgn, words)) return 1; X.sgn_cap = words; }
+    if (part > X.part_cap) { X.mem.free(X.part); X.part_cap = 0; if (X.mem.alloc(&X.part, part)) return 1; X.part_cap = part; }
     if ((size_t)K > X.f_cap) {
-        hipFree(X.f); hipFree(X.f0); X.f = X.f0 = nullptr; X.f_cap = 0;
-        if (dalloc(&X.f, (size_t)K) || dalloc(&X.f0, (size_t)K)) return 1;
+        X.mem.free(X.f); X.mem.free(X.f0); X.f_cap = 0;
+        if (X.mem.alloc(&X.f, (size_t)K) || X.mem.alloc(&X.f0, (size_t)K)) return 1;
         X.f_cap = (size_t)K;
     }
-    if (!X.ctl && dalloc(&X.ctl, 4)) return 1;
+    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
     return 0;
 }
 

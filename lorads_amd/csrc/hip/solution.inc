@@ -183,9 +183,9 @@ int cert_alloc(lorads_hip_ctx *c) {
         X.sd_off[k] = sd_tot;
         if (B.dense_a) { sd_tot += (size_t)B.npad * B.npad; nd_max = std::max(nd_max, (size_t)B.nd); }
     }
-    if (dalloc(&X.lam, (size_t)c->m) || dalloc(&X.ax, (size_t)c->m) || dalloc(&X.S, s_tot) || dalloc(&X.d, ne_max) ||
-        dalloc(&X.dA, na_max) || dalloc(&X.G, g_max) || dalloc(&X.Sd, sd_tot) || dalloc(&X.mu, nd_max) ||
-        dalloc(&X.part, (size_t)2 * CERT_GRID) || dalloc(&X.acc, (size_t)CERT_ACC + c->nb)) {
+    if (X.mem.alloc(&X.lam, (size_t)c->m) || X.mem.alloc(&X.ax, (size_t)c->m) || X.mem.alloc(&X.S, s_tot) || X.mem.alloc(&X.d, ne_max) ||
+        X.mem.alloc(&X.dA, na_max) || X.mem.alloc(&X.G, g_max) || X.mem.alloc(&X.Sd, sd_tot) || X.mem.alloc(&X.mu, nd_max) ||
+        X.mem.alloc(&X.part, (size_t)2 * CERT_GRID) || X.mem.alloc(&X.acc, (size_t)CERT_ACC + c->nb)) {
         X.release();
         return 1;
     }

@@ -471,6 +471,16 @@ class Session:
         _check(lib.lorads_hip_launch_count(ctx, C.byref(out)), "launch_count")
         return int(out.value)
 
+    @staticmethod
+    def hip_memory_stats(libpath=None):
+        """device and pinned memory the HIP library's contexts of this process hold now: {device_allocations, device_bytes,
+        pinned_allocations, pinned_bytes}.  Needs no session: it still answers after the last one has been closed."""
+        lib = C.CDLL(libpath or os.path.join(LIB_DIR, "liblorads_hip.so"))
+        out = (C.c_int64 * 4)()
+        lib.lorads_hip_memory_stats.argtypes = [C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_memory_stats(out), "memory_stats")
+        return dict(zip(("device_allocations", "device_bytes", "pinned_allocations", "pinned_bytes"), [int(out[i]) for i in range(4)]))
+
     def hip_lbfgs_team_stats(self):
         """phase 1's one-launch L-BFGS history update + direction (csrc/hip/lbfgs_team.inc): {launches, available, workgroups, pairs}"""
         lib, ctx = self._hip()

@@ -33,6 +33,31 @@ def test_abi_library_exports_every_declared_symbol(built):
     assert not (set(dev_syms) & set(declared)), "measurement entries leaked into the product header"
 
 
+def test_device_memory_has_one_owner():
+    """every hipMalloc / hipFree / hipHostMalloc / hipHostFree of the HIP backend sits inside DevPool (csrc/hip/dev_pool.inc,
+    between its two marker comments): no other source line, comment or string of csrc/hip names them, so nothing can be
+    allocated behind the owner's back or freed twice by a hand-kept list"""
+    import glob
+    src = os.path.join(ROOT, "lorads_amd", "csrc", "hip")
+    files = sorted(f for ext in ("*.hip", "*.inc", "*.cpp") for f in glob.glob(os.path.join(src, ext)))
+    assert len(files) >= 14, files
+    words = re.compile(r"\b(hipMalloc|hipFree|hipHostMalloc|hipHostFree)\b")
+    owner = re.compile(r"// >>> DevPool\n.*?// <<< DevPool\n", re.S)
+    owners, hits = 0, []
+    for f in files:
+        text = open(f).read()
+        owners += len(owner.findall(text))
+        for no, line in enumerate(owner.sub(lambda mo: "\n" * mo.group(0).count("\n"), text).split("\n"), 1):
+            if words.search(line):
+                hits.append("%s:%d: %s" % (os.path.basename(f), no, line.strip()))
+    assert owners == 1, owners
+    assert not hits, hits
+    inside = owner.search(open(os.path.join(src, "dev_pool.inc")).read()).group(0)
+    assert {mo.group(1) for mo in words.finditer(inside)} == {"hipMalloc", "hipFree", "hipHostMalloc", "hipHostFree"}
+    # the borrowed-pointer flag the old free lists needed is gone with them
+    assert not [f for f in files if "cv_borrowed" in open(f).read()]
+
+
 def test_rccl_hook_library_exports_every_declared_symbol(built):
     hdr = open(os.path.join(ROOT, "include", "lorads_rccl.h")).read()
     declared = sorted(set(re.findall(r"\b(lorads_rccl_[a-z0-9_]+)\s*\(", hdr)))
