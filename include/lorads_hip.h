@@ -166,6 +166,23 @@ int lorads_hip_get_slack(lorads_hip_ctx *ctx, int32_t blk, int64_t *nnz, int32_t
 int lorads_hip_round_pm1(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                          double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds, double *hyperplanes);
 
+/* Spectrum and rank reduction of the solution factors (no reference counterpart).  Per SDP cone k (the LP block
+ * has no factor and is passed over) F_k is the factor lorads_hip_certificate takes (src) at the cone's own rank rl_k, G_k = F_k^T F_k =
+ * Q_k Lambda_k Q_k^T with lambda_1 >= lambda_2 >= ... (ties: lower original index first): the non-zero eigenvalues of X_k = F_k F_k^T.
+ * G on the FP64 matrix cores, the eigen-solve by cyclic Jacobi in the round-robin ordering (one workgroup per cone).
+ *   eig    [sum_k rl_k]    eigenvalues, descending per SDP cone, cone after cone
+ *   q      (may be NULL)   eigenvectors, column-major rl_k x rl_k per SDP cone, cone after cone
+ *   sweeps [nblocks] (may be NULL)  Jacobi sweeps run per cone, the one that rotated nothing included (LP block: 0)
+ * lorads_hip_spectrum is read-only on the solver's state; the same state gives the same bits.  Returns 3 on a sharded context, 4 when a
+ * cone's iteration still rotates after 30 sweeps or its factor holds a value that is not finite (lorads_hip_last_error names it).
+ * lorads_hip_compress_rank replaces every factor by F_k Q_k[:, :new_rank[k]] -- the best approximation of X_k at that rank; mutually
+ * orthogonal columns of squared norms lambda_1.. -- written to R, U and V alike (Grad and the L-BFGS history cleared):
+ * 1 <= new_rank[k] <= rl_k (LP block: 1); anything else, a sharded context (3) or an eigen-solve that fails (4) is refused with host
+ * and device at the old ranks and the old bits.  new_rank[k] = rl_k is a pure rotation.  eig (may be NULL) as above, of the factor
+ * before the reduction.  Constraint values are the caller's to refresh (lorads_hip_init_constr), as after lorads_hip_resize_rank. */
+int lorads_hip_spectrum(lorads_hip_ctx *ctx, int32_t src, double *eig, double *q, int32_t *sweeps);
+int lorads_hip_compress_rank(lorads_hip_ctx *ctx, int32_t src, const int32_t *new_rank, double *eig);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

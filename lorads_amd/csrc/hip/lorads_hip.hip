@@ -503,6 +503,18 @@ struct RoundScratch {
     void release() { mem.release(); *this = RoundScratch{}; }
 };
 
+// scratch of the spectrum / rank reduction (spectral.inc): allocated on its first call, never read by the solve
+struct SpecCone { int rl, m; long long g_off, e_off, q_off; }; // one cone of a k_spec_jacobi launch: orders, places in SpecScratch::W
+struct SpecScratch {
+    double *part = nullptr;  // per-strip partial Grams of the cone at hand: [strip][tile pair][16 x 16]
+    double *W = nullptr;     // per cone of a batch: G (m x m), Q (m x m), eigenvalues (rl), sorted eigenvectors (rl x rl, column-major)
+    SpecCone *cones = nullptr;
+    int *info = nullptr;     // per cone of a batch: {sweeps, 0 = converged}
+    size_t part_cap = 0, w_cap = 0, cones_cap = 0;
+    DevPool mem;
+    void release() { mem.release(); *this = SpecScratch{}; }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -513,6 +525,7 @@ struct lorads_hip_ctx {
     std::vector<LzWorker> lz_workers; // dual-infeasibility eigen-solves (lanczos.inc)
     CertScratch cert;                 // solution export (solution.inc)
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
+    SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -830,6 +843,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     if (c->lteam) { c->lteam->release(); delete c->lteam; }
     c->cert.release();
     c->rnd.release();
+    c->spectral.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -1647,3 +1661,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "lanczos.inc"
 #include "solution.inc"
 #include "rounding.inc"
+#include "spectral.inc"

@@ -49,6 +49,8 @@ typedef struct {
     int (*get_slack)(lorads_hip_ctx *, int32_t, int64_t *, int32_t *, int32_t *, double *);                /* optional */
     int (*round_pm1)(lorads_hip_ctx *, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, int8_t *,
                      int32_t *, double *); /* optional */
+    int (*spectrum)(lorads_hip_ctx *, int32_t, double *, double *, int32_t *);           /* optional */
+    int (*compress_rank)(lorads_hip_ctx *, int32_t, const int32_t *, double *);          /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -91,6 +93,13 @@ static int b_round(void *cx, int src, int trials, uint64_t seed, int max_rounds,
                    int8_t *sign, int *rounds, double *hyp) {
     return report(H, H->round_pm1(H->ctx, src, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, sign,
                                   (int32_t *)rounds, hyp), "round_pm1");
+}
+/* spectrum / rank reduction: codes 3 (sharded) and 4 (eigen-solve not converged) pass through */
+static int b_spectrum(void *cx, int src, double *eig, double *q, int *sweeps) {
+    return report(H, H->spectrum(H->ctx, src, eig, q, (int32_t *)sweeps), "spectrum");
+}
+static int b_compress(void *cx, int src, const int *nr, double *eig) {
+    return report(H, H->compress_rank(H->ctx, src, (const int32_t *)nr, eig), "compress_rank");
 }
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
@@ -153,6 +162,9 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->get_slack) = dlsym(h->dl, "lorads_hip_get_slack");
     if (!h->get_slack) h->certificate = NULL;
     *(void **)(&h->round_pm1) = dlsym(h->dl, "lorads_hip_round_pm1");
+    *(void **)(&h->spectrum) = dlsym(h->dl, "lorads_hip_spectrum");
+    *(void **)(&h->compress_rank) = dlsym(h->dl, "lorads_hip_compress_rank");
+    if (!h->compress_rank) h->spectrum = NULL;
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -198,5 +210,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     out->alm_step = b_astep;
     if (h->certificate) { out->certificate = b_cert; out->get_slack = b_slack; }
     if (h->round_pm1) out->round_pm1 = b_round;
+    if (h->spectrum) { out->spectrum = b_spectrum; out->compress_rank = b_compress; }
     return 0;
 }

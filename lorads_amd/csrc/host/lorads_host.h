@@ -167,6 +167,10 @@ typedef struct lrd_backend {
      * lorads_hip_round_pm1, the same arguments and return codes; values in the backend's terms) */
     int (*round_pm1)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
                      int8_t *sign, int *rounds, double *hyperplanes);
+    /* OPTIONAL pair (both or neither): spectrum of the factors and their reduction to a lower rank (include/lorads_hip.h:
+     * lorads_hip_spectrum, lorads_hip_compress_rank, the same arguments and return codes) */
+    int (*spectrum)(void *ctx, int src, double *eig, double *q, int *sweeps);
+    int (*compress_rank)(void *ctx, int src, const int *new_rank, double *eig);
 } lrd_backend;
 #define LRD_CERT_N 10
 
@@ -327,6 +331,37 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
 void lrd_rounding_free(lrd_rounding *r);
 /* plain-text file, a pure function of the struct (rounding.c) */
 int lrd_rounding_write(const char *path, const lrd_rounding *r);
+
+/* ---- spectrum and rank reduction of the solution factors (spectral.c).  Per SDP cone the eigenvalues of F^T F
+ * (F = (U+V)/2 in phase 2, the phase-1 R otherwise): the non-zero eigenvalues of X = F F^T.
+ * The rank rule: max(1, min(cap, #{j : eig[j] > tol eig[0]})) for eig descending of length rl; cap <= 0: no cap. */
+int lrd_spectral_choose(const double *eig, int rl, double tol, int cap);
+int lrd_session_block_is_lp(lrd_session *s, int k); /* 1: block k of the session is the LP block (it has no factor and no spectrum) */
+typedef struct {
+    int n, is_lp;
+    int rank_before, rank_after; /* LP block: 1, 1 */
+    int sweeps;                  /* Jacobi sweeps of the eigen-solve */
+    double *eig;                 /* [rank_before] descending (NULL on the LP block) */
+    double trace_lost;           /* sum_{j > k} eig_j / sum_j eig_j */
+    double frob_lost;            /* predicted ||X - X_k||_F / ||X||_F = (sum_{j > k} eig_j^2 / sum_j eig_j^2)^(1/2) */
+} lrd_spectral_cone;
+typedef struct {
+    int nblk, src;
+    double tol;
+    int cap;
+    double pobj_before, pobj_after; /* <C, X>, file units */
+    double err1_before, err1_after; /* ||A(X) - b||_2 / (1 + ||b||_1) */
+    lrd_spectral_cone *cone;        /* [nblk], file order */
+} lrd_spectral_report;
+/* eig: [sum of the SDP cones' ranks] (cone after cone), sweeps: [nblk] (may be NULL).  Returns 2 when the table lacks the slots, 3 on a
+ * sharded deal. */
+int lrd_session_spectrum(lrd_session *s, double *eig, int *sweeps);
+/* spectrum -> ranks by the rule -> compress_rank -> the solver's ranks, constraint values, objective and err1 refreshed.  rank_max is
+ * untouched: a later AUG_RANK may grow the cone again.  *report (may be NULL) is the caller's to free with lrd_spectral_report_free. */
+int lrd_session_compress(lrd_session *s, double tol, int cap, lrd_spectral_report **report);
+/* ranks != NULL: [nblk] ranks given by the caller instead of the rule (the backend refuses what is out of range: nothing changes) */
+int lrd_session_compress_ex(lrd_session *s, double tol, int cap, const int *ranks, lrd_spectral_report **report);
+void lrd_spectral_report_free(lrd_spectral_report *r);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -1,6 +1,7 @@
 /* main.c -- command line with the reference's option names (src_semi/main.c:57-80):
  *   lorads file.dat-s [--phase1Tol x] [--timesLogRank x] ... ; solves on the MI355X backend. */
 #include <libgen.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,6 +34,8 @@ int main(int argc, char **argv) {
     const char *round_file = NULL;    /* hyperplane rounding of a +-1-structured problem (ours as well) */
     int round_trials = 0, round_ls = 100;
     unsigned long long round_seed = 0;
+    int compress = 0, compress_cap = 0; /* rank reduction of the solution (ours as well): after the solve, before the file and the rounding */
+    double compress_tol = 1e-12;
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -53,6 +56,20 @@ int main(int argc, char **argv) {
             if (argv[i][7] == 'T') round_trials = (int)v;
             else if (argv[i][7] == 'S') round_seed = v;
             else round_ls = (int)v;
+            continue;
+        }
+        if (!strcmp(argv[i], "--compressTol") || !strcmp(argv[i], "--compressRank")) {
+            char *end = NULL;
+            const int is_tol = argv[i][10] == 'T';
+            const double t = is_tol ? strtod(argv[i + 1], &end) : 0.0;
+            const long kcap = is_tol ? 1 : strtol(argv[i + 1], &end, 10);
+            if (!end || end == argv[i + 1] || *end || !(t >= 0) || !(t < HUGE_VAL) || kcap < 1 || kcap > 512) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                return 2;
+            }
+            if (is_tol) compress_tol = t;
+            else compress_cap = (int)kcap;
+            compress = 1;
             continue;
         }
         if (strncmp(argv[i], "--", 2) || lrd_session_set_param(s, argv[i] + 2, argv[i + 1])) {
@@ -104,6 +121,25 @@ int main(int argc, char **argv) {
     printf("-----------------------------------------------------------------------\n");
     printf("phase 1: %f s, phase 2: %f s (%d ADMM iterations, %d CG iterations), dual infeasibility: %f s\n", r[10], r[11],
            (int)r[13], (int)r[14], r2[2]);
+    if (compress) {
+        lrd_spectral_report *x = NULL;
+        if (lrd_session_compress(s, compress_tol, compress_cap, &x)) {
+            fprintf(stderr, "lorads: the rank reduction failed\n");
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Rank reduction of the solution:\n");
+        for (int k = 0; k < x->nblk; ++k) {
+            const lrd_spectral_cone *q = &x->cone[k];
+            if (q->is_lp) { printf("\t block %d: lp %d, left alone\n", k + 1, q->n); continue; }
+            printf("\t block %d: sdp %d, rank %d -> %d (%d Jacobi sweeps), lambda_1 %.6e, lambda_%d %.6e, trace share lost %.3e, "
+                   "||X - X_k||_F / ||X||_F %.3e\n", k + 1, q->n, q->rank_before, q->rank_after, q->sweeps, q->eig[0], q->rank_before,
+                   q->eig[q->rank_before - 1], q->trace_lost, q->frob_lost);
+        }
+        printf("\t primal objective <C, X>         : %.10e -> %.10e\n\t err1 ||A(X) - b||_2 rel.        : %.6e -> %.6e\n",
+               x->pobj_before, x->pobj_after, x->err1_before, x->err1_after);
+        lrd_spectral_report_free(x);
+    }
     if (solution_file) {
         lrd_solution *x = NULL;
         if (lrd_session_solution(s, 1e-8, &x) || lrd_solution_write(solution_file, x)) {

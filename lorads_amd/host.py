@@ -62,7 +62,22 @@ class BackendStruct(C.Structure):
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
         ("round_pm1", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
                                   C.POINTER(C.c_int8), _ip, _dp)),
+        ("spectrum", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _dp, _dp, _ip)),
+        ("compress_rank", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _ip, _dp)),
     ]
+
+
+class SpectralConeStruct(C.Structure):
+    """lrd_spectral_cone (csrc/host/lorads_host.h)"""
+    _fields_ = [("n", C.c_int), ("is_lp", C.c_int), ("rank_before", C.c_int), ("rank_after", C.c_int), ("sweeps", C.c_int),
+                ("eig", _dp), ("trace_lost", C.c_double), ("frob_lost", C.c_double)]
+
+
+class SpectralReportStruct(C.Structure):
+    """lrd_spectral_report (csrc/host/lorads_host.h)"""
+    _fields_ = [("nblk", C.c_int), ("src", C.c_int), ("tol", C.c_double), ("cap", C.c_int),
+                ("pobj_before", C.c_double), ("pobj_after", C.c_double), ("err1_before", C.c_double), ("err1_after", C.c_double),
+                ("cone", C.POINTER(SpectralConeStruct))]
 
 
 def _check(rc, what):
@@ -184,6 +199,48 @@ class Backend:
         arr = (C.c_int * len(new_rank))(*[int(x) for x in new_rank])
         _check(self._s.resize_rank(self._s.ctx, arr), "resize_rank")
         self._session._rank_override = [int(x) for x in new_rank]
+
+    def has_spectrum(self):
+        return bool(self._s.spectrum) and bool(self._s.compress_rank)
+
+    def _sdp_ranks(self):
+        lp = self._session._lp_blocks()
+        return [0 if lp[k] else self._session.block_shape(k)[1] for k in range(self._session.nblk)]
+
+    def spectrum(self, src, vectors=False):
+        """the table's slot as it is: per block the eigenvalues (descending) of F^T F, the Jacobi sweep counts and, with
+        vectors=True, the eigenvectors (columns); an empty array for the LP block.  Returns (code, eigenvalues, sweeps, eigenvectors):
+        code != 0 is the slot's refusal and the rest is None; eigenvectors is None without vectors=True."""
+        ranks = self._sdp_ranks()
+        eig = np.zeros(max(sum(ranks), 1))
+        q = np.zeros(max(sum(r * r for r in ranks), 1)) if vectors else None
+        sw = np.zeros(max(len(ranks), 1), dtype=np.int32)
+        rc = self._s.spectrum(self._s.ctx, src, eig.ctypes.data_as(_dp), q.ctypes.data_as(_dp) if vectors else None, sw.ctypes.data_as(_ip))
+        if rc:
+            return rc, None, None, None
+        lam, Q, at, qat = [], [], 0, 0
+        for r in ranks:
+            lam.append(eig[at:at + r].copy())
+            if vectors:
+                Q.append(q[qat:qat + r * r].reshape(r, r).T.copy())  # (column-major on the wire)
+            at += r
+            qat += r * r
+        return 0, lam, [int(x) for x in sw[:len(ranks)]], (Q if vectors else None)
+
+    def compress_rank(self, src, new_rank):
+        """the table's slot as it is (constraint values are the caller's to refresh): returns (code, eigenvalues per block)"""
+        ranks = self._sdp_ranks()
+        eig = np.zeros(max(sum(ranks), 1))
+        arr = (C.c_int * len(new_rank))(*[int(x) for x in new_rank])
+        rc = self._s.compress_rank(self._s.ctx, src, arr, eig.ctypes.data_as(_dp))
+        if rc:
+            return rc, None
+        self._session._rank_override = [int(x) for x in new_rank]
+        lam, at = [], 0
+        for r in ranks:
+            lam.append(eig[at:at + r].copy())
+            at += r
+        return 0, lam
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -697,6 +754,69 @@ class Session:
             _check(self.lib.lrd_rounding_write(os.fsencode(path), ptr), "rounding_write")
         finally:
             self.lib.lrd_rounding_free(ptr)
+
+    def _spectral_refused(self, rc, what):
+        if rc == 2:
+            raise NotImplementedError("the attached backend (%s) cannot compute the %s: only the HIP backend does"
+                                      % (self.be.name if self.be else "none", what))
+        if rc == 3:
+            raise NotImplementedError("the %s of a sharded deal (world > 1) is not supported" % what)
+        _check(rc, what)
+
+    def spectrum(self, sweeps=False):
+        """Per SDP cone the eigenvalues (descending) of F^T F, F = (U + V) / 2 in phase 2 and the phase-1 R otherwise, at the cone's
+        own rank: the non-zero eigenvalues of X = F F^T.  Computed on the device (Gram on the matrix cores, cyclic Jacobi); read-only
+        on the solver's state.  A list with one array per block (empty for the LP block); sweeps=True: also the Jacobi sweep counts."""
+        ranks = [self.block_shape(k)[1] for k in range(self.nblk)]
+        lp = self._lp_blocks()
+        ranks = [0 if lp[k] else ranks[k] for k in range(self.nblk)]
+        eig = np.zeros(max(sum(ranks), 1))
+        sw = np.zeros(max(self.nblk, 1), dtype=np.int32)
+        self.lib.lrd_session_spectrum.argtypes = [C.c_void_p, _dp, _ip]
+        self._spectral_refused(self.lib.lrd_session_spectrum(self.h, eig.ctypes.data_as(_dp), sw.ctypes.data_as(_ip)), "spectrum of the solution")
+        out, at = [], 0
+        for r in ranks:
+            out.append(eig[at:at + r].copy())
+            at += r
+        return (out, [int(x) for x in sw[:self.nblk]]) if sweeps else out
+
+    def _lp_blocks(self):
+        self.lib.lrd_session_block_is_lp.argtypes = [C.c_void_p, C.c_int]
+        return [bool(self.lib.lrd_session_block_is_lp(self.h, k)) for k in range(self.nblk)]
+
+    def compress_rank(self, tol=1e-12, max_rank=None, ranks=None):
+        """Replace every SDP cone's factor by its top-k spectral factor F Q[:, :k] (R = U = V; mutually orthogonal columns of squared
+        norms lambda_1 >= lambda_2 >= ...), k = max(1, min(max_rank, #{j : lambda_j > tol lambda_1})) -- or ranks[k] given per block
+        (1 <= ranks[k] <= current rank; the current rank: a pure rotation, X unchanged).  Constraint values, objective and err1 are
+        refreshed.  Returns the report as a dict: per block rank before / after, eigenvalues, sweeps, the trace share lost and the
+        predicted ||X - X_k||_F / ||X||_F; pobj and err1 before and after."""
+        ptr = C.POINTER(SpectralReportStruct)()
+        self.lib.lrd_session_compress_ex.argtypes = [C.c_void_p, C.c_double, C.c_int, _ip, C.POINTER(C.POINTER(SpectralReportStruct))]
+        self.lib.lrd_spectral_report_free.argtypes = [C.POINTER(SpectralReportStruct)]
+        if self._rank_override is not None and \
+                self._rank_override != [self.lib.lrd_session_current_rank(self.h, k) for k in range(self.nblk)]:
+            # (Backend.resize_rank / Backend.compress_rank went past the host: its record sizes the buffers and feeds the rank rule)
+            raise RuntimeError("the ranks were changed through the backend table (%s), the host's record is stale: use "
+                               "Backend.compress_rank" % self._rank_override)
+        rk = None if ranks is None else np.ascontiguousarray(ranks, dtype=np.int32)
+        if rk is not None and len(rk) != self.nblk:
+            raise ValueError("ranks: one entry per block")
+        rc = self.lib.lrd_session_compress_ex(self.h, float(tol), int(max_rank) if max_rank else 0,
+                                              rk.ctypes.data_as(_ip) if rk is not None else None, C.byref(ptr))
+        self._spectral_refused(rc, "rank reduction of the solution")
+        self._rank_override = None  # (the host's record of the ranks is the current one)
+        try:
+            r = ptr.contents
+            cones = []
+            for k in range(r.nblk):
+                q = r.cone[k]
+                cones.append(dict(n=q.n, is_lp=bool(q.is_lp), rank_before=q.rank_before, rank_after=q.rank_after, sweeps=q.sweeps,
+                                  eig=np.array([q.eig[j] for j in range(q.rank_before)]) if q.eig else np.zeros(0),
+                                  trace_lost=q.trace_lost, frob_lost=q.frob_lost))
+            return dict(src=r.src, tol=r.tol, max_rank=r.cap or None, pobj_before=r.pobj_before, pobj_after=r.pobj_after,
+                        err1_before=r.err1_before, err1_after=r.err1_after, cones=cones)
+        finally:
+            self.lib.lrd_spectral_report_free(ptr)
 
     def dual_infeasibility(self):
         """DIMACS error 2 of the current multipliers, data/lorads_solver.c:1007-1037 (-1: slot missing)"""
