@@ -30,26 +30,30 @@ def load_oracle():
     return _oracle
 
 
-def oracle_session(path, world=1, rank=0, separable=False, **params):
+def oracle_session(path, world=1, rank=0, separable=False, lbfgs_len=None, **params):
     """Session driven by the CPU oracle table (tests / cpu_baseline only)."""
     lib = load_oracle()
     s = host.Session.open(path, lib=lib)
+    if lbfgs_len is not None:  # (the history length of the table and of the host's parameters together)
+        params = dict(params, lbfgsListLength=lbfgs_len)
     s.set_params(verbose=0, **params)
     s.prepare(world, rank, separable=separable)
     st = host.BackendStruct()
-    assert lib.lorads_oracle_backend_create(s.problem_ptr(), 2, C.byref(st)) == 0
+    assert lib.lorads_oracle_backend_create(s.problem_ptr(), lbfgs_len or 2, C.byref(st)) == 0
     s.attach(st)
     return s
 
 
-def hip_session(path, world=1, rank=0, separable=None, **params):
+def hip_session(path, world=1, rank=0, separable=None, lbfgs_len=None, **params):
     s = host.Session.open(path)
+    if lbfgs_len is not None:  # (the history length of the table and of the host's parameters together)
+        params = dict(params, lbfgsListLength=lbfgs_len)
     s.set_params(verbose=0, **params)
     # (sharded: a block-separable deal runs on per-rank sub-problems sharing scalars only; LORADS_SEPARABLE=0: the general form)
     if separable is None:
         separable = world > 1 and os.environ.get("LORADS_SEPARABLE", "1") != "0"
     s.prepare(world, rank, separable=separable)
-    s.attach_hip()
+    s.attach_hip(lbfgs_len=lbfgs_len or 2)
     return s
 
 
@@ -249,6 +253,24 @@ def load_uv_state(be, U, V, lam):
         be.set_mat(host.MAT_V, k, v)
     be.set_vec(host.VEC_LAMBDA, lam)
     be.init_constr(host.PAIR_UV)
+
+
+def random_r_state(sess, seed, lam_scale=0.1):
+    """seeded phase-1 state of the session's shapes: R = N(0, 1) / sqrt(n) per cone, lambda = lam_scale N(0, 1)"""
+    rng = np.random.default_rng(seed)
+    R = []
+    for k in range(sess.nblk):
+        n, r = sess.block_shape(k)
+        R.append(rng.standard_normal((n, r)) / np.sqrt(n))
+    return R, lam_scale * rng.standard_normal(sess.m)
+
+
+def load_r_state(be, R, lam):
+    """a phase-1 state into a table: R, lambda and the constraint sums of (R, R)"""
+    for k, r in enumerate(R):
+        be.set_mat(host.MAT_R, k, r)
+    be.set_vec(host.VEC_LAMBDA, lam)
+    be.init_constr(host.PAIR_RR)
 
 
 def rel_to_scale(got, want):
