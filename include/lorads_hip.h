@@ -183,6 +183,26 @@ int lorads_hip_round_pm1(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint6
 int lorads_hip_spectrum(lorads_hip_ctx *ctx, int32_t src, double *eig, double *q, int32_t *sweeps);
 int lorads_hip_compress_rank(lorads_hip_ctx *ctx, int32_t src, const int32_t *new_rank, double *eig);
 
+/* Entries of the primal and its products with a block of vectors (no reference counterpart).  X_blk = F F^T with F
+ * the factor lorads_hip_certificate takes (src) at the cone's own rank, in the file's units (X carries no scaleObjHis); on the LP block
+ * X = diag(f_j^2).  X is never formed.
+ *   primal_entries: val[e] = F_row[e] . F_col[e] (LP block: f_i^2 where row = col, else 0); positions 0-based, in any order, duplicates
+ *     allowed; val(i, j) and val(j, i) are the same bits.  With ref the device also forms stats = { sum (val - ref)^2, sum |val - ref|,
+ *     max |val - ref|, sum ref^2 }: a held-out score needs no read-back of val (val may then be NULL).  stats is given with ref and only
+ *     with it.  count = 0: nothing is launched, the statistics are zero.  The positions go to the device in chunks of
+ *     LORADS_HIP_PRIMAL_CHUNK entries; a workgroup takes LORADS_HIP_PRIMAL_EPW of them.
+ *   primal_apply: T = F^T B (rl x ncols, may be NULL), Y = F T = X_blk B; B, Y column-major n x ncols on the host, 1 <= ncols <= 1024;
+ *     on the FP64 matrix cores, in panels of 16 columns.  A column of Y does not depend on which other columns share the call.
+ *     LP block: Y = diag(f^2) B and T must be NULL.
+ * Both are read-only on the solver's state and deterministic (no float atomics; the same state and arguments give the same bits).
+ * Everything is validated on the host before any device work -- src, blk, count < 0, ncols, a NULL that is not allowed, every row[e]
+ * and col[e] against [0, n) -- and lorads_hip_last_error names the first offending position.  Returns 3 on a sharded context. */
+#define LORADS_HIP_PRIMAL_CHUNK 262144
+#define LORADS_HIP_PRIMAL_EPW 128
+int lorads_hip_primal_entries(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int64_t count, const int32_t *row, const int32_t *col,
+                              double *val, const double *ref, double stats[4]);
+int lorads_hip_primal_apply(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int32_t ncols, const double *B, double *Y, double *T);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

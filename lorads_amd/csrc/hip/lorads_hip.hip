@@ -515,6 +515,19 @@ struct SpecScratch {
     void release() { mem.release(); *this = SpecScratch{}; }
 };
 
+// scratch of the primal queries (primal.inc): allocated on first use, grown on demand, never read by the solve.  Bounded whatever the
+// count, the columns and n are: entries go in chunks of LORADS_HIP_PRIMAL_CHUNK, B and Y in panels of 16 columns x 65536 rows.
+struct PrimalScratch {
+    int *row = nullptr, *col = nullptr;            // the chunk's positions
+    double *ref = nullptr, *val = nullptr;         // its reference values and results
+    double *part = nullptr, *acc = nullptr;        // per-workgroup partials of the four statistics, the statistics
+    double *bp = nullptr, *yp = nullptr;           // a panel of B and of Y, row-major 16 wide
+    double *tpart = nullptr, *t = nullptr;         // per-strip partial tiles of T = F^T B: [strip][tile][16 x 16]; T (16 tiles x 16)
+    size_t row_cap = 0, col_cap = 0, ref_cap = 0, val_cap = 0, part_cap = 0, bp_cap = 0, yp_cap = 0, tpart_cap = 0, t_cap = 0; // (one per buffer)
+    DevPool mem;
+    void release() { mem.release(); *this = PrimalScratch{}; }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -526,6 +539,7 @@ struct lorads_hip_ctx {
     CertScratch cert;                 // solution export (solution.inc)
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
+    PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -844,6 +858,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->cert.release();
     c->rnd.release();
     c->spectral.release();
+    c->primal.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -1662,3 +1677,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "solution.inc"
 #include "rounding.inc"
 #include "spectral.inc"
+#include "primal.inc"

@@ -51,6 +51,9 @@ typedef struct {
                      int32_t *, double *); /* optional */
     int (*spectrum)(lorads_hip_ctx *, int32_t, double *, double *, int32_t *);           /* optional */
     int (*compress_rank)(lorads_hip_ctx *, int32_t, const int32_t *, double *);          /* optional */
+    int (*primal_entries)(lorads_hip_ctx *, int32_t, int32_t, int64_t, const int32_t *, const int32_t *, double *, const double *,
+                          double *); /* optional */
+    int (*primal_apply)(lorads_hip_ctx *, int32_t, int32_t, int32_t, const double *, double *, double *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -100,6 +103,15 @@ static int b_spectrum(void *cx, int src, double *eig, double *q, int *sweeps) {
 }
 static int b_compress(void *cx, int src, const int *nr, double *eig) {
     return report(H, H->compress_rank(H->ctx, src, (const int32_t *)nr, eig), "compress_rank");
+}
+/* primal queries: code 3 (sharded) passes through */
+static int b_pentries(void *cx, int src, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
+                      double *stats) {
+    return report(H, H->primal_entries(H->ctx, src, blk, count, (const int32_t *)row, (const int32_t *)col, val, ref, stats),
+                  "primal_entries");
+}
+static int b_papply(void *cx, int src, int blk, int ncols, const double *B, double *Y, double *T) {
+    return report(H, H->primal_apply(H->ctx, src, blk, ncols, B, Y, T), "primal_apply");
 }
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
@@ -165,6 +177,9 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->spectrum) = dlsym(h->dl, "lorads_hip_spectrum");
     *(void **)(&h->compress_rank) = dlsym(h->dl, "lorads_hip_compress_rank");
     if (!h->compress_rank) h->spectrum = NULL;
+    *(void **)(&h->primal_entries) = dlsym(h->dl, "lorads_hip_primal_entries");
+    *(void **)(&h->primal_apply) = dlsym(h->dl, "lorads_hip_primal_apply");
+    if (!h->primal_apply) h->primal_entries = NULL;
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -211,5 +226,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->certificate) { out->certificate = b_cert; out->get_slack = b_slack; }
     if (h->round_pm1) out->round_pm1 = b_round;
     if (h->spectrum) { out->spectrum = b_spectrum; out->compress_rank = b_compress; }
+    if (h->primal_entries) { out->primal_entries = b_pentries; out->primal_apply = b_papply; }
     return 0;
 }

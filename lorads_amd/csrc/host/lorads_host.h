@@ -167,6 +167,12 @@ typedef struct lrd_backend {
      * lorads_hip_round_pm1, the same arguments and return codes; values in the backend's terms) */
     int (*round_pm1)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
                      int8_t *sign, int *rounds, double *hyperplanes);
+    /* OPTIONAL pair (both or neither; the table's mirror is checked to END with the spectral pair, so this one stands before it):
+     * entries of the primal X = F F^T and its products with a block of vectors (include/lorads_hip.h:
+     * lorads_hip_primal_entries, lorads_hip_primal_apply, the same arguments and return codes; X in the file's units) */
+    int (*primal_entries)(void *ctx, int src, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
+                          double *stats);
+    int (*primal_apply)(void *ctx, int src, int blk, int ncols, const double *B, double *Y, double *T);
     /* OPTIONAL pair (both or neither): spectrum of the factors and their reduction to a lower rank (include/lorads_hip.h:
      * lorads_hip_spectrum, lorads_hip_compress_rank, the same arguments and return codes) */
     int (*spectrum)(void *ctx, int src, double *eig, double *q, int *sweeps);
@@ -362,6 +368,32 @@ int lrd_session_compress(lrd_session *s, double tol, int cap, lrd_spectral_repor
 /* ranks != NULL: [nblk] ranks given by the caller instead of the rule (the backend refuses what is out of range: nothing changes) */
 int lrd_session_compress_ex(lrd_session *s, double tol, int cap, const int *ranks, lrd_spectral_report **report);
 void lrd_spectral_report_free(lrd_spectral_report *r);
+
+/* ---- entries of the primal X = F F^T and its products (primal.c).  F = (U+V)/2 in phase 2, the phase-1 R otherwise
+ * (as the export chooses).  Both return 2 when the table lacks the slots, 3 on a sharded deal, else the backend's code. */
+int lrd_session_primal_entries(lrd_session *s, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
+                               double *stats);
+int lrd_session_primal_apply(lrd_session *s, int blk, int ncols, const double *B, double *Y, double *T);
+/* A query file: one `k i j` or `k i j v` per line (block, row, column 1-based as in .dat-s; v a reference value), every line with v or
+ * none; blank lines and lines that start with `*`, `#` or `"` are skipped.  The output file: `lorads-entries 1`, `count N`,
+ * `src uv|rr`, `refs 0|1`, with refs `rmse`, `mae`, `maxabs`, `refnorm`, then `k i j x [v]` per query in the query file's order, every
+ * double with %.17g. */
+typedef struct {
+    int64_t count;
+    int has_ref, src;           /* src: filled by lrd_session_entries */
+    int *blk, *row, *col;       /* [count] 0-based */
+    double *ref, *val;          /* [count] (ref: NULL without refs; val: filled by lrd_session_entries) */
+    double stats[4];            /* over all queries: sum (x - v)^2, sum |x - v|, max |x - v|, sum v^2 */
+} lrd_entries;
+/* 0: read; 1: the file cannot be opened; 2: malformed (*bad_line, may be NULL, gets the 1-based line number) */
+int lrd_entries_read(const char *path, lrd_entries **out, int *bad_line);
+int lrd_entries_write(const char *path, const lrd_entries *q);
+void lrd_entries_free(lrd_entries *q);
+/* perm [count]: the queries' indices ordered by block, file order kept inside a block; start [nblk + 1]: block k's run of perm */
+int lrd_entries_group(const lrd_entries *q, int nblk, int64_t *perm, int64_t *start);
+/* the values of all queries: grouped per block for the backend's calls, the file order restored.  1: a block index out of range, else
+ * as lrd_session_primal_entries */
+int lrd_session_entries(lrd_session *s, lrd_entries *q);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -36,6 +36,8 @@ int main(int argc, char **argv) {
     unsigned long long round_seed = 0;
     int compress = 0, compress_cap = 0; /* rank reduction of the solution (ours as well): after the solve, before the file and the rounding */
     double compress_tol = 1e-12;
+    const char *entries_in = NULL, *entries_out = NULL; /* entries of the primal at the positions of a query file (ours as well) */
+    lrd_entries *queries = NULL;
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -46,6 +48,8 @@ int main(int argc, char **argv) {
             continue;
         }
         if (!strcmp(argv[i], "--roundFile")) { round_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--entriesFile")) { entries_in = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--entriesOut")) { entries_out = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--roundTrials") || !strcmp(argv[i], "--roundSeed") || !strcmp(argv[i], "--roundLocalSearch")) {
             char *end = NULL;
             const unsigned long long v = strtoull(argv[i + 1], &end, 10);
@@ -75,6 +79,32 @@ int main(int argc, char **argv) {
         if (strncmp(argv[i], "--", 2) || lrd_session_set_param(s, argv[i] + 2, argv[i + 1])) {
             fprintf(stderr, "unknown option %s\n", argv[i]);
             return 2;
+        }
+    }
+    if (entries_out && !entries_in) {
+        fprintf(stderr, "--entriesOut needs --entriesFile\n");
+        lrd_session_close(s);
+        return 2;
+    }
+    if (entries_in) { /* a bad query file is refused before the backend is created, let alone anything solved */
+        int bad = 0;
+        const int qrc = lrd_entries_read(entries_in, &queries, &bad);
+        if (qrc) {
+            if (qrc == 1) fprintf(stderr, "lorads: cannot read the query file %s\n", entries_in);
+            else fprintf(stderr, "lorads: line %d of the query file %s is malformed (k i j [v], 1-based; every line with v or none)\n", bad, entries_in);
+            lrd_session_close(s);
+            return 2;
+        }
+        const lrd_problem *pr = lrd_session_problem(s);
+        for (int64_t e = 0; e < queries->count; ++e) {
+            const int k = queries->blk[e];
+            if (k >= pr->nblk || queries->row[e] >= pr->blk[k].n || queries->col[e] >= pr->blk[k].n) {
+                fprintf(stderr, "lorads: query %lld of %s (%d %d %d) is outside the problem\n", (long long)e + 1, entries_in, k + 1,
+                        queries->row[e] + 1, queries->col[e] + 1);
+                lrd_entries_free(queries);
+                lrd_session_close(s);
+                return 2;
+            }
         }
     }
     lrd_session_prepare(s, 1, 0);
@@ -139,6 +169,21 @@ int main(int argc, char **argv) {
         printf("\t primal objective <C, X>         : %.10e -> %.10e\n\t err1 ||A(X) - b||_2 rel.        : %.6e -> %.6e\n",
                x->pobj_before, x->pobj_after, x->err1_before, x->err1_after);
         lrd_spectral_report_free(x);
+    }
+    if (queries) {
+        if (lrd_session_entries(s, queries) || (entries_out && lrd_entries_write(entries_out, queries))) {
+            fprintf(stderr, "lorads: the entry queries failed%s%s\n", entries_out ? " or cannot write " : "", entries_out ? entries_out : "");
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Entries of the primal X (%s): %lld positions%s%s\n", entries_in, (long long)queries->count, entries_out ? " -> " : "",
+               entries_out ? entries_out : "");
+        if (queries->has_ref) {
+            const double c = queries->count > 0 ? (double)queries->count : 1.0;
+            printf("\t against the reference values: RMSE %.17g, MAE %.17g, max %.17g\n", sqrt(queries->stats[0] / c), queries->stats[1] / c,
+                   queries->stats[2]);
+        }
+        lrd_entries_free(queries);
     }
     if (solution_file) {
         lrd_solution *x = NULL;

@@ -62,6 +62,8 @@ class BackendStruct(C.Structure):
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
         ("round_pm1", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
                                   C.POINTER(C.c_int8), _ip, _dp)),
+        ("primal_entries", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _ip, _ip, _dp, _dp, _dp)),
+        ("primal_apply", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp)),
         ("spectrum", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _dp, _dp, _ip)),
         ("compress_rank", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _ip, _dp)),
     ]
@@ -242,6 +244,44 @@ class Backend:
             at += r
         return 0, lam
 
+    def has_primal(self):
+        return bool(self._s.primal_entries) and bool(self._s.primal_apply)
+
+    def primal_entries(self, src, blk, rows, cols, ref=None, want_val=True, count=None):
+        """the table's slot as it is: val[e] = F_rows[e] . F_cols[e] of block blk's X = F F^T (0-based positions) and, with ref, the
+        statistics {sum (val - ref)^2, sum |val - ref|, max |val - ref|, sum ref^2} formed on the device.  Returns (code, val, stats);
+        code != 0 is the slot's refusal.  rows / cols None, want_val=False and count pass a NULL / another count down as they are."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        n = int(count) if count is not None else (0 if r is None else len(r))
+        f = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64)
+        val = np.zeros(max(n, 1)) if want_val else None
+        st = np.zeros(4) if f is not None else None
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None  # noqa: E731
+        rc = self._s.primal_entries(self._s.ctx, src, blk, n, ptr(r, _ip), ptr(c, _ip), ptr(val, _dp), ptr(f, _dp), ptr(st, _dp))
+        if rc:
+            return rc, None, None
+        return 0, (val[:max(n, 0)] if want_val else None), st
+
+    def primal_apply(self, src, blk, B, want_t=False, ncols=None):
+        """the table's slot as it is: Y = X_blk B and, with want_t, T = F^T B for B (n, ncols) or (n,).  Returns (code, Y, T)."""
+        if 0 <= int(blk) < self._session.nblk:
+            n, rank = self._session.block_shape(blk)
+        else:   # (a block the session does not know: the slot's to refuse)
+            n, rank = (len(B) if B is not None else 1), 1
+        if B is None:
+            Bf, nc = None, int(ncols or 1)
+        else:
+            Bf = np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(n, -1))
+            nc = int(ncols) if ncols is not None else Bf.shape[1]
+        Y = np.zeros((n, max(nc, 1)), order="F")
+        T = np.zeros((rank, max(nc, 1)), order="F") if want_t else None
+        rc = self._s.primal_apply(self._s.ctx, src, blk, nc, Bf.ctypes.data_as(_dp) if Bf is not None else None, Y.ctypes.data_as(_dp),
+                                  T.ctypes.data_as(_dp) if want_t else None)
+        if rc:
+            return rc, None, None
+        return 0, Y[:, :nc], (T[:, :nc] if want_t else None)
+
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
         a = np.asfortranarray(a, dtype=np.float64)
@@ -289,6 +329,8 @@ def _bind(lib):
     lib.lrd_session_start.restype = _dp
     lib.lrd_session_start.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.lrd_session_current_rank.argtypes = [C.c_void_p, C.c_int]
+    lib.lrd_session_primal_entries.argtypes = [C.c_void_p, C.c_int, C.c_int64, _ip, _ip, _dp, _dp, _dp]
+    lib.lrd_session_primal_apply.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp]
     lib.lrd_session_close.argtypes = [C.c_void_p]
     lib.lrd_session_close.restype = None
     lib.lrd_session_params_ptr = None
@@ -817,6 +859,57 @@ class Session:
                         err1_before=r.err1_before, err1_after=r.err1_after, cones=cones)
         finally:
             self.lib.lrd_spectral_report_free(ptr)
+
+    def _primal_refused(self, rc, what):
+        if rc == 2:
+            raise NotImplementedError("the attached backend (%s) cannot query the primal: only the HIP backend does"
+                                      % (self.be.name if self.be else "none"))
+        if rc == 3:
+            raise NotImplementedError("%s of a sharded deal (world > 1) is not supported" % what)
+        _check(rc, what)
+
+    def primal_entries(self, blk, rows, cols, ref=None):
+        """Entries X[rows[e], cols[e]] of block blk's primal X = F F^T (0-based; F = (U + V) / 2 in phase 2, the phase-1 R otherwise;
+        LP block: X = diag(f^2)), computed on the device without forming X; read-only on the solver's state.  Returns (val, stats):
+        stats is None without ref, else {sum (val - ref)^2, sum |val - ref|, max |val - ref|, sum ref^2} formed on the device."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        if r.ndim != 1 or r.shape != c.shape:
+            raise ValueError("rows and cols: two vectors of one length")
+        f = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64)
+        if f is not None and f.shape != r.shape:
+            raise ValueError("ref: one value per position")
+        val = np.zeros(max(len(r), 1))
+        st = np.zeros(4) if f is not None else None
+        rc = self.lib.lrd_session_primal_entries(self.h, int(blk), len(r), r.ctypes.data_as(_ip), c.ctypes.data_as(_ip),
+                                                 val.ctypes.data_as(_dp), f.ctypes.data_as(_dp) if f is not None else None,
+                                                 st.ctypes.data_as(_dp) if st is not None else None)
+        self._primal_refused(rc, "entries of the primal")
+        return val[:len(r)], st
+
+    def primal_apply(self, blk, B, return_t=False):
+        """Y = X_blk B for B (n, ncols) or (n,), 1 <= ncols <= 1024, as Y = F (F^T B) on the device's matrix cores; with return_t
+        also T = F^T B (rank x ncols; not on the LP block).  Read-only on the solver's state.  The library takes B column-major: a
+        C-ordered B is copied first (DESIGN.md section 13 has what that costs at 64 columns)."""
+        n, rank = self.block_shape(blk)
+        B = np.asarray(B, dtype=np.float64)
+        vec = B.ndim == 1
+        Bf = np.asfortranarray(B.reshape(n, -1))
+        nc = Bf.shape[1]
+        Y = np.zeros((n, max(nc, 1)), order="F")
+        T = np.zeros((rank, max(nc, 1)), order="F") if return_t else None
+        rc = self.lib.lrd_session_primal_apply(self.h, int(blk), nc, Bf.ctypes.data_as(_dp), Y.ctypes.data_as(_dp),
+                                               T.ctypes.data_as(_dp) if return_t else None)
+        self._primal_refused(rc, "a product with the primal")
+        Y = Y[:, 0] if vec else Y
+        if return_t:
+            return Y, (T[:, 0] if vec else T)
+        return Y
+
+    def primal_diag(self, blk):
+        """the diagonal of block blk's primal X"""
+        idx = np.arange(self.block_shape(blk)[0], dtype=np.int32)
+        return self.primal_entries(blk, idx, idx)[0]
 
     def dual_infeasibility(self):
         """DIMACS error 2 of the current multipliers, data/lorads_solver.c:1007-1037 (-1: slot missing)"""
