@@ -61,9 +61,19 @@ int lorads_hip_scalar_exchange_count(lorads_hip_ctx *ctx, int64_t *n);
  * the launch, rows per 8-lane group, column steps, bytes of LDS per workgroup} */
 int lorads_hip_persist_stats(lorads_hip_ctx *ctx, int64_t stats[6]);
 /* enable != 0: the leader workgroup of cone 0's team leaves the 100 MHz clock at its phase boundaries in every such launch;
- * ticks[0..15] = those of the latest launch {start, U front done, U solve done, V front done, V solve done, evaluation done,
- * hand-over begins, 0 ...} (reads after synchronising the stream) */
+ * ticks[0..14] = those of the latest launch {start, U front done, U solve done, V front done, V solve done, evaluation done,
+ * hand-over begins, 0 ...} (reads after synchronising the stream); ticks[15] = what that launch decided behind its first
+ * all-reduce: bit 0 set, bit 1: the placement was verified and the exchanges go through the XCD's L2, bit 2: so do the factor rows */
 int lorads_hip_persist_stamps(lorads_hip_ctx *ctx, int32_t enable, uint64_t ticks[16]);
+/* the host's plan of that launch (built on first use, as by lorads_hip_persist_stats): out = {the tag its next launch starts from (-1: no plan is valid now), 1 if every
+ * team sits on the blocks of one residue class mod 8 (0: blocks dealt team by team), workgroups of the largest team, most sub-teams
+ * of a team, workgroups of the largest sub-team, workgroups per compute unit the plan counts on, compute units, 1 if a launch may
+ * take the L2 forms (LORADS_PERSIST_L2)} */
+int lorads_hip_persist_plan(lorads_hip_ctx *ctx, int64_t out[8]);
+/* measurement: the tag the next such launch starts from (every launch uses up to 16384 consecutive tags of 32 bits; near the end of
+ * the range the host clears the granules and starts over at 0 -- due after 262144 launches, reached by a test only this way).
+ * Clears the granules.  Refused when no plan is valid. */
+int lorads_hip_persist_set_tag(lorads_hip_ctx *ctx, uint32_t tag);
 
 /* phase 1, single rank, history length <= 2: setlbfgsHisTwo + LBFGSDirection + LBFGSDirectionUseGrad of an inner iteration
  * (src_semi/lorads_alg/lorads_alm.c:230-391,469-489,540-560) as ONE launch of resident workgroups inside lorads_hip_alm_step

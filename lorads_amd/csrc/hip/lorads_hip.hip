@@ -588,6 +588,8 @@ struct lorads_hip_ctx {
     int shared_gpu_fd = -1;                  // LORADS_SHARED_GPU=1: lock file of the device (several processes on one card take turns, see run_sweep_persist)
     bool opt_persist_carry = true;           // the evaluation leaves (C V) for the next iteration's U front (LORADS_PERSIST_CARRY=0: every front gathers)
     bool opt_persist_l2 = true;              // granules / rows of workgroups verified to share an XCD go through its L2 (LORADS_PERSIST_L2=0: always written through)
+    int opt_persist_rows = 0;                // LORADS_PERSIST_ROWS=1|2|4: only that many rows per lane group (0: the first that fits; read at creation)
+    bool opt_persist_linear = false;         // LORADS_PERSIST_MAP=linear: blocks dealt team by team even where every team fits one XCD (read at creation)
     bool persist_stamps = false;             // team 0's leader leaves its phase times (lorads_hip_persist_stamps)
     long long n_persist = 0;                 // ADMM iterations run that way
     long long n_launch = 0;                  // kernels enqueued through LAUNCH / the one-launch forms (lorads_hip_launch_count: bench.py's launches per step)
@@ -811,6 +813,8 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->opt_persist = env_on("LORADS_PERSIST");
     c->opt_persist_l2 = env_on("LORADS_PERSIST_L2");
     c->opt_persist_carry = env_on("LORADS_PERSIST_CARRY");
+    c->opt_persist_rows = getenv("LORADS_PERSIST_ROWS") ? atoi(getenv("LORADS_PERSIST_ROWS")) : 0; // (measurements and tests)
+    c->opt_persist_linear = getenv("LORADS_PERSIST_MAP") && getenv("LORADS_PERSIST_MAP")[0] == 'l';
     c->lteam = new LTeamPlan();
     c->opt_lbfgs_team = env_on("LORADS_LBFGS_TEAM");
     c->opt_alm_fused_tail = env_on("LORADS_ALM_FUSED_TAIL");
@@ -1613,6 +1617,31 @@ int lorads_hip_persist_stats(lorads_hip_ctx *c, int64_t stats[6]) {
     stats[3] = ok ? c->persist->rows : 0;
     stats[4] = ok ? c->persist->ns : 0;
     stats[5] = ok ? (int64_t)c->persist->lds : 0;
+    return 0;
+}
+
+int lorads_hip_persist_plan(lorads_hip_ctx *c, int64_t out[8]) {
+    const bool ok = c->persist && persist_ready(c, 800);
+    const PersistPlan *P = c->persist;
+    out[0] = ok ? (int64_t)P->tag : -1;
+    out[1] = ok && P->xcd_map ? 1 : 0;
+    out[2] = ok ? P->g_max : 0;
+    out[3] = ok ? P->nsub_max : 0;
+    out[4] = ok ? P->ssz_max : 0;
+    out[5] = ok ? P->occ : 0;
+    out[6] = ok ? P->ncu : 0;
+    out[7] = ok && c->opt_persist_l2 ? 1 : 0;
+    return 0;
+}
+
+int lorads_hip_persist_set_tag(lorads_hip_ctx *c, uint32_t tag) {
+    if (!c->persist || !c->persist->valid) return fail_msg("persist_set_tag: no plan of the one-launch ADMM iteration is valid");
+    PersistPlan &P = *c->persist;
+    flush_pending(c);
+    HC(hipStreamSynchronize(c->stream));
+    // (granules of earlier launches carry earlier tags: a tag set below them must not meet one of its own values)
+    HC(hipMemset(P.gran, 0, sizeof(unsigned long long) * std::max<size_t>(P.gran_words, 1)));
+    P.tag = tag;
     return 0;
 }
 

@@ -568,6 +568,7 @@ __global__ __launch_bounds__(TPB, 2) void k_admm_diag(PArgs A) {
             three0[0] = five[0]; three0[1] = five[1]; three0[2] = five[2];
             // all d equal  <=>  G sum d^2 == (sum d)^2  (small integers: exact)
             if (A.allow_l2 && T.G > 1 && (double)T.G * five[4] == five[3] * five[3]) { T.l2 = 1; rows_l2 = T.nsub == 1; }
+            if (stamp) A.stamps[15] = 1ull | (T.l2 ? 2ull : 0ull) | (rows_l2 ? 4ull : 0ull); // (what this launch decided, for the tests)
         } else team_allreduce<3>(T, three0, sh, false);
         if (stamp && nstamp < 15) A.stamps[nstamp++] = pk_ticks();
         double rr = three0[0], beta = 0.0, pq = three0[2];
@@ -770,7 +771,7 @@ __global__ __launch_bounds__(TPB, 2) void k_admm_diag(PArgs A) {
         sh[0] = tot[0]; sh[1] = tot[1]; sh[2] = tot[2]; sh[3] = ab ? 1.0 : 0.0;
     }
     __syncthreads();
-    if (stamp && nstamp < 16) A.stamps[nstamp++] = pk_ticks();
+    if (stamp && nstamp < 15) A.stamps[nstamp++] = pk_ticks();
     if (!A.publish) return;
     const unsigned long long seq = *A.seq_dev + 1;
     for (int i = threadIdx.x; i < A.nwords; i += TPB) {
@@ -794,6 +795,7 @@ __global__ __launch_bounds__(TPB, 2) void k_admm_diag(PArgs A) {
 struct PersistPlan {
     bool valid = false, failed = false;
     int ns = 0, rows = 0, grid = 0, occ = 0, ncu = 0;
+    int g_max = 0, nsub_max = 0, ssz_max = 0; // largest team, most sub-teams of a team, largest sub-team (lorads_hip_persist_plan)
     bool xcd_map = false;      // every team on the blocks of one residue class mod 8 (one XCD under round-robin placement: speed only)
     size_t lds = 0;
     std::vector<int> sig;      // what the plan was built for: {n, r} of every cone
@@ -852,7 +854,7 @@ int persist_build(lorads_hip_ctx *c) {
     int dev = 0, ncu_dev = 0;
     HC(hipGetDevice(&dev));
     HC(hipDeviceGetAttribute(&ncu_dev, hipDeviceAttributeMultiprocessorCount, dev)); // (hipGetDeviceProperties takes milliseconds)
-    const int force_rows = getenv("LORADS_PERSIST_ROWS") ? atoi(getenv("LORADS_PERSIST_ROWS")) : 0; // (measurements)
+    const int force_rows = c->opt_persist_rows; // (LORADS_PERSIST_ROWS: measurements and tests)
     const int cand[3] = {1, 2, 4};
     for (int ci = 0; ci < 3 && !P.valid; ++ci) {
         const int rows = cand[ci];
@@ -896,12 +898,11 @@ int persist_build(lorads_hip_ctx *c) {
       // through that L2.  Possible when every team fits the CUs of one XCD and the teams can be dealt so that no XCD is overbooked
       // (largest first to the emptiest XCD); otherwise the blocks are dealt team by team and a team's workgroups of one residue
       // class mod 8 form its sub-teams (LORADS_PERSIST_MAP=linear forces that)
-        const char *mpe = getenv("LORADS_PERSIST_MAP");
         const int cap_x = P.occ * (P.ncu / 8);
         std::vector<int> order(c->nb), load(8, 0), xcd_of(c->nb, 0);
         for (int k = 0; k < c->nb; ++k) order[k] = k;
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cones[a].G > cones[b].G; });
-        bool ok = !(mpe && mpe[0] == 'l') && P.ncu % 8 == 0;
+        bool ok = !c->opt_persist_linear && P.ncu % 8 == 0;
         for (int k : order) {
             int x = 0;
             for (int y = 1; y < 8; ++y) if (load[y] < load[x]) x = y;
@@ -927,6 +928,7 @@ int persist_build(lorads_hip_ctx *c) {
         for (size_t b = 0; b < blocks.size(); ++b)
             if (blocks[b].first >= 0) cls_members[blocks[b].first][b % 8].push_back((int)b);
         for (size_t b = 0; b < blocks.size(); ++b) map[b] = PMap{-1, 0, 0, 0, 0, 0, (int)(b % 8), 0};
+        P.g_max = 0; P.nsub_max = 0; P.ssz_max = 0;
         for (int k = 0; k < c->nb; ++k) {
             int sid = 0, soff = 0;
             for (int x = 0; x < 8; ++x) {
@@ -936,8 +938,11 @@ int persist_build(lorads_hip_ctx *c) {
                     map[mem[i]] = PMap{k, blocks[mem[i]].second, (int)i, (int)mem.size(), sid, soff, (int)(mem[i] % 8), 0};
                 soff += (int)mem.size();
                 ++sid;
+                P.ssz_max = std::max(P.ssz_max, (int)mem.size());
             }
             cones[k].nsub = sid;
+            P.g_max = std::max(P.g_max, cones[k].G);
+            P.nsub_max = std::max(P.nsub_max, sid);
         }
     }
     size_t words = 0;

@@ -562,6 +562,21 @@ class Session:
         _check(lib.lorads_hip_persist_stats(ctx, out), "persist_stats")
         return dict(zip(["iterations", "available", "workgroups", "rows", "column_steps", "lds_bytes"], [int(out[i]) for i in range(6)]))
 
+    def hip_persist_plan(self):
+        """the host's plan of the one-launch ADMM iteration: {next tag (-1: no valid plan), xcd_map (every team on one XCD's blocks; 0: dealt team by team),
+        largest team, most sub-teams of a team, largest sub-team, workgroups per CU counted on, CUs, allow_l2}"""
+        lib, ctx = self._hip()
+        out = (C.c_int64 * 8)()
+        lib.lorads_hip_persist_plan.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_persist_plan(ctx, out), "persist_plan")
+        return dict(zip(["tag", "xcd_map", "team", "sub_teams", "sub_team", "occ", "ncu", "allow_l2"], [int(out[i]) for i in range(8)]))
+
+    def hip_persist_set_tag(self, tag):
+        """measurement: the 32-bit tag the next one-launch iteration starts from (refused when no plan is valid)"""
+        lib, ctx = self._hip()
+        lib.lorads_hip_persist_set_tag.argtypes = [C.c_void_p, C.c_uint32]
+        _check(lib.lorads_hip_persist_set_tag(ctx, int(tag)), "persist_set_tag")
+
     def hip_launch_count(self):
         """kernels this context has enqueued so far"""
         lib, ctx = self._hip()

@@ -247,23 +247,27 @@ class AdmmModel:
         return its, p, d, e, log
 
 
-def stopping_tol(model, rho, js, maxit, ratio=1.5, margin=1.05):
+def stopping_tol(model, rho, js, maxit, ratio=1.5, margin=1.05, probe_maxit=None):
     """A tolerance that stops some solve of the next sweep after exactly j iterations, for the first j of `js` that has one: the
     geometric mean of that solve's smallest residual before iteration j and its residual after iteration j, taken only where they
     differ by >= `ratio` (CG residuals need not decrease).  Checked on a copy of the model over the whole sweep: no solve may have a
     residual within a factor `margin` of it before it stops (rounding cannot then move a stop), and no solve may pass on its initial
-    residual.  Returns (tol, j, index of that solve in the sweep), or None when no such tolerance exists."""
+    residual.  probe_maxit: the model's sweeps run at most that many iterations per solve, whatever `maxit` is, and EVERY solve must
+    stop by the tolerance before them -- the tolerance then holds for any iteration limit from probe_maxit on (a limit of thousands,
+    which no solve may come near).  Returns (tol, j, index of that solve in the sweep), or None when no such tolerance exists."""
     import copy
+    run = maxit if probe_maxit is None else min(maxit, probe_maxit)
     probe = copy.deepcopy(model)
-    _, log = probe.sweep(rho, 0.0, maxit)
+    _, log = probe.sweep(rho, 0.0, run)
     for j in js:
         for idx, (_, _, _, hist) in enumerate(log):
             if len(hist) <= j or min(hist[:j]) < ratio * hist[j]:
                 continue
             tol = float(np.sqrt(min(hist[:j]) * hist[j]))
             probe = copy.deepcopy(model)
-            _, log2 = probe.sweep(rho, tol, maxit)
+            _, log2 = probe.sweep(rho, tol, run)
             if len(log2) > idx and log2[idx][2] == j and all(
-                    h[0] >= tol and not any(tol / margin < x < tol * margin for x in h) for _, _, _, h in log2):
+                    h[0] >= tol and not any(tol / margin < x < tol * margin for x in h) for _, _, _, h in log2) and (
+                    probe_maxit is None or all(h[-1] < tol for _, _, _, h in log2)):
                 return tol, j, idx
     return None

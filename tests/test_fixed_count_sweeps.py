@@ -25,6 +25,8 @@ RHO = 1.5
 # worst rel-to-scale error measured on the MI355X over all cases of a group (factors / m-vectors / scalars), and its bound
 BOUNDS = {
     "default": 1e-12,  # measured 1.5e-13 (theta30, constraint sums); theta50 1.6e-13, hub16 1.4e-14, every other case <= 1e-14
+    # (the variants of the one-launch iteration, tests/test_one_launch_variants.py: this cap and below it max(32 x the spread of the
+    # model in float64, 1e-14) per case; measured <= 1.3e-14 (n = 4128, factors), every other case <= 4.9e-15)
 }
 
 
@@ -54,9 +56,17 @@ HEADLINE = [("step", 1, 0.0), ("sweep", 2, 0.0), ("step", 2, 0.0)]
 RANKS = [("sweep", 2, 0.0), ("step", 1, 0.0)]
 
 
-def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=None, hook=False, seed=5):
-    """runs the schedule on the device and the model; returns (session facts, worst errors by group)"""
-    path = _path(name)
+def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=None, hook=False, seed=5, path=None, tag=None,
+             stamps=False, spread=False):
+    """runs the schedule on the device and the model; returns (session facts, worst errors by group).
+    path: the instance's file where `name` is no named one.  A schedule entry may carry a fourth field "fixed": its maxit stays
+    what it says whatever tolerance the model finds (the tolerance is then looked for among the first iterations only, and every
+    solve of the sweep must stop by it).  tag: the one-launch form's next tag (lorads_hip_persist_set_tag), set once its plan
+    exists.  stamps: the one-launch form's stamps are on for the schedule and facts["l2"] holds what its latest launch decided
+    (lorads_hip_persist_stamps, word 15; None: no such launch).  spread: the same schedule also runs on the model in float64 and
+    worst["spread"] is the largest difference between the two models over every compared quantity (what the reference's own
+    arithmetic leaves open: a bound taken from it owes nothing to the device)."""
+    path = path or _path(name)
     s = _session(path, env or {}, params or {}, separable)
     try:
         calls = []
@@ -71,10 +81,29 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
         common.load_uv_state(be, U, V, lam)
         model.set_state(U, V, lam)
         worst = dict(factors=0.0, vectors=0.0, scalars=0.0)
+        m64 = None
+        if spread:
+            m64 = AdmmModel.from_file(path, dtype=np.float64)
+            m64.set_state(U, V, lam)
+            worst["spread"] = 0.0
         n0, p0 = s.hip_launch_count(), s.hip_persist_stats()["iterations"]
-        counts, stops = [], []
-        for i, (kind, maxit, tol) in enumerate(schedule):
-            if isinstance(tol, tuple):
+        if tag is not None:
+            s.hip_persist_set_tag(tag)
+        if stamps:
+            s.hip_persist_stamps(True)
+        counts, stops, persist_calls = [], [], []
+        for i, entry in enumerate(schedule):
+            kind, maxit, tol = entry[:3]
+            fixed = len(entry) > 3 and entry[3] == "fixed"
+            pnow = s.hip_persist_stats()["iterations"]
+            if isinstance(tol, tuple) and fixed:
+                # the stop is looked for among the first 40 iterations; with every solve stopped by then, maxit plays no part
+                js = tuple(j for j in tol if j not in stops) + tol
+                found = stopping_tol(model, RHO, js, maxit, probe_maxit=40) or stopping_tol(model, RHO, js, maxit, ratio=1.25, probe_maxit=40)
+                tol = found[0] if found else 0.0
+                stops.append(found[1] if found else None)
+                assert found, (name, i, "no tolerance that stops every solve early", js)
+            elif isinstance(tol, tuple):
                 pref = tol + tuple(j for j in range(1, 16) if j not in tol)
                 found = None
                 # a stop not taken yet first; a solve that never nears the tolerance runs to maxit, so a smaller maxit leaves fewer
@@ -100,7 +129,19 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
                     err = abs(x - float(y)) / max(abs(float(y)), sc, 1e-300)
                     worst["scalars"] = max(worst["scalars"], err)
             counts.append(its)
+            persist_calls.append(s.hip_persist_stats()["iterations"] - pnow)
             assert its == mits, (name, i, "CG iterations", its, mits)
+            if m64 is not None:
+                if kind == "sweep":
+                    its64, _ = m64.sweep(RHO, tol, maxit)
+                else:
+                    its64, p64, d64, e64, _ = m64.step(RHO, tol, maxit)
+                    for x, y, sc in ((p64, mp, 1.0), (d64, md, dscale), (e64, me, 0.0)):
+                        worst["spread"] = max(worst["spread"], abs(float(x) - float(y)) / max(abs(float(y)), sc, 1e-300))
+                assert its64 == mits, (name, i, "CG iterations of the model in float64", its64, mits)
+                for k in range(s.nblk):
+                    worst["spread"] = max(worst["spread"], common.rel_to_scale(m64.U[k], model.U[k]), common.rel_to_scale(m64.V[k], model.V[k]))
+                worst["spread"] = max(worst["spread"], common.rel_to_scale(m64.csum, model.csum))
             Ud = [be.get_mat(host.MAT_U, k) for k in range(s.nblk)]
             Vd = [be.get_mat(host.MAT_V, k) for k in range(s.nblk)]
             for k in range(s.nblk):
@@ -115,12 +156,19 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
             be.update_dual_var(RHO)
             model.update_dual(RHO)
             worst["vectors"] = max(worst["vectors"], common.rel_to_scale(be.get_vec(host.VEC_LAMBDA), model.lam))
+            if m64 is not None:
+                m64.update_dual(RHO)
+                worst["spread"] = max(worst["spread"], common.rel_to_scale(m64.lam, model.lam))
         # every tolerance sweep found its stop, and at different iterations where there are two (speculation over- and undershoots)
         assert all(stops), (name, "no tolerance that stops a solve at a clear iteration", stops)
         assert len(stops) < 2 or len(set(stops)) >= 2, (name, "the tolerance sweeps stop at the same iteration", stops)
         facts = dict(kinds=[s.hip_operator_kind(k) for k in range(s.nblk)], images=[s.hip_block_image(k) for k in range(s.nblk)],
                      persist=s.hip_persist_stats()["iterations"] - p0, launches=s.hip_launch_count() - n0, calls=len(calls),
-                     ranks=[s.block_shape(k)[1] for k in range(s.nblk)], stops=stops, counts=counts)
+                     ranks=[s.block_shape(k)[1] for k in range(s.nblk)], stops=stops, counts=counts, persist_calls=persist_calls,
+                     stats=s.hip_persist_stats(), plan=s.hip_persist_plan())
+        if stamps:
+            word = s.hip_persist_stamps(False)[15]
+            facts["l2"] = (word >> 1) & 3 if word & 1 else None  # bit 0: granules through the XCD's L2, bit 1: factor rows too
         print(name, env, "worst", {k: "%.2e" % v for k, v in worst.items()}, "counts", counts, "stops at", stops,
               "kinds", facts["kinds"], "launches", facts["launches"], "persist", facts["persist"])
         return facts, worst
