@@ -240,6 +240,10 @@ int lorads_hip_set_scalar_exchange(lorads_hip_ctx *ctx, lorads_hip_scalar_exchan
 int lorads_hip_selfcheck_allreduce(lorads_hip_ctx *ctx);
 
 int lorads_hip_sync(lorads_hip_ctx *ctx);
+/* the U front of the next ADMM step, enqueued behind a step's result hand-over (LORADS_SPEC_FRONT=0 switches it off): out = {fronts
+ * enqueued ahead, taken by the next lorads_hip_admm_step, discarded (the caller did something other than lorads_hip_update_dual_var
+ * and lorads_hip_admm_step with the same rho), blocked by their gate (the step's V-solve resumed: they wrote nothing)} */
+int lorads_hip_spec_front_stats(lorads_hip_ctx *ctx, int64_t out[4]);
 
 #ifdef __cplusplus
 }

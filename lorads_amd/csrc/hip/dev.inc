@@ -4,6 +4,7 @@
 // under rocprofv3 every variant shows up under its own name.  Inputs are the cone's U and V, outputs go to the CG
 // scratch vectors.  Only for the shape of the headline (r = 40); profiles/tools/ubench.py drives it.
 int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms) {
+    spec_touch(c);
     if (c->nb < 1) return fail_msg("ubench: no cone");
     Block &B = c->blk[0];
     if (which >= 100) { // single-entry cones (matrix completion): the whole-operator kernels, any rank

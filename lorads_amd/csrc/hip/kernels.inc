@@ -1180,8 +1180,11 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const do
 __global__ __launch_bounds__(TPB) void k_wsum(int nrow, int cw, const double *__restrict__ contrib, double *__restrict__ w_out, Guard g,
                                               InitArgs ia, int dual_on, DS rho_dual_s, int m_all,
                                               const double *__restrict__ b, const double *__restrict__ csum,
-                                              double *__restrict__ lambda, double *__restrict__ part_ww = nullptr) {
+                                              double *__restrict__ lambda, double *__restrict__ part_ww = nullptr,
+                                              CGState *reset = nullptr, int nreset = 0) {
     __shared__ double sh[8];
+    // (behind a front that was enqueued ahead of its step, see spec_front_enqueue: the sweep's reset words, which that front left alone)
+    if (reset && blockIdx.x == 0 && threadIdx.x < nreset) reset[threadIdx.x].done = 0;
     const Gate gt = gate_load(ia.st ? Guard{nullptr, g.need} : g);
     double iv[2] = {0.0, 0.0};
     if (ia.st) init_private(ia, iv);

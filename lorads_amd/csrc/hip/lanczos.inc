@@ -302,6 +302,7 @@ int lanczos_min_eig(lorads_hip_ctx *c, hipStream_t st, double *pinned, Block &B,
 
 extern "C" int lorads_hip_dual_infeasibility(lorads_hip_ctx *c, double tol, int32_t ncv, int32_t max_restarts, double *sum_neg,
                                              double *lam_min, int32_t *matvecs) {
+    spec_touch(c);
     if (!c || !sum_neg || ncv < 2 || tol <= 0) return fail_msg("dual_infeasibility: bad argument");
     flush_pending(c); // (a dual update still waiting for a carrier: the multipliers must be final here)
     double acc = 0.0;

@@ -626,6 +626,20 @@ struct lorads_hip_ctx {
     bool opt_front_cw = true; // k_front_cw + k_wsum instead of k_sval + k_spmm2<FRONT> + iteration 0's k_cw (LORADS_FRONT_CW=0: the latter)
     bool opt_fuse_cg0 = true; // CG iteration 0 of a front_cw_ok cone: the update inside k_spmm_ell (LORADS_FUSE_CG0=0: k_cg_update)
     bool pend_dual_virtual = false; // the pending dual update has already been USED (formed on the fly by k_front_cw) but not stored
+    // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
+    // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
+    bool opt_spec_front = true;
+    struct SpecFront {
+        bool live = false;        // a front is enqueued and its step finished in its first pass: the next admm_step may take it
+        bool dual_seen = false;   // update_dual_var has been called since (once: see there)
+        double rho = 0.0, rho_dual = 0.0; // what it guessed: the next step's rho, the rho of the dual update in between
+        int wmode = 0;
+        unsigned long long epoch = 0; // spec_epoch when it was enqueued
+        CGState *reset = nullptr; // adopted: the sweep's reset words wait for the k_wsum behind it
+        int nreset = 0;
+    } spec;
+    unsigned long long spec_epoch = 0; // bumped by spec_touch: every C-ABI entry but update_dual_var, admm_step and the statistics' own
+    long long n_spec_enq = 0, n_spec_adopt = 0, n_spec_discard = 0, n_spec_blocked = 0;
     bool opt_exact_refresh = false, opt_split_front = false; // test knobs (read at creation): see constr_by_recurrence, fused_front
     bool final_pending = false;              // an evaluation's closing sums wait for the next hand-over (k_publish_final)
     EvalFinalArgs final_args;
@@ -718,6 +732,12 @@ inline bool shard_vec(const lorads_hip_ctx *c) { return c->ar && !c->sep; }
 // the rank the kernels run at (see Block::rl): odd ranks take a zero column along; the LP block's "rank" 1 is not a factor width
 inline int dev_rank(const lorads_hip_ctx *c, int r, bool is_lp) { return (c->opt_pad_rank && !is_lp && (r & 1) && r < 512) ? r + 1 : r; }
 
+// whatever a front enqueued ahead of its step has guessed or left in scratch no longer holds: the next step launches its own
+inline void spec_touch(lorads_hip_ctx *c) {
+    if (!c) return; // (entries that refuse a null context call it first)
+    if (c->spec.live) { c->spec.live = false; ++c->n_spec_discard; }
+    ++c->spec_epoch;
+}
 inline void persist_touch(lorads_hip_ctx *c); // (persist.inc: what the one-launch iteration keeps between launches belongs to the V in memory)
 #include "build.inc"
 #include "sweep.inc"
@@ -787,6 +807,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->opt_front_cw = env_on("LORADS_FRONT_CW");
     c->opt_fuse_cg0 = env_on("LORADS_FUSE_CG0");
     c->opt_front_lds = env_on("LORADS_FRONT_LDS");
+    c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
     c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
     c->opt_tile_update = env_on("LORADS_TILE_UPDATE");
@@ -872,12 +893,14 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
 }
 
 int lorads_hip_sync(lorads_hip_ctx *c) {
+    spec_touch(c);
     flush_pending(c);
     HC(hipStreamSynchronize(c->stream));
     return 0;
 }
 
 int lorads_hip_set_allreduce(lorads_hip_ctx *c, lorads_hip_allreduce_fn fn, void *user) {
+    spec_touch(c);
     c->ar = fn;
     c->ar_user = user;
     c->ar_fast_all = -1;
@@ -885,6 +908,7 @@ int lorads_hip_set_allreduce(lorads_hip_ctx *c, lorads_hip_allreduce_fn fn, void
 }
 
 int lorads_hip_set_scalar_exchange(lorads_hip_ctx *c, lorads_hip_scalar_exchange_fn fn, void *user) {
+    spec_touch(c);
     if (!c) return fail_msg("set_scalar_exchange: no context");
     if (c->sx_pending || c->sep_pending) { // (an evaluation's sums are still on their way: finish that hand-over under the old rule first)
         if (read_states(c)) return 1;
@@ -893,6 +917,7 @@ int lorads_hip_set_scalar_exchange(lorads_hip_ctx *c, lorads_hip_scalar_exchange
     return 0;
 }
 int lorads_hip_set_separable(lorads_hip_ctx *c, int32_t on) {
+    spec_touch(c);
     flush_pending(c);
     c->sep = on != 0;
     if (c->sep && !c->sepbuf && c->mem.alloc(&c->sepbuf, 32)) return 1;
@@ -900,14 +925,16 @@ int lorads_hip_set_separable(lorads_hip_ctx *c, int32_t on) {
 }
 
 int lorads_hip_set_allreduce_stream_ordered(lorads_hip_ctx *c, int32_t on) {
+    spec_touch(c);
     c->ar_stream_ordered = on != 0;
     return 0;
 }
 
-void *lorads_hip_stream(lorads_hip_ctx *c) { return (void *)c->stream; }
+void *lorads_hip_stream(lorads_hip_ctx *c) { spec_touch(c); return (void *)c->stream; }
 
 /* all-reduce constrValSum through the registered hook (self-check of a hook / of the stream-ordered mode) */
 int lorads_hip_selfcheck_allreduce(lorads_hip_ctx *c) {
+    spec_touch(c);
     LAUNCH(k_scale, grid1d((size_t)c->m), (size_t)c->m, 1.0, c->csum); // some work on the stream before the collective
     if (c->ar && c->sep) {
         // separable shards hold different numbers of constraints: the collective is one double (constrValSum[0]), spread over the
@@ -926,6 +953,7 @@ int lorads_hip_selfcheck_allreduce(lorads_hip_ctx *c) {
 }
 
 int lorads_hip_init_constr(lorads_hip_ctx *c, int32_t pair) {
+    spec_touch(c);
     c->ls_np = 0;
     const double *X = pair == LORADS_HIP_PAIR_RR ? c->R : c->U, *Y = pair == LORADS_HIP_PAIR_RR ? c->R : c->V;
     LAUNCH(k_zero, grid1d((size_t)c->m + 2), (size_t)c->m + 2, c->csum, NOGUARD);
@@ -955,11 +983,13 @@ static int enqueue_alm_grad(lorads_hip_ctx *c, double rho, bool reduce = true) {
     return reduce ? allreduce_dev(c, c->scal + 8, 1) : 0;
 }
 int lorads_hip_alm_cal_grad(lorads_hip_ctx *c, double rho, double *lag) {
+    spec_touch(c);
     if (enqueue_alm_grad(c, rho)) return 1;
     return read_scalars(c, 8, 1, lag);
 }
 
 int lorads_hip_lbfgs_direction(lorads_hip_ctx *c, int32_t inner) {
+    spec_touch(c);
     c->merged.t_uv_valid = false;
     for (auto &B : c->blk) B.t_uv_valid = false; // U is overwritten by the direction D
     const size_t n = c->all_elem;
@@ -1098,6 +1128,7 @@ static int enqueue_q12p12(lorads_hip_ctx *c, int *defer_p12 = nullptr) {
     return shard_vec(c) ? allreduce_dev(c, c->q12, 2 * m + 2) : 0;
 }
 int lorads_hip_alm_q12p12(lorads_hip_ctx *c, double p12[2]) {
+    spec_touch(c);
     if (enqueue_q12p12(c)) return 1;
     if (c->ar && c->sep) {
         // the slot-by-slot line search that follows takes p1, p2 from the host: the summed pair goes to a buffer of its own
@@ -1126,6 +1157,7 @@ static void launch_linesearch(lorads_hip_ctx *c, double rho, int np_obj) {
            np_obj ? part_slot(c, 4) : (const double *)nullptr, np_obj ? part_slot(c, 6) : (const double *)nullptr, np_obj, c->maxpart);
 }
 int lorads_hip_alm_linesearch_coeffs(lorads_hip_ctx *c, double rho, double p1, double p2, double k[4]) {
+    spec_touch(c);
     launch_linesearch(c, rho, 0);
     if (c->ar && c->sep && allreduce_dev(c, c->scal + 16, 5)) return 1; // the five sums over every rank's constraints
     double s[5];
@@ -1135,11 +1167,13 @@ int lorads_hip_alm_linesearch_coeffs(lorads_hip_ctx *c, double rho, double p1, d
 }
 
 int lorads_hip_set_y_as_neg_grad(lorads_hip_ctx *c) {
+    spec_touch(c);
     LAUNCH(k_scale_copy, grid1d(c->all_elem), c->all_elem, -1.0, c->G, c->ring[c->head].y);
     return 0;
 }
 
 int lorads_hip_alm_update_var(lorads_hip_ctx *c, double tau) {
+    spec_touch(c);
     c->ls_np = 0;
     LAUNCH(k_axpy, grid1d(c->all_elem), c->all_elem, tau, c->U, c->R);
     LAUNCH(k_csum_step, nblocks_for((size_t)c->m, TPB), c->m, tau, c->q12, c->q12 + c->m, c->csum);
@@ -1147,6 +1181,7 @@ int lorads_hip_alm_update_var(lorads_hip_ctx *c, double tau) {
 }
 
 int lorads_hip_set_lbfgs_his_two(lorads_hip_ctx *c, double tau) {
+    spec_touch(c);
     Ring &h = c->ring[c->head];
     if (!c->ar) {
         const int g = grid_lbfgs(c->all_elem);
@@ -1178,6 +1213,7 @@ static int enqueue_alm_front(lorads_hip_ctx *c, double rho, int32_t inner, bool 
     return (c->ar && c->sep) ? allreduce_dev(c, c->scal + 16, 7) : 0;
 }
 int lorads_hip_alm_front(lorads_hip_ctx *c, double rho, int32_t inner, double out[6]) {
+    spec_touch(c);
     if (enqueue_alm_front(c, rho, inner)) return 1;
     double s[7];
     if (read_scalars(c, 16, 7, s)) return 1;
@@ -1186,6 +1222,7 @@ int lorads_hip_alm_front(lorads_hip_ctx *c, double rho, int32_t inner, double ou
     return 0;
 }
 int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_inner, double out[8]) {
+    spec_touch(c);
     Block *S1 = solo(c);
     bool team = false;
     if (S1 && !c->ar && S1->nrow == c->m && c->m > 0 && !S1->dense_c && !S1->dense_a) {
@@ -1303,6 +1340,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
 }
 
 int lorads_hip_update_dimacs(lorads_hip_ctx *c, int32_t pair, double *err1) {
+    spec_touch(c);
     if (enqueue_eval(c, pair, nullptr, false)) return 1;
     double s[3];
     if (read_scalars(c, 0, 3, s)) return 1;
@@ -1311,6 +1349,7 @@ int lorads_hip_update_dimacs(lorads_hip_ctx *c, int32_t pair, double *err1) {
 }
 
 int lorads_hip_cal_obj(lorads_hip_ctx *c, int32_t pair, double *pobj) {
+    spec_touch(c);
     if (pair == LORADS_HIP_PAIR_UV) LAUNCH(k_average, grid1d(c->all_elem), c->all_elem, c->U, c->V, c->R, NOGUARD);
     LAUNCH(k_zero, 1, (size_t)1, c->scal + 3, NOGUARD);
     std::vector<Block *> cones;
@@ -1327,6 +1366,7 @@ int lorads_hip_cal_obj(lorads_hip_ctx *c, int32_t pair, double *pobj) {
 }
 
 int lorads_hip_admm_update_var(lorads_hip_ctx *c, double rho, double tol, int32_t maxit, int32_t *iters) {
+    spec_touch(c);
     if (run_sweep(c, rho, tol, maxit, false)) return 1;
     int its = 0;
     finish_sweep(c, &its);
@@ -1349,6 +1389,8 @@ int lorads_hip_admm_step(lorads_hip_ctx *c, double rho, double tol, int32_t maxi
 
 int lorads_hip_update_dual_var(lorads_hip_ctx *c, double rho) {
     c->ls_np = 0;
+    // (a front enqueued ahead of its step has formed exactly ONE dual update on the fly: a second one finds the first stored)
+    if (c->spec.live) { if (c->spec.dual_seen) spec_touch(c); else c->spec.dual_seen = true; }
     // (see pend_dual; with sharded cones only the one-kernel front can take it: it needs no owner pairs, k_wsum stores all of lambda)
     // (lockstep sweep of a Max-Cut-type merged cone that sees every constraint: its U front takes it, see enqueue_batched)
     const bool merged_front = c->has_merged && c->opt_seg_carry_dual && c->merged.diag_only && c->merged.rc_w > 0 && c->merged.w_uv &&
@@ -1365,6 +1407,7 @@ int lorads_hip_update_dual_var(lorads_hip_ctx *c, double rho) {
 }
 
 int lorads_hip_cal_dual_obj(lorads_hip_ctx *c, double *dobj) {
+    spec_touch(c);
     const int g = std::min(grid1d((size_t)c->m), 256);
     LAUNCH(k_dot, g, (size_t)c->m, c->b, c->lambda, part_slot(c, 7), NOGUARD);
     LAUNCH(k_finalize, 1, part_slot(c, 7), g, 1.0, 0, c->scal + 4, NOGUARD);
@@ -1379,6 +1422,7 @@ static void invalidate_t(lorads_hip_ctx *c) {
 }
 
 int lorads_hip_alm_to_admm(lorads_hip_ctx *c) {
+    spec_touch(c);
     flush_pending(c);
     invalidate_t(c);
     HC(hipMemcpyAsync(c->V, c->R, sizeof(double) * c->all_elem, hipMemcpyDeviceToDevice, c->stream));
@@ -1387,6 +1431,7 @@ int lorads_hip_alm_to_admm(lorads_hip_ctx *c) {
 }
 
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *c) {
+    spec_touch(c);
     invalidate_t(c);
     LAUNCH(k_average, grid1d(c->all_elem), c->all_elem, c->U, c->V, c->R, NOGUARD);
     HC(hipMemcpyAsync(c->V, c->R, sizeof(double) * c->all_elem, hipMemcpyDeviceToDevice, c->stream));
@@ -1394,6 +1439,7 @@ int lorads_hip_average_uv_to_v(lorads_hip_ctx *c) {
 }
 
 int lorads_hip_scale_obj(lorads_hip_ctx *c, double s) {
+    spec_touch(c);
     c->ls_np = 0;
     persist_touch(c);
     for (auto &B0 : c->blk) B0.wj_for = nullptr; // (kept products C Y of a dense objective are those of the old C)
@@ -1414,6 +1460,7 @@ int lorads_hip_scale_obj(lorads_hip_ctx *c, double s) {
 }
 
 int lorads_hip_set_mat(lorads_hip_ctx *c, int32_t which, int32_t k, const double *cm) {
+    spec_touch(c);
     flush_pending(c);
     double *base = mat_base(c, which);
     if (!base || k < 0 || k >= c->nb) return fail_msg("set_mat: bad argument");
@@ -1431,6 +1478,7 @@ int lorads_hip_set_mat(lorads_hip_ctx *c, int32_t which, int32_t k, const double
 }
 
 int lorads_hip_get_mat(lorads_hip_ctx *c, int32_t which, int32_t k, double *cm) {
+    spec_touch(c);
     flush_pending(c);
     double *base = mat_base(c, which);
     if (!base || k < 0 || k >= c->nb) return fail_msg("get_mat: bad argument");
@@ -1444,6 +1492,7 @@ int lorads_hip_get_mat(lorads_hip_ctx *c, int32_t which, int32_t k, double *cm) 
 }
 
 int lorads_hip_set_vec(lorads_hip_ctx *c, int32_t which, const double *v) {
+    spec_touch(c);
     flush_pending(c);
     c->ls_np = 0;
     double *d = vec_base(c, which);
@@ -1454,6 +1503,7 @@ int lorads_hip_set_vec(lorads_hip_ctx *c, int32_t which, const double *v) {
 }
 
 int lorads_hip_get_vec(lorads_hip_ctx *c, int32_t which, double *v) {
+    spec_touch(c);
     flush_pending(c);
     double *d = vec_base(c, which);
     if (!d) return fail_msg("get_vec: bad argument");
@@ -1463,6 +1513,7 @@ int lorads_hip_get_vec(lorads_hip_ctx *c, int32_t which, double *v) {
 }
 
 int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
+    spec_touch(c);
     flush_pending(c);
     persist_touch(c);
     // AUG_RANK (data/lorads_solver.c:806-906): keep the old columns, new columns = 1/sqrt(k) on their
@@ -1507,6 +1558,7 @@ int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
 }
 
 int lorads_hip_profile(lorads_hip_ctx *c, int32_t enable, int32_t every) {
+    spec_touch(c);
     flush_pending(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
@@ -1524,12 +1576,14 @@ int lorads_hip_profile(lorads_hip_ctx *c, int32_t enable, int32_t every) {
 }
 
 int lorads_hip_profile_target(lorads_hip_ctx *c, int32_t target) {
+    spec_touch(c);
     if (target != 0 && target != 1) return fail_msg("profile_target: 0 (operator applications) or 1 (solve fronts)");
     c->prof_target = target;
     return 0;
 }
 
 int lorads_hip_profile_samples(lorads_hip_ctx *c, double *out, int32_t cap, int32_t *n) {
+    spec_touch(c);
     flush_pending(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
@@ -1539,6 +1593,7 @@ int lorads_hip_profile_samples(lorads_hip_ctx *c, double *out, int32_t cap, int3
 }
 
 int lorads_hip_profile_read(lorads_hip_ctx *c, double s[8]) {
+    spec_touch(c);
     flush_pending(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
@@ -1556,6 +1611,7 @@ int lorads_hip_profile_read(lorads_hip_ctx *c, double s[8]) {
 // `reps` applications of the live CG operator of cone 0, back to back between ONE event pair, nothing riding along (milliseconds for
 // all of them): bench.py's operator_alone_back_to_back
 int lorads_hip_time_operator(lorads_hip_ctx *c, int32_t reps, double *ms) {
+    spec_touch(c);
     if (c->nb < 1) return fail_msg("time_operator: no cone");
     Block &B = c->blk[0];
     flush_pending(c);
@@ -1587,6 +1643,7 @@ int lorads_hip_time_operator(lorads_hip_ctx *c, int32_t reps, double *ms) {
 #endif
 
 int lorads_hip_operator_kind(lorads_hip_ctx *c, int32_t k, int32_t *kind) {
+    spec_touch(c);
     if (k < 0 || k >= c->nb) return fail_msg("bad block");
     const Block &B = c->blk[k];
     *kind = B.diag_only ? 2 : B.entry_only ? 3 : B.use_cw ? 4 : B.has_gram ? 0 : 1;
@@ -1596,6 +1653,7 @@ int lorads_hip_operator_kind(lorads_hip_ctx *c, int32_t k, int32_t *kind) {
 }
 
 int lorads_hip_block_image(lorads_hip_ctx *c, int32_t k, int64_t im[16]) {
+    spec_touch(c);
     if (k < 0 || k >= c->nb) return fail_msg("bad block");
     const Block &B = c->blk[k];
     const int64_t v[16] = {B.n, B.rl, B.nrow, B.na, B.nc, B.pa.ne, B.pu.ne, B.dense_c, B.dense_a ? B.nd : 0, B.diag_only, B.entry_only,
@@ -1605,11 +1663,13 @@ int lorads_hip_block_image(lorads_hip_ctx *c, int32_t k, int64_t im[16]) {
 }
 
 int lorads_hip_scalar_exchange_count(lorads_hip_ctx *c, int64_t *n) {
+    spec_touch(c);
     *n = c->n_sx;
     return 0;
 }
 
 int lorads_hip_persist_stats(lorads_hip_ctx *c, int64_t stats[6]) {
+    spec_touch(c);
     const bool ok = c->persist && persist_ready(c, 800);
     stats[0] = c->n_persist;
     stats[1] = ok ? 1 : 0;
@@ -1621,6 +1681,7 @@ int lorads_hip_persist_stats(lorads_hip_ctx *c, int64_t stats[6]) {
 }
 
 int lorads_hip_persist_plan(lorads_hip_ctx *c, int64_t out[8]) {
+    spec_touch(c);
     const bool ok = c->persist && persist_ready(c, 800);
     const PersistPlan *P = c->persist;
     out[0] = ok ? (int64_t)P->tag : -1;
@@ -1635,6 +1696,7 @@ int lorads_hip_persist_plan(lorads_hip_ctx *c, int64_t out[8]) {
 }
 
 int lorads_hip_persist_set_tag(lorads_hip_ctx *c, uint32_t tag) {
+    spec_touch(c);
     if (!c->persist || !c->persist->valid) return fail_msg("persist_set_tag: no plan of the one-launch ADMM iteration is valid");
     PersistPlan &P = *c->persist;
     flush_pending(c);
@@ -1646,6 +1708,7 @@ int lorads_hip_persist_set_tag(lorads_hip_ctx *c, uint32_t tag) {
 }
 
 int lorads_hip_launch_count(lorads_hip_ctx *c, int64_t *n) {
+    spec_touch(c);
     *n = c->n_launch;
     return 0;
 }
@@ -1656,6 +1719,7 @@ int lorads_hip_memory_stats(int64_t stats[4]) {
 }
 
 int lorads_hip_lbfgs_team_stats(lorads_hip_ctx *c, int64_t stats[4]) {
+    spec_touch(c);
     const bool ok = c->lteam && c->lteam->valid;
     stats[0] = c->lteam ? c->lteam->launches : 0;
     stats[1] = ok ? 1 : 0;
@@ -1665,6 +1729,7 @@ int lorads_hip_lbfgs_team_stats(lorads_hip_ctx *c, int64_t stats[4]) {
 }
 
 int lorads_hip_persist_stamps(lorads_hip_ctx *c, int32_t enable, uint64_t ticks[16]) {
+    spec_touch(c);
     flush_pending(c);
     HC(hipStreamSynchronize(c->stream));
     for (int i = 0; i < 16; ++i) ticks[i] = 0;
@@ -1678,12 +1743,20 @@ int lorads_hip_persist_stamps(lorads_hip_ctx *c, int32_t enable, uint64_t ticks[
 }
 
 int lorads_hip_presolve_stats(lorads_hip_ctx *c, int64_t stats[2]) {
+    spec_touch(c);
     stats[0] = c->n_dev_patterns;
     stats[1] = c->n_checked_patterns;
     return 0;
 }
 
+int lorads_hip_spec_front_stats(lorads_hip_ctx *c, int64_t out[4]) { // (leaves a front in flight alone: tests read it between steps)
+    if (!c || !out) return fail_msg("spec_front_stats: bad argument");
+    out[0] = c->n_spec_enq; out[1] = c->n_spec_adopt; out[2] = c->n_spec_discard; out[3] = c->n_spec_blocked;
+    return 0;
+}
+
 int lorads_hip_graph_stats(lorads_hip_ctx *c, int64_t stats[4]) {
+    spec_touch(c);
     stats[0] = c->graphs ? c->graphs->n_capture : 0;
     stats[1] = c->graphs ? c->graphs->n_replay : 0;
     stats[2] = c->graphs ? (int64_t)c->graphs->map.size() : 0;
@@ -1692,6 +1765,7 @@ int lorads_hip_graph_stats(lorads_hip_ctx *c, int64_t stats[4]) {
 }
 
 int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, double *cg) {
+    spec_touch(c);
     if (k < 0 || k >= c->nb) return fail_msg("bad block");
     const Block &B = c->blk[k]; // (from the CURRENT rank: phase 1 may have grown it since the cone was built)
     const double F = 8.0 * (double)B.n * (double)B.rl; // (the problem's rank, not the padded one)

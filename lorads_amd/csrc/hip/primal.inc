@@ -256,6 +256,7 @@ int primal_args(const lorads_hip_ctx *c, int32_t src, int32_t blk, const char *w
 
 extern "C" int lorads_hip_primal_entries(lorads_hip_ctx *c, int32_t src, int32_t blk, int64_t count, const int32_t *row, const int32_t *col,
                                          double *val, const double *ref, double stats[4]) {
+    spec_touch(c);
     if (primal_args(c, src, blk, "primal_entries")) return 1;
     if (count < 0) return fail_msg("primal_entries: count " + std::to_string((long long)count) + " is negative");
     if (count > 0 && (!row || !col)) return fail_msg("primal_entries: row and col must not be NULL");
@@ -302,6 +303,7 @@ extern "C" int lorads_hip_primal_entries(lorads_hip_ctx *c, int32_t src, int32_t
 }
 
 extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t blk, int32_t ncols, const double *B, double *Y, double *T) {
+    spec_touch(c);
     if (primal_args(c, src, blk, "primal_apply")) return 1;
     if (ncols < 1 || ncols > 1024) return fail_msg("primal_apply: ncols " + std::to_string(ncols) + " is outside [1, 1024]");
     if (!B || !Y) return fail_msg("primal_apply: B and Y must not be NULL");

@@ -321,6 +321,7 @@ void rnd_eval(lorads_hip_ctx *c, int K, double *f) {
 extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                                     double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds,
                                     double *hyperplanes) {
+    spec_touch(c);
     if (!c || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) || trials < 0 || trials > RND_MAXK || max_rounds < 0 ||
         (trials > 0 && !obj))
         return fail_msg("round_pm1: bad argument");

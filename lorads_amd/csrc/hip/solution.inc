@@ -240,6 +240,7 @@ void cert_dot_into(lorads_hip_ctx *c, size_t len, const double *a, const double 
 extern "C" int lorads_hip_certificate(lorads_hip_ctx *c, int32_t src, double tol, int32_t ncv, int32_t max_restarts,
                                       double out[LORADS_HIP_CERT_N], double *lam_min, double *residual,
                                       double *lambda) {
+    spec_touch(c);
     if (!c || !out || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) || (tol > 0 && ncv < 2))
         return fail_msg("certificate: bad argument");
     if (cert_refuse_sharded(c, "certificate") || cert_alloc(c)) return 1;
@@ -314,6 +315,7 @@ extern "C" int lorads_hip_certificate(lorads_hip_ctx *c, int32_t src, double tol
 }
 
 extern "C" int lorads_hip_get_slack(lorads_hip_ctx *c, int32_t k, int64_t *nnz, int32_t *row, int32_t *col, double *val) {
+    spec_touch(c);
     if (!c || !nnz || k < 0 || k >= c->nb) return fail_msg("get_slack: bad argument");
     if (cert_refuse_sharded(c, "get_slack")) return 1;
     Block &B = c->blk[k];

@@ -349,6 +349,7 @@ void spec_shapes(const lorads_hip_ctx *c, std::vector<size_t> &off, std::vector<
 } // namespace
 
 extern "C" int lorads_hip_spectrum(lorads_hip_ctx *c, int32_t src, double *eig, double *q, int32_t *sweeps) {
+    spec_touch(c);
     if (!c || !eig || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV)) return fail_msg("spectrum: bad argument");
     if (spec_refuse_sharded(c, "spectrum")) return 3;
     const int uv = src == LORADS_HIP_PAIR_UV;
@@ -364,6 +365,7 @@ extern "C" int lorads_hip_spectrum(lorads_hip_ctx *c, int32_t src, double *eig, 
 }
 
 extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const int32_t *nr, double *eig) {
+    spec_touch(c);
     if (!c || !nr || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV)) return fail_msg("compress_rank: bad argument");
     if (spec_refuse_sharded(c, "compress_rank")) return 3;
     // (refuse before anything is touched: a refused call leaves host and device at the old ranks and the old bits)

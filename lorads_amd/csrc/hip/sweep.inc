@@ -366,8 +366,12 @@ int wsum(lorads_hip_ctx *c, Block &B, Guard g, double *part_ww = nullptr) {
     int dual_on = 0;
     if (c->pend_dual_virtual) { c->pend_dual_virtual = false; rho_dual = c->pend_dual_rho; dual_on = 1; } // this kernel stores the multipliers
     const int grid = nblocks_for((size_t)B.nrow, TPB / 8);
+    // (behind an adopted front: the sweep's reset words, see spec_front_adopt)
+    CGState *reset = c->spec.reset;
+    const int nreset = c->spec.nreset;
+    c->spec.reset = nullptr; c->spec.nreset = 0;
     LAUNCH(k_wsum, grid, B.nrow, B.cs_w, (const double *)B.w_contrib, B.w_op, g, ia, dual_on, ds_rho_dual(c, rho_dual), c->m, (const double *)c->b,
-           (const double *)c->csum, c->lambda, part_ww);
+           (const double *)c->csum, c->lambda, part_ww, reset, nreset);
     return grid;
 }
 
@@ -566,6 +570,57 @@ struct Solve {
     int tile = 0, tile_w = 0; // k_cg_update on the operator's own row tiles (see there)
 };
 
+// the one-kernel front (k_front_cw): its argument pack for weights of mode `wmode` at `rho`, no dual update on board ...
+FrontCwArgs front_cw_args(lorads_hip_ctx *c, const Block &B, double rho, int wmode) {
+    FrontCwArgs A{};
+    A.fc_ptr = B.fc_ptr; A.fc_col = B.fc_col; A.fc_val = B.fc_val; A.sl_ptr = B.cadj_ptr; A.sl_col = B.cadj_col; A.sl_con = B.cadj_con;
+    A.sl_a = B.cadj_a; A.ell_col = B.cell_col; A.ell_con = B.cell_con; A.ell_a = B.cell_a; A.ell_dst = B.cell_dst; A.sl_dst = B.cadj_dst; A.csum = c->csum; A.b = c->b;
+    A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_uv; A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = ds_rho(c, rho);
+    A.wmode = wmode;
+    A.contrib = B.w_contrib;
+    return A;
+}
+// ... and its launch for the solve `s` under gate `g`; returns its grid (= the number of partials it leaves in slots 18 and 1)
+int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Guard g, Deferred d) {
+    Block &B = *s.B;
+    double *r = c->cr + B.off, *rhs = c->rhs + B.off;
+    double *pA = part_slot(c, 18), *pB = part_slot(c, 1);
+    const int grid = nblocks_for((size_t)B.n, TPB / 8);
+    const int ns = (B.r + 15) / 16;
+    // (LAUNCH would send a virtual dual update off as its own kernel: this launch is the one that uses it)
+    const bool keep = c->pend_dual_virtual;
+    c->pend_dual_virtual = false;
+    FrontSample fs(c);
+#define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
+    // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
+#define FCWL(NSV, EWV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4>), grid, sizeof(double2) * 32 * 4 * NSV * 8, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
+    if (c->opt_front_lds && ns <= 3) {
+        if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8); else if (ns == 2) FCWL(2, 8); else FCWL(3, 8); }
+        else { if (ns == 1) FCWL(1, 16); else if (ns == 2) FCWL(2, 16); else FCWL(3, 16); }
+    } else if (B.cell_w == 8) { FCW(8) } else { FCW(16) }
+#undef FCWL
+#undef FCW
+    fs.done();
+    c->pend_dual_virtual = keep;
+    return grid;
+}
+// the host-side state behind a one-kernel front: its launch, or the adoption of one that was enqueued ahead of its step
+void front_cw_started(lorads_hip_ctx *c, const Solve &s, int grid, double tol) {
+    s.B->w0_ready = true;
+    if (c->opt_lazy_scalars) {
+        c->pend_init = InitArgs{s.st, shadow_of(c, s.st), part_slot(c, 18), part_slot(c, 1), grid, grid, ds_tol(c, tol)};
+        c->pend_init_g = s.front;
+    } else {
+        LAUNCH(k_cg_init, 1, s.st, part_slot(c, 18), grid, part_slot(c, 1), grid, ds_tol(c, tol), s.front, shadow_of(c, s.st));
+    }
+}
+// may the U front of a fresh sweep take a waiting dual update along?  (see solve_front)
+bool front_carries_dual(const lorads_hip_ctx *c, const Solve &s, int wmode) {
+    return c->pend_dual && wmode == W_ADMM && !s.front.need && !s.front.skip && c->nb == 1 && !c->pend_init.st && !c->pend_chk.st &&
+           !c->pend_dir.kind;
+}
+bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGState *reset, int nreset);
+
 // rhs = V - (C + sum_i M1_i A_i) V / rho, initial residual, state  (lorads_admm.c:432-463, lorads_cgs.c:115,149-172)
 void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGState *reset = nullptr, int nreset = 0) {
     Block &B = *s.B;
@@ -585,19 +640,14 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
             cw(c, B, s.x, s.V, 1.0, B.w_uv, (double *)nullptr, (int)CV_SET, (double *)nullptr, s.front);
             B.t_uv_valid = true;
         }
-        FrontCwArgs A{};
-        A.fc_ptr = B.fc_ptr; A.fc_col = B.fc_col; A.fc_val = B.fc_val; A.sl_ptr = B.cadj_ptr; A.sl_col = B.cadj_col; A.sl_con = B.cadj_con;
-        A.sl_a = B.cadj_a; A.ell_col = B.cell_col; A.ell_con = B.cell_con; A.ell_a = B.cell_a; A.ell_dst = B.cell_dst; A.sl_dst = B.cadj_dst; A.csum = c->csum; A.b = c->b;
-        A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_uv; A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = ds_rho(c, rho);
-        A.wmode = c->virt_refresh ? W_ADMM_V : W_ADMM;
+        if (spec_front_adopt(c, s, rho, tol, reset, nreset)) return;
+        FrontCwArgs A = front_cw_args(c, B, rho, c->virt_refresh ? W_ADMM_V : W_ADMM);
         c->virt_refresh = false;
-        A.contrib = B.w_contrib; A.reset = reset; A.nreset = nreset;
+        A.reset = reset; A.nreset = nreset;
         // a dual update that is still waiting is used on the fly by the ungated first kernel of the sweep of a cone that sees
         // every constraint, and stored by the k_wsum that follows (or by k_dual_update if anything else comes first)
         // (sharded: the cone sees its own constraints only -- the front needs no others -- and k_wsum updates the whole vector)
-        const bool carry_dual = c->pend_dual && A.wmode == W_ADMM && !s.front.need && !s.front.skip && c->nb == 1 &&
-                                !c->pend_init.st && !c->pend_chk.st && !c->pend_dir.kind;
-        if (carry_dual) {
+        if (front_carries_dual(c, s, A.wmode)) {
             c->pend_dual = false;
             c->pend_dual_virtual = true;
             A.rho_dual = ds_rho_dual(c, c->pend_dual_rho);
@@ -606,31 +656,7 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         // a waiting convergence test whose gate is this kernel's gate rides on it (the V-solve's front after a virtual refresh)
         const Deferred d = (c->pend_chk.st && !c->pend_init.st && !c->pend_dir.kind && !s.front.skip && s.front.need == &c->pend_chk.st->done)
                                ? take_check(c) : Deferred{};
-        const int grid = nblocks_for((size_t)B.n, TPB / 8);
-        const int ns = (B.r + 15) / 16;
-        { // (LAUNCH would send a virtual dual update off as its own kernel: this launch is the one that uses it)
-            const bool keep = c->pend_dual_virtual;
-            c->pend_dual_virtual = false;
-            FrontSample fs(c);
-#define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, s.front, d))
-            // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
-#define FCWL(NSV, EWV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4>), grid, sizeof(double2) * 32 * 4 * NSV * 8, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, s.front, d)
-            if (c->opt_front_lds && ns <= 3) {
-                if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8); else if (ns == 2) FCWL(2, 8); else FCWL(3, 8); }
-                else { if (ns == 1) FCWL(1, 16); else if (ns == 2) FCWL(2, 16); else FCWL(3, 16); }
-            } else if (B.cell_w == 8) { FCW(8) } else { FCW(16) }
-#undef FCWL
-#undef FCW
-            fs.done();
-            c->pend_dual_virtual = keep;
-        }
-        B.w0_ready = true;
-        if (c->opt_lazy_scalars) {
-            c->pend_init = InitArgs{s.st, shadow_of(c, s.st), pA, pB, grid, grid, ds_tol(c, tol)};
-            c->pend_init_g = s.front;
-        } else {
-            LAUNCH(k_cg_init, 1, s.st, pA, grid, pB, grid, ds_tol(c, tol), s.front, shadow_of(c, s.st));
-        }
+        front_cw_started(c, s, launch_front_cw(c, s, A, s.front, d), tol);
         return;
     }
     if (fused_front(c, B)) {
@@ -909,6 +935,52 @@ Solve make_solve(lorads_hip_ctx *c, int k, int half, const int *need) {
         if (g <= c->maxpart && rows * B.r >= TPB / 2) { s.gv = g; s.tile = rows * B.r; s.tile_w = rows; }
     }
     return s;
+}
+
+// ---- the U front of the NEXT ADMM step, enqueued behind this step's hand-over (LORADS_SPEC_FRONT, DESIGN.md 4)
+// Between the hand-over kernel and the next step's first kernel the GPU waits for the host: the flag's way to the host, the caller's
+// stop decisions, update_dual_var, the next enqueue.  The next step's U front reads U, V, csum, cv, w_uv, b, lambda, rho and the
+// dual step -- all final once the evaluation has run -- and writes scratch alone (cr, rhs, w_contrib, partial slots 18 and 1; the
+// dual update it forms on the fly is stored later, by k_wsum).  So it is enqueued now, on the guess that the host goes on as
+// lrd_admm_optimize does between two steps: update_dual_var(rho), admm_step(rho).  Anything else (spec_touch) leaves its output unused.
+// May this step, whose sweep and evaluation are about to be enqueued, be followed by such a front?
+bool spec_front_ok(lorads_hip_ctx *c) {
+    if (!c->opt_spec_front || !c->use_publish || c->ar || c->nb != 1 || !c->opt_lazy_scalars || !c->lambda_alt) return false;
+    if (c->prof && c->prof_every < (1 << 20)) return false; // (a window that times launches between events: nothing runs differently in it)
+    return front_cw_ok(c, c->blk[0]) && !c->blk[0].is_lp;
+}
+void spec_front_enqueue(lorads_hip_ctx *c, double rho) {
+    Block &B = c->blk[0];
+    if (!B.t_uv_valid || c->pend_dual || c->pend_dual_virtual) return;
+    const Solve s = make_solve(c, 0, 0, nullptr);
+    FrontCwArgs A = front_cw_args(c, B, rho, W_ADMM);
+    A.dual_on = 1;
+    A.rho_dual = ds_rho_dual(c, rho);
+    // gated like the evaluation: if this step's V-solve missed its speculation the resume still needs cr and rhs, and a blocked
+    // front writes nothing.  No reset words: they would shut the very gate it waits at (the k_wsum behind it takes them).
+    launch_front_cw(c, s, A, Guard{nullptr, &c->st[2 * c->nb - 1].done}, Deferred{});
+    c->spec.live = true; c->spec.dual_seen = false;
+    c->spec.rho = rho; c->spec.rho_dual = rho; c->spec.wmode = W_ADMM; c->spec.epoch = c->spec_epoch;
+    ++c->n_spec_enq;
+}
+// stage 0 of a fresh sweep: take the front that is already there instead of launching one?
+bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGState *reset, int nreset) {
+    if (!c->spec.live) return false;
+    c->spec.live = false;
+    Block &B = *s.B;
+    const bool ok = s.st == c->st && reset && !c->par_mode && c->spec.epoch == c->spec_epoch && memcmp(&rho, &c->spec.rho, sizeof(double)) == 0 &&
+                    c->spec.dual_seen && c->pend_dual && memcmp(&c->pend_dual_rho, &c->spec.rho_dual, sizeof(double)) == 0 && !c->virt_refresh &&
+                    c->spec.wmode == W_ADMM && front_carries_dual(c, s, W_ADMM) && B.t_uv_valid && c->opt_lazy_scalars &&
+                    B.spec[0] >= 1; // (iteration 0 is enqueued: its k_wsum is the next launch and takes the reset words)
+    if (!ok) { ++c->n_spec_discard; return false; }
+    ++c->n_spec_adopt;
+    c->pend_dual = false;
+    c->pend_dual_virtual = true;
+    c->virt_refresh = false;
+    c->spec.reset = reset; c->spec.nreset = nreset;
+    c->n_front++; // (as the launch would have counted it)
+    front_cw_started(c, s, nblocks_for((size_t)B.n, TPB / 8), tol);
+    return true;
 }
 
 // the LP block's ADMM update (see k_lp_sweep); st = the block's two stage states
@@ -1443,15 +1515,18 @@ bool persist_ready(lorads_hip_ctx *c, int maxit);
 int run_sweep_persist(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_eval);
 int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_eval) {
     // every cone of Max-Cut type with separable constraints: the whole iteration is ONE launch (persist.inc)
-    if (persist_ready(c, maxit)) return run_sweep_persist(c, rho, tol, maxit, with_eval);
+    if (persist_ready(c, maxit)) { spec_touch(c); return run_sweep_persist(c, rho, tol, maxit, with_eval); }
     persist_touch(c);
     // (no cross-rank sum inside the sweep: with sharded cones the lockstep form works unchanged)
-    if (c->has_merged && !getenv("LORADS_NO_BATCH")) return run_sweep_batched(c, rho, tol, maxit, with_eval);
+    if (c->has_merged && !getenv("LORADS_NO_BATCH")) { spec_touch(c); return run_sweep_batched(c, rho, tol, maxit, with_eval); }
     int first = 0, resume = -1;
     bool first_pass = true, any_missed = false;
     const bool graph = graph_this_step(c, rho, tol, maxit);
     if (graph && set_step_params(c, rho, tol, maxit)) return 1;
     ParMode pm(c, graph);
+    if (graph || maxit < 1) spec_touch(c); // (a replayed chain has its own front)
+    // an admm_step that is enqueued launch by launch: the next step's U front goes behind its hand-over (see spec_front_enqueue)
+    const bool spec = with_eval && !graph && spec_front_ok(c);
     for (;;) {
         // With sharded cones the evaluation contains the all-reduce, a collective every rank must enter the same
         // number of times, whatever its own speculation did.  Every rank enters it once in the first pass, and the
@@ -1470,10 +1545,12 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
             std::vector<uint64_t> key{1, (uint64_t)with_eval, (uint64_t)maxit, (uint64_t)((c->n_sweeps % 32) == 31)};
             if (graph_step(c, key, enq)) return 1;
         } else if (enq()) return 1;
+        if (spec && first_pass) spec_front_enqueue(c, rho);
         if (c->use_publish ? wait_publish(c) : read_states(c)) return 1;
         if (eval_now && c->ar) any_missed = c->h_scal[5] > 0.5;
-        first_pass = false;
         const int stg = first_unfinished(c, first);
+        if (first_pass && c->spec.live && stg >= 0) { c->spec.live = false; ++c->n_spec_blocked; } // (its gate was shut: it wrote nothing)
+        first_pass = false;
         if (stg < 0) break;
         first = stg;
         resume = c->h_st[stg].iter;

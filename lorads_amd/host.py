@@ -545,6 +545,14 @@ class Session:
                 "has_gram", "front_cw", "slot_width", "bip_rows0"]
         return dict(zip(keys, [int(out[i]) for i in range(16)]))
 
+    def hip_spec_front_stats(self):
+        """{enqueued, adopted, discarded, blocked} of the next step's U front enqueued behind a step's hand-over (LORADS_SPEC_FRONT)"""
+        lib, ctx = self._hip()
+        out = (C.c_int64 * 4)()
+        lib.lorads_hip_spec_front_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_spec_front_stats(ctx, out), "spec_front_stats")
+        return dict(zip(["enqueued", "adopted", "discarded", "blocked"], [int(out[i]) for i in range(4)]))
+
     def hip_graph_stats(self):
         """{captured, replayed, held, enabled} of the launch-chain replay (hipGraph) of this context"""
         lib, ctx = self._hip()
