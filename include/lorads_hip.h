@@ -203,6 +203,23 @@ int lorads_hip_primal_entries(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int
                               double *val, const double *ref, double stats[4]);
 int lorads_hip_primal_apply(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int32_t ncols, const double *B, double *Y, double *T);
 
+/* Separation of the triangle inequalities of a +-1-structured context (no reference counterpart).  With F the
+ * factor lorads_hip_certificate takes (src) of SDP cone blk at its own rank, t as lorads_hip_round_pm1 derives it and
+ * rho_xy = (F_x . F_y) / (t_x t_y), every triple p < q < s has four inequalities, class 0..3:
+ *     rho_pq + rho_ps + rho_qs >= -1,   rho_pq - rho_ps - rho_qs >= -1,   -rho_pq + rho_ps - rho_qs >= -1,   -rho_pq - rho_ps + rho_qs >= -1
+ * and v = -1 - lhs is the violation, evaluated on the device in one fixed order of operations.
+ *   count: the exact number of (triple, class) pairs with v > min_violation among all 4 C(n, 3) (X is never formed);
+ *   p, q, s, cls, viol [max_cuts]: the *kept = min(count, max_cuts) largest pairs in the total order "v descending, then p, q, s, class
+ *     ascending" (0-based rows), written in that order -- exact with respect to the device's v whatever ties at the cut-off;
+ *   max_cuts = 0 counts only (the five arrays and kept may then be NULL); passes (may be NULL): enumeration passes that ran.
+ * Read-only on the solver's state and deterministic (no float atomics; the same state and arguments give the same bits and list).
+ * Scratch: the packed factor, max_cuts + 16384 keys rounded up to a power of two, one histogram.
+ * Returns 1 on a bad argument (src, blk out of range or the LP block, max_cuts outside [0, 2^20], min_violation negative or not finite,
+ * a required array NULL), 3 on a sharded context, 2 with lorads_hip_round_pm1's reason when the context is not +-1-structured -- all
+ * before any device work.  n < 3: count 0, nothing is launched. */
+int lorads_hip_triangle_cuts(lorads_hip_ctx *ctx, int32_t src, int32_t blk, double min_violation, int32_t max_cuts, int64_t *count,
+                             int32_t *p, int32_t *q, int32_t *s, int8_t *cls, double *viol, int32_t *kept, int32_t *passes);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

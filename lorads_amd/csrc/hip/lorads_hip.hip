@@ -528,6 +528,17 @@ struct PrimalScratch {
     void release() { mem.release(); *this = PrimalScratch{}; }
 };
 
+// scratch of the triangle-inequality separation (cuts.inc): allocated on first use, grown on demand, never read by the solve.
+// O(n r) for the packed factor, max_cuts + a fixed slack (rounded up to a power of two) keys, one histogram.
+struct CutScratch {
+    double *Fp = nullptr, *tp = nullptr;                   // F zero-padded to whole tiles and steps of 4 columns, t padded with ones
+    unsigned long long *khi = nullptr, *klo = nullptr;     // the emitted keys: bit pattern of v, complement of the packed index
+    unsigned long long *ctl = nullptr;                     // [0] violated pairs, [1] emitted keys, [2..] the histogram of a digit
+    size_t fp_cap = 0, tp_cap = 0, khi_cap = 0, klo_cap = 0;
+    DevPool mem;
+    void release() { mem.release(); *this = CutScratch{}; }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -540,6 +551,7 @@ struct lorads_hip_ctx {
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
+    CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -884,6 +896,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->rnd.release();
     c->spectral.release();
     c->primal.release();
+    c->cuts.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -1781,3 +1794,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "rounding.inc"
 #include "spectral.inc"
 #include "primal.inc"
+#include "cuts.inc"

@@ -1,0 +1,169 @@
+/* cuts.c -- separation of the triangle inequalities of a +-1-structured problem and the tightened problem file (DESIGN.md
+ * section 14).  The enumeration is the backend's (lrd_backend.triangle_cuts); here: the session-level driver that merges the cones'
+ * lists, and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem image and
+ * the cut list (so the format can be checked without a GPU). */
+#include "lorads_host.h"
+
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+lrd_problem *lrd_session_problem(lrd_session *s);
+lrd_solver *lrd_session_solver(lrd_session *s);
+lrd_backend *lrd_session_backend(lrd_session *s);
+
+/* coefficients of rho_pq, rho_ps, rho_qs in the four classes */
+static const int cut_sign[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
+
+void lrd_cuts_free(lrd_cuts *c) {
+    if (!c) return;
+    free(c->count); free(c->cone); free(c->p); free(c->q); free(c->s); free(c->cls); free(c->viol);
+    free(c);
+}
+
+/* is a before b in (v descending, cone, p, q, s, class ascending)? */
+static int cut_before(const lrd_cuts *c, int a, int b) {
+    if (c->viol[a] != c->viol[b]) return c->viol[a] > c->viol[b];
+    if (c->cone[a] != c->cone[b]) return c->cone[a] < c->cone[b];
+    if (c->p[a] != c->p[b]) return c->p[a] < c->p[b];
+    if (c->q[a] != c->q[b]) return c->q[a] < c->q[b];
+    if (c->s[a] != c->s[b]) return c->s[a] < c->s[b];
+    return c->cls[a] < c->cls[b];
+}
+
+int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts, lrd_cuts **out) {
+    *out = NULL;
+    lrd_solver *v = lrd_session_solver(s);
+    lrd_backend *be = lrd_session_backend(s);
+    if (!v || !be) return 1;
+    if (!be->triangle_cuts) {
+        fprintf(stderr, "lorads: the %s backend cannot separate triangle inequalities\n", be->name ? be->name : "attached");
+        return 2;
+    }
+    const lrd_problem *pr = lrd_session_problem(s);
+    if (pr->separable || pr->nblk != pr->nblk_global || v->allreduce) {
+        fprintf(stderr, "lorads: the separation of a sharded deal (world > 1) is not supported\n");
+        return 3;
+    }
+    const int nb = pr->nblk, cap = max_cuts > 0 ? max_cuts : 1;
+    lrd_cuts *c = (lrd_cuts *)calloc(1, sizeof *c);
+    c->nblk = nb;
+    c->src = v->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    c->min_violation = min_violation;
+    c->max_cuts = max_cuts;
+    c->count = (int64_t *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int64_t));
+    /* room for the merged list and one cone's list behind it */
+    c->cone = (int *)calloc(2 * (size_t)cap, sizeof(int));
+    c->p = (int *)calloc(2 * (size_t)cap, sizeof(int));
+    c->q = (int *)calloc(2 * (size_t)cap, sizeof(int));
+    c->s = (int *)calloc(2 * (size_t)cap, sizeof(int));
+    c->cls = (int8_t *)calloc(2 * (size_t)cap, sizeof(int8_t));
+    c->viol = (double *)calloc(2 * (size_t)cap, sizeof(double));
+    int *order = (int *)malloc(2 * (size_t)cap * sizeof(int)), *tmp = (int *)malloc(2 * (size_t)cap * sizeof(int));
+    int8_t *tmp8 = (int8_t *)malloc(2 * (size_t)cap);
+    double *tmpd = (double *)malloc(2 * (size_t)cap * sizeof(double));
+    int rc = 0;
+    for (int k = 0; k < nb && !rc; ++k) {
+        const int at = c->kept;
+        int got = 0, np = 0;
+        rc = be->triangle_cuts(be->ctx, c->src, k, min_violation, max_cuts, &c->count[k], c->p + at, c->q + at, c->s + at, c->cls + at,
+                               c->viol + at, &got, &np);
+        if (rc) break;
+        c->passes += np;
+        for (int e = 0; e < got; ++e) c->cone[at + e] = k;
+        /* two sorted runs [0, at) and [at, at + got): merge, keep max_cuts */
+        int i = 0, j = at, n = 0;
+        const int tot = at + got, keep = tot < max_cuts ? tot : max_cuts;
+        while (n < keep) {
+            if (j >= tot || (i < at && cut_before(c, i, j))) order[n++] = i++;
+            else order[n++] = j++;
+        }
+#define CUT_PERMUTE(arr, t)                                   \
+    do {                                                      \
+        for (int e = 0; e < keep; ++e) (t)[e] = (arr)[order[e]]; \
+        memcpy((arr), (t), sizeof(*(arr)) * (size_t)keep);    \
+    } while (0)
+        CUT_PERMUTE(c->cone, tmp); CUT_PERMUTE(c->p, tmp); CUT_PERMUTE(c->q, tmp); CUT_PERMUTE(c->s, tmp);
+        CUT_PERMUTE(c->cls, tmp8); CUT_PERMUTE(c->viol, tmpd);
+#undef CUT_PERMUTE
+        c->kept = keep;
+    }
+    free(order); free(tmp); free(tmp8); free(tmpd);
+    if (rc) { lrd_cuts_free(c); return rc; }
+    *out = c;
+    return 0;
+}
+
+/* t_p = sqrt(b_i / a_i) of the one constraint a_i X[p,p] = b_i on diagonal p of cone k; 0 where no such constraint is found */
+static double *cone_t(const lrd_problem *pr, int k) {
+    const lrd_block *b = &pr->blk[k];
+    double *t = (double *)calloc((size_t)(b->n > 0 ? b->n : 1), sizeof(double));
+    for (int i = 0; i < b->nrow; ++i) {
+        if (b->a_ptr[i + 1] - b->a_ptr[i] != 1) continue;
+        const int e = b->a_ptr[i];
+        if (b->a_row[e] != b->a_col[e]) continue;
+        const double ratio = pr->b[b->row_idx[i]] / b->a_val[e];
+        if (ratio > 0 && isfinite(ratio)) t[b->a_row[e]] = sqrt(ratio);
+    }
+    return t;
+}
+
+int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts) {
+    const lrd_problem *pr = lrd_session_problem(s);
+    if (!pr || !path) return 1;
+    if (pr->separable || pr->nblk != pr->nblk_global) return 3;
+    const int ncut = cuts ? cuts->kept : 0, nb = pr->nblk;
+    for (int k = 0; k < nb && ncut > 0; ++k)
+        if (pr->blk[k].is_lp) {
+            fprintf(stderr, "lorads: a problem with an LP block cannot take cuts\n");
+            return 2;
+        }
+    double **t = (double **)calloc((size_t)(nb > 0 ? nb : 1), sizeof(double *));
+    int bad = 0;
+    for (int e = 0; e < ncut && !bad; ++e) {
+        const int k = cuts->cone[e], p = cuts->p[e], q = cuts->q[e], r = cuts->s[e];
+        if (k < 0 || k >= nb || !(0 <= p && p < q && q < r && r < pr->blk[k].n) || cuts->cls[e] < 0 || cuts->cls[e] > 3) { bad = 1; break; }
+        if (!t[k]) t[k] = cone_t(pr, k);
+        if (!(t[k][p] > 0) || !(t[k][q] > 0) || !(t[k][r] > 0)) bad = 2;
+    }
+    FILE *f = bad ? NULL : fopen(path, "w");
+    if (!f) {
+        if (bad) fprintf(stderr, bad == 1 ? "lorads: a cut is outside the problem\n" : "lorads: a cut names a row whose diagonal no constraint fixes\n");
+        for (int k = 0; k < nb; ++k) free(t[k]);
+        free(t);
+        return bad ? 2 : 1;
+    }
+    fprintf(f, "%d\n%d\n", pr->m + ncut, nb + (ncut > 0 ? 1 : 0));
+    for (int k = 0; k < nb; ++k) fprintf(f, "%s%d", k ? " " : "", pr->blk[k].is_lp ? -pr->blk[k].n : pr->blk[k].n);
+    if (ncut > 0) fprintf(f, " %d", -ncut);
+    fputc('\n', f);
+    for (int i = 0; i < pr->m; ++i) fprintf(f, "%s%.17g", i ? " " : "", pr->b[i]);
+    for (int e = 0; e < ncut; ++e) fprintf(f, "%s-1", pr->m + e ? " " : "");
+    fputc('\n', f);
+    /* the stored entries: lower triangle inside, upper triangle (i <= j) in the file; F0 = -C */
+    for (int k = 0; k < nb; ++k) {
+        const lrd_block *b = &pr->blk[k];
+        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
+    }
+    for (int k = 0; k < nb; ++k) {
+        const lrd_block *b = &pr->blk[k];
+        for (int i = 0; i < b->nrow; ++i)
+            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1]; ++e)
+                fprintf(f, "%d %d %d %d %.17g\n", b->row_idx[i] + 1, k + 1, b->a_col[e] + 1, b->a_row[e] + 1, b->a_val[e]);
+    }
+    /* the cuts: sum of sign_xy X_xy / (t_x t_y) - slack = -1; an off-diagonal entry counts twice in <A, X> */
+    for (int e = 0; e < ncut; ++e) {
+        const int k = cuts->cone[e], x[3] = {cuts->p[e], cuts->q[e], cuts->s[e]};
+        const int *sg = cut_sign[cuts->cls[e]];
+        const int pair[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+        for (int w = 0; w < 3; ++w) {
+            const int a = x[pair[w][0]], c = x[pair[w][1]];
+            fprintf(f, "%d %d %d %d %.17g\n", pr->m + e + 1, k + 1, a + 1, c + 1, (double)sg[w] / (2.0 * (t[k][a] * t[k][c])));
+        }
+        fprintf(f, "%d %d %d %d -1\n", pr->m + e + 1, nb + 1, e + 1, e + 1);
+    }
+    for (int k = 0; k < nb; ++k) free(t[k]);
+    free(t);
+    return fclose(f) ? 1 : 0;
+}

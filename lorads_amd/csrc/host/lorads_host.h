@@ -173,6 +173,11 @@ typedef struct lrd_backend {
     int (*primal_entries)(void *ctx, int src, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
                           double *stats);
     int (*primal_apply)(void *ctx, int src, int blk, int ncols, const double *B, double *Y, double *T);
+    /* OPTIONAL (before the spectral pair for the same reason): separation of the triangle inequalities of one SDP cone of a
+     * +-1-structured context, read-only on the state (include/lorads_hip.h: lorads_hip_triangle_cuts, the same arguments and
+     * return codes) */
+    int (*triangle_cuts)(void *ctx, int src, int blk, double min_violation, int max_cuts, int64_t *count, int *p, int *q, int *s,
+                         int8_t *cls, double *viol, int *kept, int *passes);
     /* OPTIONAL pair (both or neither): spectrum of the factors and their reduction to a lower rank (include/lorads_hip.h:
      * lorads_hip_spectrum, lorads_hip_compress_rank, the same arguments and return codes) */
     int (*spectrum)(void *ctx, int src, double *eig, double *q, int *sweeps);
@@ -394,6 +399,30 @@ int lrd_entries_group(const lrd_entries *q, int nblk, int64_t *perm, int64_t *st
 /* the values of all queries: grouped per block for the backend's calls, the file order restored.  1: a block index out of range, else
  * as lrd_session_primal_entries */
 int lrd_session_entries(lrd_session *s, lrd_entries *q);
+
+/* ---- triangle inequalities of +-1-structured problems (cuts.c).  With rho_xy = X_xy / (t_x t_y) (t as the
+ * rounding's) every triple p < q < s of a cone has four inequalities sign . (rho_pq, rho_ps, rho_qs) >= -1, class 0..3 with the signs
+ * (+,+,+), (+,-,-), (-,+,-), (-,-,+); v = -1 - lhs > 0 is a violation. */
+typedef struct {
+    int nblk, src;              /* src: LRD_PAIR_UV or LRD_PAIR_RR, where F came from */
+    double min_violation;
+    int max_cuts;
+    int64_t *count;             /* [nblk] pairs (triple, class) with v > min_violation per cone, exact */
+    int kept, passes;           /* cuts listed (<= max_cuts in total); enumeration passes of all cones */
+    int *cone, *p, *q, *s;      /* [kept] 0-based, ordered by (v descending, cone, p, q, s, class ascending) */
+    int8_t *cls;
+    double *viol;
+} lrd_cuts;
+/* F = (U+V)/2 in phase 2, the phase-1 R otherwise; the slot once per SDP cone, the cones' lists merged.  Returns 2 when the table
+ * lacks the slot or the context is not +-1-structured, 3 on a sharded deal, else the backend's code. */
+int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts, lrd_cuts **out);
+void lrd_cuts_free(lrd_cuts *c);
+/* The problem of the session as it was read (m, blocks, b, every stored entry; doubles %.17g) in SDPA sparse format plus, per cut e,
+ * constraint m + 1 + e: the three entries sign / (2 t_x t_y) in the cut's cone (an off-diagonal entry counts twice in <A, X>), -1 in
+ * column e of a new last LP block of dimension -(cuts), b = -1.  Only kept, cone, p, q, s and cls of `cuts` are read; NULL or no cuts
+ * writes the problem alone.  A pure function of the problem image and the list.  1: cannot write; 2: a cut outside the problem or a
+ * problem with an LP block; 3: sharded. */
+int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

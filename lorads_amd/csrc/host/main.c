@@ -38,6 +38,10 @@ int main(int argc, char **argv) {
     double compress_tol = 1e-12;
     const char *entries_in = NULL, *entries_out = NULL; /* entries of the primal at the positions of a query file (ours as well) */
     lrd_entries *queries = NULL;
+    int cuts_max = -1;                /* separation of the triangle inequalities of a +-1-structured problem (ours as well) */
+    double cuts_minv = 1e-3;
+    int cuts_minv_given = 0;
+    const char *cuts_file = NULL;
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -50,6 +54,21 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "--roundFile")) { round_file = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--entriesFile")) { entries_in = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--entriesOut")) { entries_out = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--cutsFile")) { cuts_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--cutsMax") || !strcmp(argv[i], "--cutsMinViolation")) {
+            char *end = NULL;
+            const int is_max = argv[i][7] == 'a';
+            const double t = is_max ? 0.0 : strtod(argv[i + 1], &end);
+            const long k = is_max ? strtol(argv[i + 1], &end, 10) : 1;
+            if (!end || end == argv[i + 1] || *end || !(t >= 0) || !(t < HUGE_VAL) || k < 1 || k > (1L << 20)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            if (is_max) cuts_max = (int)k;
+            else { cuts_minv = t; cuts_minv_given = 1; }
+            continue;
+        }
         if (!strcmp(argv[i], "--roundTrials") || !strcmp(argv[i], "--roundSeed") || !strcmp(argv[i], "--roundLocalSearch")) {
             char *end = NULL;
             const unsigned long long v = strtoull(argv[i + 1], &end, 10);
@@ -86,6 +105,11 @@ int main(int argc, char **argv) {
         lrd_session_close(s);
         return 2;
     }
+    if ((cuts_file || cuts_minv_given) && cuts_max < 0) {
+        fprintf(stderr, "%s needs --cutsMax\n", cuts_file ? "--cutsFile" : "--cutsMinViolation");
+        lrd_session_close(s);
+        return 2;
+    }
     if (entries_in) { /* a bad query file is refused before the backend is created, let alone anything solved */
         int bad = 0;
         const int qrc = lrd_entries_read(entries_in, &queries, &bad);
@@ -119,11 +143,12 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (lrd_session_attach(s, &be)) return 1;
-    if (round_trials > 0) { /* applicability before any solving */
+    if (round_trials > 0 || cuts_max > 0) { /* applicability before any solving */
         lrd_rounding *none = NULL;
         const int rrc = lrd_session_round(s, 0, round_seed, round_ls, 0.0, &none);
         if (rrc) {
-            fprintf(stderr, "lorads: --roundTrials needs a +-1-structured problem (see above); nothing was solved\n");
+            fprintf(stderr, "lorads: %s needs a +-1-structured problem (see above); nothing was solved\n",
+                    round_trials > 0 ? "--roundTrials" : "--cutsMax");
             lrd_session_close(s);
             return 2;
         }
@@ -184,6 +209,20 @@ int main(int argc, char **argv) {
                    queries->stats[2]);
         }
         lrd_entries_free(queries);
+    }
+    if (cuts_max > 0) {
+        lrd_cuts *x = NULL;
+        if (lrd_session_triangle_cuts(s, cuts_minv, cuts_max, &x) || (cuts_file && lrd_session_write_tightened(s, cuts_file, x))) {
+            fprintf(stderr, "lorads: the separation failed%s%s\n", cuts_file ? " or cannot write " : "", cuts_file ? cuts_file : "");
+            lrd_cuts_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        long long total = 0;
+        for (int k = 0; k < x->nblk; ++k) total += (long long)x->count[k];
+        printf("Triangle inequalities violated by more than %g: %lld, kept %d, largest violation %.6e%s%s\n", cuts_minv, total, x->kept,
+               x->kept > 0 ? x->viol[0] : 0.0, cuts_file ? " -> " : "", cuts_file ? cuts_file : "");
+        lrd_cuts_free(x);
     }
     if (solution_file) {
         lrd_solution *x = NULL;

@@ -64,6 +64,8 @@ class BackendStruct(C.Structure):
                                   C.POINTER(C.c_int8), _ip, _dp)),
         ("primal_entries", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _ip, _ip, _dp, _dp, _dp)),
         ("primal_apply", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp)),
+        ("triangle_cuts", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
+                                      C.POINTER(C.c_int8), _dp, _ip, _ip)),
         ("spectrum", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _dp, _dp, _ip)),
         ("compress_rank", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _ip, _dp)),
     ]
@@ -281,6 +283,31 @@ class Backend:
         if rc:
             return rc, None, None
         return 0, Y[:, :nc], (T[:, :nc] if want_t else None)
+
+    def has_triangle_cuts(self):
+        return bool(self._s.triangle_cuts)
+
+    def triangle_cuts(self, src, blk, min_violation, max_cuts, want_arrays=True):
+        """the table's slot as it is: the (triple, class) pairs of cone blk whose triangle inequality is violated by more than
+        min_violation.  Returns (code, count, p, q, s, cls, violation, passes) with the min(count, max_cuts) largest pairs in the
+        order (violation descending, p, q, s, cls ascending); code != 0 is the slot's refusal.  want_arrays=False passes NULL
+        arrays down."""
+        cap = max(int(max_cuts), 1) if -1 < max_cuts <= (1 << 20) else 1
+        cnt, kept, passes = C.c_int64(0), C.c_int(0), C.c_int(0)
+        p, q, s = (np.zeros(cap, dtype=np.int32) for _ in range(3))
+        cls, v = np.zeros(cap, dtype=np.int8), np.zeros(cap)
+        i8 = C.POINTER(C.c_int8)
+        if want_arrays:
+            rc = self._s.triangle_cuts(self._s.ctx, src, blk, float(min_violation), int(max_cuts), C.byref(cnt), p.ctypes.data_as(_ip),
+                                       q.ctypes.data_as(_ip), s.ctypes.data_as(_ip), cls.ctypes.data_as(i8), v.ctypes.data_as(_dp),
+                                       C.byref(kept), C.byref(passes))
+        else:
+            rc = self._s.triangle_cuts(self._s.ctx, src, blk, float(min_violation), int(max_cuts), C.byref(cnt), None, None, None, None,
+                                       None, None, C.byref(passes))
+        if rc:
+            return (rc,) + (None,) * 7
+        k = kept.value
+        return 0, cnt.value, p[:k], q[:k], s[:k], cls[:k], v[:k], passes.value
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -819,6 +846,44 @@ class Session:
             _check(self.lib.lrd_rounding_write(os.fsencode(path), ptr), "rounding_write")
         finally:
             self.lib.lrd_rounding_free(ptr)
+
+    def triangle_cuts(self, max_cuts=1000, min_violation=1e-3):
+        """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device
+        (lorads_amd.cuts.Cuts): with rho_xy = X_xy / (t_x t_y) all 4 C(n, 3) inequalities of every cone are enumerated (X is never
+        formed), the ones violated by more than min_violation counted exactly, and the max_cuts most violated returned, ordered by
+        (violation descending, cone, p, q, s, cls ascending).  Read-only on the solver's state, deterministic."""
+        from .cuts import Cuts, CutsStruct
+        ptr = C.POINTER(CutsStruct)()
+        self.lib.lrd_session_triangle_cuts.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.POINTER(CutsStruct))]
+        self.lib.lrd_cuts_free.argtypes = [C.POINTER(CutsStruct)]
+        self.lib.lrd_cuts_free.restype = None
+        rc = self.lib.lrd_session_triangle_cuts(self.h, float(min_violation), int(max_cuts), C.byref(ptr))
+        if rc == 2:
+            msg = None
+            if self.be is not None and self.be.name == "hip-gfx950":
+                lib, _ = self._hip()
+                lib.lorads_hip_last_error.restype = C.c_char_p
+                msg = lib.lorads_hip_last_error()
+            raise NotImplementedError("triangle inequalities cannot be separated: the problem is not +-1-structured or the %s backend "
+                                      "cannot separate%s" % (self.be.name if self.be else "attached", (": " + msg.decode()) if msg else ""))
+        if rc == 3:
+            raise NotImplementedError("the separation of a sharded deal (world > 1) is not supported")
+        _check(rc, "triangle_cuts")
+        try:
+            return Cuts.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_cuts_free(ptr)
+
+    def write_tightened(self, path, cuts):
+        """The problem as it was read plus one constraint and one slack column (a new last LP block) per cut, in SDPA sparse format
+        (the command line's --cutsFile: the same C writer, the same bytes).  cuts: a lorads_amd.cuts.Cuts or None."""
+        from .cuts import CutsStruct
+        self.lib.lrd_session_write_tightened.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct)]
+        st = cuts.to_struct() if cuts is not None else None
+        rc = self.lib.lrd_session_write_tightened(self.h, os.fsencode(path), C.byref(st) if st is not None else None)
+        if rc == 2:
+            raise ValueError("a cut lies outside the problem, names a row no constraint fixes, or the problem has an LP block")
+        _check(rc, "write_tightened")
 
     def _spectral_refused(self, rc, what):
         if rc == 2:
