@@ -67,13 +67,14 @@ __global__ __launch_bounds__(TPB) void k_cut_pack(int n, int npad, int rl, int r
     const size_t len = (size_t)npad * rl4;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
         const size_t row = i / rl4, j = i % rl4;
-        Fp[i] = (row < (size_t)n && j < (size_t)rl) ? spec_ld(U, V, uv != 0, row * r + j) : 0.0;
+        Fp[i] = (row < (size_t)n && j < (size_t)rl) ? factor_ld(U, V, uv != 0, row * r + j) : 0.0;
         if (j == 0) tp[row] = row < (size_t)n ? t[row] : 1.0;
     }
 }
 
 // out <- the tile rho[A][B] (transposed: out[b][a]): wavefront w forms the 16 x 16 quarter (w >> 1, w & 1) as D = F_A F_B^T in steps of
-// four columns (k_primal_ft's operand layout: lane (nn, kk) supplies row nn, column k0 + kk of both and holds D[kk + 4 q][nn]), then
+// four columns (the operand layout of postsolve.inc's tiles: lane (nn, kk) supplies row nn, column k0 + kk of both and holds
+// D[kk + 4 q][nn]; not mfma_fm_tile itself: both operands are rows of the packed, padded F, with nothing to clamp or mask), then
 // divides by t_x t_y.  An entry's value depends on its two rows alone, not on the tile or the quarter it is formed in.
 __device__ __forceinline__ void cut_tile(const CutArgs &a, int A, int B, double (*out)[CUT_LD], bool transposed) {
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, nn = l & 15, kk = l >> 4;
@@ -231,14 +232,6 @@ __global__ __launch_bounds__(TPB) void k_cut_bitonic(unsigned long long P, unsig
     if ((i & k) == 0 ? less : greater) { hi[i] = hi_l; lo[i] = lo_l; hi[l] = hi_i; lo[l] = lo_i; }
 }
 
-template <typename T> int cut_grow(DevPool &mem, T *&p, size_t &cap, size_t need) {
-    if (need <= cap) return 0;
-    mem.free(p); cap = 0;
-    if (mem.alloc(&p, need)) return 1;
-    cap = need;
-    return 0;
-}
-
 int cut_launch(lorads_hip_ctx *c, const CutArgs &a, int nt) {
     const long long npairs = (long long)nt * (nt + 1) / 2;
     // tiles I are dealt over blockIdx.y: at most CUT_ITERS per workgroup (the longest workgroups would otherwise run nt of them while
@@ -254,7 +247,7 @@ int cut_launch(lorads_hip_ctx *c, const CutArgs &a, int nt) {
 extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t blk, double min_violation, int32_t max_cuts, int64_t *count,
                                         int32_t *p, int32_t *q, int32_t *s, int8_t *cls, double *viol, int32_t *kept, int32_t *passes) {
     spec_touch(c);
-    if (primal_args(c, src, blk, "triangle_cuts")) return 1;
+    if (postsolve_args(c, src, &blk, "triangle_cuts", false)) return 1;
     if (c->blk[blk].is_lp) return fail_msg("triangle_cuts: block " + std::to_string(blk) + " is the LP block");
     if (max_cuts < 0 || max_cuts > (1 << 20)) return fail_msg("triangle_cuts: max_cuts " + std::to_string(max_cuts) + " is outside [0, 2^20]");
     if (!(min_violation >= 0.0) || !std::isfinite(min_violation))
@@ -262,7 +255,7 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     if (!count) return fail_msg("triangle_cuts: count must not be NULL");
     if (max_cuts > 0 && (!p || !q || !s || !cls || !viol || !kept))
         return fail_msg("triangle_cuts: p, q, s, cls, viol and kept must not be NULL when max_cuts > 0");
-    if (spec_refuse_sharded(c, "triangle_cuts")) return 3;
+    if (postsolve_sharded(c, "triangle_cuts", "are not supported")) return 3;
     if (rnd_check(c)) return 1;
     if (!c->rnd.qualifies) {
         fail_msg("triangle_cuts: the context is not +-1-structured: " + c->rnd.why);
@@ -279,12 +272,12 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     const int nt = nblocks_for((size_t)n, CUT_T), npad = nt * CUT_T, rl4 = (B.rl + 3) & ~3;
     size_t P = 1;
     while (P < (size_t)max_cuts + CUT_SLACK) P <<= 1;
-    if (cut_grow(X.mem, X.Fp, X.fp_cap, (size_t)npad * rl4) || cut_grow(X.mem, X.tp, X.tp_cap, (size_t)npad)) return 1;
-    if (max_cuts > 0 && (cut_grow(X.mem, X.khi, X.khi_cap, P) || cut_grow(X.mem, X.klo, X.klo_cap, P))) return 1;
+    if (X.Fp.grow(X.mem, (size_t)npad * rl4) || X.tp.grow(X.mem, (size_t)npad)) return 1;
+    if (max_cuts > 0 && (X.khi.grow(X.mem, P) || X.klo.grow(X.mem, P))) return 1;
     if (!X.ctl && X.mem.alloc(&X.ctl, 2 + (size_t)CUT_BINS)) return 1;
-    const int uv = src == LORADS_HIP_PAIR_UV;
+    const FactorView F = factor_view(c, src, blk);
     hipLaunchKernelGGL(k_cut_pack, dim3(std::min(grid1d((size_t)npad * rl4), 1024)), dim3(TPB), 0, c->stream, n, npad, B.rl, rl4, B.r,
-                       (const double *)((uv ? c->U : c->R) + B.off), (const double *)((uv ? c->V : c->R) + B.off), uv,
+                       F.U, F.V, F.uv,
                        (const double *)(c->rnd.t + c->rnd.t_off[blk]), X.Fp, X.tp);
     CutArgs a{};
     a.n = n; a.rl4 = rl4; a.mode = 0; a.shift = 128 - CUT_DIGIT; a.width = CUT_DIGIT;

@@ -124,6 +124,25 @@ __device__ __forceinline__ double block_sum(double v, double *sh) {
     __syncthreads();
     return t;
 }
+// max / min over the 256-thread workgroup, result in every thread; sh = 4 doubles of LDS
+__device__ __forceinline__ double block_max(double v, double *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double t = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+    __syncthreads();
+    return t;
+}
+__device__ __forceinline__ double block_min(double v, double *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double t = fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3]));
+    __syncthreads();
+    return t;
+}
 // N sums over the workgroup with one barrier pair; sh = 4*N doubles of LDS, results in every thread.  Each value is
 // reduced exactly as block_sum reduces it.
 template <int N>
@@ -474,6 +493,22 @@ struct LzWorker {
     double *pinned = nullptr;     // (owned by lorads_hip_ctx::mem)
 };
 
+// A scratch buffer of the post-solve entry points that is grown on demand: the address and the elements it was made for, in one
+// place.  grow() does nothing while the buffer is large enough; otherwise the old one goes and exactly `need` elements are made
+// (what it held is not kept).  Reads as the plain pointer wherever one is wanted; its owner's pool releases it.
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    int grow(DevPool &mem, size_t need) {
+        if (need <= cap) return 0;
+        mem.free(p); cap = 0;
+        if (mem.alloc(&p, need)) return 1;
+        cap = need;
+        return 0;
+    }
+    operator T *() const { return p; }
+};
+
 // scratch of the solution export (solution.inc): allocated on its first call, never read by the solve
 struct CertScratch {
     bool ready = false;
@@ -495,10 +530,9 @@ struct RoundScratch {
     double *t = nullptr;                      // t_p = sqrt(b_i / a_i), cone k at t_off[k]
     std::vector<std::vector<int>> cls_ptr;    // per cone: colour class -> its range of the class-sorted row list
     int *cls_rows = nullptr;                  // class-sorted rows, cone k at t_off[k]
-    double *G = nullptr, *part = nullptr, *f = nullptr, *f0 = nullptr; // hyperplanes, field partials, f after / before the search
-    unsigned long long *sgn = nullptr;        // sign words, cone k at t_off[k] * W
+    DevBuf<double> G, part, f, f0;            // hyperplanes, field partials, f after / before the search
+    DevBuf<unsigned long long> sgn;           // sign words, cone k at t_off[k] * W
     int *ctl = nullptr;                       // [0] flip flag, [1] best before, [2] best after the search
-    size_t g_cap = 0, sgn_cap = 0, part_cap = 0, f_cap = 0;
     DevPool mem;
     void release() { mem.release(); *this = RoundScratch{}; }
 };
@@ -506,11 +540,10 @@ struct RoundScratch {
 // scratch of the spectrum / rank reduction (spectral.inc): allocated on its first call, never read by the solve
 struct SpecCone { int rl, m; long long g_off, e_off, q_off; }; // one cone of a k_spec_jacobi launch: orders, places in SpecScratch::W
 struct SpecScratch {
-    double *part = nullptr;  // per-strip partial Grams of the cone at hand: [strip][tile pair][16 x 16]
-    double *W = nullptr;     // per cone of a batch: G (m x m), Q (m x m), eigenvalues (rl), sorted eigenvectors (rl x rl, column-major)
-    SpecCone *cones = nullptr;
-    int *info = nullptr;     // per cone of a batch: {sweeps, 0 = converged}
-    size_t part_cap = 0, w_cap = 0, cones_cap = 0;
+    DevBuf<double> part;     // per-strip partial Grams of the cone at hand: [strip][tile pair][16 x 16]
+    DevBuf<double> W;        // per cone of a batch: G (m x m), Q (m x m), eigenvalues (rl), sorted eigenvectors (rl x rl, column-major)
+    DevBuf<SpecCone> cones;
+    DevBuf<int> info;        // per cone of a batch: {sweeps, 0 = converged}
     DevPool mem;
     void release() { mem.release(); *this = SpecScratch{}; }
 };
@@ -518,12 +551,12 @@ struct SpecScratch {
 // scratch of the primal queries (primal.inc): allocated on first use, grown on demand, never read by the solve.  Bounded whatever the
 // count, the columns and n are: entries go in chunks of LORADS_HIP_PRIMAL_CHUNK, B and Y in panels of 16 columns x 65536 rows.
 struct PrimalScratch {
-    int *row = nullptr, *col = nullptr;            // the chunk's positions
-    double *ref = nullptr, *val = nullptr;         // its reference values and results
-    double *part = nullptr, *acc = nullptr;        // per-workgroup partials of the four statistics, the statistics
-    double *bp = nullptr, *yp = nullptr;           // a panel of B and of Y, row-major 16 wide
-    double *tpart = nullptr, *t = nullptr;         // per-strip partial tiles of T = F^T B: [strip][tile][16 x 16]; T (16 tiles x 16)
-    size_t row_cap = 0, col_cap = 0, ref_cap = 0, val_cap = 0, part_cap = 0, bp_cap = 0, yp_cap = 0, tpart_cap = 0, t_cap = 0; // (one per buffer)
+    DevBuf<int> row, col;                          // the chunk's positions
+    DevBuf<double> ref, val;                       // its reference values and results
+    DevBuf<double> part;                           // per-workgroup partials of the four statistics
+    double *acc = nullptr;                         // the statistics
+    DevBuf<double> bp, yp;                         // a panel of B and of Y, row-major 16 wide
+    DevBuf<double> tpart, t;                       // per-strip partial tiles of T = F^T B: [strip][tile][16 x 16]; T (16 tiles x 16)
     DevPool mem;
     void release() { mem.release(); *this = PrimalScratch{}; }
 };
@@ -531,10 +564,9 @@ struct PrimalScratch {
 // scratch of the triangle-inequality separation (cuts.inc): allocated on first use, grown on demand, never read by the solve.
 // O(n r) for the packed factor, max_cuts + a fixed slack (rounded up to a power of two) keys, one histogram.
 struct CutScratch {
-    double *Fp = nullptr, *tp = nullptr;                   // F zero-padded to whole tiles and steps of 4 columns, t padded with ones
-    unsigned long long *khi = nullptr, *klo = nullptr;     // the emitted keys: bit pattern of v, complement of the packed index
+    DevBuf<double> Fp, tp;                                 // F zero-padded to whole tiles and steps of 4 columns, t padded with ones
+    DevBuf<unsigned long long> khi, klo;                   // the emitted keys: bit pattern of v, complement of the packed index
     unsigned long long *ctl = nullptr;                     // [0] violated pairs, [1] emitted keys, [2..] the histogram of a digit
-    size_t fp_cap = 0, tp_cap = 0, khi_cap = 0, klo_cap = 0;
     DevPool mem;
     void release() { mem.release(); *this = CutScratch{}; }
 };
@@ -1790,6 +1822,7 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 } // extern "C"
 
 #include "lanczos.inc"
+#include "postsolve.inc"
 #include "solution.inc"
 #include "rounding.inc"
 #include "spectral.inc"

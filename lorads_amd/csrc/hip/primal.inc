@@ -6,9 +6,9 @@
 //   k_primal_entries + k_primal_stats_close   val_e = F_row . F_col by one 8-lane group per entry (16-byte row loads, PRIMAL_EPG entries
 //                                             of a group in flight); with reference values the four statistics ride along as
 //                                             per-workgroup partials, closed in order by one workgroup
-//   k_primal_ftb + k_primal_ftb_sum           T = F^T B on the FP64 matrix cores (operand layout of k_spec_gram): row strips give
+//   k_primal_ftb + k_primal_ftb_sum           T = F^T B on the FP64 matrix cores (postsolve.inc: mfma_strip_tile): row strips give
 //                                             partial tiles, added in strip order
-//   k_primal_ft                               Y = F T (as k_spec_rotate: a wavefront takes 16 rows, 128-byte row segments out)
+//   k_primal_ft                               Y = F T (mfma_fm_tile: a wavefront takes 16 rows, 128-byte row segments out)
 //   k_primal_lp                               Y = diag(f^2) B on the LP block
 // Both entry points are read-only on the solver's state: the scratch is the feature's own (PrimalScratch), every launch goes straight
 // to the stream (never through LAUNCH, which would flush a pending dual update into the state).  No float atomics: every sum is a
@@ -20,7 +20,7 @@ constexpr int PRIMAL_EPG = 4;                          // entries one 8-lane gro
 constexpr int PRIMAL_EPW = (TPB / 8) * PRIMAL_EPG;     // entries per workgroup (LORADS_HIP_PRIMAL_EPW)
 constexpr int PRIMAL_PW = 16;                          // columns of a panel of B and Y: one MFMA tile, one 128-byte row segment
 constexpr int PRIMAL_ROWS = 1 << 16;                   // rows of a panel held on the device at a time
-constexpr int PRIMAL_MAX_STRIPS = 256;
+constexpr int PRIMAL_MAX_STRIPS = 256;                 // strips of a row panel (row_strips)
 constexpr int PRIMAL_MAXR = 512;                       // largest rank (as lorads_hip_resize_rank)
 static_assert(PRIMAL_EPW == LORADS_HIP_PRIMAL_EPW, "the header states the entries per workgroup");
 static_assert(LORADS_HIP_PRIMAL_CHUNK % PRIMAL_EPW == 0, "a chunk is whole workgroups");
@@ -62,21 +62,8 @@ __global__ __launch_bounds__(TPB) void k_primal_entries(int cnt, const int *__re
             double2 a[PRIMAL_EPG], b[PRIMAL_EPG];
 #pragma unroll
             for (int t = 0; t < PRIMAL_EPG; ++t) {
-                a[t] = ((const double2 *)(U + (size_t)p[t] * r))[jc];
-                b[t] = ((const double2 *)(U + (size_t)q[t] * r))[jc];
-            }
-            if (UV) {
-                double2 c[PRIMAL_EPG], d[PRIMAL_EPG];
-#pragma unroll
-                for (int t = 0; t < PRIMAL_EPG; ++t) {
-                    c[t] = ((const double2 *)(V + (size_t)p[t] * r))[jc];
-                    d[t] = ((const double2 *)(V + (size_t)q[t] * r))[jc];
-                }
-#pragma unroll
-                for (int t = 0; t < PRIMAL_EPG; ++t) {
-                    a[t] = make_double2((a[t].x + c[t].x) / 2, (a[t].y + c[t].y) / 2);
-                    b[t] = make_double2((b[t].x + d[t].x) / 2, (b[t].y + d[t].y) / 2);
-                }
+                a[t] = factor_ld((const double2 *)(U + (size_t)p[t] * r), (const double2 *)(V + (size_t)p[t] * r), UV, jc);
+                b[t] = factor_ld((const double2 *)(U + (size_t)q[t] * r), (const double2 *)(V + (size_t)q[t] * r), UV, jc);
             }
 #pragma unroll
             for (int t = 0; t < PRIMAL_EPG; ++t) {
@@ -90,9 +77,7 @@ __global__ __launch_bounds__(TPB) void k_primal_entries(int cnt, const int *__re
             const double m = j < r ? 1.0 : 0.0;
 #pragma unroll
             for (int t = 0; t < PRIMAL_EPG; ++t) {
-                double a = U[(size_t)p[t] * r + jc], b = U[(size_t)q[t] * r + jc];
-                if (UV) { a = (a + V[(size_t)p[t] * r + jc]) / 2; b = (b + V[(size_t)q[t] * r + jc]) / 2; }
-                s[t] += (a * b) * m;
+                s[t] += (factor_ld(U, V, UV, (size_t)p[t] * r + jc) * factor_ld(U, V, UV, (size_t)q[t] * r + jc)) * m;
             }
         }
     }
@@ -145,48 +130,19 @@ __global__ __launch_bounds__(TPB) void k_primal_stats_close(int nb, const double
     }
 }
 
-// Partial tile of T = F^T B of one row strip (blockIdx.x) and one 16-row tile I of T (blockIdx.y): D[m][n] = sum_k A[m][k] B[k][n] with
-// A[m][k] = F[row k][16 I + m] (F transposed, from the row's 128-byte segment) and B[k][n] = Bp[row k][n] (the panel, row-major 16 wide:
-// a 128-byte segment too).  Lane (nn = l & 15, kk = l >> 4) supplies both from row kk of the four at hand and holds D[kk + 4 q][nn] in
-// register q (k_spec_gram's layout).  Columns >= rl and rows >= n are clamped loads times zero.  The four wavefronts take a quarter of
-// the strip each; their tiles are added in wave order through LDS.  Column nn of D is made of column nn of Bp alone.
+// Partial tile of T = F^T B of one row strip (blockIdx.x) and one 16-row tile I of T (blockIdx.y): mfma_strip_tile with A[m][k] =
+// F[row k][16 I + m] (F transposed) and B[k][n] = Bp[row k][n] (the panel, row-major 16 wide: a 128-byte segment too).  Columns >= rl
+// and rows >= n are clamped loads times zero.  Column nn of D is made of column nn of Bp alone.
 __global__ __launch_bounds__(TPB) void k_primal_ftb(int n, int rl, int r, int rows_per_strip, int ntile, const double *__restrict__ U,
                                                     const double *__restrict__ V, int uv, const double *__restrict__ Bp,
                                                     double *__restrict__ part) {
-    __shared__ double red[3][4][64];
-    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, nn = l & 15, kk = l >> 4;
+    const int nn = threadIdx.x & 15;
     const int ca = 16 * blockIdx.y + nn, cac = ca < rl ? ca : 0;
     const double ma = ca < rl ? 1.0 : 0.0;
-    const int q4 = rows_per_strip / 4; // (a multiple of 16: see primal_strips)
-    const int rbeg = blockIdx.x * rows_per_strip + wave * q4;
-    v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < q4; k0 += 16) {
-        double a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int rw = rbeg + k0 + 4 * u + kk;
-            const bool ok = rw < n;
-            const size_t rc = (size_t)(ok ? rw : 0);
-            const double mr = ok ? 1.0 : 0.0;
-            a[u] = spec_ld(U, V, uv != 0, rc * r + cac) * (ma * mr);
-            b[u] = Bp[rc * PRIMAL_PW + nn] * mr;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave - 1][q][l] = acc[q];
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    double *out = part + ((size_t)blockIdx.x * ntile + blockIdx.y) * 256;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v = acc[q];
-        v += red[0][q][l]; v += red[1][q][l]; v += red[2][q][l];
-        out[(kk + 4 * q) * 16 + nn] = v;
-    }
+    mfma_strip_tile(n, rows_per_strip, ntile, part, [=](size_t row, double mr, double &a, double &b) {
+        a = factor_ld(U, V, uv != 0, row * r + cac) * (ma * mr);
+        b = Bp[row * PRIMAL_PW + nn] * mr;
+    });
 }
 
 // T (16 ntile x 16, row-major) = [T +] the strips' partial tiles added in strip order (first: the row panel that opens the sum)
@@ -198,22 +154,15 @@ __global__ __launch_bounds__(TPB) void k_primal_ftb_sum(int strips, int ntile, i
     T[o] = v;
 }
 
-// Yp (rows x 16, row-major) = F T.  A wavefront takes 16 rows: A[m][k] = F[row0 + m][k0 + k], B[k][n] = T[k0 + k][n], D[kk + 4 q][nn]
-// = row row0 + kk + 4 q, column nn: 128-byte row segments on the way out.  k >= rl: clamped loads times zero (T's rows >= rl are zero
-// as well).  (k_spec_rotate's layout)
+// Yp (rows x 16, row-major) = F T.  A wavefront takes 16 rows: mfma_fm_tile with M = T (T's rows >= rl are zero, as F's columns there
+// count for zero).
 __global__ __launch_bounds__(TPB) void k_primal_ft(int n, int rl, int r, const double *__restrict__ U, const double *__restrict__ V, int uv,
                                                    const double *__restrict__ T, double *__restrict__ Yp) {
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, nn = l & 15, kk = l >> 4;
     const int row0 = (blockIdx.x * (TPB / 64) + wave) * 16;
     if (row0 >= n) return; // (wave-uniform)
     const size_t ao = (size_t)(row0 + nn < n ? row0 + nn : n - 1) * r;
-    v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < rl; k0 += 4) {
-        const int k = k0 + kk, kc = k < rl ? k : 0;
-        const double a = spec_ld(U, V, uv != 0, ao + kc) * (k < rl ? 1.0 : 0.0);
-        const double b = T[(size_t)kc * PRIMAL_PW + nn];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
+    const v4f64 acc = mfma_fm_tile(U, V, uv != 0, ao, rl, kk, [=](int k) { return T[(size_t)k * PRIMAL_PW + nn]; });
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int rw = row0 + kk + 4 * q;
@@ -225,31 +174,9 @@ __global__ __launch_bounds__(TPB) void k_primal_ft(int n, int rl, int r, const d
 __global__ __launch_bounds__(TPB) void k_primal_lp(size_t len, int r, const double *__restrict__ U, const double *__restrict__ V, int uv,
                                                    const double *__restrict__ Bp, double *__restrict__ Yp) {
     for (size_t t = (size_t)blockIdx.x * TPB + threadIdx.x; t < len; t += (size_t)gridDim.x * TPB) {
-        const double f = spec_ld(U, V, uv != 0, (t / PRIMAL_PW) * r);
+        const double f = factor_ld(U, V, uv != 0, (t / PRIMAL_PW) * r);
         Yp[t] = (f * f) * Bp[t];
     }
-}
-
-template <typename T> int primal_grow(DevPool &mem, T *&p, size_t &cap, size_t need) {
-    if (need <= cap) return 0;
-    mem.free(p); cap = 0;
-    if (mem.alloc(&p, need)) return 1;
-    cap = need;
-    return 0;
-}
-
-// strips of a row panel: rows_per_strip a multiple of 64, at most PRIMAL_MAX_STRIPS strips (a function of the rows alone)
-inline void primal_strips(int rows, int &strips, int &rps) {
-    const int s = std::max(1, std::min(PRIMAL_MAX_STRIPS, nblocks_for((size_t)rows, 256)));
-    rps = std::max(64, (nblocks_for((size_t)rows, s) + 63) & ~63);
-    strips = std::max(1, nblocks_for((size_t)rows, rps));
-}
-
-int primal_args(const lorads_hip_ctx *c, int32_t src, int32_t blk, const char *what) {
-    if (!c) return fail_msg(std::string(what) + ": no context");
-    if (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) return fail_msg(std::string(what) + ": src " + std::to_string(src) + " is neither RR nor UV");
-    if (blk < 0 || blk >= c->nb) return fail_msg(std::string(what) + ": block " + std::to_string(blk) + " is outside [0, " + std::to_string(c->nb) + ")");
-    return 0;
 }
 
 } // namespace
@@ -257,13 +184,13 @@ int primal_args(const lorads_hip_ctx *c, int32_t src, int32_t blk, const char *w
 extern "C" int lorads_hip_primal_entries(lorads_hip_ctx *c, int32_t src, int32_t blk, int64_t count, const int32_t *row, const int32_t *col,
                                          double *val, const double *ref, double stats[4]) {
     spec_touch(c);
-    if (primal_args(c, src, blk, "primal_entries")) return 1;
+    if (postsolve_args(c, src, &blk, "primal_entries", false)) return 1;
     if (count < 0) return fail_msg("primal_entries: count " + std::to_string((long long)count) + " is negative");
     if (count > 0 && (!row || !col)) return fail_msg("primal_entries: row and col must not be NULL");
     if (!val && !ref && count > 0) return fail_msg("primal_entries: val may be NULL only when ref is given");
     if ((ref != nullptr) != (stats != nullptr))
         return fail_msg("primal_entries: stats must be given with ref and only with it");
-    if (spec_refuse_sharded(c, "primal_entries")) return 3;
+    if (postsolve_sharded(c, "primal_entries", "are not supported")) return 3;
     const Block &K = c->blk[blk];
     for (int64_t e = 0; e < count; ++e) { // (no index reaches a kernel before every one has been looked at)
         if (row[e] < 0 || row[e] >= K.n)
@@ -275,23 +202,21 @@ extern "C" int lorads_hip_primal_entries(lorads_hip_ctx *c, int32_t src, int32_t
     if (count == 0) return 0;
     PrimalScratch &X = c->primal;
     const size_t cap = (size_t)std::min<int64_t>(count, LORADS_HIP_PRIMAL_CHUNK);
-    if (primal_grow(X.mem, X.row, X.row_cap, cap) || primal_grow(X.mem, X.col, X.col_cap, cap)) return 1;
-    if (primal_grow(X.mem, X.val, X.val_cap, cap)) return 1;
-    if (ref && (primal_grow(X.mem, X.ref, X.ref_cap, cap) || primal_grow(X.mem, X.part, X.part_cap, 4 * (size_t)nblocks_for(cap, PRIMAL_EPW)))) return 1;
+    if (X.row.grow(X.mem, cap) || X.col.grow(X.mem, cap) || X.val.grow(X.mem, cap)) return 1;
+    if (ref && (X.ref.grow(X.mem, cap) || X.part.grow(X.mem, 4 * (size_t)nblocks_for(cap, PRIMAL_EPW)))) return 1;
     if (!X.acc && X.mem.alloc(&X.acc, 4)) return 1;
-    const int uv = src == LORADS_HIP_PAIR_UV;
-    const double *Ub = (uv ? c->U : c->R) + K.off, *Vb = (uv ? c->V : c->R) + K.off;
+    const FactorView F = factor_view(c, src, blk);
     if (ref) HC(hipMemsetAsync(X.acc, 0, sizeof(double) * 4, c->stream));
     for (int64_t e0 = 0; e0 < count; e0 += LORADS_HIP_PRIMAL_CHUNK) {
         const int cnt = (int)std::min<int64_t>(count - e0, LORADS_HIP_PRIMAL_CHUNK), grid = nblocks_for((size_t)cnt, PRIMAL_EPW);
         HC(hipMemcpyAsync(X.row, row + e0, sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
         HC(hipMemcpyAsync(X.col, col + e0, sizeof(int) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
         if (ref) HC(hipMemcpyAsync(X.ref, ref + e0, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
-        if (uv)
-            hipLaunchKernelGGL(k_primal_entries<true>, dim3(grid), dim3(TPB), 0, c->stream, cnt, (const int *)X.row, (const int *)X.col, Ub, Vb,
+        if (F.uv)
+            hipLaunchKernelGGL(k_primal_entries<true>, dim3(grid), dim3(TPB), 0, c->stream, cnt, (const int *)X.row, (const int *)X.col, F.U, F.V,
                                K.r, K.is_lp ? 1 : 0, X.val, ref ? (const double *)X.ref : nullptr, X.part);
         else
-            hipLaunchKernelGGL(k_primal_entries<false>, dim3(grid), dim3(TPB), 0, c->stream, cnt, (const int *)X.row, (const int *)X.col, Ub, Vb,
+            hipLaunchKernelGGL(k_primal_entries<false>, dim3(grid), dim3(TPB), 0, c->stream, cnt, (const int *)X.row, (const int *)X.col, F.U, F.V,
                                K.r, K.is_lp ? 1 : 0, X.val, ref ? (const double *)X.ref : nullptr, X.part);
         if (ref) hipLaunchKernelGGL(k_primal_stats_close, dim3(1), dim3(TPB), 0, c->stream, grid, (const double *)X.part, X.acc);
         HC(hipGetLastError());
@@ -304,11 +229,11 @@ extern "C" int lorads_hip_primal_entries(lorads_hip_ctx *c, int32_t src, int32_t
 
 extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t blk, int32_t ncols, const double *B, double *Y, double *T) {
     spec_touch(c);
-    if (primal_args(c, src, blk, "primal_apply")) return 1;
+    if (postsolve_args(c, src, &blk, "primal_apply", false)) return 1;
     if (ncols < 1 || ncols > 1024) return fail_msg("primal_apply: ncols " + std::to_string(ncols) + " is outside [1, 1024]");
     if (!B || !Y) return fail_msg("primal_apply: B and Y must not be NULL");
     if (c->blk[blk].is_lp && T) return fail_msg("primal_apply: the LP block has no factor: T must be NULL");
-    if (spec_refuse_sharded(c, "primal_apply")) return 3;
+    if (postsolve_sharded(c, "primal_apply", "are not supported")) return 3;
     const Block &K = c->blk[blk];
     const int n = K.n, rl = K.rl;
     if (n == 0) return 0;
@@ -316,12 +241,10 @@ extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t b
     PrimalScratch &X = c->primal;
     const int rcap = std::min(n, PRIMAL_ROWS), ntile = K.is_lp ? 1 : (rl + 15) / 16;
     int smax = 0, rps0 = 0;
-    primal_strips(rcap, smax, rps0);
-    if (primal_grow(X.mem, X.bp, X.bp_cap, (size_t)rcap * PRIMAL_PW) || primal_grow(X.mem, X.yp, X.yp_cap, (size_t)rcap * PRIMAL_PW)) return 1;
-    if (!K.is_lp && (primal_grow(X.mem, X.tpart, X.tpart_cap, (size_t)smax * ntile * 256) || primal_grow(X.mem, X.t, X.t_cap, (size_t)ntile * 256)))
-        return 1;
-    const int uv = src == LORADS_HIP_PAIR_UV;
-    const double *Ub = (uv ? c->U : c->R) + K.off, *Vb = (uv ? c->V : c->R) + K.off;
+    row_strips(rcap, PRIMAL_MAX_STRIPS, smax, rps0);
+    if (X.bp.grow(X.mem, (size_t)rcap * PRIMAL_PW) || X.yp.grow(X.mem, (size_t)rcap * PRIMAL_PW)) return 1;
+    if (!K.is_lp && (X.tpart.grow(X.mem, (size_t)smax * ntile * 256) || X.t.grow(X.mem, (size_t)ntile * 256))) return 1;
+    const FactorView F = factor_view(c, src, blk);
     std::vector<double> hb((size_t)rcap * PRIMAL_PW), ht((size_t)ntile * 256);
     // one row panel of one column panel of B, row-major 16 wide (columns past ncols: zero), to the device
     auto send_b = [&](int c0, int pw, int r0, int rows) -> int {
@@ -346,7 +269,7 @@ extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t b
                 const int rows = std::min(PRIMAL_ROWS, n - r0);
                 if (send_b(c0, pw, r0, rows)) return 1;
                 hipLaunchKernelGGL(k_primal_lp, dim3(std::min(4096, nblocks_for((size_t)rows * PRIMAL_PW, TPB))), dim3(TPB), 0, c->stream,
-                                   (size_t)rows * PRIMAL_PW, K.r, Ub + (size_t)r0 * K.r, Vb + (size_t)r0 * K.r, uv, (const double *)X.bp, X.yp);
+                                   (size_t)rows * PRIMAL_PW, K.r, F.U + (size_t)r0 * K.r, F.V + (size_t)r0 * K.r, F.uv, (const double *)X.bp, X.yp);
                 HC(hipGetLastError());
                 if (fetch_y(c0, pw, r0, rows)) return 1;
             }
@@ -355,10 +278,10 @@ extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t b
         for (int r0 = 0; r0 < n; r0 += PRIMAL_ROWS) { // T = F^T B: row panels in order
             const int rows = std::min(PRIMAL_ROWS, n - r0);
             int strips, rps;
-            primal_strips(rows, strips, rps);
+            row_strips(rows, PRIMAL_MAX_STRIPS, strips, rps);
             if (send_b(c0, pw, r0, rows)) return 1;
-            hipLaunchKernelGGL(k_primal_ftb, dim3(strips, ntile), dim3(TPB), 0, c->stream, rows, rl, K.r, rps, ntile, Ub + (size_t)r0 * K.r,
-                               Vb + (size_t)r0 * K.r, uv, (const double *)X.bp, X.tpart);
+            hipLaunchKernelGGL(k_primal_ftb, dim3(strips, ntile), dim3(TPB), 0, c->stream, rows, rl, K.r, rps, ntile, F.U + (size_t)r0 * K.r,
+                               F.V + (size_t)r0 * K.r, F.uv, (const double *)X.bp, X.tpart);
             hipLaunchKernelGGL(k_primal_ftb_sum, dim3(ntile), dim3(TPB), 0, c->stream, strips, ntile, r0 == 0 ? 1 : 0, (const double *)X.tpart, X.t);
             HC(hipGetLastError());
             HC(hipStreamSynchronize(c->stream)); // (the staging array is packed anew)
@@ -372,7 +295,7 @@ extern "C" int lorads_hip_primal_apply(lorads_hip_ctx *c, int32_t src, int32_t b
         for (int r0 = 0; r0 < n; r0 += PRIMAL_ROWS) { // Y = F T
             const int rows = std::min(PRIMAL_ROWS, n - r0);
             hipLaunchKernelGGL(k_primal_ft, dim3(nblocks_for((size_t)rows, 16 * (TPB / 64))), dim3(TPB), 0, c->stream, rows, rl, K.r,
-                               Ub + (size_t)r0 * K.r, Vb + (size_t)r0 * K.r, uv, (const double *)X.t, X.yp);
+                               F.U + (size_t)r0 * K.r, F.V + (size_t)r0 * K.r, F.uv, (const double *)X.t, X.yp);
             HC(hipGetLastError());
             if (fetch_y(c0, pw, r0, rows)) return 1;
         }

@@ -59,9 +59,7 @@ __global__ __launch_bounds__(TPB) void k_rnd_sign(int n, int rk, int r, int K, i
 #pragma unroll
         for (int i = 0; i < RND_RPW; ++i) {
             const int p = p0 + i < n ? p0 + i : n - 1;
-            double a = U[(size_t)p * r + j];
-            if (uv) a = (a + V[(size_t)p * r + j]) / 2;
-            s[i] += a * g;
+            s[i] += factor_ld(U, V, uv != 0, (size_t)p * r + j) * g;
         }
     }
 #pragma unroll
@@ -282,14 +280,8 @@ int rnd_reserve(lorads_hip_ctx *c, int K) {
     size_t g = 0;
     for (auto &B : c->blk) g += (size_t)B.rl * K;
     const size_t words = (size_t)X.t_off[c->nb] * W, part = (size_t)K * RND_STRIPS;
-    if (g > X.g_cap) { X.mem.free(X.G); X.g_cap = 0; if (X.mem.alloc(&X.G, g)) return 1; X.g_cap = g; }
-    if (words > X.sgn_cap) { X.mem.free(X.sgn); X.sgn_cap = 0; if (X.mem.alloc(&X.sgn, words)) return 1; X.sgn_cap = words; }
-    if (part > X.part_cap) { X.mem.free(X.part); X.part_cap = 0; if (X.mem.alloc(&X.part, part)) return 1; X.part_cap = part; }
-    if ((size_t)K > X.f_cap) {
-        X.mem.free(X.f); X.mem.free(X.f0); X.f_cap = 0;
-        if (X.mem.alloc(&X.f, (size_t)K) || X.mem.alloc(&X.f0, (size_t)K)) return 1;
-        X.f_cap = (size_t)K;
-    }
+    if (X.G.grow(X.mem, g) || X.sgn.grow(X.mem, words) || X.part.grow(X.mem, part)) return 1;
+    if (X.f.grow(X.mem, (size_t)K) || X.f0.grow(X.mem, (size_t)K)) return 1;
     if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
     return 0;
 }
@@ -322,13 +314,9 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
                                     double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds,
                                     double *hyperplanes) {
     spec_touch(c);
-    if (!c || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) || trials < 0 || trials > RND_MAXK || max_rounds < 0 ||
-        (trials > 0 && !obj))
-        return fail_msg("round_pm1: bad argument");
-    if (c->ar || c->sep || c->sx) {
-        fail_msg("round_pm1: sharded contexts (world > 1) cannot be rounded");
-        return 3;
-    }
+    if (postsolve_args(c, src, nullptr, "round_pm1", true)) return 1;
+    if (trials < 0 || trials > RND_MAXK || max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_pm1: bad argument");
+    if (postsolve_sharded(c, "round_pm1", "cannot be rounded")) return 3;
     if (rnd_check(c)) return 1;
     RoundScratch &X = c->rnd;
     if (!X.qualifies) {
@@ -338,7 +326,6 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64;
     if (rnd_reserve(c, K) || (max_rounds > 0 && rnd_colour(c))) return 1;
-    const int uv = src == LORADS_HIP_PAIR_UV;
     // hyperplanes and sign words
     size_t goff = 0;
     for (int k = 0; k < c->nb; ++k) {
@@ -346,9 +333,9 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
         double *G = X.G + goff;
         const size_t glen = (size_t)B.rl * K;
         if (glen) hipLaunchKernelGGL(k_rnd_hyper, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, B.rl, K, k, seed, G);
-        const double *U = (uv ? c->U : c->R) + B.off, *V = (uv ? c->V : c->R) + B.off;
+        const FactorView F = factor_view(c, src, k);
         const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
-        hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, U, V, uv,
+        hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, F.U, F.V, F.uv,
                            (const double *)G, X.sgn + (size_t)X.t_off[k] * W);
         goff += glen;
     }

@@ -18,21 +18,12 @@ __device__ __forceinline__ double cert_row_dot(const double *__restrict__ U, con
         const double2 *up = (const double2 *)(U + (size_t)p * r), *uq = (const double2 *)(U + (size_t)q * r);
         const double2 *vp = (const double2 *)(V + (size_t)p * r), *vq = (const double2 *)(V + (size_t)q * r);
         for (int j = lane; j < r / 2; j += 8) {
-            double2 a = up[j], b = uq[j];
-            if (uv) {
-                const double2 c = vp[j], d = vq[j];
-                a = make_double2((a.x + c.x) / 2, (a.y + c.y) / 2);
-                b = make_double2((b.x + d.x) / 2, (b.y + d.y) / 2);
-            }
+            const double2 a = factor_ld(up, vp, uv, j), b = factor_ld(uq, vq, uv, j);
             s += a.x * b.x;
             s += a.y * b.y;
         }
     } else {
-        for (int j = lane; j < r; j += 8) {
-            double a = U[(size_t)p * r + j], b = U[(size_t)q * r + j];
-            if (uv) { a = (a + V[(size_t)p * r + j]) / 2; b = (b + V[(size_t)q * r + j]) / 2; }
-            s += a * b;
-        }
+        for (int j = lane; j < r; j += 8) s += factor_ld(U, V, uv, (size_t)p * r + j) * factor_ld(U, V, uv, (size_t)q * r + j);
     }
     return s;
 }
@@ -87,11 +78,7 @@ __global__ __launch_bounds__(TPB) void k_cert_gram(int n, int npad, const double
         const int p = (int)(t / npad), q = (int)(t % npad);
         double s = 0.0;
         if (p < n && q < n)
-            for (int j = 0; j < r; ++j) {
-                double a = U[(size_t)p * r + j], b = U[(size_t)q * r + j];
-                if (uv) { a = (a + V[(size_t)p * r + j]) / 2; b = (b + V[(size_t)q * r + j]) / 2; }
-                s += a * b;
-            }
+            for (int j = 0; j < r; ++j) s += factor_ld(U, V, uv != 0, (size_t)p * r + j) * factor_ld(U, V, uv != 0, (size_t)q * r + j);
         G[t] = s;
     }
 }
@@ -116,16 +103,6 @@ __global__ __launch_bounds__(TPB) void k_cert_fin(const double *__restrict__ par
     if (threadIdx.x == 0) dst[idx ? idx[i] : i] += s;
 }
 
-__device__ __forceinline__ double cert_block_max(double v, double *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-    __syncthreads();
-    return t;
-}
-
 // one workgroup: ax <- A(X) - b in place; acc[2..5] = { ||A(X) - b||_2^2, ||A(X) - b||_inf, ||b||_inf, b . lambda }
 __global__ __launch_bounds__(TPB) void k_cert_close(int m, double *__restrict__ ax, const double *__restrict__ b,
                                                     const double *__restrict__ lam, double *__restrict__ acc) {
@@ -141,8 +118,8 @@ __global__ __launch_bounds__(TPB) void k_cert_close(int m, double *__restrict__ 
     }
     s2 = block_sum(s2, sh);
     bl = block_sum(bl, sh);
-    rinf = cert_block_max(rinf, sh);
-    binf = cert_block_max(binf, sh);
+    rinf = block_max(rinf, sh);
+    binf = block_max(binf, sh);
     if (threadIdx.x == 0) { acc[2] = s2; acc[3] = rinf; acc[4] = binf; acc[5] = bl; }
 }
 
@@ -151,20 +128,12 @@ __global__ __launch_bounds__(TPB) void k_cert_min(int n, const double *__restric
     __shared__ double sh[4];
     double s = INFINITY;
     for (int t = threadIdx.x; t < n; t += TPB) s = fmin(s, v[t]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s = fmin(s, __shfl_xor(s, o));
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *out = fmin(fmin(sh[0], sh[1]), fmin(sh[2], sh[3]));
+    s = block_min(s, sh);
+    if (threadIdx.x == 0) *out = s;
 }
 
 constexpr int CERT_GRID = 1024; // workgroups of the pattern pass (bounded: its partials fit the scratch)
 constexpr int CERT_ACC = 16;    // accumulators in front of the per-cone minima of LP blocks
-
-int cert_refuse_sharded(const lorads_hip_ctx *c, const char *what) {
-    if (c->ar || c->sep || c->sx) return fail_msg(std::string(what) + ": sharded contexts (world > 1) cannot export a solution");
-    return 0;
-}
 
 // scratch of the export, allocated on first use (CertScratch::release frees it with the context)
 int cert_alloc(lorads_hip_ctx *c) {
@@ -241,35 +210,34 @@ extern "C" int lorads_hip_certificate(lorads_hip_ctx *c, int32_t src, double tol
                                       double out[LORADS_HIP_CERT_N], double *lam_min, double *residual,
                                       double *lambda) {
     spec_touch(c);
-    if (!c || !out || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV) || (tol > 0 && ncv < 2))
-        return fail_msg("certificate: bad argument");
-    if (cert_refuse_sharded(c, "certificate") || cert_alloc(c)) return 1;
+    if (postsolve_args(c, src, nullptr, "certificate", true)) return 1;
+    if (!out || (tol > 0 && ncv < 2)) return fail_msg("certificate: bad argument");
+    if (postsolve_sharded(c, "certificate", "cannot export a solution") || cert_alloc(c)) return 1;
     CertScratch &X = c->cert;
-    const int uv = src == LORADS_HIP_PAIR_UV;
     cert_lambda(c);
     HC(hipMemsetAsync(X.ax, 0, sizeof(double) * (size_t)std::max(c->m, 1), c->stream));
     HC(hipMemsetAsync(X.acc, 0, sizeof(double) * ((size_t)CERT_ACC + c->nb), c->stream));
     for (int k = 0; k < c->nb; ++k) {
         Block &B = c->blk[k];
-        const double *U = (uv ? c->U : c->R) + B.off, *V = (uv ? c->V : c->R) + B.off;
+        const FactorView F = factor_view(c, src, k);
         cert_slack(c, k);
         if (B.pu.ne > 0) { // <C, X> and <S, X> over the union pattern (d_e kept in the scratch)
             const int g = std::min(nblocks_for((size_t)B.pu.ne, TPB / 8), CERT_GRID);
-            hipLaunchKernelGGL(k_cert_pat, dim3(g), dim3(TPB), 0, c->stream, B.pu.ne, (const int *)B.pu.erow, (const int *)B.pu.ecol, U, V,
-                               uv, B.r, X.d, (const double *)B.pu.cbase, (const double *)(X.S + X.s_off[k]), X.part);
+            hipLaunchKernelGGL(k_cert_pat, dim3(g), dim3(TPB), 0, c->stream, B.pu.ne, (const int *)B.pu.erow, (const int *)B.pu.ecol, F.U, F.V,
+                               F.uv, B.r, X.d, (const double *)B.pu.cbase, (const double *)(X.S + X.s_off[k]), X.part);
             hipLaunchKernelGGL(k_cert_fin, dim3(1), dim3(TPB), 0, c->stream, (const double *)X.part, g, X.acc, (const int *)nullptr, 0);
             hipLaunchKernelGGL(k_cert_fin, dim3(1), dim3(TPB), 0, c->stream, (const double *)(X.part + g), g, X.acc, (const int *)nullptr, 1);
         }
         if (B.pa.ne > 0 && B.nrow > 0) { // A_k(X_k) by constraint over the A-pattern
             const int g = std::min(nblocks_for((size_t)B.pa.ne, TPB / 8), CERT_GRID);
-            hipLaunchKernelGGL(k_cert_pat, dim3(g), dim3(TPB), 0, c->stream, B.pa.ne, (const int *)B.pa.erow, (const int *)B.pa.ecol, U, V,
-                               uv, B.r, X.dA, (const double *)nullptr, (const double *)nullptr, (double *)nullptr);
+            hipLaunchKernelGGL(k_cert_pat, dim3(g), dim3(TPB), 0, c->stream, B.pa.ne, (const int *)B.pa.erow, (const int *)B.pa.ecol, F.U, F.V,
+                               F.uv, B.r, X.dA, (const double *)nullptr, (const double *)nullptr, (double *)nullptr);
             hipLaunchKernelGGL(k_cert_cv, dim3(nblocks_for((size_t)B.nrow, TPB / 8)), dim3(TPB), 0, c->stream, B.nrow, (const int *)B.a_ptr,
                                (const int *)B.a_e, (const double *)B.a_val, (const double *)X.dA, (const int *)B.row_idx, X.ax);
         }
         if (B.dense_a || B.dense_c) { // the dense shares through G = R R^T
             const size_t msz = (size_t)B.npad * B.npad;
-            hipLaunchKernelGGL(k_cert_gram, dim3(grid1d(msz)), dim3(TPB), 0, c->stream, B.n, B.npad, U, V, uv, B.r, X.G);
+            hipLaunchKernelGGL(k_cert_gram, dim3(grid1d(msz)), dim3(TPB), 0, c->stream, B.n, B.npad, F.U, F.V, F.uv, B.r, X.G);
             if (B.dense_c) cert_dot_into(c, msz, B.Cfull, X.G, X.acc, nullptr, 0);
             cert_dot_into(c, msz, cert_dense_slack(c, k), X.G, X.acc, nullptr, 1);
             for (int j = 0; j < B.nd; ++j)
@@ -317,7 +285,7 @@ extern "C" int lorads_hip_certificate(lorads_hip_ctx *c, int32_t src, double tol
 extern "C" int lorads_hip_get_slack(lorads_hip_ctx *c, int32_t k, int64_t *nnz, int32_t *row, int32_t *col, double *val) {
     spec_touch(c);
     if (!c || !nnz || k < 0 || k >= c->nb) return fail_msg("get_slack: bad argument");
-    if (cert_refuse_sharded(c, "get_slack")) return 1;
+    if (postsolve_sharded(c, "get_slack", "cannot export a solution")) return 1;
     Block &B = c->blk[k];
     const bool dense = B.dense_a || B.dense_c;
     const int64_t cnt = B.is_lp ? B.n : dense ? (int64_t)B.n * (B.n + 1) / 2 : B.pu.ne;

@@ -4,10 +4,10 @@
 // no common-rank columns); G = F^T F (rl x rl) = Q Lambda Q^T with lambda_1 >= lambda_2 >= ... (ties: lower original index first).
 // The non-zero eigenvalues of X = F F^T are those of G, F Q has mutually orthogonal columns of squared norm lambda_j, and its first
 // k columns are the best rank-k approximation of X.
-//   k_spec_gram + k_spec_gram_sum   G on the FP64 matrix cores (v_mfma_f64_16x16x4_f64, operand layout as k_dense_cx_b): row strips
-//                                   give partial Grams, a second stage adds them in strip order (no float atomics: same state, same bits)
+//   k_spec_gram + k_spec_gram_sum   G on the FP64 matrix cores (postsolve.inc: mfma_strip_tile): row strips give partial Grams, a
+//                                   second stage adds them in strip order (no float atomics: same state, same bits)
 //   k_spec_jacobi                   one workgroup per cone: cyclic Jacobi in the round-robin ordering, then the sort
-//   k_spec_rotate                   F' = F Q[:, :k] on the matrix cores, written to the new R, U and V alike
+//   k_spec_rotate                   F' = F Q[:, :k] on the matrix cores (mfma_fm_tile), written to the new R, U and V alike
 // lorads_hip_spectrum is read-only on the solver's state: the scratch is the feature's own (SpecScratch) and every launch goes
 // straight to the stream (never through LAUNCH, which would flush a pending dual update into the state).
 
@@ -22,20 +22,11 @@ constexpr size_t SPEC_PART_CAP = (size_t)4 << 20; // doubles of Gram partials (3
 constexpr size_t SPEC_W_CAP = (size_t)3 << 20;    // doubles of G, Q, eigenvalues and sorted Q per k_spec_jacobi launch (24 MB): cones
                                                   // beyond it go to a further launch (one cone of order 512 takes 0.79 M)
 
-__device__ __forceinline__ double spec_ld(const double *__restrict__ U, const double *__restrict__ V, bool uv, size_t i) {
-    double a = U[i];
-    if (uv) a = (a + V[i]) / 2;
-    return a;
-}
-
-// Partial Gram of one row strip and one tile pair I <= J (blockIdx.y): D[m][n] = sum_k A[m][k] B[k][n] with A[m][k] = F[row k][16 I + m]
-// (F transposed) and B[k][n] = F[row k][16 J + n] -- lane (nn = l & 15, kk = l >> 4) supplies both from row kk of the four at hand,
-// the same 128-byte row segments -- and holds D[kk + 4 q][nn] in register q.  Columns >= rl and rows >= n are clamped loads times
-// zero, not branches.  The four wavefronts take a quarter of the strip's rows each; their tiles are added in wave order through LDS.
+// Partial Gram of one row strip and one tile pair I <= J (blockIdx.y): mfma_strip_tile with A[m][k] = F[row k][16 I + m] (F transposed)
+// and B[k][n] = F[row k][16 J + n], segments of the same row.  Columns >= rl and rows >= n are clamped loads times zero.
 __global__ __launch_bounds__(TPB) void k_spec_gram(int n, int rl, int r, int rows_per_strip, int npairs, const double *__restrict__ U,
                                                    const double *__restrict__ V, int uv, double *__restrict__ part) {
-    __shared__ double red[3][4][64];
-    const int wave = threadIdx.x >> 6, l = threadIdx.x & 63, nn = l & 15, kk = l >> 4;
+    const int nn = threadIdx.x & 15;
     const int T = (rl + 15) / 16;
     int I = 0, pi = blockIdx.y;
     while (pi >= T - I) { pi -= T - I; ++I; }
@@ -43,36 +34,11 @@ __global__ __launch_bounds__(TPB) void k_spec_gram(int n, int rl, int r, int row
     const int ca = 16 * I + nn, cb = 16 * J + nn;
     const int cac = ca < rl ? ca : 0, cbc = cb < rl ? cb : 0;
     const double ma = ca < rl ? 1.0 : 0.0, mb = cb < rl ? 1.0 : 0.0;
-    const int q4 = rows_per_strip / 4; // (a multiple of 16: see spec_gram)
-    const int rbeg = blockIdx.x * rows_per_strip + wave * q4;
-    v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < q4; k0 += 16) {
-        double a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int row = rbeg + k0 + 4 * u + kk;
-            const bool ok = row < n;
-            const size_t o = (size_t)(ok ? row : 0) * r;
-            const double mr = ok ? 1.0 : 0.0;
-            a[u] = spec_ld(U, V, uv != 0, o + cac) * (ma * mr);
-            b[u] = spec_ld(U, V, uv != 0, o + cbc) * mb;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave - 1][q][l] = acc[q];
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    double *out = part + ((size_t)blockIdx.x * npairs + blockIdx.y) * 256;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v = acc[q];
-        v += red[0][q][l]; v += red[1][q][l]; v += red[2][q][l];
-        out[(kk + 4 * q) * 16 + nn] = v; // D[m = kk + 4 q][n = nn]
-    }
+    mfma_strip_tile(n, rows_per_strip, npairs, part, [=](size_t row, double mr, double &a, double &b) {
+        const size_t o = row * r;
+        a = factor_ld(U, V, uv != 0, o + cac) * (ma * mr);
+        b = factor_ld(U, V, uv != 0, o + cbc) * mb;
+    });
 }
 
 // G (m x m, m = rl rounded up to even) = the strips' partial Grams added in strip order; tile pair I < J mirrored into (J, I)
@@ -197,8 +163,8 @@ __global__ __launch_bounds__(SPEC_JT) void k_spec_jacobi(const SpecCone *__restr
 }
 
 // F' = F Q[:, :knew] into the new factor arrays (row stride rnew; columns >= knew stay as alloc_factors zeroed them).  A wavefront
-// takes 16 rows: A[m][k] = F[row0 + m][k0 + k], B[k][n] = Q[k0 + k][j0 + n] (Qs column-major rl x rl), D[kk + 4 q][nn] = row
-// row0 + kk + 4 q, column j0 + nn: 128-byte row segments on the way out.  k >= rl: clamped loads times zero.
+// takes 16 rows and, 16 columns j0 at a time, mfma_fm_tile with M[k][n] = Q[k][j0 + n] (Qs column-major rl x rl; columns >= knew: a
+// clamped load times zero).
 __global__ __launch_bounds__(TPB) void k_spec_rotate(int n, int rl, int r, int knew, int rnew, const double *__restrict__ U,
                                                      const double *__restrict__ V, int uv, const double *__restrict__ Qs,
                                                      double *__restrict__ oR, double *__restrict__ oU, double *__restrict__ oV) {
@@ -210,13 +176,7 @@ __global__ __launch_bounds__(TPB) void k_spec_rotate(int n, int rl, int r, int k
         const int jb = j0 + nn;
         const size_t bo = (size_t)(jb < knew ? jb : 0) * rl;
         const double mb = jb < knew ? 1.0 : 0.0;
-        v4f64 acc = (v4f64){0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < rl; k0 += 4) {
-            const int k = k0 + kk, kc = k < rl ? k : 0;
-            const double a = spec_ld(U, V, uv != 0, ao + kc) * (k < rl ? 1.0 : 0.0);
-            const double b = Qs[bo + kc] * mb;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-        }
+        const v4f64 acc = mfma_fm_tile(U, V, uv != 0, ao, rl, kk, [=](int k) { return Qs[bo + k] * mb; });
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int row = row0 + kk + 4 * q;
@@ -228,21 +188,13 @@ __global__ __launch_bounds__(TPB) void k_spec_rotate(int n, int rl, int r, int k
     }
 }
 
-int spec_refuse_sharded(const lorads_hip_ctx *c, const char *what) {
-    if (c->ar || c->sep || c->sx) {
-        fail_msg(std::string(what) + ": sharded contexts (world > 1) are not supported");
-        return 3;
-    }
-    return 0;
-}
-
 inline int spec_m(int rl) { return (rl + 1) & ~1; }
 inline size_t spec_w_need(int rl) { const size_t m = (size_t)spec_m(rl); return 2 * m * m + (size_t)rl + (size_t)rl * rl; }
 
-// Gram + Jacobi of the SDP cones [k0, k1) (one k_spec_jacobi launch) of the factor arrays U, V (uv: F = (U + V) / 2, else F = U) with the
+// Gram + Jacobi of the SDP cones [k0, k1) (one k_spec_jacobi launch) of the factor arrays F (a view of whole arrays: offset 0) with the
 // cones' CURRENT shapes `off`, `r`, `rl`; eigenvalues, sweep counts and (q != null) eigenvectors to the host arrays at the cones' places.
 // The sorted eigenvectors of cone k stay in the scratch at W + qoff[k] until the next call.
-int spec_run(lorads_hip_ctx *c, const double *Ub, const double *Vb, int uv, int k0, int k1, const std::vector<size_t> &off,
+int spec_run(lorads_hip_ctx *c, const FactorView &F, int k0, int k1, const std::vector<size_t> &off,
              const std::vector<int> &r, const std::vector<int> &rl, double *eig, double *q, int32_t *sweeps,
              std::vector<size_t> &qoff) {
     SpecScratch &X = c->spectral;
@@ -268,18 +220,11 @@ int spec_run(lorads_hip_ctx *c, const double *Ub, const double *Vb, int uv, int 
         const int n = c->blk[which[i]].n, T = (cones[i].rl + 15) / 16;
         npairs[i] = T * (T + 1) / 2;
         const int smax = (int)std::max<size_t>(1, std::min<size_t>(SPEC_MAX_STRIPS, SPEC_PART_CAP / ((size_t)npairs[i] * 256)));
-        int s = std::max(1, std::min(smax, nblocks_for((size_t)n, 256)));
-        rps[i] = std::max(64, (nblocks_for((size_t)n, s) + 63) & ~63);
-        strips[i] = std::max(1, nblocks_for((size_t)n, rps[i]));
+        row_strips(n, smax, strips[i], rps[i]);
         part_need = std::max(part_need, (size_t)strips[i] * npairs[i] * 256);
     }
-    if (part_need > X.part_cap) { X.mem.free(X.part); X.part_cap = 0; if (X.mem.alloc(&X.part, part_need)) return 1; X.part_cap = part_need; }
-    if (need > X.w_cap) { X.mem.free(X.W); X.w_cap = 0; if (X.mem.alloc(&X.W, need)) return 1; X.w_cap = need; }
-    if (cones.size() > X.cones_cap) {
-        X.mem.free(X.cones); X.mem.free(X.info); X.cones_cap = 0;
-        if (X.mem.alloc(&X.cones, cones.size()) || X.mem.alloc(&X.info, 2 * cones.size())) return 1;
-        X.cones_cap = cones.size();
-    }
+    if (X.part.grow(X.mem, part_need) || X.W.grow(X.mem, need)) return 1;
+    if (X.cones.grow(X.mem, cones.size()) || X.info.grow(X.mem, 2 * cones.size())) return 1;
     const int lds = (int)(sizeof(double) * 2 * (size_t)lds_m * (lds_m + 1));
     // (the attribute belongs to the kernel on the current device, not to a context: set before every launch, to the most it can ask for)
     HC(hipFuncSetAttribute((const void *)k_spec_jacobi, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -291,8 +236,8 @@ int spec_run(lorads_hip_ctx *c, const double *Ub, const double *Vb, int uv, int 
             HC(hipMemsetAsync(X.W + cones[i].g_off, 0, sizeof(double) * (size_t)cones[i].m * cones[i].m, c->stream));
             continue;
         }
-        hipLaunchKernelGGL(k_spec_gram, dim3(strips[i], npairs[i]), dim3(TPB), 0, c->stream, B.n, rl[k], r[k], rps[i], npairs[i], Ub + off[k],
-                           Vb + off[k], uv, X.part);
+        hipLaunchKernelGGL(k_spec_gram, dim3(strips[i], npairs[i]), dim3(TPB), 0, c->stream, B.n, rl[k], r[k], rps[i], npairs[i], F.U + off[k],
+                           F.V + off[k], F.uv, X.part);
         hipLaunchKernelGGL(k_spec_gram_sum, dim3(npairs[i]), dim3(TPB), 0, c->stream, rl[k], cones[i].m, strips[i], npairs[i],
                            (const double *)X.part, X.W + cones[i].g_off);
     }
@@ -350,15 +295,16 @@ void spec_shapes(const lorads_hip_ctx *c, std::vector<size_t> &off, std::vector<
 
 extern "C" int lorads_hip_spectrum(lorads_hip_ctx *c, int32_t src, double *eig, double *q, int32_t *sweeps) {
     spec_touch(c);
-    if (!c || !eig || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV)) return fail_msg("spectrum: bad argument");
-    if (spec_refuse_sharded(c, "spectrum")) return 3;
-    const int uv = src == LORADS_HIP_PAIR_UV;
+    if (postsolve_args(c, src, nullptr, "spectrum", true)) return 1;
+    if (!eig) return fail_msg("spectrum: bad argument");
+    if (postsolve_sharded(c, "spectrum", "are not supported")) return 3;
+    const FactorView F = factor_view(src, c->R, c->U, c->V, 0);
     std::vector<size_t> off, qoff(c->nb, 0);
     std::vector<int> r, rl;
     spec_shapes(c, off, r, rl);
     if (sweeps) for (int k = 0; k < c->nb; ++k) sweeps[k] = 0;
     for (auto &b : spec_batches(c)) {
-        const int rc = spec_run(c, uv ? c->U : c->R, uv ? c->V : c->R, uv, b.first, b.second, off, r, rl, eig, q, sweeps, qoff);
+        const int rc = spec_run(c, F, b.first, b.second, off, r, rl, eig, q, sweeps, qoff);
         if (rc) return rc;
     }
     return 0;
@@ -366,8 +312,9 @@ extern "C" int lorads_hip_spectrum(lorads_hip_ctx *c, int32_t src, double *eig, 
 
 extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const int32_t *nr, double *eig) {
     spec_touch(c);
-    if (!c || !nr || (src != LORADS_HIP_PAIR_RR && src != LORADS_HIP_PAIR_UV)) return fail_msg("compress_rank: bad argument");
-    if (spec_refuse_sharded(c, "compress_rank")) return 3;
+    if (postsolve_args(c, src, nullptr, "compress_rank", true)) return 1;
+    if (!nr) return fail_msg("compress_rank: bad argument");
+    if (postsolve_sharded(c, "compress_rank", "are not supported")) return 3;
     // (refuse before anything is touched: a refused call leaves host and device at the old ranks and the old bits)
     for (int k = 0; k < c->nb; ++k) {
         const Block &B = c->blk[k];
@@ -376,7 +323,6 @@ extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const in
         if (nblocks_for((size_t)B.n, TPB / lg_for(nd)) > c->maxpart)
             return fail_msg("compress_rank: cone dimension too large for the partial-sum slots at this rank");
     }
-    const int uv = src == LORADS_HIP_PAIR_UV;
     std::vector<size_t> off_old, qoff(c->nb, 0);
     std::vector<int> r_old, rl_old;
     spec_shapes(c, off_old, r_old, rl_old);
@@ -387,7 +333,7 @@ extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const in
     ev.resize(std::max<size_t>(ne, 1));
     // every cone's eigen-solve before the state is touched: one that does not converge is a refusal too
     for (auto &b : batches) {
-        const int rc = spec_run(c, uv ? c->U : c->R, uv ? c->V : c->R, uv, b.first, b.second, off_old, r_old, rl_old, ev.data(), nullptr,
+        const int rc = spec_run(c, factor_view(src, c->R, c->U, c->V, 0), b.first, b.second, off_old, r_old, rl_old, ev.data(), nullptr,
                                 nullptr, qoff);
         if (rc) return rc;
     }
@@ -402,11 +348,11 @@ extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const in
     common_rank(c);
     refresh_merged(c);
     if (alloc_factors(c)) return 1; // (every new array zero: pad columns, pad rows, Grad, the L-BFGS ring)
-    const double *Uo = uv ? old[1] : old[0], *Vo = uv ? old[2] : old[0];
+    const FactorView Fo = factor_view(src, old[0], old[1], old[2], 0);
     for (auto &b : batches) {
         // (several launches: the eigenvectors of this one are formed again -- the same bits -- since the scratch holds one launch's)
         if (batches.size() > 1) {
-            const int rc = spec_run(c, Uo, Vo, uv, b.first, b.second, off_old, r_old, rl_old, nullptr, nullptr, nullptr, qoff);
+            const int rc = spec_run(c, Fo, b.first, b.second, off_old, r_old, rl_old, nullptr, nullptr, nullptr, qoff);
             if (rc) return rc;
         }
         for (int k = b.first; k < b.second; ++k) {
@@ -419,7 +365,7 @@ extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const in
             }
             if (B.n == 0) continue;
             hipLaunchKernelGGL(k_spec_rotate, dim3(nblocks_for((size_t)B.n, 16 * (TPB / 64))), dim3(TPB), 0, c->stream, B.n, rl_old[k], r_old[k],
-                               B.rl, B.r, Uo + off_old[k], Vo + off_old[k], uv, (const double *)(c->spectral.W + qoff[k]), c->R + B.off,
+                               B.rl, B.r, Fo.U + off_old[k], Fo.V + off_old[k], Fo.uv, (const double *)(c->spectral.W + qoff[k]), c->R + B.off,
                                c->U + B.off, c->V + B.off);
         }
     }

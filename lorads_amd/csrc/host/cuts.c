@@ -9,10 +9,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-lrd_problem *lrd_session_problem(lrd_session *s);
-lrd_solver *lrd_session_solver(lrd_session *s);
-lrd_backend *lrd_session_backend(lrd_session *s);
-
 /* coefficients of rho_pq, rho_ps, rho_qs in the four classes */
 static const int cut_sign[4][3] = {{1, 1, 1}, {1, -1, -1}, {-1, 1, -1}, {-1, -1, 1}};
 
@@ -34,22 +30,15 @@ static int cut_before(const lrd_cuts *c, int a, int b) {
 
 int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts, lrd_cuts **out) {
     *out = NULL;
-    lrd_solver *v = lrd_session_solver(s);
     lrd_backend *be = lrd_session_backend(s);
-    if (!v || !be) return 1;
-    if (!be->triangle_cuts) {
-        fprintf(stderr, "lorads: the %s backend cannot separate triangle inequalities\n", be->name ? be->name : "attached");
-        return 2;
-    }
-    const lrd_problem *pr = lrd_session_problem(s);
-    if (pr->separable || pr->nblk != pr->nblk_global || v->allreduce) {
-        fprintf(stderr, "lorads: the separation of a sharded deal (world > 1) is not supported\n");
-        return 3;
-    }
-    const int nb = pr->nblk, cap = max_cuts > 0 ? max_cuts : 1;
+    int src;
+    const int refused = lrd_session_postsolve(s, be && be->triangle_cuts, "separate triangle inequalities",
+                                              "the separation of a sharded deal (world > 1) is", NULL, NULL, &src);
+    if (refused) return refused;
+    const int nb = lrd_session_problem(s)->nblk, cap = max_cuts > 0 ? max_cuts : 1;
     lrd_cuts *c = (lrd_cuts *)calloc(1, sizeof *c);
     c->nblk = nb;
-    c->src = v->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    c->src = src;
     c->min_violation = min_violation;
     c->max_cuts = max_cuts;
     c->count = (int64_t *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int64_t));

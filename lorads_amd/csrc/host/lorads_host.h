@@ -305,6 +305,16 @@ typedef struct {
 /* fill *out from the session's current state (tol: Lanczos tolerance of lambda_min); refuses (non-zero) when the table lacks the
  * export slots or the session holds a sharded deal.  lrd_solution_free releases what it allocated. */
 typedef struct lrd_session lrd_session;
+/* what a session holds (session.c): the solver and the table are NULL until a backend has been attached */
+lrd_problem *lrd_session_problem(lrd_session *s);
+lrd_solver *lrd_session_solver(lrd_session *s);
+lrd_backend *lrd_session_backend(lrd_session *s);
+/* The way in of every post-solve entry point below.  0: the session can be asked -- *v, *be and *src (the pair the solver's phase
+ * works on: LRD_PAIR_UV in ADMM, LRD_PAIR_RR before) are filled (each may be NULL); 1: no solver; 2: the table lacks the slots
+ * (have_slots == 0: "lorads: the <name> backend cannot <cannot>" on stderr); 3: the session holds a sharded deal ("lorads: <sharded>
+ * not supported"). */
+int lrd_session_postsolve(lrd_session *s, int have_slots, const char *cannot, const char *sharded, lrd_solver **v, lrd_backend **be,
+                          int *src);
 int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out);
 void lrd_solution_free(lrd_solution *sol);
 /* plain-text file of a solution (a pure function of the struct): "lorads-solution 1", status, pobj, dobj, the certificate, "y m" and

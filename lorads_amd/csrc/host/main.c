@@ -17,7 +17,6 @@ int lrd_session_attach(lrd_session *s, const lrd_backend *be);
 int lrd_session_solve(lrd_session *s);
 int lrd_session_results(lrd_session *s, double out[16]);
 int lrd_session_results2(lrd_session *s, double out[4]);
-lrd_problem *lrd_session_problem(lrd_session *s);
 lrd_params *lrd_session_params(lrd_session *s);
 void lrd_session_close(lrd_session *s);
 int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libpath, lrd_backend *out);

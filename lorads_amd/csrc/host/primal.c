@@ -9,40 +9,25 @@
 #include <stdlib.h>
 #include <string.h>
 
-lrd_problem *lrd_session_problem(lrd_session *s);
-lrd_solver *lrd_session_solver(lrd_session *s);
-lrd_backend *lrd_session_backend(lrd_session *s);
-
-/* 0: the session can be asked; 1: no solver; 2: the table lacks the slots; 3: sharded */
-static int primal_refuse(lrd_session *s) {
-    lrd_solver *v = lrd_session_solver(s);
-    lrd_backend *be = lrd_session_backend(s);
-    if (!v || !be) return 1;
-    if (!be->primal_entries || !be->primal_apply) {
-        fprintf(stderr, "lorads: the %s backend cannot query the primal\n", be->name ? be->name : "attached");
-        return 2;
-    }
-    const lrd_problem *p = lrd_session_problem(s);
-    if (p->separable || p->nblk != p->nblk_global || v->allreduce) {
-        fprintf(stderr, "lorads: primal queries of a sharded deal (world > 1) are not supported\n");
-        return 3;
-    }
-    return 0;
+static int primal_refuse(lrd_session *s, lrd_backend **be, int *src) {
+    const lrd_backend *t = lrd_session_backend(s);
+    return lrd_session_postsolve(s, t && t->primal_entries && t->primal_apply, "query the primal",
+                                 "primal queries of a sharded deal (world > 1) are", NULL, be, src);
 }
 
 int lrd_session_primal_entries(lrd_session *s, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
                                double *stats) {
-    const int rc = primal_refuse(s);
-    if (rc) return rc;
-    lrd_backend *be = lrd_session_backend(s);
-    return be->primal_entries(be->ctx, lrd_session_solver(s)->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR, blk, count, row, col, val, ref, stats);
+    lrd_backend *be;
+    int src;
+    const int rc = primal_refuse(s, &be, &src);
+    return rc ? rc : be->primal_entries(be->ctx, src, blk, count, row, col, val, ref, stats);
 }
 
 int lrd_session_primal_apply(lrd_session *s, int blk, int ncols, const double *B, double *Y, double *T) {
-    const int rc = primal_refuse(s);
-    if (rc) return rc;
-    lrd_backend *be = lrd_session_backend(s);
-    return be->primal_apply(be->ctx, lrd_session_solver(s)->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR, blk, ncols, B, Y, T);
+    lrd_backend *be;
+    int src;
+    const int rc = primal_refuse(s, &be, &src);
+    return rc ? rc : be->primal_apply(be->ctx, src, blk, ncols, B, Y, T);
 }
 
 void lrd_entries_free(lrd_entries *q) {
@@ -150,7 +135,7 @@ int lrd_entries_group(const lrd_entries *q, int nblk, int64_t *perm, int64_t *st
 }
 
 int lrd_session_entries(lrd_session *s, lrd_entries *q) {
-    int rc = primal_refuse(s);
+    int rc = primal_refuse(s, NULL, &q->src);
     if (rc) return rc;
     const lrd_problem *p = lrd_session_problem(s);
     const int nb = p->nblk;
@@ -158,7 +143,6 @@ int lrd_session_entries(lrd_session *s, lrd_entries *q) {
     int64_t *perm = (int64_t *)malloc(sizeof(int64_t) * cnt), *start = (int64_t *)malloc(sizeof(int64_t) * (size_t)(nb + 1));
     int *row = (int *)malloc(sizeof(int) * cnt), *col = (int *)malloc(sizeof(int) * cnt);
     double *val = (double *)malloc(sizeof(double) * cnt), *ref = (double *)malloc(sizeof(double) * cnt);
-    q->src = lrd_session_solver(s)->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
     q->stats[0] = q->stats[1] = q->stats[2] = q->stats[3] = 0.0;
     rc = lrd_entries_group(q, nb, perm, start);
     if (rc) fprintf(stderr, "lorads: a query names a block outside 1..%d\n", nb);

@@ -15,7 +15,6 @@ typedef struct lrd_session {
     int have_be;
     lrd_solver sol;
     int have_sol;
-    int nblk_all;          /* blocks in the file (before sharding) */
     double **R0, **U0, **V0; /* start point of the blocks this process holds */
     char fname[4096];
 } lrd_session;
@@ -33,7 +32,6 @@ lrd_session *lrd_session_open(const char *fname) {
         free(s);
         return NULL;
     }
-    s->nblk_all = s->prob->nblk;
     return s;
 }
 
@@ -48,7 +46,6 @@ lrd_session *lrd_session_from_triplets(int m, const double *b, int nblk, const i
         free(s);
         return NULL;
     }
-    s->nblk_all = s->prob->nblk;
     return s;
 }
 
@@ -206,22 +203,33 @@ int lrd_session_results(lrd_session *s, double out[16]) {
     return 0;
 }
 
+int lrd_session_postsolve(lrd_session *s, int have_slots, const char *cannot, const char *sharded, lrd_solver **v, lrd_backend **be,
+                          int *src) {
+    if (!s->have_sol) return 1;
+    if (!have_slots) {
+        fprintf(stderr, "lorads: the %s backend cannot %s\n", s->be.name ? s->be.name : "attached", cannot);
+        return 2;
+    }
+    if (s->prob->separable || s->prob->nblk != s->prob->nblk_global || s->sol.allreduce) {
+        fprintf(stderr, "lorads: %s not supported\n", sharded);
+        return 3;
+    }
+    if (v) *v = &s->sol;
+    if (be) *be = &s->be;
+    if (src) *src = s->sol.in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    return 0;
+}
+
 /* the current point with its certificate, in the file's units (lorads_host.h: lrd_solution) */
 int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out) {
     *out = NULL;
-    if (!s->have_sol) return 1;
     lrd_backend *be = &s->be;
     const lrd_problem *p = s->prob;
-    if (!be->certificate || !be->get_slack) {
-        fprintf(stderr, "lorads: the %s backend cannot export a solution\n", be->name ? be->name : "attached");
-        return 2;
-    }
-    if (p->separable || p->nblk != s->nblk_all || s->sol.allreduce) {
-        fprintf(stderr, "lorads: exporting the solution of a sharded deal (world > 1) is not supported\n");
-        return 3;
-    }
+    int src;
+    const int refused = lrd_session_postsolve(s, be->certificate && be->get_slack, "export a solution",
+                                              "exporting the solution of a sharded deal (world > 1) is", NULL, NULL, &src);
+    if (refused) return refused;
     const double sc = s->sol.scaleObjHis;
-    const int src = s->sol.in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
     double c[LRD_CERT_N];
     double *lm = (double *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(double));
     lrd_solution *x = (lrd_solution *)calloc(1, sizeof *x);
@@ -275,18 +283,12 @@ int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out) {
 int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_hyperplanes,
                          lrd_rounding **out) {
     *out = NULL;
-    if (!s->have_sol) return 1;
     lrd_backend *be = &s->be;
     const lrd_problem *p = s->prob;
-    if (!be->round_pm1) {
-        fprintf(stderr, "lorads: the %s backend cannot round a solution\n", be->name ? be->name : "attached");
-        return 2;
-    }
-    if (p->separable || p->nblk != s->nblk_all || s->sol.allreduce) {
-        fprintf(stderr, "lorads: rounding the solution of a sharded deal (world > 1) is not supported\n");
-        return 3;
-    }
-    const int src = s->sol.in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    int src;
+    const int refused = lrd_session_postsolve(s, be->round_pm1 != NULL, "round a solution",
+                                              "rounding the solution of a sharded deal (world > 1) is", NULL, NULL, &src);
+    if (refused) return refused;
     if (trials <= 0) return trials < 0 ? 1 : be->round_pm1(be->ctx, src, 0, seed, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
     const double sc = s->sol.scaleObjHis;
     size_t ntot = 0, gtot = 0;

@@ -8,10 +8,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-lrd_problem *lrd_session_problem(lrd_session *s);
-lrd_solver *lrd_session_solver(lrd_session *s);
-lrd_backend *lrd_session_backend(lrd_session *s);
-
 int lrd_session_block_is_lp(lrd_session *s, int k) {
     const lrd_problem *p = lrd_session_problem(s);
     return k >= 0 && k < p->nblk && p->blk[k].is_lp;
@@ -26,29 +22,17 @@ int lrd_spectral_choose(const double *eig, int rl, double tol, int cap) {
     return k < 1 ? 1 : k;
 }
 
-/* 0: the session can be looked at; 1: no solver; 2: the table lacks the slots; 3: sharded */
-static int spectral_refuse(lrd_session *s, const char *what) {
-    lrd_solver *v = lrd_session_solver(s);
-    lrd_backend *be = lrd_session_backend(s);
-    if (!v || !be) return 1;
-    if (!be->spectrum || !be->compress_rank) {
-        fprintf(stderr, "lorads: the %s backend cannot compute the %s\n", be->name ? be->name : "attached", what);
-        return 2;
-    }
-    const lrd_problem *p = lrd_session_problem(s);
-    if (p->separable || p->nblk != p->nblk_global || v->allreduce) {
-        fprintf(stderr, "lorads: the %s of a sharded deal (world > 1) is not supported\n", what);
-        return 3;
-    }
-    return 0;
+static int spectral_slots(lrd_session *s) {
+    const lrd_backend *be = lrd_session_backend(s);
+    return be && be->spectrum && be->compress_rank;
 }
 
 int lrd_session_spectrum(lrd_session *s, double *eig, int *sweeps) {
-    const int rc = spectral_refuse(s, "spectrum of the solution");
-    if (rc) return rc;
-    lrd_solver *v = lrd_session_solver(s);
-    lrd_backend *be = lrd_session_backend(s);
-    return be->spectrum(be->ctx, v->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR, eig, NULL, sweeps);
+    lrd_backend *be;
+    int src;
+    const int rc = lrd_session_postsolve(s, spectral_slots(s), "compute the spectrum of the solution",
+                                         "the spectrum of the solution of a sharded deal (world > 1) is", NULL, &be, &src);
+    return rc ? rc : be->spectrum(be->ctx, src, eig, NULL, sweeps);
 }
 
 void lrd_spectral_report_free(lrd_spectral_report *r) {
@@ -64,13 +48,15 @@ int lrd_session_compress(lrd_session *s, double tol, int cap, lrd_spectral_repor
 
 int lrd_session_compress_ex(lrd_session *s, double tol, int cap, const int *ranks, lrd_spectral_report **report) {
     if (report) *report = NULL;
-    int rc = spectral_refuse(s, "rank reduction of the solution");
+    lrd_solver *v;
+    lrd_backend *be;
+    int src;
+    int rc = lrd_session_postsolve(s, spectral_slots(s), "compute the rank reduction of the solution",
+                                   "the rank reduction of the solution of a sharded deal (world > 1) is", &v, &be, &src);
     if (rc) return rc;
     if (!(tol >= 0)) return 1;
-    lrd_solver *v = lrd_session_solver(s);
-    lrd_backend *be = lrd_session_backend(s);
     const lrd_problem *p = lrd_session_problem(s);
-    const int nb = p->nblk, src = v->in_admm ? LRD_PAIR_UV : LRD_PAIR_RR;
+    const int nb = p->nblk;
     const double sc = v->scaleObjHis;
     for (int k = 0; k < nb && ranks; ++k) /* (refused before anything is asked of the backend) */
         if (p->blk[k].is_lp ? ranks[k] != 1 : (ranks[k] < 1 || ranks[k] > v->rank[k])) {
