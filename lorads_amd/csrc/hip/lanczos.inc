@@ -110,41 +110,57 @@ __global__ __launch_bounds__(TPB) void k_basis_rotate(int n, const double *__res
 }
 
 // eigen-decomposition of a small symmetric matrix (row-major m x m, destroyed): cyclic Jacobi, ascending order;
-// Y column-major (eigenvector c at Y[c*m ...])
+// Y column-major (eigenvector c at Y[c*m ...]).  The rotations are applied in Rutishauser's form: the diagonal moves by t a_pq (the
+// corrections of a sweep are summed apart and added once), the rotated entry is set to zero, the others move by s (x -+ tau y), and an
+// entry below the rounding of both its diagonals is dropped.  The eigenvalues then carry a few eps ||A|| of rounding whatever m is:
+// a rotation written out as two matrix products loses about m eps ||A|| (5e-14 relative at m = 40), and a thick restart carries
+// theta into the next projected matrix, so that with a small subspace and hundreds of restarts the loss adds up.
 void small_sym_eig(int m, std::vector<double> &A, std::vector<double> &theta, std::vector<double> &Y) {
     Y.assign((size_t)m * m, 0.0);
     for (int i = 0; i < m; ++i) Y[(size_t)i * m + i] = 1.0;
+    std::vector<double> d(m), d0(m), z(m, 0.0);
+    for (int i = 0; i < m; ++i) d[i] = d0[i] = A[(size_t)i * m + i];
+    auto rot = [&](double s, double tau, size_t x, size_t y) {
+        const double g = A[x], h = A[y];
+        A[x] = g - s * (h + g * tau);
+        A[y] = h + s * (g - h * tau);
+    };
     for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, dia = 0.0;
-        for (int i = 0; i < m; ++i) {
-            dia += A[(size_t)i * m + i] * A[(size_t)i * m + i];
-            for (int j = i + 1; j < m; ++j) off += A[(size_t)i * m + j] * A[(size_t)i * m + j];
-        }
-        if (off <= 1e-32 * (dia + off) || off == 0.0) break;
+        double sm = 0.0;
+        for (int p = 0; p < m - 1; ++p)
+            for (int q = p + 1; q < m; ++q) sm += std::fabs(A[(size_t)p * m + q]);
+        if (sm == 0.0) break;
+        const double tresh = sweep < 3 ? 0.2 * sm / ((double)m * m) : 0.0;
         for (int p = 0; p < m - 1; ++p)
             for (int q = p + 1; q < m; ++q) {
-                const double apq = A[(size_t)p * m + q];
-                if (apq == 0.0) continue;
-                const double tau = (A[(size_t)q * m + q] - A[(size_t)p * m + p]) / (2.0 * apq);
-                const double t = (tau >= 0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
-                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = t * cs;
-                for (int k = 0; k < m; ++k) { // columns p, q
-                    const double akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
-                    A[(size_t)k * m + p] = cs * akp - sn * akq;
-                    A[(size_t)k * m + q] = sn * akp + cs * akq;
+                double &apq = A[(size_t)p * m + q];
+                const double g = 100.0 * std::fabs(apq);
+                if (sweep > 3 && std::fabs(d[p]) + g == std::fabs(d[p]) && std::fabs(d[q]) + g == std::fabs(d[q])) { apq = 0.0; continue; }
+                if (!(std::fabs(apq) > tresh)) continue;
+                double h = d[q] - d[p], t;
+                if (std::fabs(h) + g == std::fabs(h)) t = apq / h;
+                else {
+                    const double th = 0.5 * h / apq;
+                    t = 1.0 / (std::fabs(th) + std::sqrt(1.0 + th * th));
+                    if (th < 0.0) t = -t;
                 }
-                for (int k = 0; k < m; ++k) { // rows p, q
-                    const double apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
-                    A[(size_t)p * m + k] = cs * apk - sn * aqk;
-                    A[(size_t)q * m + k] = sn * apk + cs * aqk;
-                }
-                for (int k = 0; k < m; ++k) { // eigenvectors are stored as rows of Y^T here: Y[c*m + k]
-                    const double ykp = Y[(size_t)p * m + k], ykq = Y[(size_t)q * m + k];
-                    Y[(size_t)p * m + k] = cs * ykp - sn * ykq;
-                    Y[(size_t)q * m + k] = sn * ykp + cs * ykq;
+                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = t * cs, tau = sn / (1.0 + cs);
+                h = t * apq;
+                z[p] -= h; z[q] += h;
+                d[p] -= h; d[q] += h;
+                apq = 0.0;
+                for (int j = 0; j < p; ++j) rot(sn, tau, (size_t)j * m + p, (size_t)j * m + q);         // (upper triangle only)
+                for (int j = p + 1; j < q; ++j) rot(sn, tau, (size_t)p * m + j, (size_t)j * m + q);
+                for (int j = q + 1; j < m; ++j) rot(sn, tau, (size_t)p * m + j, (size_t)q * m + j);
+                for (int j = 0; j < m; ++j) { // eigenvectors are stored as rows of Y^T here: Y[c*m + j]
+                    const double yp = Y[(size_t)p * m + j], yq = Y[(size_t)q * m + j];
+                    Y[(size_t)p * m + j] = yp - sn * (yq + yp * tau);
+                    Y[(size_t)q * m + j] = yq + sn * (yp - yq * tau);
                 }
             }
+        for (int i = 0; i < m; ++i) { d0[i] += z[i]; d[i] = d0[i]; z[i] = 0.0; }
     }
+    for (int i = 0; i < m; ++i) A[(size_t)i * m + i] = d[i];
     std::vector<int> ord(m);
     for (int i = 0; i < m; ++i) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](int a, int b) { return A[(size_t)a * m + a] < A[(size_t)b * m + b]; });

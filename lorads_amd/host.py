@@ -562,6 +562,29 @@ class Session:
         _check(lib.lorads_hip_dual_infeasibility(ctx, tol, ncv, max_restarts, C.byref(v), lm, C.byref(mv)), "dual_infeasibility")
         return v.value, [lm[i] for i in range(nb)], mv.value
 
+    def hip_certificate(self, src, tol=1e-8, ncv=40, max_restarts=600):
+        """(out[LORADS_HIP_CERT_N], per-cone lambda_min, A(X) - b, the multipliers of the certificate) straight from the C ABI;
+        src: PAIR_UV (R = (U + V) / 2) or PAIR_RR; tol <= 0: no eigen-solves (NaN)"""
+        lib, ctx = self._hip()
+        lib.lorads_hip_certificate.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+        nb, m = self.nblk, self.m
+        out, lm = (C.c_double * 10)(), (C.c_double * max(nb, 1))()
+        res, lam = (C.c_double * max(m, 1))(), (C.c_double * max(m, 1))()
+        _check(lib.lorads_hip_certificate(ctx, int(src), tol, ncv, max_restarts, out, lm, res, lam), "certificate")
+        return (np.array(out[:10]), np.array(lm[:nb]), np.array(res[:m]), np.array(lam[:m]))
+
+    def hip_get_slack(self, blk):
+        """(row, col, val) of S_blk as lower-triangle triplets, straight from the C ABI (lorads_hip_get_slack)"""
+        lib, ctx = self._hip()
+        i32p = C.POINTER(C.c_int32)
+        lib.lorads_hip_get_slack.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), i32p, i32p, _dp]
+        nnz = C.c_int64()
+        _check(lib.lorads_hip_get_slack(ctx, int(blk), C.byref(nnz), None, None, None), "get_slack")
+        row, col, val = np.zeros(nnz.value, dtype=np.int32), np.zeros(nnz.value, dtype=np.int32), np.zeros(nnz.value)
+        _check(lib.lorads_hip_get_slack(ctx, int(blk), C.byref(nnz), row.ctypes.data_as(i32p), col.ctypes.data_as(i32p),
+                                        val.ctypes.data_as(_dp)), "get_slack")
+        return row, col, val
+
     def hip_block_image(self, blk=0):
         """what lorads_hip_create built for cone blk (see lorads_hip_dev.h)"""
         lib, ctx = self._hip()

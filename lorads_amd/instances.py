@@ -190,6 +190,30 @@ def randsparse(n, m, seed, c_edges=None, n_diag=2, n_off=8, r0=5, dense_c=False)
     return dict(m=m, blocks=[n], b=b, entries=ent)
 
 
+def prescribed_slack(S):
+    """Max-Cut-type instance (X_ii = 1, one constraint per row) whose objective is the off-diagonal part of the symmetric matrix S:
+    with the multipliers lambda = -diag(S) the slack C - sum_i lambda_i e_i e_i^T is S itself, entry for entry and without rounding
+    (inputs of the dual-side tests whose spectrum is known in closed form).  Off-diagonal zeros of S are not stored."""
+    S = np.asarray(S, dtype=np.float64)
+    n = S.shape[0]
+    assert S.shape == (n, n) and np.array_equal(S, S.T)
+    iu, ju = np.nonzero(np.triu(S, 1))
+    ent = [(0, 1, int(i) + 1, int(j) + 1, float(-S[i, j])) for i, j in zip(iu, ju)]  # F0 = -C
+    for i in range(n):
+        ent.append((i + 1, 1, i + 1, i + 1, 1.0))
+    return dict(m=n, blocks=[n], b=np.ones(n), entries=ent)
+
+
+def randsparse_untouched_rows(n, m, seed, rows, **kw):
+    """randsparse on n rows of which `rows` (0-based) are touched by no entry of C or of any A_i: the cone's union pattern has
+    rows with an empty adjacency"""
+    rows = sorted(set(int(r) for r in rows))
+    live = [i for i in range(n) if i not in set(rows)]
+    base = randsparse(len(live), m, seed, **kw)
+    ent = [(mat, blk, live[i - 1] + 1, live[j - 1] + 1, v) for mat, blk, i, j, v in base["entries"]]
+    return dict(m=m, blocks=[n], b=base["b"], entries=ent)
+
+
 def with_dense_constraints(prob, n_dense, seed, r0=2):
     """appends n_dense constraints whose A_i is a DENSE symmetric matrix (every entry non-zero, N(0,1)/n): the reference stores
     such a coefficient packed (sdp_coeff_dense: nnz > 0.1 n(n+1)/2, data/lorads_sdp_data.c:811-828) and runs its dense

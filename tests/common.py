@@ -57,6 +57,21 @@ def hip_session(path, world=1, rank=0, separable=None, lbfgs_len=None, **params)
     return s
 
 
+def hip_session_with_env(path, env, params, separable=None):
+    """hip_session with the environment variables `env` set while the context is created (the HIP library reads its switches
+    then), restored afterwards"""
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return hip_session(path, separable=separable, **params)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def golden_trace(name):
     return dict(np.load(os.path.join(GOLD, name + ".trace.npz")))
 

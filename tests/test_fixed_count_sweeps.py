@@ -34,17 +34,7 @@ def _path(name):
     return common.instance_path(name) if os.path.exists(common.instance_path(name)) else common.generated_instance(name)
 
 
-def _session(path, env, params, separable=None):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return common.hip_session(path, separable=separable, **params)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+_session = common.hip_session_with_env
 
 
 # schedules: (entry point, maxit, tol) -- tol 0.0 runs exactly maxit iterations per solve; a tuple (j, ...) asks the model for a
