@@ -220,6 +220,24 @@ int lorads_hip_primal_apply(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int32
 int lorads_hip_triangle_cuts(lorads_hip_ctx *ctx, int32_t src, int32_t blk, double min_violation, int32_t max_cuts, int64_t *count,
                              int32_t *p, int32_t *q, int32_t *s, int8_t *cls, double *viol, int32_t *kept, int32_t *passes);
 
+/* Separation of entry bounds on the primal X = F F^T (no reference counterpart).  With F the factor
+ * lorads_hip_certificate takes (src) of SDP cone blk at its own rank, every pair p < q has two inequalities:
+ *     class 0: X_pq >= lower, v = lower - X_pq        class 1: X_pq <= upper, v = X_pq - upper
+ * and v > min_violation is a violation; lower = -inf or upper = +inf switches a class off.  X_pq is one chain of FP64 matrix-core steps
+ * over the columns in fours, then one subtraction: |v - exact| <= (r + 2) 2^-53 (|F_p| |F_q| + |bound|).
+ *   count: the exact number of (pair, class) with v > min_violation among all n (n - 1) (X is never formed);
+ *   p, q, cls, viol [max_cuts]: the *kept = min(count, max_cuts) largest in the total order "v descending, then p, q, class ascending"
+ *     (0-based rows), written in that order -- exact with respect to the device's v whatever ties at the cut-off;
+ *   max_cuts = 0 counts only (the four arrays and kept may then be NULL); passes (may be NULL): enumeration passes that ran.
+ * Any SDP cone of any context; read-only on the solver's state and deterministic (no float atomics).
+ * Scratch: the packed factor, max_cuts + 16384 keys rounded up to a power of two, one histogram.
+ * Returns 1 on a bad argument (src, blk out of range or the LP block, max_cuts outside [0, 2^20], min_violation negative or not finite,
+ * a NaN bound, lower > upper, both classes off, a required array NULL, n above 2^24), 3 on a sharded context -- all before any device
+ * work.  n < 2: count 0, nothing is launched. */
+int lorads_hip_entry_bounds(lorads_hip_ctx *ctx, int32_t src, int32_t blk, double lower, double upper, double min_violation,
+                            int32_t max_cuts, int64_t *count, int32_t *p, int32_t *q, int8_t *cls, double *viol, int32_t *kept,
+                            int32_t *passes);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

@@ -11,12 +11,10 @@
 //                  of the four v per triple, the triples that pass queued and handled densely.  Three modes:
 //                  0 counts the pairs with v > min_violation and histograms the top digit of their keys, 1 histograms one digit of
 //                  the keys under a prefix, 2 emits the keys at or above a threshold
-//   k_cut_bitonic  one compare-exchange step of a bitonic sort of the emitted keys, largest first
 // The key of a (triple, class) pair is 128 bits: the bit pattern of v (positive, so the patterns order as the values do) above the
 // complement of ((p n + q) n + s) 4 + class -- larger keys come earlier in "v descending, then p, q, s, class ascending", and no two
-// pairs share a key.  The selection is a radix select on the key: digits of CUT_DIGIT bits from the top narrow the prefix of the
-// kept-th largest key until everything at or above it fits the buffer (max_cuts + CUT_SLACK keys); ties of v are told apart by the
-// digits of the index, so any number of them is handled exactly.  Every pass enumerates anew (v is the same bits every time).
+// pairs share a key.  The selection is select.inc's radix select on the key (shared with bounds.inc): ties of v are told apart by
+// the digits of the index, so any number of them is handled exactly.  Every pass enumerates anew (v is the same bits every time).
 // Read-only on the solver's state: the scratch is the feature's own (CutScratch), launches go straight to the stream (never through
 // LAUNCH).  No float atomics; the integer atomics of the counts, the histograms and the emit cursor commute, and the emitted keys are
 // sorted, so the same state and arguments give the same bits.
@@ -25,10 +23,7 @@ namespace {
 
 constexpr int CUT_T = 32;                 // rows of a tile: 3 tiles of rho take 25 KB of LDS, the histogram 16 KB, the queue 8 KB
 constexpr int CUT_LD = CUT_T + 1;
-constexpr int CUT_DIGIT = 12;
-constexpr int CUT_BINS = 1 << CUT_DIGIT;
 constexpr int CUT_QUEUE = 4096;           // triples of one tile triple (of 32768) queued in LDS for the dense pass
-constexpr int CUT_SLACK = 16384;          // keys the buffer holds beyond max_cuts
 constexpr int CUT_MAXN = 1 << 20;         // the packed index ((p n + q) n + s) 4 + class stays below 2^62
 constexpr int CUT_ITERS = 16;              // tiles I one workgroup walks at most (its 32-bit LDS bins hold 2^32 / 2^17 of them)
 static_assert(CUT_T == 32, "k_cut_enum keeps one bit per s of a tile in a 32-bit word");
@@ -44,22 +39,6 @@ struct CutArgs {
     unsigned long long *ohi, *olo;        // emitted keys
     unsigned long long cap;
 };
-
-// digit [shift, shift + width) of the key (hi, lo), width <= CUT_DIGIT
-__device__ __host__ __forceinline__ unsigned cut_digit(unsigned long long hi, unsigned long long lo, int shift, int width) {
-    unsigned long long v;
-    if (shift >= 64) v = hi >> (shift - 64);
-    else if (shift == 0) v = lo;
-    else v = (lo >> shift) | (hi << (64 - shift));
-    return (unsigned)(v & ((1ull << width) - 1));
-}
-// do the keys agree on every bit at or above top (0 < top <= 128)?
-__device__ __forceinline__ bool cut_same_prefix(unsigned long long hi, unsigned long long lo, unsigned long long phi,
-                                                unsigned long long plo, int top) {
-    if (top >= 128) return true;
-    if (top >= 64) return (hi >> (top - 64)) == (phi >> (top - 64));
-    return hi == phi && (lo >> top) == (plo >> top);
-}
 
 __global__ __launch_bounds__(TPB) void k_cut_pack(int n, int npad, int rl, int rl4, int r, const double *__restrict__ U,
                                                   const double *__restrict__ V, int uv, const double *__restrict__ t,
@@ -214,24 +193,6 @@ __global__ __launch_bounds__(TPB) void k_cut_enum(CutArgs a) {
         if (hist[b]) atomicAdd(a.hist + b, (unsigned long long)hist[b]);
 }
 
-// the keys at [m, P) become the smallest key (no pair has it: v > 0 gives hi > 0)
-__global__ __launch_bounds__(TPB) void k_cut_fill(unsigned long long m, unsigned long long P, unsigned long long *__restrict__ hi,
-                                                  unsigned long long *__restrict__ lo) {
-    const unsigned long long i = m + (unsigned long long)blockIdx.x * TPB + threadIdx.x;
-    if (i < P) { hi[i] = 0; lo[i] = 0; }
-}
-
-// one compare-exchange step (j inside the stage k) of the bitonic sort of P keys, largest first
-__global__ __launch_bounds__(TPB) void k_cut_bitonic(unsigned long long P, unsigned long long j, unsigned long long k,
-                                                     unsigned long long *__restrict__ hi, unsigned long long *__restrict__ lo) {
-    const unsigned long long i = (unsigned long long)blockIdx.x * TPB + threadIdx.x, l = i ^ j;
-    if (i >= P || l <= i) return;
-    const unsigned long long hi_i = hi[i], lo_i = lo[i], hi_l = hi[l], lo_l = lo[l];
-    const bool less = hi_i < hi_l || (hi_i == hi_l && lo_i < lo_l);
-    const bool greater = hi_i > hi_l || (hi_i == hi_l && lo_i > lo_l);
-    if ((i & k) == 0 ? less : greater) { hi[i] = hi_l; lo[i] = lo_l; hi[l] = hi_i; lo[l] = lo_i; }
-}
-
 int cut_launch(lorads_hip_ctx *c, const CutArgs &a, int nt) {
     const long long npairs = (long long)nt * (nt + 1) / 2;
     // tiles I are dealt over blockIdx.y: at most CUT_ITERS per workgroup (the longest workgroups would otherwise run nt of them while
@@ -286,75 +247,18 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     a.ctl = X.ctl; a.hist = X.ctl + 2;
     a.ohi = X.khi; a.olo = X.klo;
     a.cap = (unsigned long long)max_cuts + CUT_SLACK;
-    std::vector<unsigned long long> h(2 + (size_t)CUT_BINS);
-    // pass 1: the count and the top digit
-    HC(hipMemsetAsync(X.ctl, 0, sizeof(unsigned long long) * h.size(), c->stream));
-    if (cut_launch(c, a, nt)) return 1;
-    HC(hipMemcpyAsync(h.data(), X.ctl, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    int np = 1;
-    const unsigned long long total = h[0];
-    *count = (int64_t)total;
-    if (passes) *passes = np;
-    const unsigned long long want = std::min<unsigned long long>(total, (unsigned long long)max_cuts);
+    std::vector<unsigned long long> khi, klo;
+    if (select_largest(c, "triangle_cuts", X.ctl, X.khi, X.klo, max_cuts, a, [&] { return cut_launch(c, a, nt); }, count, passes, khi, klo))
+        return 1;
+    const size_t want = khi.size();
     if (want == 0) return 0;
-    // narrow the prefix of the want-th largest key until what is at or above it fits the buffer
-    unsigned long long above = 0, emit_n = 0;
-    for (;;) {
-        unsigned long long before = 0;
-        int d = (1 << a.width) - 1;
-        while (d > 0 && above + before + h[2 + d] < want) before += h[2 + d--];
-        if (a.shift >= 64) a.khi |= (unsigned long long)d << (a.shift - 64);
-        else {
-            a.klo |= (unsigned long long)d << a.shift;
-            if (a.shift + a.width > 64) a.khi |= (unsigned long long)d >> (64 - a.shift);
-        }
-        emit_n = above + before + h[2 + d];
-        if (emit_n < want) return fail_msg("triangle_cuts: the histogram of a pass does not add up to the count");
-        if (emit_n <= a.cap) break;
-        if (a.shift == 0) return fail_msg("triangle_cuts: the selection did not close");
-        above += before;
-        a.width = std::min(CUT_DIGIT, a.shift);
-        a.shift -= a.width;
-        a.mode = 1;
-        HC(hipMemsetAsync(X.ctl, 0, sizeof(unsigned long long) * h.size(), c->stream));
-        if (cut_launch(c, a, nt)) return 1;
-        HC(hipMemcpyAsync(h.data(), X.ctl, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, c->stream));
-        HC(hipStreamSynchronize(c->stream));
-        ++np;
-    }
-    // emit everything at or above the prefix (its lower bits zero), sort, hand the first `want` over
-    a.mode = 2;
-    HC(hipMemsetAsync(X.ctl, 0, sizeof(unsigned long long) * 2, c->stream));
-    if (cut_launch(c, a, nt)) return 1;
-    ++np;
-    unsigned long long emitted = 0;
-    HC(hipMemcpyAsync(&emitted, X.ctl + 1, sizeof emitted, hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    if (emitted != emit_n) return fail_msg("triangle_cuts: the emit pass found " + std::to_string(emitted) + " keys, the histograms " + std::to_string(emit_n));
-    unsigned long long Ps = 1;
-    while (Ps < emitted) Ps <<= 1;
-    if (Ps > emitted)
-        hipLaunchKernelGGL(k_cut_fill, dim3(nblocks_for((size_t)(Ps - emitted), TPB)), dim3(TPB), 0, c->stream, emitted, Ps, X.khi, X.klo);
-    for (unsigned long long k = 2; k <= Ps; k <<= 1)
-        for (unsigned long long j = k >> 1; j > 0; j >>= 1)
-            hipLaunchKernelGGL(k_cut_bitonic, dim3(nblocks_for((size_t)Ps, TPB)), dim3(TPB), 0, c->stream, Ps, j, k, X.khi, X.klo);
-    HC(hipGetLastError());
-    std::vector<unsigned long long> khi((size_t)want), klo((size_t)want);
-    HC(hipMemcpyAsync(khi.data(), X.khi, sizeof(unsigned long long) * khi.size(), hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(klo.data(), X.klo, sizeof(unsigned long long) * klo.size(), hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
     for (size_t e = 0; e < (size_t)want; ++e) {
-        unsigned long long idx = ~klo[e];
-        double v;
-        memcpy(&v, &khi[e], sizeof v);
-        viol[e] = v;
+        unsigned long long idx = select_unpack(khi[e], klo[e], viol[e]);
         cls[e] = (int8_t)(idx & 3); idx >>= 2;
         s[e] = (int32_t)(idx % (unsigned long long)n); idx /= (unsigned long long)n;
         q[e] = (int32_t)(idx % (unsigned long long)n);
         p[e] = (int32_t)(idx / (unsigned long long)n);
     }
     *kept = (int32_t)want;
-    if (passes) *passes = np;
     return 0;
 }

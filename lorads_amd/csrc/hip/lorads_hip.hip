@@ -571,6 +571,16 @@ struct CutScratch {
     void release() { mem.release(); *this = CutScratch{}; }
 };
 
+// scratch of the separation of entry bounds (bounds.inc): allocated on first use, grown on demand, never read by the solve.
+// O(n r) for the packed factor, max_cuts + a fixed slack (rounded up to a power of two) keys, one histogram.
+struct BoundScratch {
+    DevBuf<double> Fp;                                     // F zero-padded to whole tiles and steps of 4 columns
+    DevBuf<unsigned long long> khi, klo;                   // the emitted keys: bit pattern of v, complement of the packed index
+    unsigned long long *ctl = nullptr;                     // [0] violated pairs, [1] emitted keys, [2..] the histogram of a digit
+    DevPool mem;
+    void release() { mem.release(); *this = BoundScratch{}; }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -584,6 +594,7 @@ struct lorads_hip_ctx {
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
+    BoundScratch bounds;              // separation of entry bounds on X (bounds.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -929,6 +940,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->spectral.release();
     c->primal.release();
     c->cuts.release();
+    c->bounds.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -1827,4 +1839,6 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "rounding.inc"
 #include "spectral.inc"
 #include "primal.inc"
+#include "select.inc"
 #include "cuts.inc"
+#include "bounds.inc"

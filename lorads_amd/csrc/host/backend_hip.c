@@ -56,6 +56,8 @@ typedef struct {
     int (*primal_apply)(lorads_hip_ctx *, int32_t, int32_t, int32_t, const double *, double *, double *); /* optional */
     int (*triangle_cuts)(lorads_hip_ctx *, int32_t, int32_t, double, int32_t, int64_t *, int32_t *, int32_t *, int32_t *, int8_t *,
                          double *, int32_t *, int32_t *); /* optional */
+    int (*entry_bounds)(lorads_hip_ctx *, int32_t, int32_t, double, double, double, int32_t, int64_t *, int32_t *, int32_t *, int8_t *,
+                        double *, int32_t *, int32_t *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -120,6 +122,12 @@ static int b_cuts(void *cx, int src, int blk, double minv, int max_cuts, int64_t
                   double *viol, int *kept, int *passes) {
     return report(H, H->triangle_cuts(H->ctx, src, blk, minv, max_cuts, count, (int32_t *)p, (int32_t *)q, (int32_t *)s, cls, viol,
                                       (int32_t *)kept, (int32_t *)passes), "triangle_cuts");
+}
+/* entry bounds: code 3 (sharded) passes through */
+static int b_bounds(void *cx, int src, int blk, double lower, double upper, double minv, int max_cuts, int64_t *count, int *p, int *q,
+                    int8_t *cls, double *viol, int *kept, int *passes) {
+    return report(H, H->entry_bounds(H->ctx, src, blk, lower, upper, minv, max_cuts, count, (int32_t *)p, (int32_t *)q, cls, viol,
+                                     (int32_t *)kept, (int32_t *)passes), "entry_bounds");
 }
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
@@ -189,6 +197,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->primal_apply) = dlsym(h->dl, "lorads_hip_primal_apply");
     if (!h->primal_apply) h->primal_entries = NULL;
     *(void **)(&h->triangle_cuts) = dlsym(h->dl, "lorads_hip_triangle_cuts");
+    *(void **)(&h->entry_bounds) = dlsym(h->dl, "lorads_hip_entry_bounds");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -237,5 +246,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->spectrum) { out->spectrum = b_spectrum; out->compress_rank = b_compress; }
     if (h->primal_entries) { out->primal_entries = b_pentries; out->primal_apply = b_papply; }
     if (h->triangle_cuts) out->triangle_cuts = b_cuts;
+    if (h->entry_bounds) out->entry_bounds = b_bounds;
     return 0;
 }

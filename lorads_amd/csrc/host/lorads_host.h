@@ -178,6 +178,10 @@ typedef struct lrd_backend {
      * return codes) */
     int (*triangle_cuts)(void *ctx, int src, int blk, double min_violation, int max_cuts, int64_t *count, int *p, int *q, int *s,
                          int8_t *cls, double *viol, int *kept, int *passes);
+    /* OPTIONAL (before the spectral pair for the same reason): separation of the entry bounds lower <= X_pq <= upper of one SDP cone
+     * of any context, read-only on the state (include/lorads_hip.h: lorads_hip_entry_bounds, the same arguments and return codes) */
+    int (*entry_bounds)(void *ctx, int src, int blk, double lower, double upper, double min_violation, int max_cuts, int64_t *count,
+                        int *p, int *q, int8_t *cls, double *viol, int *kept, int *passes);
     /* OPTIONAL pair (both or neither): spectrum of the factors and their reduction to a lower rank (include/lorads_hip.h:
      * lorads_hip_spectrum, lorads_hip_compress_rank, the same arguments and return codes) */
     int (*spectrum)(void *ctx, int src, double *eig, double *q, int *sweeps);
@@ -433,6 +437,33 @@ void lrd_cuts_free(lrd_cuts *c);
  * writes the problem alone.  A pure function of the problem image and the list.  1: cannot write; 2: a cut outside the problem or a
  * problem with an LP block; 3: sharded. */
 int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts);
+
+/* ---- entry bounds on the primal X (bounds.c).  Every pair p < q of an SDP cone has two inequalities: class 0,
+ * X_pq >= lower with v = lower - X_pq, and class 1, X_pq <= upper with v = X_pq - upper; v > min_violation is a violation. */
+typedef struct {
+    int nblk, src;              /* src: LRD_PAIR_UV or LRD_PAIR_RR, where F came from */
+    double lower, upper, min_violation;
+    int max_cuts;
+    int64_t *count;             /* [nblk] (pair, class) with v > min_violation per cone, exact (LP block: 0) */
+    int kept, passes;           /* cuts listed (<= max_cuts in total); enumeration passes of all cones */
+    int *cone, *p, *q;          /* [kept] 0-based, ordered by (v descending, cone, p, q, class ascending) */
+    int8_t *cls;
+    double *viol;
+    double *bound;              /* [kept] the cut's own bound (lower for class 0, upper for class 1): lists of calls with different
+                                 * bounds can be concatenated */
+} lrd_bounds;
+/* F = (U+V)/2 in phase 2, the phase-1 R otherwise; the slot once per SDP cone (LP blocks are passed over), the cones' lists merged.
+ * Returns 2 when the table lacks the slot, 3 on a sharded deal, else the backend's code. */
+int lrd_session_entry_bounds(lrd_session *s, double lower, double upper, double min_violation, int max_cuts, lrd_bounds **out);
+void lrd_bounds_free(lrd_bounds *c);
+/* The problem of the session as it was read (m, blocks, b, every stored entry; doubles %.17g, F0 = -C) in SDPA sparse format plus, per
+ * cut e, constraint m + 1 + e: 0.5 at (p, q) of the cut's cone (an off-diagonal entry counts twice in <A, X>) and one slack column,
+ * class 0: -1 with b = bound, class 1: +1 with b = bound.  The slack columns form a new last LP block when the problem has none and
+ * are appended to the LP block (which keeps its position and its columns their indices) when it has one.  Only kept, cone, p, q, cls and
+ * bound of `bounds` are read; NULL or no cuts writes the problem alone.  A pure function of the problem image and the list.
+ * 1: cannot write; 2: a cut outside the problem (p >= q, a cone out of range or an LP block, a class outside {0, 1}, a bound that is
+ * not finite) or a problem with more than one LP block; 3: sharded. */
+int lrd_session_write_bounded(lrd_session *s, const char *path, const lrd_bounds *bounds);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -41,6 +41,9 @@ int main(int argc, char **argv) {
     double cuts_minv = 1e-3;
     int cuts_minv_given = 0;
     const char *cuts_file = NULL;
+    int bounds_max = -1;              /* separation of entry bounds lower <= X_pq <= upper (ours as well) */
+    double bounds_lower = 0.0, bounds_upper = HUGE_VAL, bounds_minv = 1e-3;
+    const char *bounds_file = NULL, *bounds_other = NULL; /* bounds_other: some --bounds* option other than --boundsMax was given */
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -66,6 +69,31 @@ int main(int argc, char **argv) {
             }
             if (is_max) cuts_max = (int)k;
             else { cuts_minv = t; cuts_minv_given = 1; }
+            continue;
+        }
+        if (!strcmp(argv[i], "--boundsFile")) { bounds_other = argv[i]; bounds_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--boundsMax") || !strcmp(argv[i], "--boundsLower") || !strcmp(argv[i], "--boundsUpper") ||
+            !strcmp(argv[i], "--boundsMinViolation")) {
+            char *end = NULL;
+            const char w = argv[i][9] == 'a' ? 'K' : argv[i][9] == 'i' ? 'V' : argv[i][8]; /* K, L, U or V */
+            const double t = w == 'K' ? 0.0 : strtod(argv[i + 1], &end);
+            const long k = w == 'K' ? strtol(argv[i + 1], &end, 10) : 1;
+            int bad = !end || end == argv[i + 1] || *end || t != t || k < 1 || k > (1L << 20);
+            if (w == 'V') bad = bad || !(t >= 0) || !(t < HUGE_VAL);
+            if (w == 'L') bad = bad || t == HUGE_VAL;   /* (-inf switches the class off) */
+            if (w == 'U') bad = bad || t == -HUGE_VAL;
+            if (bad) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            if (w == 'K') bounds_max = (int)k;
+            else {
+                bounds_other = argv[i];
+                if (w == 'L') bounds_lower = t;
+                else if (w == 'U') bounds_upper = t;
+                else bounds_minv = t;
+            }
             continue;
         }
         if (!strcmp(argv[i], "--roundTrials") || !strcmp(argv[i], "--roundSeed") || !strcmp(argv[i], "--roundLocalSearch")) {
@@ -106,6 +134,17 @@ int main(int argc, char **argv) {
     }
     if ((cuts_file || cuts_minv_given) && cuts_max < 0) {
         fprintf(stderr, "%s needs --cutsMax\n", cuts_file ? "--cutsFile" : "--cutsMinViolation");
+        lrd_session_close(s);
+        return 2;
+    }
+    if (bounds_other && bounds_max < 0) {
+        fprintf(stderr, "%s needs --boundsMax\n", bounds_other);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (bounds_max > 0 && (bounds_lower > bounds_upper || (bounds_lower == -HUGE_VAL && bounds_upper == HUGE_VAL))) {
+        fprintf(stderr, "bad value of --boundsLower and --boundsUpper: %g, %g (lower above upper, or both classes off)\n", bounds_lower,
+                bounds_upper);
         lrd_session_close(s);
         return 2;
     }
@@ -222,6 +261,23 @@ int main(int argc, char **argv) {
         printf("Triangle inequalities violated by more than %g: %lld, kept %d, largest violation %.6e%s%s\n", cuts_minv, total, x->kept,
                x->kept > 0 ? x->viol[0] : 0.0, cuts_file ? " -> " : "", cuts_file ? cuts_file : "");
         lrd_cuts_free(x);
+    }
+    if (bounds_max > 0) {
+        lrd_bounds *x = NULL;
+        if (lrd_session_entry_bounds(s, bounds_lower, bounds_upper, bounds_minv, bounds_max, &x) ||
+            (bounds_file && lrd_session_write_bounded(s, bounds_file, x))) {
+            fprintf(stderr, "lorads: the separation of the entry bounds failed%s%s\n", bounds_file ? " or cannot write " : "",
+                    bounds_file ? bounds_file : "");
+            lrd_bounds_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        long long total = 0;
+        for (int k = 0; k < x->nblk; ++k) total += (long long)x->count[k];
+        printf("Entry bounds [%g, %g] violated by more than %g: %lld, kept %d, largest violation %.6e, %d passes%s%s\n", bounds_lower,
+               bounds_upper, bounds_minv, total, x->kept, x->kept > 0 ? x->viol[0] : 0.0, x->passes, bounds_file ? " -> " : "",
+               bounds_file ? bounds_file : "");
+        lrd_bounds_free(x);
     }
     if (solution_file) {
         lrd_solution *x = NULL;

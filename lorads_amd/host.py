@@ -66,6 +66,8 @@ class BackendStruct(C.Structure):
         ("primal_apply", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp)),
         ("triangle_cuts", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_int8), _dp, _ip, _ip)),
+        ("entry_bounds", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                     C.POINTER(C.c_int64), _ip, _ip, C.POINTER(C.c_int8), _dp, _ip, _ip)),
         ("spectrum", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _dp, _dp, _ip)),
         ("compress_rank", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _ip, _dp)),
     ]
@@ -308,6 +310,29 @@ class Backend:
             return (rc,) + (None,) * 7
         k = kept.value
         return 0, cnt.value, p[:k], q[:k], s[:k], cls[:k], v[:k], passes.value
+
+    def has_entry_bounds(self):
+        return bool(self._s.entry_bounds)
+
+    def entry_bounds(self, src, blk, lower, upper, min_violation, max_cuts, want_arrays=True):
+        """the table's slot as it is: the (pair, class) of cone blk whose bound lower <= X_pq <= upper is violated by more than
+        min_violation.  Returns (code, count, p, q, cls, violation, passes) with the min(count, max_cuts) largest in the order
+        (violation descending, p, q, cls ascending); code != 0 is the slot's refusal.  want_arrays=False passes NULL arrays down."""
+        cap = max(int(max_cuts), 1) if -1 < max_cuts <= (1 << 20) else 1
+        cnt, kept, passes = C.c_int64(0), C.c_int(0), C.c_int(0)
+        p, q = (np.zeros(cap, dtype=np.int32) for _ in range(2))
+        cls, v = np.zeros(cap, dtype=np.int8), np.zeros(cap)
+        i8 = C.POINTER(C.c_int8)
+        args = (self._s.ctx, src, blk, float(lower), float(upper), float(min_violation), int(max_cuts), C.byref(cnt))
+        if want_arrays:
+            rc = self._s.entry_bounds(*args, p.ctypes.data_as(_ip), q.ctypes.data_as(_ip), cls.ctypes.data_as(i8), v.ctypes.data_as(_dp),
+                                      C.byref(kept), C.byref(passes))
+        else:
+            rc = self._s.entry_bounds(*args, None, None, None, None, None, C.byref(passes))
+        if rc:
+            return (rc,) + (None,) * 6
+        k = kept.value
+        return 0, cnt.value, p[:k], q[:k], cls[:k], v[:k], passes.value
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -907,6 +932,45 @@ class Session:
         if rc == 2:
             raise ValueError("a cut lies outside the problem, names a row no constraint fixes, or the problem has an LP block")
         _check(rc, "write_tightened")
+
+    def entry_bounds(self, max_cuts=1000, lower=0.0, upper=None, min_violation=1e-3):
+        """Separation of the entry bounds lower <= X_pq <= upper (p < q) of every SDP cone at the current point, on the device
+        (lorads_amd.bounds.Bounds): all n (n - 1) inequalities of every cone are enumerated (X is never formed), the ones violated by
+        more than min_violation counted exactly, and the max_cuts most violated returned, ordered by (violation descending, cone, p,
+        q, cls ascending).  lower=None / upper=None: no such bound.  Any problem; read-only on the solver's state, deterministic."""
+        from .bounds import Bounds, BoundsStruct
+        ptr = C.POINTER(BoundsStruct)()
+        self.lib.lrd_session_entry_bounds.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                      C.POINTER(C.POINTER(BoundsStruct))]
+        self.lib.lrd_bounds_free.argtypes = [C.POINTER(BoundsStruct)]
+        self.lib.lrd_bounds_free.restype = None
+        lo = -np.inf if lower is None else float(lower)
+        up = np.inf if upper is None else float(upper)
+        rc = self.lib.lrd_session_entry_bounds(self.h, lo, up, float(min_violation), int(max_cuts), C.byref(ptr))
+        if rc == 2:
+            raise NotImplementedError("entry bounds cannot be separated: the %s backend has no such slot"
+                                      % (self.be.name if self.be else "attached"))
+        if rc == 3:
+            raise NotImplementedError("the separation of a sharded deal (world > 1) is not supported")
+        _check(rc, "entry_bounds")
+        try:
+            return Bounds.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_bounds_free(ptr)
+
+    def write_bounded(self, path, bounds):
+        """The problem as it was read plus one constraint and one slack column per bound cut, in SDPA sparse format (the command
+        line's --boundsFile: the same C writer, the same bytes).  The slack columns join the problem's LP block, or form a new last
+        one.  bounds: a lorads_amd.bounds.Bounds or None."""
+        from .bounds import BoundsStruct
+        self.lib.lrd_session_write_bounded.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BoundsStruct)]
+        st = bounds.to_struct() if bounds is not None else None
+        rc = self.lib.lrd_session_write_bounded(self.h, os.fsencode(path), C.byref(st) if st is not None else None)
+        if rc == 2:
+            raise ValueError("a bound cut lies outside the problem, or the problem has more than one LP block")
+        if rc == 3:
+            raise NotImplementedError("the bounded problem of a sharded deal (world > 1) is not supported")
+        _check(rc, "write_bounded")
 
     def _spectral_refused(self, rc, what):
         if rc == 2:

@@ -137,6 +137,28 @@ def theta(n, n_edges, seed):
     return dict(m=n_edges + 1, blocks=[n], b=b, entries=ent)
 
 
+def hamming_theta(d, max_distance):
+    """Lovasz theta of the graph on {0,1}^d with an edge where the Hamming distance is 1 ... max_distance, in the form of theta():
+    n = 2^d.  An independent set is a binary code of minimum distance max_distance + 1; theta' (theta with X >= 0 entry-wise,
+    Schrijver) is the Delsarte bound: d = 5, max_distance = 2 has theta = 16/3 and theta' = 4."""
+    n = 1 << d
+    ent = []
+    for i in range(n):
+        for j in range(i, n):
+            ent.append((0, 1, i + 1, j + 1, 1.0))
+    for i in range(n):
+        ent.append((1, 1, i + 1, i + 1, 1.0))
+    k = 2
+    for i in range(n):
+        for j in range(i + 1, n):
+            if bin(i ^ j).count("1") <= max_distance:
+                ent.append((k, 1, i + 1, j + 1, 1.0))
+                k += 1
+    b = np.zeros(k - 1)
+    b[0] = 1.0
+    return dict(m=k - 1, blocks=[n], b=b, entries=ent)
+
+
 def randsparse(n, m, seed, c_edges=None, n_diag=2, n_off=8, r0=5, dense_c=False):
     """cfg3b: m random sparse symmetric A_i with n_diag diagonal + n_off off-diagonal entries, values
     N(0,1); b = A(R0 R0^T), R0 ~ N(0,1)/sqrt(n) (n x r0) so the problem is feasible.  The objective
