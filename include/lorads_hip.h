@@ -166,6 +166,33 @@ int lorads_hip_get_slack(lorads_hip_ctx *ctx, int32_t blk, int64_t *nnz, int32_t
 int lorads_hip_round_pm1(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                          double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds, double *hyperplanes);
 
+/* Frieze-Jerrum rounding of a k-cut-structured context into `parts` parts, with a 1-move local search (no
+ * reference counterpart).  Qualifies: at least one SDP cone, at most one LP block, no dense constraint matrices; every constraint
+ * without an LP entry one stored entry a_i X_k[p,p] = b_i with b_i / a_i > 0, every diagonal of every cone fixed by exactly one
+ * (t_p = sqrt(b_i / a_i)); every constraint with an LP entry a bound row 2 a X_pq + c x_j = b: one off-diagonal cone entry and one LP
+ * column, which occurs in no other constraint and has no objective coefficient (what lrd_session_write_bounded writes).  Without an LP
+ * block that is lorads_hip_round_pm1's rule.  For labels l_p in {0 .. parts-1} the point X(l)_pq = t_p t_q where l_p = l_q and
+ * -t_p t_q / (parts - 1) elsewhere is PSD and meets every diagonal constraint; it meets a bound row X_pq >= lower when
+ * lower <= -t_p t_q / (parts - 1).  Per cone k, trial t and part a a Gaussian g of the cone's own rank, lorads_hip_round_pm1's generator
+ * at the counter (k << 32) | (a << 26) | (t << 10) | column (part 0 is that call's hyperplane); l_p = the lowest a that attains
+ * max_a R_p . g_a, every score one chain of FP64 matrix-core steps over the columns in fours; f_t = sum_k <C_k, X(l_k)>; then at most
+ * max_rounds rounds of the 1-move local search by colour classes (0: none).  Values in device terms (C scaled by scaleObjHis).
+ * Read-only on the solver's state; the same state and arguments give the same bits.
+ *   obj [trials]            f after the local search        obj0 [trials] (may be NULL)  f before it
+ *   best / best0            argmin of obj / obj0 (lowest index on ties; may be NULL)
+ *   label [sum_k n_k]       the best trial's labels, SDP cone after SDP cone (may be NULL)
+ *   rounds                  local-search rounds run (may be NULL)
+ *   vectors                 per SDP cone parts x rank_k x trials (part, then column, then trial), cone after cone (may be NULL)
+ *   t [sum_k n_k]           t_p, SDP cone after SDP cone (may be NULL)
+ *   lp_upper [LP columns]   u_j = (|b| + 2 |a| t_p t_q) / |c| of the column's row: x_j <= u_j at every feasible point (may be NULL)
+ * trials = 0 checks applicability only (t and lp_upper are still filled).  Returns 1 on a bad argument (src, parts outside [2, 64],
+ * trials outside [0, 65536], trials x parts above 2^20, max_rounds < 0, obj NULL with trials > 0) or a failed allocation (the context
+ * stays usable), 2 when the context does not qualify (lorads_hip_last_error names the first offending constraint, cone or column),
+ * 3 when it is sharded -- all before any device work. */
+int lorads_hip_round_kcut(lorads_hip_ctx *ctx, int32_t src, int32_t parts, int32_t trials, uint64_t seed, int32_t max_rounds,
+                          double *obj, double *obj0, int32_t *best, int32_t *best0, uint8_t *label, int32_t *rounds, double *vectors,
+                          double *t, double *lp_upper);
+
 /* Spectrum and rank reduction of the solution factors (no reference counterpart).  Per SDP cone k (the LP block
  * has no factor and is passed over) F_k is the factor lorads_hip_certificate takes (src) at the cone's own rank rl_k, G_k = F_k^T F_k =
  * Q_k Lambda_k Q_k^T with lambda_1 >= lambda_2 >= ... (ties: lower original index first): the non-zero eigenvalues of X_k = F_k F_k^T.

@@ -1,0 +1,427 @@
+// kcut.inc -- Frieze-Jerrum rounding of the factors into k parts and a 1-move local search (Max-k-Cut-type SDPs and the bounded
+// problems lrd_session_write_bounded makes of them), included by lorads_hip.hip after rounding.inc.  DESIGN.md section 16.
+//
+// A context qualifies ("k-cut-structured") when every constraint without an LP entry is a_i X_k[p,p] = b_i with b_i / a_i > 0, one
+// per diagonal position of every cone (t_p = sqrt(b_i / a_i), as rounding.inc), and every constraint with an LP entry is a bound row
+// 2 a X_pq + c x_j = b: one off-diagonal SDP entry and one LP column that occurs nowhere else and has no objective.  For labels l_p
+// in {0..k-1} the point X(l)_pq = t_p t_q (l_p = l_q), -t_p t_q / (k - 1) (otherwise) is PSD and meets every diagonal constraint.
+// Per cone, trial and part a Gaussian g_a (rounding.inc's generator with the part in bits 26..31 of the counter: part 0 is the +-1
+// rounding's hyperplane); l_p = the lowest a that attains max_a R_p . g_a; f = sum_k <C_k, X(l_k)>; then a deterministic 1-move local
+// search by colour classes of the cone's stored off-diagonal graph (rnd_colour).
+//
+// Labels: one byte per (row, trial) in blocks of 64 trials, lab[(w * n + p) * 64 + lane]: a wavefront of the field pass (lane = trial)
+// reads a neighbour's 64 labels as one 64-byte segment.  Everything is read-only on the solver's state, as in rounding.inc: R is formed
+// on the fly, the scratch is the feature's own (KCutScratch), launches go straight to the stream, every sum has one fixed order.
+
+namespace {
+
+constexpr int KCUT_MAXPARTS = 64;
+constexpr int KCUT_MAXPROD = 1 << 20;  // trials x parts
+constexpr int KCUT_CH = 16;            // parts whose sums h_a a walk of the row list holds at once (LDS, one column per thread)
+
+// G of cone `cone` (parts x rk x K, G[(a * rk + j) * K + t]): k_rnd_hyper's value at the counter (cone << 32) | (a << 26) | (t << 10) | j
+__global__ __launch_bounds__(TPB) void k_kcut_hyper(int rk, int K, int parts, int cone, uint64_t seed, double *__restrict__ G) {
+    const size_t per = (size_t)rk * K, len = per * parts;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
+        const uint64_t a = i / per, rem = i % per, j = rem / K, t = rem % K;
+        const uint64_t ctr = ((uint64_t)cone << 32) | (a << 26) | (t << 10) | j;
+        const uint64_t x = rnd_sm(seed ^ rnd_sm(2 * ctr)), y = rnd_sm(seed ^ rnd_sm(2 * ctr + 1));
+        const double u1 = (double)((x >> 11) + 1) * 0x1p-53, u2 = (double)(y >> 11) * 0x1p-53;
+        G[i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+    }
+}
+
+// N steps of a score chain from column k0 on: mfma_fm_tile's steps -- the same operands (A's element times zero and a clamped load
+// past rl) in the same order, so the same bits -- with the operands of all N asked for before the first step waits for its own
+template <int N>
+__device__ __forceinline__ v4f64 kcut_steps(const double *__restrict__ U, const double *__restrict__ V, bool uv, size_t ao,
+                                            const double *__restrict__ Ga, size_t K, int rl, int k0, int kk, v4f64 d) {
+    double x[N], y[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const int k = k0 + 4 * u + kk, kc = k < rl ? k : 0;
+        x[u] = factor_ld(U, V, uv, ao + kc) * (k < rl ? 1.0 : 0.0);
+        y[u] = Ga[(size_t)kc * K];
+    }
+#pragma unroll
+    for (int u = 0; u < N; ++u) d = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u], y[u], d, 0, 0, 0);
+    return d;
+}
+// the whole chain of one part over the rl columns in fours, ascending (eight, four, two steps and one at a time: mfma_fm_tile's chain
+// with more loads in flight, as bounds.inc's bnd_dot)
+__device__ __forceinline__ v4f64 kcut_chain(const double *__restrict__ U, const double *__restrict__ V, bool uv, size_t ao,
+                                            const double *__restrict__ Ga, size_t K, int rl, int kk) {
+    v4f64 d = (v4f64){0.0, 0.0, 0.0, 0.0};
+    const int rl4 = (rl + 3) & ~3;
+    int k0 = 0;
+    for (; k0 + 32 <= rl4; k0 += 32) d = kcut_steps<8>(U, V, uv, ao, Ga, K, rl, k0, kk, d);
+    if (k0 + 16 <= rl4) { d = kcut_steps<4>(U, V, uv, ao, Ga, K, rl, k0, kk, d); k0 += 16; }
+    if (k0 + 8 <= rl4) { d = kcut_steps<2>(U, V, uv, ao, Ga, K, rl, k0, kk, d); k0 += 8; }
+    if (k0 < rl4) d = kcut_steps<1>(U, V, uv, ao, Ga, K, rl, k0, kk, d);
+    return d;
+}
+
+// Labels of 16 rows x 16 trials per wavefront on the FP64 matrix cores.  For a = 0 .. parts - 1 one chain of mfma_fm_tile's steps
+// (kcut_chain) over the cone's own rl columns with B[kk][nn] = g_a[column kk][trial t0 + nn] (a 128-byte segment of G's row);
+// result register q of lane (nn, kk) is the score of row p0 + kk + 4 q and trial t0 + nn, and the lane keeps its running maximum
+// and the a that gave it (strict > in ascending a: the lowest a wins a tie).  No cross-lane work; rows past n and trials past K are
+// clamped loads whose results are not stored (rows) or stored as label 0 (trials: the label blocks are whole, nobody reads their
+// pad lanes into a result).
+// Wavefronts of one trial tile are neighbours in the grid, so the tile's part of G stays in cache while the rows go by.
+__global__ __launch_bounds__(TPB) void k_kcut_label(int n, int rl, int r, int K, int W, int parts, const double *__restrict__ U,
+                                                    const double *__restrict__ V, int uv, const double *__restrict__ G,
+                                                    unsigned char *__restrict__ lab) {
+    const int l = threadIdx.x & 63, nn = l & 15, kk = l >> 4;
+    const int nrt = (n + 15) / 16;
+    const int gw = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (TPB / 64) + (threadIdx.x >> 6)));
+    if (gw >= nrt * W * 4) return;
+    const int p0 = (gw % nrt) * 16, t = (gw / nrt) * 16 + nn, tc = t < K ? t : K - 1;
+    const size_t ao = (size_t)(p0 + nn < n ? p0 + nn : n - 1) * r;
+    double best[4] = {0.0, 0.0, 0.0, 0.0};
+    int arg[4] = {0, 0, 0, 0};
+    for (int a = 0; a < parts; ++a) {
+        const double *Ga = G + (size_t)a * rl * K + tc;
+        const v4f64 acc = kcut_chain(U, V, uv != 0, ao, Ga, (size_t)K, rl, kk);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (a == 0 || acc[q] > best[q]) { best[q] = acc[q]; arg[q] = a; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int p = p0 + kk + 4 * q;
+        if (p < n) lab[((size_t)(t >> 6) * n + p) * 64 + (t & 63)] = (unsigned char)(t < K ? arg[q] : 0);
+    }
+}
+
+// row p's list in its stored order: f(q, C_pq) for every stored position of the row, the diagonal included.  A sparse cone walks the
+// union pattern's adjacency with C from cbase (adj_sval is not C on the slots a bound row touches); a dense-C cone walks the row of
+// Cfull and passes over its zeros.
+template <typename F>
+__device__ __forceinline__ void kcut_walk(int p, int n, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,
+                                          const int *__restrict__ adj_e, const double *__restrict__ cbase,
+                                          const double *__restrict__ Cfull, int npad, F f) {
+    if (Cfull) {
+        const double *crow = Cfull + (size_t)p * npad;
+        for (int q = 0; q < n; ++q) {
+            const double cq = crow[q];
+            if (cq != 0.0) f(q, cq);
+        }
+    } else {
+        for (int s = adj_ptr[p]; s < adj_ptr[p + 1]; ++s) f(adj_col[s], cbase[adj_e[s]]);
+    }
+}
+
+// The field pass, one wavefront per (row, block of 64 trials), lane = trial.
+//   eval (rows == null): per-workgroup partials of sum_p t_p (C_pp t_p + (same_p - other_p / (k - 1))), same_p / other_p the sums of
+//   C_pq t_q over the q != p of p's part / of the other parts, each in the row list's order; part[t * RND_STRIPS + strip].
+//   local search: the rows of one colour class.  h_a = sum_{q != p, l_q = a} C_pq t_q, every h_a on its own in the row list's order
+//   (KCUT_CH of them per walk, one LDS column per thread); a* = the lowest a that attains min_a h_a; the row moves to a* where
+//   Delta = coef t_p (h_a* - h_lp) < -tau_p, tau_p = 2^-40 coef t_p sum_{q != p} |C_pq| t_q, coef = 2 k / (k - 1); a mover stores its
+//   label and 1 to *flag.  No two rows of a class are adjacent: no row reads a label this launch writes, except across a zero of a
+//   dense C, which kcut_walk passes over.
+__global__ __launch_bounds__(TPB) void k_kcut_field(int nrows, const int *__restrict__ rows, int n, int K, int parts, double inv,
+                                                    double coef, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,
+                                                    const int *__restrict__ adj_e, const double *__restrict__ cbase,
+                                                    const double *__restrict__ Cfull, int npad, const double *__restrict__ tv,
+                                                    unsigned char *__restrict__ lab, double *__restrict__ part, int *__restrict__ flag) {
+    __shared__ double sh[KCUT_CH][TPB];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int w = blockIdx.y, strip = blockIdx.x;
+    const int t = w * 64 + lane;
+    const bool valid = t < K;
+    unsigned char *lw = lab + (size_t)w * n * 64 + lane;
+    double acc = 0.0;
+    for (int i = strip * (TPB / 64) + wv; i < nrows; i += gridDim.x * (TPB / 64)) {
+        const int p = __builtin_amdgcn_readfirstlane(rows ? rows[i] : i);
+        const int lp = lw[(size_t)p * 64];
+        const double tp = tv[p];
+        if (!rows) {
+            double same = 0.0, other = 0.0, cpp = 0.0;
+            kcut_walk(p, n, adj_ptr, adj_col, adj_e, cbase, Cfull, npad, [&](int q, double cq) {
+                if (q == p) { cpp = cq; return; }
+                const double v = cq * tv[q];
+                if (lw[(size_t)q * 64] == lp) same += v; else other += v;
+            });
+            acc += tp * (cpp * tp + (same - other * inv));
+            continue;
+        }
+        double hmin = INFINITY, hcur = 0.0, asum = 0.0;
+        int amin = 0;
+        for (int a0 = 0; a0 < parts; a0 += KCUT_CH) {
+#pragma unroll
+            for (int j = 0; j < KCUT_CH; ++j) sh[j][tid] = 0.0;
+            kcut_walk(p, n, adj_ptr, adj_col, adj_e, cbase, Cfull, npad, [&](int q, double cq) {
+                if (q == p) return;
+                const double tq = tv[q];
+                const unsigned j = (unsigned)((int)lw[(size_t)q * 64] - a0);
+                if (j < (unsigned)KCUT_CH) sh[j][tid] += cq * tq;
+                if (a0 == 0) asum += fabs(cq) * tq;
+            });
+            const int na = parts - a0 < KCUT_CH ? parts - a0 : KCUT_CH;
+            for (int j = 0; j < na; ++j) {
+                const double h = sh[j][tid];
+                if (h < hmin) { hmin = h; amin = a0 + j; }
+                if (a0 + j == lp) hcur = h;
+            }
+        }
+        const double delta = coef * tp * (hmin - hcur), tau = 0x1p-40 * coef * tp * asum;
+        if (valid && delta < -tau) { lw[(size_t)p * 64] = (unsigned char)amin; flag[0] = 1; }
+    }
+    if (rows) return;
+    sh[0][tid] = acc;
+    __syncthreads();
+    if (wv == 0 && valid) part[(size_t)t * RND_STRIPS + strip] = ((sh[0][lane] + sh[0][64 + lane]) + sh[0][128 + lane]) + sh[0][192 + lane];
+}
+
+// Applicability (once per context: the constraint data never changes).  Without an LP block it is rnd_check's answer and t; with one
+// the constraint data is read back and checked here, and t and the bounds u_j of the LP columns are kept.
+int kcut_check(lorads_hip_ctx *c) {
+    KCutScratch &X = c->kcut;
+    if (X.checked) return 0;
+    if (rnd_check(c)) return 1;
+    const RoundScratch &Rn = c->rnd;
+    X.qualifies = false;
+    X.why.clear();
+    X.t = nullptr;
+    X.lp_u.clear();
+    int nlp = 0, lpk = -1, nsdp = 0;
+    for (int k = 0; k < c->nb; ++k) {
+        if (c->blk[k].is_lp) { ++nlp; lpk = k; } else ++nsdp;
+    }
+    if (nlp == 0) {
+        X.qualifies = Rn.qualifies;
+        X.why = Rn.why;
+        X.t = Rn.t;
+        X.checked = true;
+        return 0;
+    }
+    char msg[256];
+    if (nlp > 1) X.why = "more than one LP block";
+    else if (nsdp == 0) X.why = "no cone";
+    for (int k = 0; k < c->nb && X.why.empty(); ++k)
+        if (c->blk[k].dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); X.why = msg; }
+    if (!X.why.empty()) { X.checked = true; return 0; }
+    // every stored entry, constraint by constraint: (block, row, column, coefficient)
+    struct Ent { int k, p, q; double a; };
+    std::vector<std::vector<Ent>> con((size_t)c->m);
+    std::vector<double> b((size_t)c->m), th((size_t)Rn.t_off[c->nb], 0.0), cobj;
+    if (c->m) HC(hipMemcpyAsync(b.data(), c->b, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        std::vector<int> ri(B.nrow), ap(B.nrow + 1), ae(B.na), er(B.pa.ne), ec(B.pa.ne);
+        std::vector<double> av(B.na);
+        if (B.nrow) {
+            HC(hipMemcpyAsync(ri.data(), B.row_idx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(ap.data(), B.a_ptr, sizeof(int) * ap.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (B.na) {
+            HC(hipMemcpyAsync(ae.data(), B.a_e, sizeof(int) * ae.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(av.data(), B.a_val, sizeof(double) * av.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (B.pa.ne) {
+            HC(hipMemcpyAsync(er.data(), B.pa.erow, sizeof(int) * er.size(), hipMemcpyDeviceToHost, c->stream));
+            HC(hipMemcpyAsync(ec.data(), B.pa.ecol, sizeof(int) * ec.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        if (B.is_lp) {
+            cobj.resize((size_t)B.n);
+            if (B.n) HC(hipMemcpyAsync(cobj.data(), B.lp_cobj, sizeof(double) * cobj.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        HC(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < B.nrow; ++i)
+            for (int s = ap[i]; s < ap[i + 1]; ++s) con[(size_t)ri[i]].push_back({k, er[ae[s]], ec[ae[s]], av[s]});
+    }
+    const int nl = c->blk[lpk].n;
+    std::vector<int> col_use((size_t)nl, 0);
+    std::vector<std::vector<int>> cover((size_t)c->nb);
+    for (int k = 0; k < c->nb; ++k) cover[k].assign((size_t)c->blk[k].n, 0);
+    X.lp_u.assign((size_t)nl, 0.0);
+    struct Row { int i, k, p, q, j; double a, cc; };
+    std::vector<Row> brow;
+    for (int i = 0; i < c->m && X.why.empty(); ++i) {
+        const std::vector<Ent> &E = con[(size_t)i];
+        int lp = 0, sdp = 0;
+        const Ent *el = nullptr, *es = nullptr;
+        for (const Ent &e : E) {
+            if (e.k == lpk) { ++lp; el = &e; } else { ++sdp; es = &e; }
+        }
+        if (lp == 0) {
+            if (sdp != 1) { snprintf(msg, sizeof msg, "constraint %d has %d stored entries", i + 1, sdp); X.why = msg; break; }
+            if (es->p != es->q) { snprintf(msg, sizeof msg, "constraint %d is not on a diagonal", i + 1); X.why = msg; break; }
+            const double ratio = b[(size_t)i] / es->a;
+            if (!(ratio > 0) || !std::isfinite(ratio)) {
+                snprintf(msg, sizeof msg, "constraint %d has b / a = %g (not positive)", i + 1, ratio);
+                X.why = msg;
+                break;
+            }
+            cover[es->k][es->p]++;
+            th[(size_t)Rn.t_off[es->k] + es->p] = std::sqrt(ratio);
+        } else {
+            if (lp != 1) { snprintf(msg, sizeof msg, "constraint %d has %d LP entries", i + 1, lp); X.why = msg; break; }
+            if (sdp != 1) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and %d cone entries", i + 1, sdp); X.why = msg; break; }
+            if (es->p == es->q) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and a diagonal entry", i + 1); X.why = msg; break; }
+            if (el->a == 0.0 || es->a == 0.0) { snprintf(msg, sizeof msg, "constraint %d has a zero coefficient", i + 1); X.why = msg; break; }
+            col_use[(size_t)el->p]++;
+            brow.push_back({i, es->k, es->p, es->q, el->p, es->a, el->a});
+        }
+    }
+    for (int k = 0; k < c->nb && X.why.empty(); ++k) {
+        if (k == lpk) continue;
+        for (int p = 0; p < c->blk[k].n && X.why.empty(); ++p)
+            if (cover[k][p] != 1) {
+                snprintf(msg, sizeof msg, "diagonal %d of cone %d is fixed by %d constraints", p + 1, k + 1, cover[k][p]);
+                X.why = msg;
+            }
+    }
+    for (int j = 0; j < nl && X.why.empty(); ++j) {
+        if (col_use[(size_t)j] != 1) { snprintf(msg, sizeof msg, "LP column %d occurs in %d constraints", j + 1, col_use[(size_t)j]); X.why = msg; }
+        else if (cobj[(size_t)j] != 0.0) { snprintf(msg, sizeof msg, "LP column %d has an objective coefficient", j + 1); X.why = msg; }
+    }
+    X.qualifies = X.why.empty();
+    if (X.qualifies) {
+        for (const Row &r : brow) // x_j = (b - 2 a X_pq) / c and |X_pq| <= t_p t_q
+            X.lp_u[(size_t)r.j] = (std::fabs(b[(size_t)r.i]) + 2.0 * std::fabs(r.a) * th[(size_t)Rn.t_off[r.k] + r.p] * th[(size_t)Rn.t_off[r.k] + r.q]) /
+                                  std::fabs(r.cc);
+        if (X.mem.upload(&X.t_own, th)) return 1;
+        X.t = X.t_own;
+    }
+    X.checked = true;
+    return 0;
+}
+
+// buffers for K trials of `parts` parts (grown on demand, freed with the context)
+int kcut_reserve(lorads_hip_ctx *c, int K, int parts) {
+    KCutScratch &X = c->kcut;
+    const size_t W = (size_t)(K + 63) / 64;
+    size_t g = 0;
+    for (auto &B : c->blk)
+        if (!B.is_lp) g += (size_t)B.rl * K * parts;
+    const size_t bytes = (size_t)c->rnd.t_off[c->nb] * W * 64;
+    if (X.G.grow(X.mem, g) || X.lab.grow(X.mem, bytes) || X.part.grow(X.mem, (size_t)K * RND_STRIPS)) return 1;
+    if (X.f.grow(X.mem, (size_t)K) || X.f0.grow(X.mem, (size_t)K)) return 1;
+    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
+    return 0;
+}
+
+// one field pass of cone k over nrows rows (rows == null: all of them, evaluation)
+void kcut_field(lorads_hip_ctx *c, int k, int K, int parts, const int *rows, int nrows) {
+    const Block &B = c->blk[k];
+    KCutScratch &X = c->kcut;
+    const int W = (K + 63) / 64;
+    const int strips = rows ? std::max(1, std::min(RND_STRIPS, nblocks_for((size_t)nrows, TPB / 64))) : RND_STRIPS;
+    hipLaunchKernelGGL(k_kcut_field, dim3(strips, W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, parts, 1.0 / (parts - 1),
+                       2.0 * parts / (parts - 1), (const int *)B.pu.adj_ptr, (const int *)B.pu.adj_col, (const int *)B.pu.adj_e,
+                       (const double *)B.pu.cbase, (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad,
+                       (const double *)(X.t + c->rnd.t_off[k]), X.lab + (size_t)c->rnd.t_off[k] * W * 64, X.part, X.ctl);
+}
+
+// f (K values) of the current labels: every cone's field pass, its strips added per trial in cone order
+void kcut_eval(lorads_hip_ctx *c, int K, int parts, double *f) {
+    bool first = true;
+    for (int k = 0; k < c->nb; ++k) {
+        if (c->blk[k].is_lp) continue;
+        kcut_field(c, k, K, parts, nullptr, c->blk[k].n);
+        hipLaunchKernelGGL(k_rnd_sum, dim3(nblocks_for((size_t)K, TPB)), dim3(TPB), 0, c->stream, K, (int)RND_STRIPS,
+                           (const double *)c->kcut.part, f, (int)first);
+        first = false;
+    }
+}
+
+} // namespace
+
+extern "C" int lorads_hip_round_kcut(lorads_hip_ctx *c, int32_t src, int32_t parts, int32_t trials, uint64_t seed, int32_t max_rounds,
+                                     double *obj, double *obj0, int32_t *best, int32_t *best0, uint8_t *label, int32_t *rounds,
+                                     double *vectors, double *t, double *lp_upper) {
+    spec_touch(c);
+    if (postsolve_args(c, src, nullptr, "round_kcut", true)) return 1;
+    if (parts < 2 || parts > KCUT_MAXPARTS) return fail_msg("round_kcut: parts " + std::to_string(parts) + " is outside [2, 64]");
+    if (trials < 0 || trials > RND_MAXK) return fail_msg("round_kcut: trials " + std::to_string(trials) + " is outside [0, 65536]");
+    if ((int64_t)trials * parts > KCUT_MAXPROD)
+        return fail_msg("round_kcut: trials x parts = " + std::to_string((int64_t)trials * parts) + " is above 2^20");
+    if (max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_kcut: bad argument");
+    if (postsolve_sharded(c, "round_kcut", "cannot be rounded")) return 3;
+    if (kcut_check(c)) return 1;
+    KCutScratch &X = c->kcut;
+    if (!X.qualifies) {
+        fail_msg("round_kcut: the context is not k-cut-structured: " + X.why);
+        return 2;
+    }
+    const std::vector<int> &off = c->rnd.t_off;
+    if (t) { // t of the SDP cones, cone after cone
+        size_t at = 0;
+        for (int k = 0; k < c->nb; ++k) {
+            const Block &B = c->blk[k];
+            if (B.is_lp) continue;
+            if (B.n) HC(hipMemcpyAsync(t + at, X.t + off[k], sizeof(double) * (size_t)B.n, hipMemcpyDeviceToHost, c->stream));
+            at += (size_t)B.n;
+        }
+        HC(hipStreamSynchronize(c->stream));
+    }
+    if (lp_upper)
+        for (size_t j = 0; j < X.lp_u.size(); ++j) lp_upper[j] = X.lp_u[j];
+    if (trials == 0) return 0;
+    const int K = trials, W = (K + 63) / 64;
+    if (kcut_reserve(c, K, parts) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    // vectors and labels
+    size_t goff = 0;
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        if (B.is_lp) continue;
+        double *G = X.G + goff;
+        const size_t glen = (size_t)B.rl * K * parts;
+        if (glen) hipLaunchKernelGGL(k_kcut_hyper, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, B.rl, K, parts, k, seed, G);
+        const FactorView F = factor_view(c, src, k);
+        const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * W * 4;
+        if (B.n) hipLaunchKernelGGL(k_kcut_label, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, parts,
+                                    F.U, F.V, F.uv, (const double *)G, X.lab + (size_t)off[k] * W * 64);
+        goff += glen;
+    }
+    if (vectors && goff) HC(hipMemcpyAsync(vectors, X.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    kcut_eval(c, K, parts, X.f0);
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0, X.ctl + 1);
+    // local search: one host synchronisation per round (the flag decides whether another round runs)
+    int nr = 0;
+    for (int round = 0; round < max_rounds; ++round) {
+        HC(hipMemsetAsync(X.ctl, 0, sizeof(int), c->stream));
+        for (int k = 0; k < c->nb; ++k) {
+            if (c->blk[k].is_lp) continue;
+            const std::vector<int> &cp = c->rnd.cls_ptr[k];
+            for (size_t cl = 0; cl + 1 < cp.size(); ++cl)
+                kcut_field(c, k, K, parts, c->rnd.cls_rows + off[k] + cp[cl], cp[cl + 1] - cp[cl]);
+        }
+        int flag = 0;
+        HC(hipMemcpyAsync(&flag, X.ctl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HC(hipStreamSynchronize(c->stream));
+        nr = round + 1;
+        if (!flag) break;
+    }
+    double *f = X.f0;
+    if (nr > 0) {
+        kcut_eval(c, K, parts, X.f);
+        f = X.f;
+    }
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, X.ctl + 2);
+    int bb[2] = {0, 0};
+    HC(hipMemcpyAsync(bb, X.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    HC(hipMemcpyAsync(obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (obj0) HC(hipMemcpyAsync(obj0, X.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HC(hipStreamSynchronize(c->stream));
+    if (best) *best = bb[1];
+    if (best0) *best0 = bb[0];
+    if (rounds) *rounds = nr;
+    if (label) { // the best trial's labels, SDP cone after SDP cone: its 64-trial block of every row, then the trial's byte
+        const int w = bb[1] / 64, l = bb[1] % 64;
+        std::vector<unsigned char> blkb;
+        size_t at = 0;
+        for (int k = 0; k < c->nb; ++k) {
+            const Block &B = c->blk[k];
+            if (B.is_lp) continue;
+            blkb.resize((size_t)B.n * 64);
+            if (B.n) HC(hipMemcpyAsync(blkb.data(), X.lab + (size_t)off[k] * W * 64 + (size_t)w * B.n * 64, blkb.size(), hipMemcpyDeviceToHost,
+                                       c->stream));
+            HC(hipStreamSynchronize(c->stream));
+            for (int p = 0; p < B.n; ++p) label[at + p] = blkb[(size_t)p * 64 + l];
+            at += (size_t)B.n;
+        }
+    }
+    return 0;
+}

@@ -537,6 +537,21 @@ struct RoundScratch {
     void release() { mem.release(); *this = RoundScratch{}; }
 };
 
+// scratch of the rounding into k parts (kcut.inc): allocated on its first call, never read by the solve.  Labels n K bytes rounded up to
+// blocks of 64 trials, G 8 k K sum(rank), partials 8 x 256 K, f 16 K.  The colouring and, without an LP block, t are RoundScratch's.
+struct KCutScratch {
+    bool checked = false, qualifies = false;
+    std::string why;                          // the first reason the context does not qualify
+    const double *t = nullptr;                // t_p, cone k at RoundScratch::t_off[k]: RoundScratch's, or t_own on a context with an LP block
+    double *t_own = nullptr;
+    std::vector<double> lp_u;                 // [LP columns] u_j = (|b| + 2 |a| t_p t_q) / |c| of the column's bound row
+    DevBuf<double> G, part, f, f0;            // vectors, field partials, f after / before the search
+    DevBuf<unsigned char> lab;                // labels, cone k at t_off[k] * W * 64
+    int *ctl = nullptr;                       // [0] move flag, [1] best before, [2] best after the search
+    DevPool mem;
+    void release() { mem.release(); *this = KCutScratch{}; }
+};
+
 // scratch of the spectrum / rank reduction (spectral.inc): allocated on its first call, never read by the solve
 struct SpecCone { int rl, m; long long g_off, e_off, q_off; }; // one cone of a k_spec_jacobi launch: orders, places in SpecScratch::W
 struct SpecScratch {
@@ -591,6 +606,7 @@ struct lorads_hip_ctx {
     std::vector<LzWorker> lz_workers; // dual-infeasibility eigen-solves (lanczos.inc)
     CertScratch cert;                 // solution export (solution.inc)
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
+    KCutScratch kcut;                 // rounding into k parts (kcut.inc)
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
@@ -941,6 +957,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->primal.release();
     c->cuts.release();
     c->bounds.release();
+    c->kcut.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -1837,6 +1854,7 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "postsolve.inc"
 #include "solution.inc"
 #include "rounding.inc"
+#include "kcut.inc"
 #include "spectral.inc"
 #include "primal.inc"
 #include "select.inc"

@@ -58,6 +58,8 @@ typedef struct {
                          double *, int32_t *, int32_t *); /* optional */
     int (*entry_bounds)(lorads_hip_ctx *, int32_t, int32_t, double, double, double, int32_t, int64_t *, int32_t *, int32_t *, int8_t *,
                         double *, int32_t *, int32_t *); /* optional */
+    int (*round_kcut)(lorads_hip_ctx *, int32_t, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, uint8_t *,
+                      int32_t *, double *, double *, double *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -129,6 +131,12 @@ static int b_bounds(void *cx, int src, int blk, double lower, double upper, doub
     return report(H, H->entry_bounds(H->ctx, src, blk, lower, upper, minv, max_cuts, count, (int32_t *)p, (int32_t *)q, cls, viol,
                                      (int32_t *)kept, (int32_t *)passes), "entry_bounds");
 }
+/* rounding into k parts: codes 2 (not k-cut-structured) and 3 (sharded) pass through with the library's reason on stderr */
+static int b_kcut(void *cx, int src, int parts, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best,
+                  int *best0, uint8_t *label, int *rounds, double *vec, double *t, double *lpu) {
+    return report(H, H->round_kcut(H->ctx, src, parts, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, label,
+                                   (int32_t *)rounds, vec, t, lpu), "round_kcut");
+}
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
 static int b_a2a(void *cx) { return report(H, H->alm_to_admm(H->ctx), "alm_to_admm"); }
@@ -198,6 +206,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (!h->primal_apply) h->primal_entries = NULL;
     *(void **)(&h->triangle_cuts) = dlsym(h->dl, "lorads_hip_triangle_cuts");
     *(void **)(&h->entry_bounds) = dlsym(h->dl, "lorads_hip_entry_bounds");
+    *(void **)(&h->round_kcut) = dlsym(h->dl, "lorads_hip_round_kcut");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -247,5 +256,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->primal_entries) { out->primal_entries = b_pentries; out->primal_apply = b_papply; }
     if (h->triangle_cuts) out->triangle_cuts = b_cuts;
     if (h->entry_bounds) out->entry_bounds = b_bounds;
+    if (h->round_kcut) out->round_kcut = b_kcut;
     return 0;
 }

@@ -167,6 +167,11 @@ typedef struct lrd_backend {
      * lorads_hip_round_pm1, the same arguments and return codes; values in the backend's terms) */
     int (*round_pm1)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
                      int8_t *sign, int *rounds, double *hyperplanes);
+    /* OPTIONAL (beside round_pm1: the table's mirror is checked to end with entry_bounds and the spectral pair): Frieze-Jerrum
+     * rounding into `parts` parts + 1-move local search of a k-cut-structured context, read-only on the state (include/lorads_hip.h:
+     * lorads_hip_round_kcut, the same arguments and return codes; values in the backend's terms) */
+    int (*round_kcut)(void *ctx, int src, int parts, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best,
+                      int *best0, uint8_t *label, int *rounds, double *vectors, double *t, double *lp_upper);
     /* OPTIONAL pair (both or neither; the table's mirror is checked to END with the spectral pair, so this one stands before it):
      * entries of the primal X = F F^T and its products with a block of vectors (include/lorads_hip.h:
      * lorads_hip_primal_entries, lorads_hip_primal_apply, the same arguments and return codes; X in the file's units) */
@@ -464,6 +469,42 @@ void lrd_bounds_free(lrd_bounds *c);
  * 1: cannot write; 2: a cut outside the problem (p >= q, a cone out of range or an LP block, a class outside {0, 1}, a bound that is
  * not finite) or a problem with more than one LP block; 3: sharded. */
 int lrd_session_write_bounded(lrd_session *s, const char *path, const lrd_bounds *bounds);
+
+/* ---- rounding into k parts (kcut.c).  Everything in the file's units.  A k-cut-structured problem fixes every
+ * diagonal (t_p as the +-1 rounding's) and may bound off-diagonal entries through rows 2 a X_pq + c x_j = b with one LP column each.
+ * X(l)_pq = t_p t_q (l_p = l_q), -t_p t_q / (parts - 1) (otherwise); f = sum_k <C_k, X(l_k)>; the dual bound
+ * d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) <= the optimum <= f(l) for every l whose X(l) is feasible. */
+typedef struct {
+    int blk;           /* the cone's block in the file, 0-based */
+    int n, rank;       /* rank: the cone's own current rank (the vectors' dimension) */
+    uint8_t *label;    /* [n] the best trial's labels after the local search */
+    double *t;         /* [n] */
+    int *size;         /* [parts] vertices per part */
+    double T;          /* sum_p t_p^2 */
+    double lam_min;    /* lambda_min(S_k) (NaN without a bound) */
+    double *G;         /* parts x rank x trials (part, then column, then trial), only when asked for (else NULL) */
+} lrd_kcut_cone;
+typedef struct {
+    int nblk;           /* SDP cones */
+    int parts, trials, max_rounds, rounds;
+    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where R came from */
+    uint64_t seed;
+    double scale;       /* scaleObjHis the backend's values were divided by */
+    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
+    double f_best, f_best0;
+    double *obj, *obj0; /* [trials] f after / before the local search */
+    int nlp, lp_neg;    /* LP columns; how many of them have a dual slack s_j < 0 (0 without a bound) */
+    double *lp_upper;   /* [nlp] u_j */
+    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
+    double tol;         /* Lanczos tolerance of lambda_min */
+    lrd_kcut_cone *cone; /* [nblk], file order */
+} lrd_kcut;
+/* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
+ * lacks the slot, 3 when it is sharded.  with_vectors: also fill every cone's G. */
+int lrd_session_kcut(lrd_session *s, int parts, int trials, uint64_t seed, int max_rounds, double tol, int with_vectors, lrd_kcut **out);
+void lrd_kcut_free(lrd_kcut *r);
+/* plain-text file, a pure function of the struct (kcut.c) */
+int lrd_kcut_write(const char *path, const lrd_kcut *r);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -44,6 +44,9 @@ int main(int argc, char **argv) {
     int bounds_max = -1;              /* separation of entry bounds lower <= X_pq <= upper (ours as well) */
     double bounds_lower = 0.0, bounds_upper = HUGE_VAL, bounds_minv = 1e-3;
     const char *bounds_file = NULL, *bounds_other = NULL; /* bounds_other: some --bounds* option other than --boundsMax was given */
+    int kcut_parts = 0, kcut_trials = 1024, kcut_ls = 100; /* rounding of a k-cut-structured problem into k parts (ours as well) */
+    unsigned long long kcut_seed = 0;
+    const char *kcut_file = NULL, *kcut_other = NULL; /* kcut_other: some --kcut* option other than --kcutParts was given */
     for (int i = 2; i < argc; i += 2) {
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
@@ -108,6 +111,27 @@ int main(int argc, char **argv) {
             else round_ls = (int)v;
             continue;
         }
+        if (!strcmp(argv[i], "--kcutFile")) { kcut_other = argv[i]; kcut_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--kcutParts") || !strcmp(argv[i], "--kcutTrials") || !strcmp(argv[i], "--kcutSeed") ||
+            !strcmp(argv[i], "--kcutLocalSearch")) {
+            char *end = NULL;
+            const char w = argv[i][6]; /* P, T, S or L */
+            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
+            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'P' && (v < 2 || v > 64)) ||
+                (w == 'T' && (v < 1 || v > 65536)) || (w == 'L' && v > 65536)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            if (w == 'P') kcut_parts = (int)v;
+            else {
+                kcut_other = argv[i];
+                if (w == 'T') kcut_trials = (int)v;
+                else if (w == 'S') kcut_seed = v;
+                else kcut_ls = (int)v;
+            }
+            continue;
+        }
         if (!strcmp(argv[i], "--compressTol") || !strcmp(argv[i], "--compressRank")) {
             char *end = NULL;
             const int is_tol = argv[i][10] == 'T';
@@ -145,6 +169,16 @@ int main(int argc, char **argv) {
     if (bounds_max > 0 && (bounds_lower > bounds_upper || (bounds_lower == -HUGE_VAL && bounds_upper == HUGE_VAL))) {
         fprintf(stderr, "bad value of --boundsLower and --boundsUpper: %g, %g (lower above upper, or both classes off)\n", bounds_lower,
                 bounds_upper);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (kcut_other && kcut_parts == 0) {
+        fprintf(stderr, "%s needs --kcutParts\n", kcut_other);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (kcut_parts > 0 && (long)kcut_parts * kcut_trials > (1L << 20)) {
+        fprintf(stderr, "bad value of --kcutParts and --kcutTrials: %d x %d is above 2^20\n", kcut_parts, kcut_trials);
         lrd_session_close(s);
         return 2;
     }
@@ -187,6 +221,14 @@ int main(int argc, char **argv) {
         if (rrc) {
             fprintf(stderr, "lorads: %s needs a +-1-structured problem (see above); nothing was solved\n",
                     round_trials > 0 ? "--roundTrials" : "--cutsMax");
+            lrd_session_close(s);
+            return 2;
+        }
+    }
+    if (kcut_parts > 0) { /* applicability before any solving */
+        lrd_kcut *none = NULL;
+        if (lrd_session_kcut(s, kcut_parts, 0, kcut_seed, kcut_ls, 0.0, 0, &none)) {
+            fprintf(stderr, "lorads: --kcutParts needs a k-cut-structured problem (see above); nothing was solved\n");
             lrd_session_close(s);
             return 2;
         }
@@ -310,6 +352,19 @@ int main(int argc, char **argv) {
         printf("\t f = x^T C x before local search : %.10e\n\t f = x^T C x after local search  : %.10e\n", x->f_best0, x->f_best);
         printf("\t dual bound d                    : %.10e\n\t gap (f - d) / max(1, |d|)       : %.6e\n", x->bound, x->gap);
         lrd_rounding_free(x);
+    }
+    if (kcut_parts > 0) {
+        lrd_kcut *x = NULL;
+        if (lrd_session_kcut(s, kcut_parts, kcut_trials, (uint64_t)kcut_seed, kcut_ls, 1e-8, 0, &x) ||
+            (kcut_file && lrd_kcut_write(kcut_file, x))) {
+            fprintf(stderr, "lorads: the rounding into parts failed%s%s\n", kcut_file ? " or cannot write " : "", kcut_file ? kcut_file : "");
+            lrd_kcut_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Rounding into %d parts (%d trials, seed %llu%s%s): best f %.10e, dual bound d %.10e, gap %.6e, %d local-search rounds\n",
+               x->parts, x->trials, kcut_seed, kcut_file ? ", " : "", kcut_file ? kcut_file : "", x->f_best, x->bound, x->gap, x->rounds);
+        lrd_kcut_free(x);
     }
     lrd_session_close(s);
     return 0;

@@ -62,6 +62,8 @@ class BackendStruct(C.Structure):
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
         ("round_pm1", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
                                   C.POINTER(C.c_int8), _ip, _dp)),
+        ("round_kcut", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
+                                   C.POINTER(C.c_uint8), _ip, _dp, _dp, _dp)),
         ("primal_entries", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _ip, _ip, _dp, _dp, _dp)),
         ("primal_apply", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp)),
         ("triangle_cuts", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
@@ -333,6 +335,34 @@ class Backend:
             return (rc,) + (None,) * 6
         k = kept.value
         return 0, cnt.value, p[:k], q[:k], cls[:k], v[:k], passes.value
+
+    def has_round_kcut(self):
+        return bool(self._s.round_kcut)
+
+    def round_kcut(self, src, parts, trials, seed=0, max_rounds=0, want_vectors=False):
+        """the table's slot as it is (values in the backend's terms): returns (code, dict) with obj, obj0, best, best0, label, rounds,
+        t, lp_upper and -- want_vectors -- vectors (flat: per SDP cone parts x rank x trials); code != 0 is the slot's refusal (the
+        dict is then None).  trials = 0 checks applicability and still gives t and lp_upper."""
+        ses = self._session
+        lp = ses._lp_blocks()
+        sdp = [k for k in range(ses.nblk) if not lp[k]]
+        ntot = sum(ses.block_shape(k)[0] for k in sdp)
+        nlp = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if lp[k])
+        K = max(int(trials), 0)
+        ok = 2 <= parts <= 64 and K * parts <= (1 << 20)
+        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
+        label, t, lpu = np.zeros(max(ntot, 1), dtype=np.uint8), np.zeros(max(ntot, 1)), np.zeros(max(nlp, 1))
+        glen = sum(ses.block_shape(k)[1] for k in sdp) * K * parts if want_vectors and ok else 0
+        vec = np.zeros(max(glen, 1))
+        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self._s.round_kcut(self._s.ctx, int(src), int(parts), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
+                                obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
+                                label.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rounds), vec.ctypes.data_as(_dp) if glen else None,
+                                t.ctypes.data_as(_dp), lpu.ctypes.data_as(_dp))
+        if rc:
+            return rc, None
+        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, label=label[:ntot], rounds=rounds.value,
+                       t=t[:ntot], lp_upper=lpu[:nlp], vectors=vec[:glen] if glen else None)
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -894,6 +924,64 @@ class Session:
             _check(self.lib.lrd_rounding_write(os.fsencode(path), ptr), "rounding_write")
         finally:
             self.lib.lrd_rounding_free(ptr)
+
+    def _kcut_ptr(self, parts, trials, seed, local_search_rounds, tol, vectors):
+        from .kcut import KCutStruct
+        parts, trials, local_search_rounds = int(parts), int(trials), int(local_search_rounds)
+        if not 2 <= parts <= 64:
+            raise ValueError("round_kcut: parts %d is outside [2, 64]" % parts)
+        if not 0 <= trials <= 65536:
+            raise ValueError("round_kcut: trials %d is outside [0, 65536]" % trials)
+        if trials * parts > 1 << 20:
+            raise ValueError("round_kcut: trials x parts = %d is above 2^20" % (trials * parts))
+        if local_search_rounds < 0:
+            raise ValueError("round_kcut: local_search_rounds %d is negative" % local_search_rounds)
+        ptr = C.POINTER(KCutStruct)()
+        self.lib.lrd_session_kcut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
+                                              C.POINTER(C.POINTER(KCutStruct))]
+        self.lib.lrd_kcut_free.argtypes = [C.POINTER(KCutStruct)]
+        self.lib.lrd_kcut_free.restype = None
+        rc = self.lib.lrd_session_kcut(self.h, int(parts), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds),
+                                       float(tol), 1 if vectors else 0, C.byref(ptr))
+        if rc == 2:
+            msg = None
+            if self.be is not None and self.be.name == "hip-gfx950":
+                lib, _ = self._hip()
+                lib.lorads_hip_last_error.restype = C.c_char_p
+                msg = (lib.lorads_hip_last_error() or b"").decode()
+            raise NotImplementedError("the problem cannot be rounded into parts: it is not k-cut-structured (every diagonal fixed by one "
+                                      "constraint a_i X[p,p] = b_i with b_i / a_i > 0; LP columns only in bound rows 2 a X[p,q] + c x_j = b) "
+                                      "or the %s backend cannot round%s" % (self.be.name if self.be else "attached", (": " + msg) if msg else ""))
+        if rc == 3:
+            raise NotImplementedError("rounding the solution of a sharded deal (world > 1) is not supported")
+        _check(rc, "round_kcut")
+        return ptr
+
+    def round_kcut(self, parts, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, vectors=False):
+        """Frieze-Jerrum rounding of the current point into `parts` parts with a 1-move local search, on the device
+        (lorads_amd.kcut.KCut, file units): per trial f = sum <C, X(l)> before and after the search, the best trial's labels and
+        part sizes per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) at Lanczos
+        tolerance tol (tol <= 0: NaN).  Works on +-1-structured problems and on what write_bounded makes of them.  trials = 0
+        checks applicability alone (None).  Read-only on the solver's state."""
+        from .kcut import KCut
+        if trials == 0:
+            self._kcut_ptr(parts, 0, seed, local_search_rounds, tol, False)
+            return None
+        ptr = self._kcut_ptr(parts, trials, seed, local_search_rounds, tol, vectors)
+        try:
+            return KCut.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_kcut_free(ptr)
+
+    def write_kcut(self, path, parts, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
+        """the k-cut file of the command line's --kcutFile (the same C writer: the same bytes)"""
+        from .kcut import KCutStruct
+        ptr = self._kcut_ptr(parts, trials, seed, local_search_rounds, tol, False)
+        try:
+            self.lib.lrd_kcut_write.argtypes = [C.c_char_p, C.POINTER(KCutStruct)]
+            _check(self.lib.lrd_kcut_write(os.fsencode(path), ptr), "kcut_write")
+        finally:
+            self.lib.lrd_kcut_free(ptr)
 
     def triangle_cuts(self, max_cuts=1000, min_violation=1e-3):
         """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device

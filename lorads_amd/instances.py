@@ -75,6 +75,20 @@ def maxcut(n, n_edges, seed, weights=None):
     return dict(m=n, blocks=[n], b=np.ones(n), entries=ent)
 
 
+def kpartite(k, m):
+    """the complete k-partite graph on k m vertices (vertex v lies in part v // m) as a maxcut problem with unit weights: every
+    edge is cut by the planted partition, k (k - 1) m^2 / 2 of them"""
+    n = k * m
+    ent = [(0, 1, i + 1, i + 1, (n - m) / 4.0) for i in range(n)]
+    for i in range(n):
+        for j in range(i + 1, n):
+            if i // m != j // m:
+                ent.append((0, 1, i + 1, j + 1, -0.25))
+    for i in range(n):
+        ent.append((i + 1, 1, i + 1, i + 1, 1.0))
+    return dict(m=n, blocks=[n], b=np.ones(n), entries=ent)
+
+
 def weighted_maxcut(n, n_edges, seed):
     """Max-Cut with edge weights drawn from [0.5, 2) (not dyadic: f is compared to a relative bound)"""
     return maxcut(n, n_edges, seed, weights=lambda rng, k: rng.uniform(0.5, 2.0, k))
@@ -457,6 +471,8 @@ NAMED = {
     "wmaxcut150": lambda: weighted_maxcut(150, 400, 151),
     "scaledpm1_120": lambda: scaled_pm1(120, 300, 121),
     "densemaxcut120": lambda: dense_maxcut(120, 2000, 122),
+    "kpartite3x10": lambda: kpartite(3, 10),
+    "kpartite4x6": lambda: kpartite(4, 6),
     "maxcut_uncovered60": lambda: maxcut_uncovered(60, 120, 123),
     "maxcut_negratio60": lambda: maxcut_negative_ratio(60, 120, 124),
     # timing / log-level instances
