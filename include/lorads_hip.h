@@ -265,6 +265,27 @@ int lorads_hip_entry_bounds(lorads_hip_ctx *ctx, int32_t src, int32_t blk, doubl
                             int32_t max_cuts, int64_t *count, int32_t *p, int32_t *q, int8_t *cls, double *viol, int32_t *kept,
                             int32_t *passes);
 
+/* The k best entries per row of the primal X = F F^T (no reference counterpart).  With F the factor
+ * lorads_hip_certificate takes (src) of SDP cone blk at its own rank, X_pq = F_p . F_q: one chain of FP64 matrix-core steps over the
+ * columns in fours, ascending (|X_pq - exact| <= (r + 1) 2^-53 |F_p| |F_q|); its bits depend on the two rows alone.
+ *   row [nq]: the query rows, 0-based, any order, duplicates allowed.
+ *   Candidates of query i (p = row[i]): the columns q of the window [col_lo, col_hi), minus q = p unless include_diag, minus
+ *     skip_col[skip_ptr[i] .. skip_ptr[i + 1]) (any order, duplicates and columns outside the window allowed; both NULL: none), minus
+ *     every q whose X_pq is NaN.  +-inf order as numbers.
+ *   Order: X_pq descending (smallest = 1: ascending), then q ascending; -0.0 and +0.0 are one value.
+ *   found [nq] = min(k, candidates); idx, val [nq * k]: the first found[i] candidates of query i in the order at i * k ..., the
+ *     device's own bits of X_pq; the slots past found[i] hold idx -1 and val 0.0.
+ * 1 <= k <= 128.  nq = 0 or an empty window: found all zero, nothing is launched.  Read-only on the solver's state and deterministic (no
+ * float atomics; the same state and arguments give the same bytes).  Scratch: the packed factor and, per batch of at most 16384
+ * queries, the packed query rows, the results and the partial lists of a split window -- bounded whatever nq is.
+ * Returns 1 on a bad argument (src, blk, nq < 0, a row outside [0, n), a window not within 0 <= lo <= hi <= n, k outside [1, 128],
+ * smallest or include_diag not 0 or 1, exactly one skip pointer NULL, skip_ptr not starting at 0 or decreasing, a skip column outside
+ * [0, n), idx, val or found NULL with nq > 0) or a failed allocation (the context stays usable), 2 on the LP block, 3 on a sharded
+ * context -- all refusals before any device work. */
+int lorads_hip_primal_topk(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int32_t nq, const int32_t *row, int32_t col_lo, int32_t col_hi,
+                           int32_t k, int32_t smallest, int32_t include_diag, const int64_t *skip_ptr, const int32_t *skip_col,
+                           int32_t *idx, double *val, int32_t *found);
+
 /* state movers ("mutators outside the table") */
 int lorads_hip_alm_to_admm(lorads_hip_ctx *ctx);        /* LORADS_ALMtoADMM copies, data/lorads_solver.c:968-983 */
 int lorads_hip_average_uv_to_v(lorads_hip_ctx *ctx);    /* averageUV + copyRtoV, main.c:441-448 */

@@ -596,6 +596,21 @@ struct BoundScratch {
     void release() { mem.release(); *this = BoundScratch{}; }
 };
 
+// scratch of the top-k search per row of X (topk.inc): allocated on first use, grown on demand, never read by the solve.  Bounded
+// whatever nq is: the packed factor, and per batch of at most 16384 queries (and 2^22 skip columns beyond a batch's first query) the
+// packed query rows, the results (k <= 128: 24 MB) and, when the window is split, the runs' lists -- at most 16 x 2 CUs + 16384 lists
+// of k entries, 12 bytes each (256 CUs, k = 128: 38 MB).
+struct TopkScratch {
+    DevBuf<double> Fp, Qp;                                 // F as k_bnd_pack packs it (whole steps of 64 rows); the batch's query rows
+    DevBuf<int> row, scol, idx, found, pcol, pcnt;         // the batch's rows, skip columns, results; the runs' columns and counts
+    DevBuf<long long> sptr;
+    DevBuf<double> val;
+    DevBuf<unsigned long long> pkey;                       // the runs' keys
+    int ncu = 0;                                           // compute units of the device
+    DevPool mem;
+    void release() { mem.release(); *this = TopkScratch{}; }
+};
+
 struct lorads_hip_ctx {
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
@@ -611,6 +626,7 @@ struct lorads_hip_ctx {
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
     BoundScratch bounds;              // separation of entry bounds on X (bounds.inc)
+    TopkScratch topk;                 // the k best entries per row of X (topk.inc)
     Block merged;             // all cones as ONE block-diagonal cone (see build_merged); valid when has_merged
     bool has_merged = false;
     std::vector<int> seg_row0_h;              // padded first row of every cone in the merged cone (+ end)
@@ -957,6 +973,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->primal.release();
     c->cuts.release();
     c->bounds.release();
+    c->topk.release();
     c->kcut.release();
     c->factor_mem.release();
     c->mem.release();
@@ -1860,3 +1877,4 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "select.inc"
 #include "cuts.inc"
 #include "bounds.inc"
+#include "topk.inc"

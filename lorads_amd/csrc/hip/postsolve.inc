@@ -1,5 +1,5 @@
 // postsolve.inc -- what the post-solve entry points share, included by lorads_hip.hip after lanczos.inc and before the first of them:
-// solution.inc, rounding.inc, kcut.inc, spectral.inc, primal.inc, cuts.inc and bounds.inc (DESIGN.md sections 10 to 16).  All of them read the solution
+// solution.inc, rounding.inc, kcut.inc, spectral.inc, primal.inc, cuts.inc, bounds.inc and topk.inc (DESIGN.md sections 10 to 17).  All of them read the solution
 // factors and none is run by a solve.
 //   FactorView / factor_view, factor_ld   which arrays make up F for a `src`, and F's elements on the device
 //   mfma_strip_tile, mfma_fm_tile         the two FP64 matrix-core tile bodies, with the operand layout written down once
@@ -35,7 +35,7 @@ __device__ __forceinline__ double2 factor_ld(const double2 *__restrict__ U, cons
 // v_mfma_f64_16x16x4_f64 computes D (16 x 16) += A (16 x 4) B (4 x 16) per wavefront.  Lane l = (nn = l & 15, kk = l >> 4) supplies
 // ONE element of each operand, A[nn][kk] and B[kk][nn], and holds D[kk + 4 q][nn] in register q of its four (the FP64 result map: not
 // the FP32 one).  Both tile bodies below feed it so that a lane's two operands come from one row of the matrices in memory, and
-// mask by multiplying a clamped load with zero, never by branching.  (cuts.inc: cut_tile, bounds.inc: k_bnd_enum and kernels.inc: k_dense_cx_b use the same
+// mask by multiplying a clamped load with zero, never by branching.  (cuts.inc: cut_tile, bounds.inc: k_bnd_enum, topk.inc: k_topk_scan and kernels.inc: k_dense_cx_b use the same
 // layout on operands of their own.)
 
 // Partial tile of F^T B over one row strip: the 16 x 16 tile D[m][n] = sum over the strip's rows k of A[m][k] B[k][n], where row k of

@@ -60,6 +60,8 @@ typedef struct {
                         double *, int32_t *, int32_t *); /* optional */
     int (*round_kcut)(lorads_hip_ctx *, int32_t, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, uint8_t *,
                       int32_t *, double *, double *, double *); /* optional */
+    int (*primal_topk)(lorads_hip_ctx *, int32_t, int32_t, int32_t, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t,
+                       const int64_t *, const int32_t *, int32_t *, double *, int32_t *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -137,6 +139,12 @@ static int b_kcut(void *cx, int src, int parts, int trials, uint64_t seed, int m
     return report(H, H->round_kcut(H->ctx, src, parts, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, label,
                                    (int32_t *)rounds, vec, t, lpu), "round_kcut");
 }
+/* top-k search: codes 2 (the LP block) and 3 (sharded) pass through */
+static int b_topk(void *cx, int src, int blk, int nq, const int *row, int lo, int hi, int k, int smallest, int diag, const int64_t *sptr,
+                  const int *scol, int *idx, double *val, int *found) {
+    return report(H, H->primal_topk(H->ctx, src, blk, nq, (const int32_t *)row, lo, hi, k, smallest, diag, sptr, (const int32_t *)scol,
+                                    (int32_t *)idx, val, (int32_t *)found), "primal_topk");
+}
 static int b_dual(void *cx, double rho) { return report(H, H->update_dual_var(H->ctx, rho), "update_dual_var"); }
 static int b_dobj(void *cx, double *v) { return report(H, H->cal_dual_obj(H->ctx, v), "cal_dual_obj"); }
 static int b_a2a(void *cx) { return report(H, H->alm_to_admm(H->ctx), "alm_to_admm"); }
@@ -207,6 +215,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->triangle_cuts) = dlsym(h->dl, "lorads_hip_triangle_cuts");
     *(void **)(&h->entry_bounds) = dlsym(h->dl, "lorads_hip_entry_bounds");
     *(void **)(&h->round_kcut) = dlsym(h->dl, "lorads_hip_round_kcut");
+    *(void **)(&h->primal_topk) = dlsym(h->dl, "lorads_hip_primal_topk");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -257,5 +266,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->triangle_cuts) out->triangle_cuts = b_cuts;
     if (h->entry_bounds) out->entry_bounds = b_bounds;
     if (h->round_kcut) out->round_kcut = b_kcut;
+    if (h->primal_topk) out->primal_topk = b_topk;
     return 0;
 }

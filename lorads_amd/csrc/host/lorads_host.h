@@ -178,6 +178,11 @@ typedef struct lrd_backend {
     int (*primal_entries)(void *ctx, int src, int blk, int64_t count, const int *row, const int *col, double *val, const double *ref,
                           double *stats);
     int (*primal_apply)(void *ctx, int src, int blk, int ncols, const double *B, double *Y, double *T);
+    /* OPTIONAL (beside the primal pair: the table's mirror is checked to end with entry_bounds and the spectral pair): the k best
+     * entries per row of X = F F^T of one SDP cone, read-only on the state (include/lorads_hip.h: lorads_hip_primal_topk, the same
+     * arguments and return codes) */
+    int (*primal_topk)(void *ctx, int src, int blk, int nq, const int *row, int col_lo, int col_hi, int k, int smallest, int include_diag,
+                       const int64_t *skip_ptr, const int *skip_col, int *idx, double *val, int *found);
     /* OPTIONAL (before the spectral pair for the same reason): separation of the triangle inequalities of one SDP cone of a
      * +-1-structured context, read-only on the state (include/lorads_hip.h: lorads_hip_triangle_cuts, the same arguments and
      * return codes) */
@@ -418,6 +423,31 @@ int lrd_entries_group(const lrd_entries *q, int nblk, int64_t *perm, int64_t *st
 /* the values of all queries: grouped per block for the backend's calls, the file order restored.  1: a block index out of range, else
  * as lrd_session_primal_entries */
 int lrd_session_entries(lrd_session *s, lrd_entries *q);
+
+/* ---- the k best entries per row of the primal X (topk.c).  The backend's slot with the session's F, plus
+ * skip_constrained: for query row p every column q at which some constraint matrix of the cone stores an entry (p, q) or (q, p) is
+ * skipped as well (on a completion problem: the observed entries), combined with the caller's own list.  Returns 2 when the table lacks
+ * the slot or blk is the LP block, 3 on a sharded deal, else the backend's code (1: a bad argument, in its words). */
+int lrd_session_primal_topk(lrd_session *s, int blk, int nq, const int *row, int col_lo, int col_hi, int k, int smallest, int include_diag,
+                            const int64_t *skip_ptr, const int *skip_col, int skip_constrained, int *idx, double *val, int *found);
+/* A query file: one `blk row lo hi [skip ...]` per line (1-based as in .dat-s, the window lo..hi inclusive, then the columns to skip);
+ * blank lines and lines that start with `*`, `#` or `"` are skipped.  The output file: `lorads-topk 1`, `count N`, `k K`, `src uv|rr`,
+ * `order largest|smallest`, then per query in the query file's order `blk row found` and found lines `col value` (1-based, %.17g). */
+typedef struct {
+    int count, k, src;          /* src: filled by lrd_session_topk */
+    int smallest, include_diag, skip_constrained;
+    int *blk, *row, *lo, *hi;   /* [count] 0-based, the window [lo, hi) */
+    int64_t *skip_ptr;          /* [count + 1] */
+    int *skip_col;              /* 0-based */
+    int *found, *idx;           /* [count], [count * k] 0-based (filled by lrd_session_topk) */
+    double *val;                /* [count * k] */
+} lrd_topk;
+/* 0: read; 1: the file cannot be opened; 2: malformed (*bad_line, may be NULL, gets the 1-based line number) */
+int lrd_topk_read(const char *path, lrd_topk **out, int *bad_line);
+int lrd_topk_write(const char *path, const lrd_topk *q);
+void lrd_topk_free(lrd_topk *q);
+/* all queries of the struct: one call per (block, window), the file order restored */
+int lrd_session_topk(lrd_session *s, lrd_topk *q);
 
 /* ---- triangle inequalities of +-1-structured problems (cuts.c).  With rho_xy = X_xy / (t_x t_y) (t as the
  * rounding's) every triple p < q < s of a cone has four inequalities sign . (rho_pq, rho_ps, rho_qs) >= -1, class 0..3 with the signs

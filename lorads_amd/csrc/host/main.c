@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include <unistd.h>
 
 #include "lorads_host.h"
@@ -47,7 +48,19 @@ int main(int argc, char **argv) {
     int kcut_parts = 0, kcut_trials = 1024, kcut_ls = 100; /* rounding of a k-cut-structured problem into k parts (ours as well) */
     unsigned long long kcut_seed = 0;
     const char *kcut_file = NULL, *kcut_other = NULL; /* kcut_other: some --kcut* option other than --kcutParts was given */
+    const char *topk_in = NULL, *topk_out = NULL, *topk_other = NULL; /* the k best entries per row of the primal (ours as well);
+                                                                       * topk_other: some --topk* option other than --topkFile was given */
+    int topk_k = 0, topk_smallest = 0, topk_diag = 0, topk_constrained = 0;
+    lrd_topk *topk = NULL;
     for (int i = 2; i < argc; i += 2) {
+        if (!strcmp(argv[i], "--topkSmallest") || !strcmp(argv[i], "--topkDiag") || !strcmp(argv[i], "--topkSkipConstrained")) {
+            topk_other = argv[i]; /* (flags: no value follows) */
+            if (argv[i][7] == 'm') topk_smallest = 1;
+            else if (argv[i][6] == 'D') topk_diag = 1;
+            else topk_constrained = 1;
+            i -= 1;
+            continue;
+        }
         if (i + 1 >= argc) {
             fprintf(stderr, "option %s lacks a value\n", argv[i]);
             return 2;
@@ -60,6 +73,20 @@ int main(int argc, char **argv) {
         if (!strcmp(argv[i], "--entriesFile")) { entries_in = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--entriesOut")) { entries_out = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--cutsFile")) { cuts_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--topkFile")) { topk_in = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--topkOut")) { topk_other = argv[i]; topk_out = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--topkCount")) {
+            char *end = NULL;
+            const long k = strtol(argv[i + 1], &end, 10);
+            if (!end || end == argv[i + 1] || *end || k < 1 || k > 128) {
+                fprintf(stderr, "bad value %s of %s (1 .. 128)\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            topk_other = argv[i];
+            topk_k = (int)k;
+            continue;
+        }
         if (!strcmp(argv[i], "--cutsMax") || !strcmp(argv[i], "--cutsMinViolation")) {
             char *end = NULL;
             const int is_max = argv[i][7] == 'a';
@@ -182,12 +209,47 @@ int main(int argc, char **argv) {
         lrd_session_close(s);
         return 2;
     }
+    if (topk_other && !topk_in) {
+        fprintf(stderr, "%s needs --topkFile\n", topk_other);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (topk_in && topk_k == 0) {
+        fprintf(stderr, "--topkFile needs --topkCount\n");
+        lrd_session_close(s);
+        return 2;
+    }
+    if (topk_in) { /* as the entry queries: refused before the backend is created */
+        int bad = 0;
+        const int qrc = lrd_topk_read(topk_in, &topk, &bad);
+        if (qrc) {
+            if (qrc == 1) fprintf(stderr, "lorads: cannot read the top-k query file %s\n", topk_in);
+            else fprintf(stderr, "lorads: line %d of the top-k query file %s is malformed (blk row lo hi [skip ...], 1-based, lo <= hi)\n", bad, topk_in);
+            lrd_session_close(s);
+            return 2;
+        }
+        const lrd_problem *pr = lrd_session_problem(s);
+        for (int e = 0; e < topk->count; ++e) {
+            const int k = topk->blk[e];
+            int out = k >= pr->nblk || pr->blk[k].is_lp || topk->row[e] >= pr->blk[k].n || topk->hi[e] > pr->blk[k].n;
+            for (int64_t x = topk->skip_ptr[e]; !out && x < topk->skip_ptr[e + 1]; ++x) out = topk->skip_col[x] >= pr->blk[k].n;
+            if (out) {
+                fprintf(stderr, "lorads: query %d of %s (%d %d %d %d ...) is outside the problem or names the LP block\n", e + 1, topk_in, k + 1,
+                        topk->row[e] + 1, topk->lo[e] + 1, topk->hi[e]);
+                lrd_topk_free(topk);
+                lrd_session_close(s);
+                return 2;
+            }
+        }
+        topk->k = topk_k; topk->smallest = topk_smallest; topk->include_diag = topk_diag; topk->skip_constrained = topk_constrained;
+    }
     if (entries_in) { /* a bad query file is refused before the backend is created, let alone anything solved */
         int bad = 0;
         const int qrc = lrd_entries_read(entries_in, &queries, &bad);
         if (qrc) {
             if (qrc == 1) fprintf(stderr, "lorads: cannot read the query file %s\n", entries_in);
             else fprintf(stderr, "lorads: line %d of the query file %s is malformed (k i j [v], 1-based; every line with v or none)\n", bad, entries_in);
+            lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
         }
@@ -198,6 +260,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "lorads: query %lld of %s (%d %d %d) is outside the problem\n", (long long)e + 1, entries_in, k + 1,
                         queries->row[e] + 1, queries->col[e] + 1);
                 lrd_entries_free(queries);
+                lrd_topk_free(topk);
                 lrd_session_close(s);
                 return 2;
             }
@@ -221,6 +284,7 @@ int main(int argc, char **argv) {
         if (rrc) {
             fprintf(stderr, "lorads: %s needs a +-1-structured problem (see above); nothing was solved\n",
                     round_trials > 0 ? "--roundTrials" : "--cutsMax");
+            lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
         }
@@ -229,6 +293,7 @@ int main(int argc, char **argv) {
         lrd_kcut *none = NULL;
         if (lrd_session_kcut(s, kcut_parts, 0, kcut_seed, kcut_ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --kcutParts needs a k-cut-structured problem (see above); nothing was solved\n");
+            lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
         }
@@ -236,6 +301,7 @@ int main(int argc, char **argv) {
     const int rc = lrd_session_solve(s);
     if (rc != 0) {
         fprintf(stderr, "lorads: the solve failed (code %d): a backend call reported an error\n", rc);
+        lrd_topk_free(topk);
         lrd_session_close(s);
         return 3;
     }
@@ -289,6 +355,26 @@ int main(int argc, char **argv) {
                    queries->stats[2]);
         }
         lrd_entries_free(queries);
+    }
+    if (topk) {
+        char dflt[4096];
+        snprintf(dflt, sizeof dflt, "%s.out", topk_in);
+        const char *to = topk_out ? topk_out : dflt;
+        struct timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        const int trc = lrd_session_topk(s, topk);
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        if (trc || lrd_topk_write(to, topk)) {
+            fprintf(stderr, "lorads: the top-k search failed or cannot write %s\n", to);
+            lrd_topk_free(topk);
+            lrd_session_close(s);
+            return 4;
+        }
+        long long total = 0;
+        for (int e = 0; e < topk->count; ++e) total += topk->found[e];
+        printf("Top-k entries per row of the primal X (%s): %d queries, k %d, %lld found, %.6f s -> %s\n", topk_in, topk->count, topk->k,
+               total, (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec), to);
+        lrd_topk_free(topk);
     }
     if (cuts_max > 0) {
         lrd_cuts *x = NULL;

@@ -66,6 +66,8 @@ class BackendStruct(C.Structure):
                                    C.POINTER(C.c_uint8), _ip, _dp, _dp, _dp)),
         ("primal_entries", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, _ip, _ip, _dp, _dp, _dp)),
         ("primal_apply", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp)),
+        ("primal_topk", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int64), _ip, _ip, _dp, _ip)),
         ("triangle_cuts", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_int8), _dp, _ip, _ip)),
         ("entry_bounds", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
@@ -287,6 +289,32 @@ class Backend:
         if rc:
             return rc, None, None
         return 0, Y[:, :nc], (T[:, :nc] if want_t else None)
+
+    def has_primal_topk(self):
+        return bool(self._s.primal_topk)
+
+    def primal_topk(self, src, blk, rows, col_lo, col_hi, k, smallest=0, include_diag=0, skip_ptr=None, skip_col=None, nq=None,
+                    want_arrays=True):
+        """the table's slot as it is: per query row the k best columns of the window [col_lo, col_hi) of block blk's X = F F^T.
+        Returns (code, idx [nq, k], val [nq, k], found [nq]); code != 0 is the slot's refusal.  rows / skip_ptr / skip_col None, nq
+        and want_arrays=False pass a NULL / another count down as they are."""
+        r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int32)
+        n = int(nq) if nq is not None else (0 if r is None else len(r))
+        sp = None if skip_ptr is None else np.ascontiguousarray(skip_ptr, dtype=np.int64)
+        sc = None if skip_col is None else np.ascontiguousarray(skip_col, dtype=np.int32)
+        if sc is not None and len(sc) == 0:
+            sc = np.zeros(1, dtype=np.int32)   # (an empty list is still a list: not NULL)
+        kk = int(k) if 1 <= int(k) <= 128 else 1
+        idx = np.full((max(n, 1), kk), -2, dtype=np.int32)
+        val = np.full((max(n, 1), kk), np.nan)
+        found = np.full(max(n, 1), -2, dtype=np.int32)
+        ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None  # noqa: E731
+        out = (ptr(idx, _ip), ptr(val, _dp), ptr(found, _ip)) if want_arrays else (None, None, None)
+        rc = self._s.primal_topk(self._s.ctx, int(src), int(blk), n, ptr(r, _ip), int(col_lo), int(col_hi), int(k), int(smallest),
+                                 int(include_diag), ptr(sp, C.POINTER(C.c_int64)), ptr(sc, _ip), *out)
+        if rc:
+            return rc, None, None, None
+        return 0, idx[:max(n, 0)], val[:max(n, 0)], found[:max(n, 0)]
 
     def has_triangle_cuts(self):
         return bool(self._s.triangle_cuts)
@@ -1168,6 +1196,64 @@ class Session:
         if return_t:
             return Y, (T[:, 0] if vec else T)
         return Y
+
+    def primal_topk(self, blk, rows, k, cols=None, smallest=False, include_diag=False, skip=None, skip_constrained=False):
+        """Per query row p of `rows` the k best columns q of block blk's primal X = F F^T (0-based like primal_entries; F = (U + V) / 2
+        in phase 2, the phase-1 R otherwise), searched on the device without forming X: the largest X_pq first (smallest=True: the
+        smallest), ties by ascending q.  cols=(lo, hi): the window [lo, hi) of candidate columns (None: all).  The column p itself is
+        no candidate unless include_diag.  skip: columns to leave out, a list of integer arrays, one per query, or a (ptr, col) CSR
+        pair; skip_constrained: also every column at which a constraint matrix of the cone stores an entry in row p (on a completion
+        problem the observed entries).  1 <= k <= 128.  Returns (idx [nq, k] int32, val [nq, k], found [nq]); the slots past found[i]
+        hold idx -1 and val 0.0.  Read-only on the solver's state, deterministic."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("primal_topk: rows is one vector of query rows")
+        nq = len(r)
+        n = self.block_shape(blk)[0] if 0 <= int(blk) < self.nblk else 0
+        lo, hi = (0, n) if cols is None else (int(cols[0]), int(cols[1]))
+        sp = sc = None
+        if skip is not None:
+            if isinstance(skip, tuple) and len(skip) == 2:
+                sp = np.ascontiguousarray(skip[0], dtype=np.int64)
+                sc = np.ascontiguousarray(skip[1], dtype=np.int32)
+            else:
+                if len(skip) != nq:
+                    raise ValueError("primal_topk: skip holds one list per query, or is a (ptr, col) pair")
+                lists = [np.asarray(x, dtype=np.int32).reshape(-1) for x in skip]
+                sp = np.zeros(nq + 1, dtype=np.int64)
+                sp[1:] = np.cumsum([len(x) for x in lists])
+                sc = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.int32)
+            if len(sc) == 0:
+                sc = np.zeros(1, dtype=np.int32)
+        kk = int(k) if 1 <= int(k) <= 128 else 1
+        idx = np.full((max(nq, 1), kk), -1, dtype=np.int32)
+        val = np.zeros((max(nq, 1), kk))
+        found = np.zeros(max(nq, 1), dtype=np.int32)
+        self.lib.lrd_session_primal_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.POINTER(C.c_int64), _ip, C.c_int, _ip, _dp, _ip]
+        rc = self.lib.lrd_session_primal_topk(self.h, int(blk), nq, r.ctypes.data_as(_ip), lo, hi, int(k), int(bool(smallest)),
+                                              int(bool(include_diag)), sp.ctypes.data_as(C.POINTER(C.c_int64)) if sp is not None else None,
+                                              sc.ctypes.data_as(_ip) if sc is not None else None, int(bool(skip_constrained)),
+                                              idx.ctypes.data_as(_ip), val.ctypes.data_as(_dp), found.ctypes.data_as(_ip))
+        # (codes 1 and 2 are the slot's own refusals only where the session layer has let the call through: a solver state, the slot,
+        # no sharded deal -- otherwise the library's last message belongs to some earlier call)
+        self.lib.lrd_session_solver.restype = C.c_void_p
+        self.lib.lrd_session_solver.argtypes = [C.c_void_p]
+        reached = self.be is not None and self.be.name == "hip-gfx950" and self.be.has_primal_topk() \
+            and bool(self.lib.lrd_session_solver(self.h))
+        if rc in (1, 2) and reached:
+            lib, _ = self._hip()
+            lib.lorads_hip_last_error.restype = C.c_char_p
+            msg = (lib.lorads_hip_last_error() or b"").decode()
+            if msg.startswith("primal_topk: "):
+                raise ValueError(msg)
+        if rc == 2:
+            raise NotImplementedError("the attached backend (%s) cannot search the rows of the primal: only the HIP backend does"
+                                      % (self.be.name if self.be else "none"))
+        if rc == 3:
+            raise NotImplementedError("the top-k search of a sharded deal (world > 1) is not supported")
+        _check(rc, "primal_topk")
+        return idx[:nq], val[:nq], found[:nq]
 
     def primal_diag(self, blk):
         """the diagonal of block blk's primal X"""
