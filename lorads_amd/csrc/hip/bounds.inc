@@ -3,10 +3,11 @@
 // Per SDP cone: F as lorads_hip_certificate takes it for src, at the cone's own rank.  Every pair p < q has two inequalities,
 //   class 0:  X_pq >= lower,  v = lower - X_pq        class 1:  X_pq <= upper,  v = X_pq - upper
 // and v > min_violation is a violation; an infinite bound gives v = -inf: the class is off with no test of its own.  X_pq is one chain
-// of v_mfma_f64_16x16x4_f64 steps over the columns in fours with row p as the A operand and row q as the B operand (as cut_tile
-// forms F_x . F_y), then one subtraction: its bits depend on the two rows alone and every pass reproduces them.  All n (n - 1) of them
+// of v_mfma_f64_16x16x4_f64 steps (postsolve.inc: packed_dot) over the columns in fours with row p as the A operand and row q as the
+// B operand (as cut_tile forms F_x . F_y), then one subtraction: its bits depend on the two rows alone and every pass reproduces them.  All n (n - 1) of them
 // are enumerated and never stored:
-//   k_bnd_pack   F (the average of U and V formed once), zero-padded to whole tiles of BND_T rows and whole steps of 4 columns
+//   k_pack_factor (postsolve.inc)   F (the average of U and V formed once), zero-padded to whole tiles of BND_T rows and whole
+//                steps of 4 columns
 //   k_bnd_enum   workgroup (I, c) keeps rows of tile I of the packed F in LDS and walks the tiles J = I + BND_ITERS c ... (at most
 //                BND_ITERS of them): the 32 x 32 tile of X on the FP64 matrix cores, one 16 x 16 quarter per wavefront, every thread
 //                then tests the four entries it holds.  The three modes of select.inc.
@@ -29,72 +30,11 @@ static_assert((BND_MAXN / BND_T + BND_ITERS - 1) / BND_ITERS <= 65535, "grid.y")
 struct BndArgs {
     int n, nt, rl4, mode, shift, width, in_lds;
     double lower, upper, minv;
-    unsigned long long khi, klo;          // mode 1: the prefix (bits below shift + width ignored); mode 2: the threshold key
+    unsigned long long khi, klo;          // (these and mode, shift, width, minv, ctl, hist, ohi, olo, cap: select.inc's fields)
     const double *Fp;
-    unsigned long long *ctl;              // [0] pairs with v > minv (mode 0), [1] emitted keys (mode 2)
-    unsigned long long *hist;             // [CUT_BINS]
-    unsigned long long *ohi, *olo;        // emitted keys
+    unsigned long long *ctl, *hist, *ohi, *olo;
     unsigned long long cap;
 };
-
-__global__ __launch_bounds__(TPB) void k_bnd_pack(int n, int npad, int rl, int rl4, int r, const double *__restrict__ U,
-                                                  const double *__restrict__ V, int uv, double *__restrict__ Fp) {
-    const size_t len = (size_t)npad * rl4;
-    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
-        const size_t row = i / rl4, j = i % rl4;
-        Fp[i] = (row < (size_t)n && j < (size_t)rl) ? factor_ld(U, V, uv != 0, row * r + j) : 0.0;
-    }
-}
-
-// what one thread carries through k_bnd_enum
-struct BndAcc {
-    unsigned long long cnt = 0;
-    int cur_bin = -1;       // a run of equal bins is counted in a register and goes to LDS when the bin changes
-    unsigned cur_n = 0;
-};
-
-// one (pair, class) with its v: counted, binned or emitted when v > min_violation
-__device__ __forceinline__ void bnd_handle(const BndArgs &a, double v, unsigned long long index, unsigned *hist, BndAcc &acc) {
-    if (!(v > a.minv)) return;
-    const unsigned long long hi = (unsigned long long)__double_as_longlong(v), lo = ~index;
-    if (a.mode == 2) {
-        if (hi > a.khi || (hi == a.khi && lo >= a.klo)) {
-            const unsigned long long slot = atomicAdd(a.ctl + 1, 1ull);
-            if (slot < a.cap) { a.ohi[slot] = hi; a.olo[slot] = lo; }
-        }
-        return;
-    }
-    ++acc.cnt;
-    if (a.mode == 1 && !cut_same_prefix(hi, lo, a.khi, a.klo, a.shift + a.width)) return;
-    const int bin = (int)cut_digit(hi, lo, a.shift, a.width);
-    if (bin != acc.cur_bin) {
-        if (acc.cur_n) atomicAdd(&hist[acc.cur_bin], acc.cur_n);
-        acc.cur_bin = bin; acc.cur_n = 0;
-    }
-    ++acc.cur_n;
-}
-
-// N steps of the chain from column k0 on: the operands of all N are asked for before the first step waits for its own
-template <int N>
-__device__ __forceinline__ v4f64 bnd_steps(const double *__restrict__ A, const double *__restrict__ B, int k0, v4f64 d) {
-    double x[N], y[N];
-#pragma unroll
-    for (int u = 0; u < N; ++u) { x[u] = A[k0 + 4 * u]; y[u] = B[k0 + 4 * u]; }
-#pragma unroll
-    for (int u = 0; u < N; ++u) d = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u], y[u], d, 0, 0, 0);
-    return d;
-}
-// the whole chain over the rl4 columns, in the order of the columns (eight, four, two steps and one at a time: the same chain as a
-// loop of single steps, with more loads in flight)
-__device__ __forceinline__ v4f64 bnd_dot(const double *__restrict__ A, const double *__restrict__ B, int rl4) {
-    v4f64 d = (v4f64){0.0, 0.0, 0.0, 0.0};
-    int k0 = 0;
-    for (; k0 + 32 <= rl4; k0 += 32) d = bnd_steps<8>(A, B, k0, d);
-    if (k0 + 16 <= rl4) { d = bnd_steps<4>(A, B, k0, d); k0 += 16; }
-    if (k0 + 8 <= rl4) { d = bnd_steps<2>(A, B, k0, d); k0 += 8; }
-    if (k0 < rl4) d = bnd_steps<1>(A, B, k0, d);
-    return d;
-}
 
 // The enumeration.  Wavefront w forms the quarter (w >> 1, w & 1) of the tile X[I][J] as D = F_I F_J^T in steps of four columns (the
 // operand layout of postsolve.inc's tiles: lane (nn, kk) supplies row nn, column k0 + kk of both and holds D[kk + 4 g][nn]: row
@@ -107,9 +47,7 @@ __global__ __launch_bounds__(TPB) void k_bnd_enum(BndArgs a) {
     const int I = blockIdx.x, J0 = I + (int)blockIdx.y * BND_ITERS;
     if (J0 >= a.nt) return; // (the whole workgroup: no tile J is its own)
     const int J1 = min(a.nt, J0 + BND_ITERS), rl4 = a.rl4, ld = rl4 + 1;
-    if (a.mode != 2)
-        for (int b = threadIdx.x; b < CUT_BINS; b += TPB) hist[b] = 0;
-    if (threadIdx.x == 0) total = 0;
+    select_begin(a, hist, &total);
     if (a.in_lds)
         for (int i = threadIdx.x; i < BND_T * rl4; i += TPB) {
             const int row = i / rl4, k = i - row * rl4;
@@ -121,20 +59,21 @@ __global__ __launch_bounds__(TPB) void k_bnd_enum(BndArgs a) {
     const double *ga = a.Fp + (size_t)(I * BND_T + la0 + nn) * rl4 + kk;
     const double *sa = strip + (la0 + nn) * ld + kk;
     const unsigned long long n = (unsigned long long)a.n;
-    BndAcc acc;
+    SelAcc acc;
     for (int J = J0; J < J1; ++J) {
         const double *fb = a.Fp + (size_t)(J * BND_T + lb0 + nn) * rl4 + kk;
-        const v4f64 d = a.in_lds ? bnd_dot(sa, fb, rl4) : bnd_dot(ga, fb, rl4);
+        const v4f64 d = a.in_lds ? packed_dot(sa, fb, rl4) : packed_dot(ga, fb, rl4);
         const int q = J * BND_T + lb0 + nn;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int p = I * BND_T + la0 + kk + 4 * g;
             if (!(p < q && q < a.n)) continue;
             const unsigned long long index = ((unsigned long long)p * n + (unsigned long long)q) * 2ull;
-            bnd_handle(a, a.lower - d[g], index, hist, acc);
-            bnd_handle(a, d[g] - a.upper, index + 1, hist, acc);
+            select_item(a, a.lower - d[g], index, hist, acc);
+            select_item(a, d[g] - a.upper, index + 1, hist, acc);
         }
     }
+    // the selection's epilogue (select.inc): the same lines as k_cut_enum's
     if (a.mode == 2) return;
     if (acc.cur_n) atomicAdd(&hist[acc.cur_bin], acc.cur_n);
     if (a.mode == 0 && acc.cnt) atomicAdd(&total, acc.cnt);
@@ -159,16 +98,12 @@ extern "C" int lorads_hip_entry_bounds(lorads_hip_ctx *c, int32_t src, int32_t b
     spec_touch(c);
     if (postsolve_args(c, src, &blk, "entry_bounds", false)) return 1;
     if (c->blk[blk].is_lp) return fail_msg("entry_bounds: block " + std::to_string(blk) + " is the LP block");
-    if (max_cuts < 0 || max_cuts > (1 << 20)) return fail_msg("entry_bounds: max_cuts " + std::to_string(max_cuts) + " is outside [0, 2^20]");
-    if (!(min_violation >= 0.0) || !std::isfinite(min_violation))
-        return fail_msg("entry_bounds: min_violation must be finite and not negative");
+    if (select_check_range("entry_bounds", min_violation, max_cuts)) return 1;
     if (std::isnan(lower) || std::isnan(upper)) return fail_msg("entry_bounds: a bound is NaN");
     if (lower > upper) return fail_msg("entry_bounds: lower is above upper");
     if (lower == -INFINITY && upper == INFINITY) return fail_msg("entry_bounds: both classes are off (lower = -inf and upper = +inf)");
     if (lower == INFINITY || upper == -INFINITY) return fail_msg("entry_bounds: a bound is infinite on the wrong side");
-    if (!count) return fail_msg("entry_bounds: count must not be NULL");
-    if (max_cuts > 0 && (!p || !q || !cls || !viol || !kept))
-        return fail_msg("entry_bounds: p, q, cls, viol and kept must not be NULL when max_cuts > 0");
+    if (select_check_outputs("entry_bounds", "p, q, cls, viol and kept", max_cuts, count, p && q && cls && viol && kept)) return 1;
     if (c->blk[blk].n > BND_MAXN) return fail_msg("entry_bounds: cone dimension above 2^24");
     if (postsolve_sharded(c, "entry_bounds", "are not supported")) return 3;
     *count = 0;
@@ -179,24 +114,15 @@ extern "C" int lorads_hip_entry_bounds(lorads_hip_ctx *c, int32_t src, int32_t b
     if (n < 2) return 0;
     BoundScratch &X = c->bounds;
     const int nt = nblocks_for((size_t)n, BND_T), npad = nt * BND_T, rl4 = (B.rl + 3) & ~3;
-    size_t P = 1;
-    while (P < (size_t)max_cuts + CUT_SLACK) P <<= 1;
-    if (X.Fp.grow(X.mem, (size_t)npad * rl4)) return 1;
-    if (max_cuts > 0 && (X.khi.grow(X.mem, P) || X.klo.grow(X.mem, P))) return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 2 + (size_t)CUT_BINS)) return 1;
-    const FactorView F = factor_view(c, src, blk);
-    hipLaunchKernelGGL(k_bnd_pack, dim3(std::min(grid1d((size_t)npad * rl4), 1024)), dim3(TPB), 0, c->stream, n, npad, B.rl, rl4, B.r,
-                       F.U, F.V, F.uv, X.Fp.p);
     BndArgs a{};
-    a.n = n; a.nt = nt; a.rl4 = rl4; a.mode = 0; a.shift = 128 - CUT_DIGIT; a.width = CUT_DIGIT;
+    if (X.Fp.grow(X.mem, (size_t)npad * rl4) || select_reserve(X.sel, X.mem, max_cuts, min_violation, a)) return 1;
+    if (pack_factor(c, src, blk, npad, nullptr, X.Fp, nullptr)) return 1;
+    a.n = n; a.nt = nt; a.rl4 = rl4;
     a.in_lds = rl4 <= BND_LDS_COLS;
-    a.lower = lower; a.upper = upper; a.minv = min_violation;
+    a.lower = lower; a.upper = upper;
     a.Fp = X.Fp;
-    a.ctl = X.ctl; a.hist = X.ctl + 2;
-    a.ohi = X.khi; a.olo = X.klo;
-    a.cap = (unsigned long long)max_cuts + CUT_SLACK;
     std::vector<unsigned long long> khi, klo;
-    if (select_largest(c, "entry_bounds", X.ctl, X.khi, X.klo, max_cuts, a, [&] { return bnd_launch(c, a); }, count, passes, khi, klo))
+    if (select_largest(c, "entry_bounds", max_cuts, a, [&] { return bnd_launch(c, a); }, count, passes, khi, klo))
         return 1;
     for (size_t e = 0; e < khi.size(); ++e) {
         unsigned long long idx = select_unpack(khi[e], klo[e], viol[e]);

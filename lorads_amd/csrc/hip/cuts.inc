@@ -5,7 +5,8 @@
 // rounding.inc (rnd_check); for p < q < s and a = rho_pq, b = rho_ps, c = rho_qs the four violations are
 //   v0 = (-1 - a) - (b + c)   v1 = (-1 - a) + (b + c)   v2 = (-1 + a) - (b - c)   v3 = (-1 + a) + (b - c)
 // in exactly this order of operations.  All 4 C(n, 3) of them are enumerated and never stored:
-//   k_cut_pack     F (the average of U and V formed once) and t, zero-padded to whole tiles of CUT_T rows and whole steps of 4 columns
+//   k_pack_factor  (postsolve.inc) F (the average of U and V formed once) and t, zero-padded to whole tiles of CUT_T rows and whole
+//                  steps of 4 columns
 //   k_cut_enum     one workgroup per pair J <= K of row tiles keeps the tile rho[J][K] in LDS and walks the tiles I <= J: the tiles
 //                  rho[I][J] and rho[I][K] on the FP64 matrix cores, then the workgroup's CUT_T^3 triples: a gate on the largest
 //                  of the four v per triple, the triples that pass queued and handled densely.  Three modes:
@@ -32,24 +33,11 @@ static_assert(TPB == 256, "k_cut_enum maps 256 threads onto a tile");
 struct CutArgs {
     int n, rl4, mode, shift, width;
     double minv;
-    unsigned long long khi, klo;          // mode 1: the prefix (bits below shift + width ignored); mode 2: the threshold key
+    unsigned long long khi, klo;          // (these and mode, shift, width, minv, ctl, hist, ohi, olo, cap: select.inc's fields)
     const double *Fp, *tp;
-    unsigned long long *ctl;              // [0] pairs with v > minv (mode 0), [1] emitted keys (mode 2)
-    unsigned long long *hist;             // [CUT_BINS]
-    unsigned long long *ohi, *olo;        // emitted keys
+    unsigned long long *ctl, *hist, *ohi, *olo;
     unsigned long long cap;
 };
-
-__global__ __launch_bounds__(TPB) void k_cut_pack(int n, int npad, int rl, int rl4, int r, const double *__restrict__ U,
-                                                  const double *__restrict__ V, int uv, const double *__restrict__ t,
-                                                  double *__restrict__ Fp, double *__restrict__ tp) {
-    const size_t len = (size_t)npad * rl4;
-    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
-        const size_t row = i / rl4, j = i % rl4;
-        Fp[i] = (row < (size_t)n && j < (size_t)rl) ? factor_ld(U, V, uv != 0, row * r + j) : 0.0;
-        if (j == 0) tp[row] = row < (size_t)n ? t[row] : 1.0;
-    }
-}
 
 // out <- the tile rho[A][B] (transposed: out[b][a]): wavefront w forms the 16 x 16 quarter (w >> 1, w & 1) as D = F_A F_B^T in steps of
 // four columns (the operand layout of postsolve.inc's tiles: lane (nn, kk) supplies row nn, column k0 + kk of both and holds
@@ -71,18 +59,11 @@ __device__ __forceinline__ void cut_tile(const CutArgs &a, int A, int B, double 
     }
 }
 
-// what one thread carries through k_cut_enum's passes
-struct CutAcc {
-    unsigned long long cnt = 0;
-    int cur_bin = -1;       // a run of equal bins is counted in a register and goes to LDS when the bin changes
-    unsigned cur_n = 0;
-};
-
 // One triple with a violated class, by its code (i << 10) | (j << 5) | sl inside the tiles at hand: the four v again from the same
 // three rho in the same order of operations (the same bits as the gate saw), every class with v > min_violation counted, binned or
 // emitted.
 __device__ __forceinline__ void cut_handle(const CutArgs &a, unsigned code, int I, int J, int K, const double (*pq)[CUT_LD],
-                                           const double (*ps)[CUT_LD], const double (*qs)[CUT_LD], unsigned *hist, CutAcc &acc) {
+                                           const double (*ps)[CUT_LD], const double (*qs)[CUT_LD], unsigned *hist, SelAcc &acc) {
     const int i = code >> 10, j = (code >> 5) & 31, sl = code & 31;
     const double ra = pq[i][j], rb = ps[i][sl], rc = qs[sl][j];
     const double am = -1.0 - ra, ap = -1.0 + ra, sm = rb + rc, df = rb - rc;
@@ -91,7 +72,7 @@ __device__ __forceinline__ void cut_handle(const CutArgs &a, unsigned code, int 
     const unsigned long long base = (((unsigned long long)(I * CUT_T + i) * n + (unsigned long long)(J * CUT_T + j)) * n +
                                      (unsigned long long)(K * CUT_T + sl)) * 4ull;
 #pragma unroll
-    for (int cl = 0; cl < 4; ++cl) {
+    for (int cl = 0; cl < 4; ++cl) { // (must match select.inc's select_item)
         if (!(v[cl] > a.minv)) continue;
         const unsigned long long hi = (unsigned long long)__double_as_longlong(v[cl]), lo = ~(base + cl);
         if (a.mode == 2) {
@@ -131,15 +112,13 @@ __global__ __launch_bounds__(TPB) void k_cut_enum(CutArgs a) {
     while ((Kl + 1) * (Kl + 2) / 2 <= pi) ++Kl;
     const int K = (int)Kl, J = (int)(pi - Kl * (Kl + 1) / 2);
     if ((int)blockIdx.y > J) return; // (the whole workgroup: no tile I is its own)
-    if (a.mode != 2)
-        for (int b = threadIdx.x; b < CUT_BINS; b += TPB) hist[b] = 0;
-    if (threadIdx.x == 0) total = 0;
+    select_begin(a, hist, &total);
     cut_tile(a, J, K, qs, true);
     const int n = a.n, j = threadIdx.x & 31, ig = threadIdx.x >> 5;
     const int q = J * CUT_T + j;
     const int s_lo = J == K ? j + 1 : 0, s_hi = min(CUT_T, n - K * CUT_T);
     const double minv = a.minv;
-    CutAcc acc;
+    SelAcc acc;
     for (int I = blockIdx.y; I <= J; I += gridDim.y) {
         __syncthreads();
         if (threadIdx.x == 0) qn = 0;
@@ -184,6 +163,7 @@ __global__ __launch_bounds__(TPB) void k_cut_enum(CutArgs a) {
         const unsigned nq = min(qn, (unsigned)CUT_QUEUE);
         for (unsigned e = threadIdx.x; e < nq; e += TPB) cut_handle(a, queue[e], I, J, K, pq, ps, qs, hist, acc);
     }
+    // the selection's epilogue (select.inc): the same lines as k_bnd_enum's
     if (a.mode == 2) return;
     if (acc.cur_n) atomicAdd(&hist[acc.cur_bin], acc.cur_n);
     if (a.mode == 0 && acc.cnt) atomicAdd(&total, acc.cnt);
@@ -210,12 +190,8 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     spec_touch(c);
     if (postsolve_args(c, src, &blk, "triangle_cuts", false)) return 1;
     if (c->blk[blk].is_lp) return fail_msg("triangle_cuts: block " + std::to_string(blk) + " is the LP block");
-    if (max_cuts < 0 || max_cuts > (1 << 20)) return fail_msg("triangle_cuts: max_cuts " + std::to_string(max_cuts) + " is outside [0, 2^20]");
-    if (!(min_violation >= 0.0) || !std::isfinite(min_violation))
-        return fail_msg("triangle_cuts: min_violation must be finite and not negative");
-    if (!count) return fail_msg("triangle_cuts: count must not be NULL");
-    if (max_cuts > 0 && (!p || !q || !s || !cls || !viol || !kept))
-        return fail_msg("triangle_cuts: p, q, s, cls, viol and kept must not be NULL when max_cuts > 0");
+    if (select_check_range("triangle_cuts", min_violation, max_cuts)) return 1;
+    if (select_check_outputs("triangle_cuts", "p, q, s, cls, viol and kept", max_cuts, count, p && q && s && cls && viol && kept)) return 1;
     if (postsolve_sharded(c, "triangle_cuts", "are not supported")) return 3;
     if (rnd_check(c)) return 1;
     if (!c->rnd.qualifies) {
@@ -231,24 +207,14 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     if (n > CUT_MAXN) return fail_msg("triangle_cuts: cone dimension above 2^20");
     CutScratch &X = c->cuts;
     const int nt = nblocks_for((size_t)n, CUT_T), npad = nt * CUT_T, rl4 = (B.rl + 3) & ~3;
-    size_t P = 1;
-    while (P < (size_t)max_cuts + CUT_SLACK) P <<= 1;
-    if (X.Fp.grow(X.mem, (size_t)npad * rl4) || X.tp.grow(X.mem, (size_t)npad)) return 1;
-    if (max_cuts > 0 && (X.khi.grow(X.mem, P) || X.klo.grow(X.mem, P))) return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 2 + (size_t)CUT_BINS)) return 1;
-    const FactorView F = factor_view(c, src, blk);
-    hipLaunchKernelGGL(k_cut_pack, dim3(std::min(grid1d((size_t)npad * rl4), 1024)), dim3(TPB), 0, c->stream, n, npad, B.rl, rl4, B.r,
-                       F.U, F.V, F.uv,
-                       (const double *)(c->rnd.t + c->rnd.t_off[blk]), X.Fp, X.tp);
     CutArgs a{};
-    a.n = n; a.rl4 = rl4; a.mode = 0; a.shift = 128 - CUT_DIGIT; a.width = CUT_DIGIT;
-    a.minv = min_violation;
+    if (X.Fp.grow(X.mem, (size_t)npad * rl4) || X.tp.grow(X.mem, (size_t)npad)) return 1;
+    if (select_reserve(X.sel, X.mem, max_cuts, min_violation, a)) return 1;
+    if (pack_factor(c, src, blk, npad, c->rnd.t + c->rnd.t_off[blk], X.Fp, X.tp)) return 1;
+    a.n = n; a.rl4 = rl4;
     a.Fp = X.Fp; a.tp = X.tp;
-    a.ctl = X.ctl; a.hist = X.ctl + 2;
-    a.ohi = X.khi; a.olo = X.klo;
-    a.cap = (unsigned long long)max_cuts + CUT_SLACK;
     std::vector<unsigned long long> khi, klo;
-    if (select_largest(c, "triangle_cuts", X.ctl, X.khi, X.klo, max_cuts, a, [&] { return cut_launch(c, a, nt); }, count, passes, khi, klo))
+    if (select_largest(c, "triangle_cuts", max_cuts, a, [&] { return cut_launch(c, a, nt); }, count, passes, khi, klo))
         return 1;
     const size_t want = khi.size();
     if (want == 0) return 0;

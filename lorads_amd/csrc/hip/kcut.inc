@@ -5,13 +5,14 @@
 // per diagonal position of every cone (t_p = sqrt(b_i / a_i), as rounding.inc), and every constraint with an LP entry is a bound row
 // 2 a X_pq + c x_j = b: one off-diagonal SDP entry and one LP column that occurs nowhere else and has no objective.  For labels l_p
 // in {0..k-1} the point X(l)_pq = t_p t_q (l_p = l_q), -t_p t_q / (k - 1) (otherwise) is PSD and meets every diagonal constraint.
-// Per cone, trial and part a Gaussian g_a (rounding.inc's generator with the part in bits 26..31 of the counter: part 0 is the +-1
+// Per cone, trial and part a Gaussian g_a (rounding.inc's k_rnd_gauss, the part in bits 26..31 of the counter: part 0 is the +-1
 // rounding's hyperplane); l_p = the lowest a that attains max_a R_p . g_a; f = sum_k <C_k, X(l_k)>; then a deterministic 1-move local
 // search by colour classes of the cone's stored off-diagonal graph (rnd_colour).
 //
 // Labels: one byte per (row, trial) in blocks of 64 trials, lab[(w * n + p) * 64 + lane]: a wavefront of the field pass (lane = trial)
 // reads a neighbour's 64 labels as one 64-byte segment.  Everything is read-only on the solver's state, as in rounding.inc: R is formed
 // on the fly, the scratch is the feature's own (KCutScratch), launches go straight to the stream, every sum has one fixed order.
+// The driver around the field kernel is rounding.inc's (round_reserve, round_gauss, round_drive).
 
 namespace {
 
@@ -19,46 +20,16 @@ constexpr int KCUT_MAXPARTS = 64;
 constexpr int KCUT_MAXPROD = 1 << 20;  // trials x parts
 constexpr int KCUT_CH = 16;            // parts whose sums h_a a walk of the row list holds at once (LDS, one column per thread)
 
-// G of cone `cone` (parts x rk x K, G[(a * rk + j) * K + t]): k_rnd_hyper's value at the counter (cone << 32) | (a << 26) | (t << 10) | j
-__global__ __launch_bounds__(TPB) void k_kcut_hyper(int rk, int K, int parts, int cone, uint64_t seed, double *__restrict__ G) {
-    const size_t per = (size_t)rk * K, len = per * parts;
-    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
-        const uint64_t a = i / per, rem = i % per, j = rem / K, t = rem % K;
-        const uint64_t ctr = ((uint64_t)cone << 32) | (a << 26) | (t << 10) | j;
-        const uint64_t x = rnd_sm(seed ^ rnd_sm(2 * ctr)), y = rnd_sm(seed ^ rnd_sm(2 * ctr + 1));
-        const double u1 = (double)((x >> 11) + 1) * 0x1p-53, u2 = (double)(y >> 11) * 0x1p-53;
-        G[i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-    }
-}
-
-// N steps of a score chain from column k0 on: mfma_fm_tile's steps -- the same operands (A's element times zero and a clamped load
-// past rl) in the same order, so the same bits -- with the operands of all N asked for before the first step waits for its own
-template <int N>
-__device__ __forceinline__ v4f64 kcut_steps(const double *__restrict__ U, const double *__restrict__ V, bool uv, size_t ao,
-                                            const double *__restrict__ Ga, size_t K, int rl, int k0, int kk, v4f64 d) {
-    double x[N], y[N];
-#pragma unroll
-    for (int u = 0; u < N; ++u) {
-        const int k = k0 + 4 * u + kk, kc = k < rl ? k : 0;
-        x[u] = factor_ld(U, V, uv, ao + kc) * (k < rl ? 1.0 : 0.0);
-        y[u] = Ga[(size_t)kc * K];
-    }
-#pragma unroll
-    for (int u = 0; u < N; ++u) d = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u], y[u], d, 0, 0, 0);
-    return d;
-}
-// the whole chain of one part over the rl columns in fours, ascending (eight, four, two steps and one at a time: mfma_fm_tile's chain
-// with more loads in flight, as bounds.inc's bnd_dot)
+// the whole score chain of one part over the rl columns in fours, ascending: mfma_fm_tile's steps -- the same operands (A's element
+// times zero and a clamped load past rl) in the same order, so the same bits -- as postsolve.inc's mfma_chain issues them, with the
+// operands of several steps in flight
 __device__ __forceinline__ v4f64 kcut_chain(const double *__restrict__ U, const double *__restrict__ V, bool uv, size_t ao,
                                             const double *__restrict__ Ga, size_t K, int rl, int kk) {
-    v4f64 d = (v4f64){0.0, 0.0, 0.0, 0.0};
-    const int rl4 = (rl + 3) & ~3;
-    int k0 = 0;
-    for (; k0 + 32 <= rl4; k0 += 32) d = kcut_steps<8>(U, V, uv, ao, Ga, K, rl, k0, kk, d);
-    if (k0 + 16 <= rl4) { d = kcut_steps<4>(U, V, uv, ao, Ga, K, rl, k0, kk, d); k0 += 16; }
-    if (k0 + 8 <= rl4) { d = kcut_steps<2>(U, V, uv, ao, Ga, K, rl, k0, kk, d); k0 += 8; }
-    if (k0 < rl4) d = kcut_steps<1>(U, V, uv, ao, Ga, K, rl, k0, kk, d);
-    return d;
+    return mfma_chain((rl + 3) & ~3, [&](int k0, double &x, double &y) {
+        const int k = k0 + kk, kc = k < rl ? k : 0;
+        x = factor_ld(U, V, uv, ao + kc) * (k < rl ? 1.0 : 0.0);
+        y = Ga[(size_t)kc * K];
+    });
 }
 
 // Labels of 16 rows x 16 trials per wavefront on the FP64 matrix cores.  For a = 0 .. parts - 1 one chain of mfma_fm_tile's steps
@@ -208,27 +179,14 @@ int kcut_check(lorads_hip_ctx *c) {
     if (c->m) HC(hipMemcpyAsync(b.data(), c->b, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
     for (int k = 0; k < c->nb; ++k) {
         const Block &B = c->blk[k];
-        std::vector<int> ri(B.nrow), ap(B.nrow + 1), ae(B.na), er(B.pa.ne), ec(B.pa.ne);
-        std::vector<double> av(B.na);
-        if (B.nrow) {
-            HC(hipMemcpyAsync(ri.data(), B.row_idx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(ap.data(), B.a_ptr, sizeof(int) * ap.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (B.na) {
-            HC(hipMemcpyAsync(ae.data(), B.a_e, sizeof(int) * ae.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(av.data(), B.a_val, sizeof(double) * av.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (B.pa.ne) {
-            HC(hipMemcpyAsync(er.data(), B.pa.erow, sizeof(int) * er.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(ec.data(), B.pa.ecol, sizeof(int) * ec.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (B.is_lp) {
+        if (B.is_lp) { // (read_constraint_image below synchronises for this copy too)
             cobj.resize((size_t)B.n);
             if (B.n) HC(hipMemcpyAsync(cobj.data(), B.lp_cobj, sizeof(double) * cobj.size(), hipMemcpyDeviceToHost, c->stream));
         }
-        HC(hipStreamSynchronize(c->stream));
+        ConImage m;
+        if (read_constraint_image(c, k, m)) return 1;
         for (int i = 0; i < B.nrow; ++i)
-            for (int s = ap[i]; s < ap[i + 1]; ++s) con[(size_t)ri[i]].push_back({k, er[ae[s]], ec[ae[s]], av[s]});
+            for (int s = m.ap[i]; s < m.ap[i + 1]; ++s) con[(size_t)m.ri[i]].push_back({k, m.er[m.ae[s]], m.ec[m.ae[s]], m.av[s]});
     }
     const int nl = c->blk[lpk].n;
     std::vector<int> col_use((size_t)nl, 0);
@@ -288,44 +246,6 @@ int kcut_check(lorads_hip_ctx *c) {
     return 0;
 }
 
-// buffers for K trials of `parts` parts (grown on demand, freed with the context)
-int kcut_reserve(lorads_hip_ctx *c, int K, int parts) {
-    KCutScratch &X = c->kcut;
-    const size_t W = (size_t)(K + 63) / 64;
-    size_t g = 0;
-    for (auto &B : c->blk)
-        if (!B.is_lp) g += (size_t)B.rl * K * parts;
-    const size_t bytes = (size_t)c->rnd.t_off[c->nb] * W * 64;
-    if (X.G.grow(X.mem, g) || X.lab.grow(X.mem, bytes) || X.part.grow(X.mem, (size_t)K * RND_STRIPS)) return 1;
-    if (X.f.grow(X.mem, (size_t)K) || X.f0.grow(X.mem, (size_t)K)) return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
-    return 0;
-}
-
-// one field pass of cone k over nrows rows (rows == null: all of them, evaluation)
-void kcut_field(lorads_hip_ctx *c, int k, int K, int parts, const int *rows, int nrows) {
-    const Block &B = c->blk[k];
-    KCutScratch &X = c->kcut;
-    const int W = (K + 63) / 64;
-    const int strips = rows ? std::max(1, std::min(RND_STRIPS, nblocks_for((size_t)nrows, TPB / 64))) : RND_STRIPS;
-    hipLaunchKernelGGL(k_kcut_field, dim3(strips, W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, parts, 1.0 / (parts - 1),
-                       2.0 * parts / (parts - 1), (const int *)B.pu.adj_ptr, (const int *)B.pu.adj_col, (const int *)B.pu.adj_e,
-                       (const double *)B.pu.cbase, (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad,
-                       (const double *)(X.t + c->rnd.t_off[k]), X.lab + (size_t)c->rnd.t_off[k] * W * 64, X.part, X.ctl);
-}
-
-// f (K values) of the current labels: every cone's field pass, its strips added per trial in cone order
-void kcut_eval(lorads_hip_ctx *c, int K, int parts, double *f) {
-    bool first = true;
-    for (int k = 0; k < c->nb; ++k) {
-        if (c->blk[k].is_lp) continue;
-        kcut_field(c, k, K, parts, nullptr, c->blk[k].n);
-        hipLaunchKernelGGL(k_rnd_sum, dim3(nblocks_for((size_t)K, TPB)), dim3(TPB), 0, c->stream, K, (int)RND_STRIPS,
-                           (const double *)c->kcut.part, f, (int)first);
-        first = false;
-    }
-}
-
 } // namespace
 
 extern "C" int lorads_hip_round_kcut(lorads_hip_ctx *c, int32_t src, int32_t parts, int32_t trials, uint64_t seed, int32_t max_rounds,
@@ -360,56 +280,33 @@ extern "C" int lorads_hip_round_kcut(lorads_hip_ctx *c, int32_t src, int32_t par
         for (size_t j = 0; j < X.lp_u.size(); ++j) lp_upper[j] = X.lp_u[j];
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64;
-    if (kcut_reserve(c, K, parts) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    TrialScratch &T = X.trial;
+    if (round_reserve(c, T, X.mem, K, parts) || X.lab.grow(X.mem, (size_t)off[c->nb] * W * 64) || (max_rounds > 0 && rnd_colour(c))) return 1;
     // vectors and labels
     size_t goff = 0;
     for (int k = 0; k < c->nb; ++k) {
         const Block &B = c->blk[k];
         if (B.is_lp) continue;
-        double *G = X.G + goff;
-        const size_t glen = (size_t)B.rl * K * parts;
-        if (glen) hipLaunchKernelGGL(k_kcut_hyper, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, B.rl, K, parts, k, seed, G);
+        double *G = T.G + goff;
+        round_gauss(c, k, K, parts, seed, G);
         const FactorView F = factor_view(c, src, k);
         const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * W * 4;
         if (B.n) hipLaunchKernelGGL(k_kcut_label, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, parts,
                                     F.U, F.V, F.uv, (const double *)G, X.lab + (size_t)off[k] * W * 64);
-        goff += glen;
+        goff += (size_t)B.rl * K * parts;
     }
-    if (vectors && goff) HC(hipMemcpyAsync(vectors, X.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
-    kcut_eval(c, K, parts, X.f0);
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0, X.ctl + 1);
-    // local search: one host synchronisation per round (the flag decides whether another round runs)
-    int nr = 0;
-    for (int round = 0; round < max_rounds; ++round) {
-        HC(hipMemsetAsync(X.ctl, 0, sizeof(int), c->stream));
-        for (int k = 0; k < c->nb; ++k) {
-            if (c->blk[k].is_lp) continue;
-            const std::vector<int> &cp = c->rnd.cls_ptr[k];
-            for (size_t cl = 0; cl + 1 < cp.size(); ++cl)
-                kcut_field(c, k, K, parts, c->rnd.cls_rows + off[k] + cp[cl], cp[cl + 1] - cp[cl]);
-        }
-        int flag = 0;
-        HC(hipMemcpyAsync(&flag, X.ctl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HC(hipStreamSynchronize(c->stream));
-        nr = round + 1;
-        if (!flag) break;
-    }
-    double *f = X.f0;
-    if (nr > 0) {
-        kcut_eval(c, K, parts, X.f);
-        f = X.f;
-    }
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, X.ctl + 2);
-    int bb[2] = {0, 0};
-    HC(hipMemcpyAsync(bb, X.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    if (obj0) HC(hipMemcpyAsync(obj0, X.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    if (best) *best = bb[1];
-    if (best0) *best0 = bb[0];
-    if (rounds) *rounds = nr;
+    if (vectors && goff) HC(hipMemcpyAsync(vectors, T.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    auto field = [&](int k, const int *rows, int nrows) {
+        const Block &B = c->blk[k];
+        hipLaunchKernelGGL(k_kcut_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, parts,
+                           1.0 / (parts - 1), 2.0 * parts / (parts - 1), (const int *)B.pu.adj_ptr, (const int *)B.pu.adj_col,
+                           (const int *)B.pu.adj_e, (const double *)B.pu.cbase, (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad,
+                           (const double *)(X.t + off[k]), X.lab + (size_t)off[k] * W * 64, T.part.p, T.ctl);
+    };
+    int bt = 0;
+    if (round_drive(c, K, max_rounds, T, field, RoundOut{obj, obj0, best, best0, rounds}, &bt)) return 1;
     if (label) { // the best trial's labels, SDP cone after SDP cone: its 64-trial block of every row, then the trial's byte
-        const int w = bb[1] / 64, l = bb[1] % 64;
+        const int w = bt / 64, l = bt % 64;
         std::vector<unsigned char> blkb;
         size_t at = 0;
         for (int k = 0; k < c->nb; ++k) {

@@ -522,6 +522,13 @@ struct CertScratch {
     void release() { mem.release(); *this = CertScratch{}; }
 };
 
+// what the two roundings' shared driver (rounding.inc: round_drive) works on, for K trials: the Gaussian vectors, the field partials
+// (8 x 256 K), f after / before the search (16 K), and ctl: [0] the search's change flag, [1] best before, [2] best after the search
+struct TrialScratch {
+    DevBuf<double> G, part, f, f0;
+    int *ctl = nullptr;
+};
+
 // scratch of the rounding (rounding.inc): allocated on its first call, never read by the solve
 struct RoundScratch {
     bool checked = false, qualifies = false, coloured = false;
@@ -530,24 +537,22 @@ struct RoundScratch {
     double *t = nullptr;                      // t_p = sqrt(b_i / a_i), cone k at t_off[k]
     std::vector<std::vector<int>> cls_ptr;    // per cone: colour class -> its range of the class-sorted row list
     int *cls_rows = nullptr;                  // class-sorted rows, cone k at t_off[k]
-    DevBuf<double> G, part, f, f0;            // hyperplanes, field partials, f after / before the search
+    TrialScratch trial;                       // (G: the hyperplanes, rank x K per cone)
     DevBuf<unsigned long long> sgn;           // sign words, cone k at t_off[k] * W
-    int *ctl = nullptr;                       // [0] flip flag, [1] best before, [2] best after the search
     DevPool mem;
     void release() { mem.release(); *this = RoundScratch{}; }
 };
 
 // scratch of the rounding into k parts (kcut.inc): allocated on its first call, never read by the solve.  Labels n K bytes rounded up to
-// blocks of 64 trials, G 8 k K sum(rank), partials 8 x 256 K, f 16 K.  The colouring and, without an LP block, t are RoundScratch's.
+// blocks of 64 trials, G 8 k K sum(rank).  The colouring and, without an LP block, t are RoundScratch's.
 struct KCutScratch {
     bool checked = false, qualifies = false;
     std::string why;                          // the first reason the context does not qualify
     const double *t = nullptr;                // t_p, cone k at RoundScratch::t_off[k]: RoundScratch's, or t_own on a context with an LP block
     double *t_own = nullptr;
     std::vector<double> lp_u;                 // [LP columns] u_j = (|b| + 2 |a| t_p t_q) / |c| of the column's bound row
-    DevBuf<double> G, part, f, f0;            // vectors, field partials, f after / before the search
+    TrialScratch trial;                       // (G: the parts' vectors, k x rank x K per cone)
     DevBuf<unsigned char> lab;                // labels, cone k at t_off[k] * W * 64
-    int *ctl = nullptr;                       // [0] move flag, [1] best before, [2] best after the search
     DevPool mem;
     void release() { mem.release(); *this = KCutScratch{}; }
 };
@@ -576,22 +581,26 @@ struct PrimalScratch {
     void release() { mem.release(); *this = PrimalScratch{}; }
 };
 
-// scratch of the triangle-inequality separation (cuts.inc): allocated on first use, grown on demand, never read by the solve.
-// O(n r) for the packed factor, max_cuts + a fixed slack (rounded up to a power of two) keys, one histogram.
-struct CutScratch {
-    DevBuf<double> Fp, tp;                                 // F zero-padded to whole tiles and steps of 4 columns, t padded with ones
+// the key buffer of a selection (select.inc): max_cuts + a fixed slack (rounded up to a power of two) keys and one histogram
+struct SelectScratch {
     DevBuf<unsigned long long> khi, klo;                   // the emitted keys: bit pattern of v, complement of the packed index
     unsigned long long *ctl = nullptr;                     // [0] violated pairs, [1] emitted keys, [2..] the histogram of a digit
+};
+
+// scratch of the triangle-inequality separation (cuts.inc): allocated on first use, grown on demand, never read by the solve.
+// O(n r) for the packed factor, and the selection's keys.
+struct CutScratch {
+    DevBuf<double> Fp, tp;                                 // F zero-padded to whole tiles and steps of 4 columns, t padded with ones
+    SelectScratch sel;
     DevPool mem;
     void release() { mem.release(); *this = CutScratch{}; }
 };
 
 // scratch of the separation of entry bounds (bounds.inc): allocated on first use, grown on demand, never read by the solve.
-// O(n r) for the packed factor, max_cuts + a fixed slack (rounded up to a power of two) keys, one histogram.
+// O(n r) for the packed factor, and the selection's keys.
 struct BoundScratch {
     DevBuf<double> Fp;                                     // F zero-padded to whole tiles and steps of 4 columns
-    DevBuf<unsigned long long> khi, klo;                   // the emitted keys: bit pattern of v, complement of the packed index
-    unsigned long long *ctl = nullptr;                     // [0] violated pairs, [1] emitted keys, [2..] the histogram of a digit
+    SelectScratch sel;
     DevPool mem;
     void release() { mem.release(); *this = BoundScratch{}; }
 };
@@ -601,7 +610,7 @@ struct BoundScratch {
 // packed query rows, the results (k <= 128: 24 MB) and, when the window is split, the runs' lists -- at most 16 x 2 CUs + 16384 lists
 // of k entries, 12 bytes each (256 CUs, k = 128: 38 MB).
 struct TopkScratch {
-    DevBuf<double> Fp, Qp;                                 // F as k_bnd_pack packs it (whole steps of 64 rows); the batch's query rows
+    DevBuf<double> Fp, Qp;                                 // F as k_pack_factor packs it (whole steps of 64 rows); the batch's query rows
     DevBuf<int> row, scol, idx, found, pcol, pcnt;         // the batch's rows, skip columns, results; the runs' columns and counts
     DevBuf<long long> sptr;
     DevBuf<double> val;

@@ -4,6 +4,8 @@
 //   FactorView / factor_view, factor_ld   which arrays make up F for a `src`, and F's elements on the device
 //   mfma_strip_tile, mfma_fm_tile         the two FP64 matrix-core tile bodies, with the operand layout written down once
 //   row_strips                            the row strips of the first of them
+//   mfma_chain, packed_dot                the prefetching chain of MFMA steps over a row's columns; on two rows of a packed factor
+//   k_pack_factor / pack_factor           F (and t) zero-padded to whole tiles of rows and whole steps of 4 columns
 //   postsolve_args, postsolve_sharded     the argument checks and the sharded refusal, in the calling feature's words
 // (DevBuf, the grown scratch buffer of their scratch structs, sits with those structs in lorads_hip.hip: they are members of the
 // context, which is defined long before this file is read.)
@@ -35,7 +37,7 @@ __device__ __forceinline__ double2 factor_ld(const double2 *__restrict__ U, cons
 // v_mfma_f64_16x16x4_f64 computes D (16 x 16) += A (16 x 4) B (4 x 16) per wavefront.  Lane l = (nn = l & 15, kk = l >> 4) supplies
 // ONE element of each operand, A[nn][kk] and B[kk][nn], and holds D[kk + 4 q][nn] in register q of its four (the FP64 result map: not
 // the FP32 one).  Both tile bodies below feed it so that a lane's two operands come from one row of the matrices in memory, and
-// mask by multiplying a clamped load with zero, never by branching.  (cuts.inc: cut_tile, bounds.inc: k_bnd_enum, topk.inc: k_topk_scan and kernels.inc: k_dense_cx_b use the same
+// mask by multiplying a clamped load with zero, never by branching.  (cuts.inc: cut_tile, bounds.inc: k_bnd_enum, topk.inc: k_topk_scan, kcut.inc: k_kcut_label and kernels.inc: k_dense_cx_b use the same
 // layout on operands of their own.)
 
 // Partial tile of F^T B over one row strip: the 16 x 16 tile D[m][n] = sum over the strip's rows k of A[m][k] B[k][n], where row k of
@@ -99,6 +101,57 @@ __device__ __forceinline__ v4f64 mfma_fm_tile(const double *__restrict__ U, cons
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, load_b(kc), acc, 0, 0, 0);
     }
     return acc;
+}
+
+// N steps of a chain from column k0 on: the operands of all N are asked for before the first step waits for its own
+template <int N, typename Load>
+__device__ __forceinline__ v4f64 mfma_steps(int k0, v4f64 d, Load load) {
+    double x[N], y[N];
+#pragma unroll
+    for (int u = 0; u < N; ++u) load(k0 + 4 * u, x[u], y[u]);
+#pragma unroll
+    for (int u = 0; u < N; ++u) d = __builtin_amdgcn_mfma_f64_16x16x4f64(x[u], y[u], d, 0, 0, 0);
+    return d;
+}
+// One chain of steps over rl4 columns (a multiple of 4) in fours, ascending: `load(k0, x, y)` supplies the lane's two operands of the
+// step at column k0.  Eight, four, two steps and one at a time: the same chain as a loop of single steps, with more loads in flight.
+template <typename Load>
+__device__ __forceinline__ v4f64 mfma_chain(int rl4, Load load) {
+    v4f64 d = (v4f64){0.0, 0.0, 0.0, 0.0};
+    int k0 = 0;
+    for (; k0 + 32 <= rl4; k0 += 32) d = mfma_steps<8>(k0, d, load);
+    if (k0 + 16 <= rl4) { d = mfma_steps<4>(k0, d, load); k0 += 16; }
+    if (k0 + 8 <= rl4) { d = mfma_steps<2>(k0, d, load); k0 += 8; }
+    if (k0 < rl4) d = mfma_steps<1>(k0, d, load);
+    return d;
+}
+// the chain on two rows of packed, padded matrices (A and B at the lane's column kk of its rows): nothing to clamp
+__device__ __forceinline__ v4f64 packed_dot(const double *__restrict__ A, const double *__restrict__ B, int rl4) {
+    return mfma_chain(rl4, [&](int k0, double &x, double &y) { x = A[k0]; y = B[k0]; });
+}
+
+// ------------------------------------------------------------------ the packed factor
+// Fp (npad x rl4, row-major) <- F, the average of U and V formed once, zero past its n rows and rl columns; with t, tp (npad) <- t
+// padded with ones
+__global__ __launch_bounds__(TPB) void k_pack_factor(int n, int npad, int rl, int rl4, int r, const double *__restrict__ U,
+                                                     const double *__restrict__ V, int uv, const double *__restrict__ t,
+                                                     double *__restrict__ Fp, double *__restrict__ tp) {
+    const size_t len = (size_t)npad * rl4;
+    for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
+        const size_t row = i / rl4, j = i % rl4;
+        Fp[i] = (row < (size_t)n && j < (size_t)rl) ? factor_ld(U, V, uv != 0, row * r + j) : 0.0;
+        if (t && j == 0) tp[row] = row < (size_t)n ? t[row] : 1.0;
+    }
+}
+// block blk's factor for src, packed to npad rows and rl4 = its rank rounded up to a multiple of 4 columns (t == nullptr: no tp)
+int pack_factor(lorads_hip_ctx *c, int32_t src, int blk, int npad, const double *t, double *Fp, double *tp) {
+    const Block &B = c->blk[blk];
+    const int rl4 = (B.rl + 3) & ~3;
+    const FactorView F = factor_view(c, src, blk);
+    hipLaunchKernelGGL(k_pack_factor, dim3(std::min(grid1d((size_t)npad * rl4), 1024)), dim3(TPB), 0, c->stream, B.n, npad, B.rl, rl4, B.r,
+                       F.U, F.V, F.uv, t, Fp, tp);
+    HC(hipGetLastError());
+    return 0;
 }
 
 // ------------------------------------------------------------------ checks and refusals (0, or 1 with the message set)

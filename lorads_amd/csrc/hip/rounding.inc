@@ -10,6 +10,9 @@
 // so the words of a row's neighbours are wave-uniform loads.  Everything is read-only on the solver's state: R is formed on the fly
 // from U and V as the export forms it, the scratch is the feature's own (RoundScratch), launches go straight to the stream (never
 // through LAUNCH, which would flush a waiting dual update), and every sum is reduced per workgroup and then in a fixed order.
+//
+// Shared with kcut.inc (the rounding into k parts, DESIGN.md section 16): the Gaussian kernel k_rnd_gauss, read_constraint_image,
+// round_reserve and round_drive -- evaluate, best, the search rounds, evaluate, best, read-back -- around a feature's own field kernel.
 
 namespace {
 
@@ -25,15 +28,16 @@ __device__ __host__ __forceinline__ uint64_t rnd_sm(uint64_t x) {
     return z ^ (z >> 31);
 }
 
-// G_k (rk x K, G[j * K + t]) of cone k: c = (k << 32) | (t << 10) | j, a = sm(seed ^ sm(2c)), b = sm(seed ^ sm(2c + 1)),
-// u1 = ((a >> 11) + 1) 2^-53 in (0, 1], u2 = (b >> 11) 2^-53 in [0, 1), g = sqrt(-2 ln u1) cos(2 pi u2)
-__global__ __launch_bounds__(TPB) void k_rnd_hyper(int rk, int K, int cone, uint64_t seed, double *__restrict__ G) {
-    const size_t len = (size_t)rk * K;
+// G of cone `cone` (parts x rk x K, G[(a * rk + j) * K + t]): c = (cone << 32) | (a << 26) | (t << 10) | j, x = sm(seed ^ sm(2c)),
+// y = sm(seed ^ sm(2c + 1)), u1 = ((x >> 11) + 1) 2^-53 in (0, 1], u2 = (y >> 11) 2^-53 in [0, 1), g = sqrt(-2 ln u1) cos(2 pi u2).
+// The +-1 rounding's hyperplanes are parts = 1: part 0 of the rounding into k parts.
+__global__ __launch_bounds__(TPB) void k_rnd_gauss(int rk, int K, int parts, int cone, uint64_t seed, double *__restrict__ G) {
+    const size_t per = (size_t)rk * K, len = per * parts;
     for (size_t i = (size_t)blockIdx.x * TPB + threadIdx.x; i < len; i += (size_t)gridDim.x * TPB) {
-        const uint64_t j = i / K, t = i % K;
-        const uint64_t ctr = ((uint64_t)cone << 32) | (t << 10) | j;
-        const uint64_t a = rnd_sm(seed ^ rnd_sm(2 * ctr)), b = rnd_sm(seed ^ rnd_sm(2 * ctr + 1));
-        const double u1 = (double)((a >> 11) + 1) * 0x1p-53, u2 = (double)(b >> 11) * 0x1p-53;
+        const uint64_t a = i / per, rem = i % per, j = rem / K, t = rem % K;
+        const uint64_t ctr = ((uint64_t)cone << 32) | (a << 26) | (t << 10) | j;
+        const uint64_t x = rnd_sm(seed ^ rnd_sm(2 * ctr)), y = rnd_sm(seed ^ rnd_sm(2 * ctr + 1));
+        const double u1 = (double)((x >> 11) + 1) * 0x1p-53, u2 = (double)(y >> 11) * 0x1p-53;
         G[i] = sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
     }
 }
@@ -157,6 +161,29 @@ __global__ __launch_bounds__(TPB) void k_rnd_best(int K, const double *__restric
     if (threadIdx.x == 0) *best = si[0];
 }
 
+// cone k's constraint image read back to the host: local constraint -> its global row (ri) and its entries (ap, ae, av) on the
+// A-pattern (er, ec)
+struct ConImage { std::vector<int> ri, ap, ae, er, ec; std::vector<double> av; };
+int read_constraint_image(lorads_hip_ctx *c, int k, ConImage &m) {
+    const Block &B = c->blk[k];
+    m.ri.assign(B.nrow, 0); m.ap.assign(B.nrow + 1, 0); m.ae.assign(B.na, 0); m.er.assign(B.pa.ne, 0); m.ec.assign(B.pa.ne, 0);
+    m.av.assign(B.na, 0.0);
+    if (B.nrow) {
+        HC(hipMemcpyAsync(m.ri.data(), B.row_idx, sizeof(int) * m.ri.size(), hipMemcpyDeviceToHost, c->stream));
+        HC(hipMemcpyAsync(m.ap.data(), B.a_ptr, sizeof(int) * m.ap.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (B.na) {
+        HC(hipMemcpyAsync(m.ae.data(), B.a_e, sizeof(int) * m.ae.size(), hipMemcpyDeviceToHost, c->stream));
+        HC(hipMemcpyAsync(m.av.data(), B.a_val, sizeof(double) * m.av.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (B.pa.ne) {
+        HC(hipMemcpyAsync(m.er.data(), B.pa.erow, sizeof(int) * m.er.size(), hipMemcpyDeviceToHost, c->stream));
+        HC(hipMemcpyAsync(m.ec.data(), B.pa.ecol, sizeof(int) * m.ec.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    HC(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
 // applicability (once per context: the constraint data never changes); t of every cone to the device
 int rnd_check(lorads_hip_ctx *c) {
     RoundScratch &X = c->rnd;
@@ -175,21 +202,10 @@ int rnd_check(lorads_hip_ctx *c) {
     for (int k = 0; k < c->nb && X.why.empty(); ++k) {
         const Block &B = c->blk[k];
         if (B.dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); X.why = msg; break; }
-        std::vector<int> ri(B.nrow), ap(B.nrow + 1), ae(B.na), er(B.pa.ne), ec(B.pa.ne);
-        std::vector<double> av(B.na);
-        if (B.nrow) {
-            HC(hipMemcpyAsync(ri.data(), B.row_idx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(ap.data(), B.a_ptr, sizeof(int) * ap.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (B.na) {
-            HC(hipMemcpyAsync(ae.data(), B.a_e, sizeof(int) * ae.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(av.data(), B.a_val, sizeof(double) * av.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        if (B.pa.ne) {
-            HC(hipMemcpyAsync(er.data(), B.pa.erow, sizeof(int) * er.size(), hipMemcpyDeviceToHost, c->stream));
-            HC(hipMemcpyAsync(ec.data(), B.pa.ecol, sizeof(int) * ec.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        HC(hipStreamSynchronize(c->stream));
+        ConImage m;
+        if (read_constraint_image(c, k, m)) return 1;
+        const std::vector<int> &ri = m.ri, &ap = m.ap, &ae = m.ae, &er = m.er, &ec = m.ec;
+        const std::vector<double> &av = m.av;
         std::vector<int> cover((size_t)B.n, 0);
         for (int i = 0; i < B.nrow && X.why.empty(); ++i) {
             const int gi = ri[i], cnt = ap[i + 1] - ap[i];
@@ -273,39 +289,84 @@ int rnd_colour(lorads_hip_ctx *c) {
     return 0;
 }
 
-// buffers for K trials (grown on demand, freed with the context)
-int rnd_reserve(lorads_hip_ctx *c, int K) {
-    RoundScratch &X = c->rnd;
-    const int W = (K + 63) / 64;
+// the driver's buffers for K trials of `parts` vectors per cone (grown on demand, freed with the feature's pool `mem`)
+int round_reserve(lorads_hip_ctx *c, TrialScratch &T, DevPool &mem, int K, int parts) {
     size_t g = 0;
-    for (auto &B : c->blk) g += (size_t)B.rl * K;
-    const size_t words = (size_t)X.t_off[c->nb] * W, part = (size_t)K * RND_STRIPS;
-    if (X.G.grow(X.mem, g) || X.sgn.grow(X.mem, words) || X.part.grow(X.mem, part)) return 1;
-    if (X.f.grow(X.mem, (size_t)K) || X.f0.grow(X.mem, (size_t)K)) return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
+    for (auto &B : c->blk)
+        if (!B.is_lp) g += (size_t)B.rl * K * parts;
+    if (T.G.grow(mem, g) || T.part.grow(mem, (size_t)K * RND_STRIPS)) return 1;
+    if (T.f.grow(mem, (size_t)K) || T.f0.grow(mem, (size_t)K)) return 1;
+    if (!T.ctl && mem.alloc(&T.ctl, 4)) return 1;
     return 0;
 }
 
-// launch one field pass of cone k over nrows rows (rows == null: all of them, evaluation)
-void rnd_field(lorads_hip_ctx *c, int k, int K, const int *rows, int nrows, unsigned long long *sg) {
-    const Block &B = c->blk[k];
-    RoundScratch &X = c->rnd;
-    const int W = (K + 63) / 64;
-    const int strips = rows ? std::max(1, std::min(RND_STRIPS, nblocks_for((size_t)nrows, TPB / 64))) : RND_STRIPS;
-    hipLaunchKernelGGL(k_rnd_field, dim3(strips, W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, (const int *)B.pu.adj_ptr,
-                       (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.adj_sval, (const double *)B.pu.cbase,
-                       (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad, (const double *)(X.t + X.t_off[k]), sg, X.part, X.ctl);
+// cone k's vectors at G (parts x rank x K)
+void round_gauss(lorads_hip_ctx *c, int k, int K, int parts, uint64_t seed, double *G) {
+    const size_t glen = (size_t)c->blk[k].rl * K * parts;
+    if (glen) hipLaunchKernelGGL(k_rnd_gauss, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, c->blk[k].rl, K, parts, k, seed, G);
 }
 
-// f (K values) of the current sign words: every cone's field pass, its strips added per trial in cone order
-void rnd_eval(lorads_hip_ctx *c, int K, double *f) {
-    RoundScratch &X = c->rnd;
-    const int W = (K + 63) / 64;
-    for (int k = 0; k < c->nb; ++k) {
-        rnd_field(c, k, K, nullptr, c->blk[k].n, X.sgn + (size_t)X.t_off[k] * W);
-        hipLaunchKernelGGL(k_rnd_sum, dim3(nblocks_for((size_t)K, TPB)), dim3(TPB), 0, c->stream, K, (int)RND_STRIPS,
-                           (const double *)X.part, f, (int)(k == 0));
+// workgroups along x of a field pass over nrows rows (rows == null: all of a cone's, the evaluation: f's summation order is K's own)
+inline int field_strips(const int *rows, int nrows) {
+    return rows ? std::max(1, std::min(RND_STRIPS, nblocks_for((size_t)nrows, TPB / 64))) : RND_STRIPS;
+}
+
+// where a rounding's results go: the entry point's arguments of these names (all but obj may be NULL)
+struct RoundOut {
+    double *obj, *obj0;
+    int32_t *best, *best0, *rounds;
+};
+
+// What the two roundings do with their trials once the signs / labels stand.  `field(k, rows, nrows)` launches the feature's field
+// kernel for cone k over nrows rows (rows == null: all of them, the evaluation; otherwise a colour class of the search), leaving its
+// partials in T.part and its change flag in T.ctl[0].  LP blocks are passed over.  f0 of every trial (every cone's field pass, its
+// strips added per trial in cone order) and its best; the local search, one host synchronisation per round (the flag decides whether
+// another round runs); f and its best again; obj, obj0, best, best0 and rounds to `o`.  *trial <- the best trial after the search.
+template <typename Field>
+int round_drive(lorads_hip_ctx *c, int K, int max_rounds, TrialScratch &T, Field field, const RoundOut &o, int *trial) {
+    const RoundScratch &Rn = c->rnd;
+    auto eval = [&](double *f) {
+        bool first = true;
+        for (int k = 0; k < c->nb; ++k) {
+            if (c->blk[k].is_lp) continue;
+            field(k, (const int *)nullptr, c->blk[k].n);
+            hipLaunchKernelGGL(k_rnd_sum, dim3(nblocks_for((size_t)K, TPB)), dim3(TPB), 0, c->stream, K, (int)RND_STRIPS,
+                               (const double *)T.part, f, (int)first);
+            first = false;
+        }
+    };
+    eval(T.f0);
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)T.f0, T.ctl + 1);
+    int nr = 0;
+    for (int round = 0; round < max_rounds; ++round) {
+        HC(hipMemsetAsync(T.ctl, 0, sizeof(int), c->stream));
+        for (int k = 0; k < c->nb; ++k) {
+            if (c->blk[k].is_lp) continue;
+            const std::vector<int> &cp = Rn.cls_ptr[k];
+            for (size_t cl = 0; cl + 1 < cp.size(); ++cl) field(k, (const int *)(Rn.cls_rows + Rn.t_off[k] + cp[cl]), cp[cl + 1] - cp[cl]);
+        }
+        int flag = 0;
+        HC(hipMemcpyAsync(&flag, T.ctl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HC(hipStreamSynchronize(c->stream));
+        nr = round + 1;
+        if (!flag) break;
     }
+    double *f = T.f0;
+    if (nr > 0) {
+        eval(T.f);
+        f = T.f;
+    }
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, T.ctl + 2);
+    int bb[2] = {0, 0};
+    HC(hipMemcpyAsync(bb, T.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    HC(hipMemcpyAsync(o.obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (o.obj0) HC(hipMemcpyAsync(o.obj0, T.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HC(hipStreamSynchronize(c->stream));
+    if (o.best) *o.best = bb[1];
+    if (o.best0) *o.best0 = bb[0];
+    if (o.rounds) *o.rounds = nr;
+    *trial = bb[1];
+    return 0;
 }
 
 } // namespace
@@ -325,54 +386,32 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
     }
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64;
-    if (rnd_reserve(c, K) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    TrialScratch &T = X.trial;
+    if (round_reserve(c, T, X.mem, K, 1) || X.sgn.grow(X.mem, (size_t)X.t_off[c->nb] * W) || (max_rounds > 0 && rnd_colour(c))) return 1;
     // hyperplanes and sign words
     size_t goff = 0;
     for (int k = 0; k < c->nb; ++k) {
         const Block &B = c->blk[k];
-        double *G = X.G + goff;
-        const size_t glen = (size_t)B.rl * K;
-        if (glen) hipLaunchKernelGGL(k_rnd_hyper, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, B.rl, K, k, seed, G);
+        double *G = T.G + goff;
+        round_gauss(c, k, K, 1, seed, G);
         const FactorView F = factor_view(c, src, k);
         const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
         hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, F.U, F.V, F.uv,
                            (const double *)G, X.sgn + (size_t)X.t_off[k] * W);
-        goff += glen;
+        goff += (size_t)B.rl * K;
     }
-    if (hyperplanes && goff) HC(hipMemcpyAsync(hyperplanes, X.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
-    rnd_eval(c, K, X.f0);
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0, X.ctl + 1);
-    // local search: one host synchronisation per round (the flag decides whether another round runs)
-    int nr = 0;
-    for (int round = 0; round < max_rounds; ++round) {
-        HC(hipMemsetAsync(X.ctl, 0, sizeof(int), c->stream));
-        for (int k = 0; k < c->nb; ++k) {
-            const std::vector<int> &cp = X.cls_ptr[k];
-            for (size_t cl = 0; cl + 1 < cp.size(); ++cl)
-                rnd_field(c, k, K, X.cls_rows + X.t_off[k] + cp[cl], cp[cl + 1] - cp[cl], X.sgn + (size_t)X.t_off[k] * W);
-        }
-        int flag = 0;
-        HC(hipMemcpyAsync(&flag, X.ctl, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HC(hipStreamSynchronize(c->stream));
-        nr = round + 1;
-        if (!flag) break;
-    }
-    double *f = X.f0;
-    if (nr > 0) {
-        rnd_eval(c, K, X.f);
-        f = X.f;
-    }
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, X.ctl + 2);
-    int bb[2] = {0, 0};
-    HC(hipMemcpyAsync(bb, X.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    if (obj0) HC(hipMemcpyAsync(obj0, X.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    if (best) *best = bb[1];
-    if (best0) *best0 = bb[0];
-    if (rounds) *rounds = nr;
+    if (hyperplanes && goff) HC(hipMemcpyAsync(hyperplanes, T.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    auto field = [&](int k, const int *rows, int nrows) {
+        const Block &B = c->blk[k];
+        hipLaunchKernelGGL(k_rnd_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K,
+                           (const int *)B.pu.adj_ptr, (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.adj_sval,
+                           (const double *)B.pu.cbase, (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad,
+                           (const double *)(X.t + X.t_off[k]), X.sgn + (size_t)X.t_off[k] * W, T.part.p, T.ctl);
+    };
+    int bt = 0;
+    if (round_drive(c, K, max_rounds, T, field, RoundOut{obj, obj0, best, best0, rounds}, &bt)) return 1;
     if (sign) { // the best trial's signs, cone after cone
-        const int w = bb[1] / 64, l = bb[1] % 64;
+        const int w = bt / 64, l = bt % 64;
         std::vector<unsigned long long> words;
         for (int k = 0; k < c->nb; ++k) {
             const int n = c->blk[k].n;

@@ -8,6 +8,10 @@
 //   0  count the items and histogram the top digit of their keys
 //   1  histogram digit [shift, shift + width) of the keys that agree with a prefix above it
 //   2  emit the keys at or above a threshold into the key buffer (cursor: ctl[1])
+// The contract is all here: the eleven fields a user's kernel arguments carry by these names (below; the helpers are templates over
+// the user's struct), select_begin / select_item (the kernel's prologue and its step per item; what its epilogue has to do is said there too),
+// SelectScratch with select_reserve and select_check_range / select_check_outputs (the host's buffers, first-pass arguments and
+// argument checks).
 // select_largest drives them: digits of CUT_DIGIT bits from the top narrow the prefix of the wanted-th largest key until everything at
 // or above it fits the buffer (max_cuts + CUT_SLACK keys); ties of v are told apart by the digits of the index, so any number of them
 // is handled exactly.  Every pass enumerates anew.  The emitted keys are sorted by a bitonic network, largest first.
@@ -52,15 +56,97 @@ __global__ __launch_bounds__(TPB) void k_cut_bitonic(unsigned long long P, unsig
     if ((i & k) == 0 ? less : greater) { hi[i] = hi_l; lo[i] = lo_l; hi[l] = hi_i; lo[l] = lo_i; }
 }
 
-// The driver.  `a` is the user's kernel arguments: it starts as mode 0 with shift = 128 - CUT_DIGIT, width = CUT_DIGIT, khi = klo = 0
-// and cap = max_cuts + CUT_SLACK, and `launch()` enqueues one enumeration pass with it as it stands.  ctl [2 + CUT_BINS] on the device:
-// [0] the count (mode 0), [1] the emit cursor, [2..] the histogram; khi, klo: the key buffer (cap rounded up to a power of two; not
-// touched when max_cuts = 0).  *count and *passes (may be NULL) are written after the first pass and again at the end; khi_out,
-// klo_out get the min(count, max_cuts) largest keys, largest first.  Launches go straight to the stream.
+// The selection's share of an enumeration kernel's arguments.  A user's struct `Args` holds these fields among its own, flat (the helpers are templates
+// over the user's struct):
+//   int mode, shift, width;              the pass: see the modes above; digit [shift, shift + width)
+//   double minv;                         min_violation
+//   unsigned long long khi, klo;         mode 1: the prefix (bits below shift + width ignored); mode 2: the threshold key
+//   unsigned long long *ctl;             [0] items with v > minv (mode 0), [1] emitted keys (mode 2)
+//   unsigned long long *hist;            [CUT_BINS]
+//   unsigned long long *ohi, *olo;       emitted keys
+//   unsigned long long cap;
+
+// what one thread carries through an enumeration
+struct SelAcc {
+    unsigned long long cnt = 0;
+    int cur_bin = -1;       // a run of equal bins is counted in a register and goes to LDS when the bin changes
+    unsigned cur_n = 0;
+};
+
+// the kernel's prologue (before its first barrier): hist [CUT_BINS] and total in LDS
+template <typename Args>
+__device__ __forceinline__ void select_begin(const Args &a, unsigned *hist, unsigned long long *total) {
+    if (a.mode != 2)
+        for (int b = threadIdx.x; b < CUT_BINS; b += TPB) hist[b] = 0;
+    if (threadIdx.x == 0) *total = 0;
+}
+
+// one item with its v and packed index: counted, binned or emitted when v > min_violation
+template <typename Args>
+__device__ __forceinline__ void select_item(const Args &a, double v, unsigned long long index, unsigned *hist, SelAcc &acc) {
+    if (!(v > a.minv)) return;
+    const unsigned long long hi = (unsigned long long)__double_as_longlong(v), lo = ~index;
+    if (a.mode == 2) {
+        if (hi > a.khi || (hi == a.khi && lo >= a.klo)) {
+            const unsigned long long slot = atomicAdd(a.ctl + 1, 1ull);
+            if (slot < a.cap) { a.ohi[slot] = hi; a.olo[slot] = lo; }
+        }
+        return;
+    }
+    ++acc.cnt;
+    if (a.mode == 1 && !cut_same_prefix(hi, lo, a.khi, a.klo, a.shift + a.width)) return;
+    const int bin = (int)cut_digit(hi, lo, a.shift, a.width);
+    if (bin != acc.cur_bin) {
+        if (acc.cur_n) atomicAdd(&hist[acc.cur_bin], acc.cur_n);
+        acc.cur_bin = bin; acc.cur_n = 0;
+    }
+    ++acc.cur_n;
+}
+
+// The kernel's epilogue is each kernel's own code (k_bnd_enum's and k_cut_enum's are the same lines and must stay so): after the last
+// item a thread flushes its run into hist, mode 0 adds the workgroup's count to ctl[0], and the workgroup adds its non-zero bins to the
+// device's histogram; mode 2 has nothing left to do.  k_cut_enum's cut_handle also carries its own copy of select_item's body, per
+// class: it must match select_item.
+
+// the argument checks every user shares, in its words and in two parts, so that a user's own checks keep their place between them:
+// max_cuts and min_violation ...
+int select_check_range(const char *what, double min_violation, int max_cuts) {
+    const std::string w = std::string(what) + ": ";
+    if (max_cuts < 0 || max_cuts > (1 << 20)) return fail_msg(w + "max_cuts " + std::to_string(max_cuts) + " is outside [0, 2^20]");
+    if (!(min_violation >= 0.0) || !std::isfinite(min_violation)) return fail_msg(w + "min_violation must be finite and not negative");
+    return 0;
+}
+// ... and the outputs: `outs` names the user's output arrays, outs_ok says that none of them is NULL
+int select_check_outputs(const char *what, const char *outs, int max_cuts, const int64_t *count, bool outs_ok) {
+    const std::string w = std::string(what) + ": ";
+    if (!count) return fail_msg(w + "count must not be NULL");
+    if (max_cuts > 0 && !outs_ok) return fail_msg(w + outs + " must not be NULL when max_cuts > 0");
+    return 0;
+}
+
+// the buffers of a selection of max_cuts keys (the key buffer a power of two, untouched when max_cuts = 0) and, in the user's
+// arguments, what its first pass starts with
+template <typename Args>
+int select_reserve(SelectScratch &S, DevPool &mem, int max_cuts, double min_violation, Args &a) {
+    size_t P = 1;
+    while (P < (size_t)max_cuts + CUT_SLACK) P <<= 1;
+    if (max_cuts > 0 && (S.khi.grow(mem, P) || S.klo.grow(mem, P))) return 1;
+    if (!S.ctl && mem.alloc(&S.ctl, 2 + (size_t)CUT_BINS)) return 1;
+    a.mode = 0; a.shift = 128 - CUT_DIGIT; a.width = CUT_DIGIT;
+    a.minv = min_violation;
+    a.ctl = S.ctl; a.hist = S.ctl + 2;
+    a.ohi = S.khi; a.olo = S.klo;
+    a.cap = (unsigned long long)max_cuts + CUT_SLACK;
+    return 0;
+}
+
+// The driver.  `a` is the user's kernel arguments as select_reserve has left them (khi = klo = 0), and `launch()` enqueues one
+// enumeration pass with them as they stand.  *count and *passes (may be NULL) are written after the first pass and
+// again at the end; khi_out, klo_out get the min(count, max_cuts) largest keys, largest first.  Launches go straight to the stream.
 template <typename Args, typename Launch>
-int select_largest(lorads_hip_ctx *c, const char *what, unsigned long long *ctl, unsigned long long *khi, unsigned long long *klo,
-                   int max_cuts, Args &a, Launch launch, int64_t *count, int32_t *passes, std::vector<unsigned long long> &khi_out,
-                   std::vector<unsigned long long> &klo_out) {
+int select_largest(lorads_hip_ctx *c, const char *what, int max_cuts, Args &a, Launch launch, int64_t *count, int32_t *passes,
+                   std::vector<unsigned long long> &khi_out, std::vector<unsigned long long> &klo_out) {
+    unsigned long long *const ctl = a.ctl, *const khi = a.ohi, *const klo = a.olo;
     const std::string w = std::string(what) + ": ";
     std::vector<unsigned long long> h(2 + (size_t)CUT_BINS);
     // pass 1: the count and the top digit

@@ -3,7 +3,7 @@
 // Per SDP cone: F as lorads_hip_certificate takes it for src, at the cone's own rank.  For a query row p the candidates are the
 // columns q of a window [col_lo, col_hi), minus q = p (unless include_diag), minus the query's skip list, minus every q whose X_pq
 // is NaN.  X_pq is one chain of v_mfma_f64_16x16x4_f64 steps over the columns in fours, ascending, with the query row as the A
-// operand and the candidate row as the B operand, both rows of the packed, zero-padded F of k_bnd_pack (bnd_dot's chain): its bits
+// operand and the candidate row as the B operand, both rows of the packed, zero-padded F of k_pack_factor (packed_dot's chain): its bits
 // depend on the two rows alone, never on the window, k, the tile position or the other queries.  The chain starts from +0.0, so it
 // never ends in -0.0: the value read back from a key (below) is the chain's own bits.
 //   k_topk_gather  the query rows of the packed F, gathered into a packed query matrix of the same column padding
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(TPB) void k_topk_scan(TopkArgs a) {
     for (int t = t0; t < t1; ++t) {
         const int q = t * TOPK_STEP + 16 * wave + nn;     // (below npad: the packed F has whole steps of rows)
         const double *fb = a.Fp + (size_t)q * rl4 + kk;
-        const v4f64 d = a.in_lds ? bnd_dot(sa, fb, rl4) : bnd_dot(ga, fb, rl4);
+        const v4f64 d = a.in_lds ? packed_dot(sa, fb, rl4) : packed_dot(ga, fb, rl4);
         const bool col_ok = q >= a.lo && q < a.hi;
         int near_full = 0;                                // did an append of this lane leave its row within a step of B?
 #pragma unroll
@@ -324,10 +324,7 @@ extern "C" int lorads_hip_primal_topk(lorads_hip_ctx *c, int32_t src, int32_t bl
     }
     const int rl4 = (B.rl + 3) & ~3, npad = nblocks_for((size_t)n, TOPK_STEP) * TOPK_STEP;
     if (X.Fp.grow(X.mem, (size_t)npad * rl4)) return 1;
-    const FactorView F = factor_view(c, src, blk);
-    hipLaunchKernelGGL(k_bnd_pack, dim3(std::min(grid1d((size_t)npad * rl4), 1024)), dim3(TPB), 0, c->stream, n, npad, B.rl, rl4, B.r,
-                       F.U, F.V, F.uv, X.Fp.p);
-    HC(hipGetLastError());
+    if (pack_factor(c, src, blk, npad, nullptr, X.Fp, nullptr)) return 1;
     TopkArgs a{};
     a.n = n; a.rl4 = rl4; a.k = k; a.B = topk_cap(k); a.smallest = smallest; a.diag = include_diag;
     a.in_lds = rl4 <= TOPK_LDS_COLS;

@@ -1,6 +1,6 @@
 /* bounds.c -- separation of entry bounds lower <= X_pq <= upper on the primal and the problem file with the violated ones added
  * (DESIGN.md section 15).  The enumeration is the backend's (lrd_backend.entry_bounds); here: the session-level driver that merges the
- * cones' lists, and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem
+ * cones' lists (cuts.c: lrd_merge_runs), and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem
  * image and the list (so the format can be checked without a GPU). */
 #include "lorads_host.h"
 
@@ -16,7 +16,8 @@ void lrd_bounds_free(lrd_bounds *c) {
 }
 
 /* is a before b in (v descending, cone, p, q, class ascending)? */
-static int bound_before(const lrd_bounds *c, int a, int b) {
+static int bound_before(const void *list, int a, int b) {
+    const lrd_bounds *c = (const lrd_bounds *)list;
     if (c->viol[a] != c->viol[b]) return c->viol[a] > c->viol[b];
     if (c->cone[a] != c->cone[b]) return c->cone[a] < c->cone[b];
     if (c->p[a] != c->p[b]) return c->p[a] < c->p[b];
@@ -46,9 +47,8 @@ int lrd_session_entry_bounds(lrd_session *s, double lower, double upper, double 
     c->cls = (int8_t *)calloc(2 * (size_t)cap, sizeof(int8_t));
     c->viol = (double *)calloc(2 * (size_t)cap, sizeof(double));
     c->bound = (double *)calloc(2 * (size_t)cap, sizeof(double));
-    int *order = (int *)malloc(2 * (size_t)cap * sizeof(int)), *tmp = (int *)malloc(2 * (size_t)cap * sizeof(int));
-    int8_t *tmp8 = (int8_t *)malloc(2 * (size_t)cap);
-    double *tmpd = (double *)malloc(2 * (size_t)cap * sizeof(double));
+    const lrd_column col[5] = {{c->cone, sizeof(int)}, {c->p, sizeof(int)}, {c->q, sizeof(int)}, {c->cls, sizeof(int8_t)},
+                               {c->viol, sizeof(double)}};
     int rc = 0;
     for (int k = 0; k < nb && !rc; ++k) {
         if (pr->blk[k].is_lp) continue;
@@ -59,24 +59,8 @@ int lrd_session_entry_bounds(lrd_session *s, double lower, double upper, double 
         if (rc) break;
         c->passes += np;
         for (int e = 0; e < got; ++e) c->cone[at + e] = k;
-        /* two sorted runs [0, at) and [at, at + got): merge, keep max_cuts */
-        int i = 0, j = at, n = 0;
-        const int tot = at + got, keep = tot < max_cuts ? tot : max_cuts;
-        while (n < keep) {
-            if (j >= tot || (i < at && bound_before(c, i, j))) order[n++] = i++;
-            else order[n++] = j++;
-        }
-#define BND_PERMUTE(arr, t)                                   \
-    do {                                                      \
-        for (int e = 0; e < keep; ++e) (t)[e] = (arr)[order[e]]; \
-        memcpy((arr), (t), sizeof(*(arr)) * (size_t)keep);    \
-    } while (0)
-        BND_PERMUTE(c->cone, tmp); BND_PERMUTE(c->p, tmp); BND_PERMUTE(c->q, tmp);
-        BND_PERMUTE(c->cls, tmp8); BND_PERMUTE(c->viol, tmpd);
-#undef BND_PERMUTE
-        c->kept = keep;
+        c->kept = lrd_merge_runs(c, bound_before, col, 5, at, got, max_cuts);
     }
-    free(order); free(tmp); free(tmp8); free(tmpd);
     if (rc) { lrd_bounds_free(c); return rc; }
     for (int e = 0; e < c->kept; ++e) c->bound[e] = c->cls[e] ? upper : lower;
     *out = c;
@@ -117,17 +101,7 @@ int lrd_session_write_bounded(lrd_session *s, const char *path, const lrd_bounds
     for (int i = 0; i < pr->m; ++i) fprintf(f, "%s%.17g", i ? " " : "", pr->b[i]);
     for (int e = 0; e < ncut; ++e) fprintf(f, "%s%.17g", pr->m + e ? " " : "", bounds->bound[e]);
     fputc('\n', f);
-    /* the stored entries: lower triangle inside, upper triangle (i <= j) in the file; F0 = -C */
-    for (int k = 0; k < nb; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
-    }
-    for (int k = 0; k < nb; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int i = 0; i < b->nrow; ++i)
-            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1]; ++e)
-                fprintf(f, "%d %d %d %d %.17g\n", b->row_idx[i] + 1, k + 1, b->a_col[e] + 1, b->a_row[e] + 1, b->a_val[e]);
-    }
+    lrd_write_problem_as_read(f, pr);
     /* the cuts: X_pq -+ slack = bound; an off-diagonal entry counts twice in <A, X> */
     const int sblk = lp >= 0 ? lp + 1 : nb + 1;
     for (int e = 0; e < ncut; ++e) {

@@ -1,6 +1,6 @@
 /* cuts.c -- separation of the triangle inequalities of a +-1-structured problem and the tightened problem file (DESIGN.md
  * section 14).  The enumeration is the backend's (lrd_backend.triangle_cuts); here: the session-level driver that merges the cones'
- * lists, and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem image and
+ * lists (lrd_merge_runs, shared with bounds.c like lrd_write_problem_as_read), and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem image and
  * the cut list (so the format can be checked without a GPU). */
 #include "lorads_host.h"
 
@@ -18,8 +18,42 @@ void lrd_cuts_free(lrd_cuts *c) {
     free(c);
 }
 
+int lrd_merge_runs(const void *list, int (*before)(const void *list, int a, int b), const lrd_column *col, int ncol, int at, int got,
+                   int max_cuts) {
+    const int tot = at + got, keep = tot < max_cuts ? tot : max_cuts;
+    size_t wide = 1;
+    for (int w = 0; w < ncol; ++w) wide = col[w].size > wide ? col[w].size : wide;
+    int *order = (int *)malloc((size_t)(keep > 0 ? keep : 1) * sizeof(int));
+    char *tmp = (char *)malloc((size_t)(keep > 0 ? keep : 1) * wide);
+    for (int i = 0, j = at, n = 0; n < keep;) {
+        if (j >= tot || (i < at && before(list, i, j))) order[n++] = i++;
+        else order[n++] = j++;
+    }
+    for (int w = 0; w < ncol; ++w) {
+        const size_t sz = col[w].size;
+        for (int e = 0; e < keep; ++e) memcpy(tmp + (size_t)e * sz, (const char *)col[w].base + (size_t)order[e] * sz, sz);
+        memcpy(col[w].base, tmp, (size_t)keep * sz);
+    }
+    free(order); free(tmp);
+    return keep;
+}
+
+void lrd_write_problem_as_read(FILE *f, const lrd_problem *pr) {
+    for (int k = 0; k < pr->nblk; ++k) {
+        const lrd_block *b = &pr->blk[k];
+        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
+    }
+    for (int k = 0; k < pr->nblk; ++k) {
+        const lrd_block *b = &pr->blk[k];
+        for (int i = 0; i < b->nrow; ++i)
+            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1]; ++e)
+                fprintf(f, "%d %d %d %d %.17g\n", b->row_idx[i] + 1, k + 1, b->a_col[e] + 1, b->a_row[e] + 1, b->a_val[e]);
+    }
+}
+
 /* is a before b in (v descending, cone, p, q, s, class ascending)? */
-static int cut_before(const lrd_cuts *c, int a, int b) {
+static int cut_before(const void *list, int a, int b) {
+    const lrd_cuts *c = (const lrd_cuts *)list;
     if (c->viol[a] != c->viol[b]) return c->viol[a] > c->viol[b];
     if (c->cone[a] != c->cone[b]) return c->cone[a] < c->cone[b];
     if (c->p[a] != c->p[b]) return c->p[a] < c->p[b];
@@ -49,9 +83,8 @@ int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts
     c->s = (int *)calloc(2 * (size_t)cap, sizeof(int));
     c->cls = (int8_t *)calloc(2 * (size_t)cap, sizeof(int8_t));
     c->viol = (double *)calloc(2 * (size_t)cap, sizeof(double));
-    int *order = (int *)malloc(2 * (size_t)cap * sizeof(int)), *tmp = (int *)malloc(2 * (size_t)cap * sizeof(int));
-    int8_t *tmp8 = (int8_t *)malloc(2 * (size_t)cap);
-    double *tmpd = (double *)malloc(2 * (size_t)cap * sizeof(double));
+    const lrd_column col[6] = {{c->cone, sizeof(int)}, {c->p, sizeof(int)}, {c->q, sizeof(int)}, {c->s, sizeof(int)},
+                               {c->cls, sizeof(int8_t)}, {c->viol, sizeof(double)}};
     int rc = 0;
     for (int k = 0; k < nb && !rc; ++k) {
         const int at = c->kept;
@@ -61,24 +94,8 @@ int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts
         if (rc) break;
         c->passes += np;
         for (int e = 0; e < got; ++e) c->cone[at + e] = k;
-        /* two sorted runs [0, at) and [at, at + got): merge, keep max_cuts */
-        int i = 0, j = at, n = 0;
-        const int tot = at + got, keep = tot < max_cuts ? tot : max_cuts;
-        while (n < keep) {
-            if (j >= tot || (i < at && cut_before(c, i, j))) order[n++] = i++;
-            else order[n++] = j++;
-        }
-#define CUT_PERMUTE(arr, t)                                   \
-    do {                                                      \
-        for (int e = 0; e < keep; ++e) (t)[e] = (arr)[order[e]]; \
-        memcpy((arr), (t), sizeof(*(arr)) * (size_t)keep);    \
-    } while (0)
-        CUT_PERMUTE(c->cone, tmp); CUT_PERMUTE(c->p, tmp); CUT_PERMUTE(c->q, tmp); CUT_PERMUTE(c->s, tmp);
-        CUT_PERMUTE(c->cls, tmp8); CUT_PERMUTE(c->viol, tmpd);
-#undef CUT_PERMUTE
-        c->kept = keep;
+        c->kept = lrd_merge_runs(c, cut_before, col, 6, at, got, max_cuts);
     }
-    free(order); free(tmp); free(tmp8); free(tmpd);
     if (rc) { lrd_cuts_free(c); return rc; }
     *out = c;
     return 0;
@@ -130,17 +147,7 @@ int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts
     for (int i = 0; i < pr->m; ++i) fprintf(f, "%s%.17g", i ? " " : "", pr->b[i]);
     for (int e = 0; e < ncut; ++e) fprintf(f, "%s-1", pr->m + e ? " " : "");
     fputc('\n', f);
-    /* the stored entries: lower triangle inside, upper triangle (i <= j) in the file; F0 = -C */
-    for (int k = 0; k < nb; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
-    }
-    for (int k = 0; k < nb; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int i = 0; i < b->nrow; ++i)
-            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1]; ++e)
-                fprintf(f, "%d %d %d %d %.17g\n", b->row_idx[i] + 1, k + 1, b->a_col[e] + 1, b->a_row[e] + 1, b->a_val[e]);
-    }
+    lrd_write_problem_as_read(f, pr);
     /* the cuts: sum of sign_xy X_xy / (t_x t_y) - slack = -1; an off-diagonal entry counts twice in <A, X> */
     for (int e = 0; e < ncut; ++e) {
         const int k = cuts->cone[e], x[3] = {cuts->p[e], cuts->q[e], cuts->s[e]};

@@ -12,7 +12,6 @@
 #include "lorads_host.h"
 
 #include <inttypes.h>
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -111,7 +110,6 @@ int lrd_session_kcut(lrd_session *s, int parts, int trials, uint64_t seed, int m
             q->T += q->t[j] * q->t[j];
             if (q->label[j] < parts) q->size[q->label[j]]++;
         }
-        q->lam_min = NAN;
         if (g) {
             const size_t len = (size_t)q->rank * (size_t)trials * (size_t)parts;
             q->G = (double *)malloc((len ? len : 1) * sizeof(double));
@@ -121,39 +119,15 @@ int lrd_session_kcut(lrd_session *s, int parts, int trials, uint64_t seed, int m
         at += (size_t)n;
     }
     free(label); free(t); free(g);
-    r->by = r->bound = r->gap = NAN;
-    if (tol > 0 && be->certificate && (lpk < 0 || be->get_slack)) {
-        /* d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) from the certificate's y, eigenvalues and LP slack */
-        double c[LRD_CERT_N];
-        double *lm = (double *)zalloc((size_t)p->nblk, sizeof(double));
-        rc = be->certificate(be->ctx, src, tol, c, lm, NULL, NULL);
-        if (!rc) {
-            r->by = c[3] / sc;
-            double d = r->by;
-            for (int i = 0; i < nsdp; ++i) {
-                lrd_kcut_cone *q = &r->cone[i];
-                q->lam_min = lm[q->blk] / sc;
-                if (q->lam_min < 0) d += q->T * q->lam_min;
-            }
-            if (lpk >= 0 && nlp > 0) {
-                int64_t nnz = 0;
-                int *row = (int *)zalloc((size_t)nlp, sizeof(int)), *col = (int *)zalloc((size_t)nlp, sizeof(int));
-                double *val = (double *)zalloc((size_t)nlp, sizeof(double));
-                rc = be->get_slack(be->ctx, lpk, &nnz, NULL, NULL, NULL);
-                if (!rc && nnz != nlp) rc = 1;
-                if (!rc) rc = be->get_slack(be->ctx, lpk, &nnz, row, col, val);
-                for (int64_t e = 0; e < nnz && !rc; ++e) {
-                    const double sj = val[e] / sc;
-                    if (sj < 0) { d += r->lp_upper[row[e]] * sj; r->lp_neg++; }
-                }
-                free(row); free(col); free(val);
-            }
-            r->bound = d;
-            r->gap = (r->f_best - d) / (fabs(d) > 1.0 ? fabs(d) : 1.0);
-        }
-        free(lm);
-        if (rc) { lrd_kcut_free(r); return 1; }
-    }
+    int *blk = (int *)zalloc((size_t)nsdp, sizeof(int));
+    double *T = (double *)zalloc(2 * (size_t)(nsdp > 0 ? nsdp : 1), sizeof(double)), *lm = T + (nsdp > 0 ? nsdp : 1);
+    for (int i = 0; i < nsdp; ++i) { blk[i] = r->cone[i].blk; T[i] = r->cone[i].T; }
+    lrd_dual_bound db;
+    rc = lrd_rounded_dual_bound(be, src, tol, sc, p->nblk, nsdp, blk, T, lpk, nlp, r->lp_upper, r->f_best, &db, lm);
+    r->by = db.by; r->bound = db.bound; r->gap = db.gap; r->lp_neg = db.lp_neg;
+    for (int i = 0; i < nsdp; ++i) r->cone[i].lam_min = lm[i];
+    free(blk); free(T);
+    if (rc) { lrd_kcut_free(r); return 1; }
     *out = r;
     return 0;
 }

@@ -13,6 +13,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -335,7 +336,7 @@ void lrd_solution_free(lrd_solution *sol);
  * m values, then per cone "sdp k n r" and n rows of R, or "lp k n" and n values of x (k: 1-based block of the file); every double %.17g */
 int lrd_solution_write(const char *path, const lrd_solution *sol);
 
-/* ---- rounding of +-1-structured contexts (session.c, rounding.c).  Everything in the file's units: x = sigma o t
+/* ---- rounding of +-1-structured contexts (rounding.c).  Everything in the file's units: x = sigma o t
  * is feasible for every sigma (t_p = sqrt(b_i / a_i) of the one constraint a_i X[p,p] = b_i on the diagonal), f = sum_k x_k^T C_k x_k;
  * the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) <= every f (T_k = sum_p t_p^2, the trace of every feasible X_k). */
 typedef struct {
@@ -535,6 +536,23 @@ int lrd_session_kcut(lrd_session *s, int parts, int trials, uint64_t seed, int m
 void lrd_kcut_free(lrd_kcut *r);
 /* plain-text file, a pure function of the struct (kcut.c) */
 int lrd_kcut_write(const char *path, const lrd_kcut *r);
+
+/* ---- internal: what the post-solve drivers and writers above share (not part of the interface)
+ * Two adjacent runs [0, at) and [at, at + got) of a list kept as ncol parallel columns, each sorted by `before(list, a, b)` (is entry a
+ * before entry b?): merged in place, the first min(at + got, max_cuts) entries kept; returns how many (cuts.c). */
+typedef struct { void *base; size_t size; } lrd_column;
+int lrd_merge_runs(const void *list, int (*before)(const void *list, int a, int b), const lrd_column *col, int ncol, int at, int got,
+                   int max_cuts);
+/* the objective and constraint entries of the problem as it was read, in SDPA sparse format: lower triangle inside, upper triangle
+ * (i <= j) in the file; F0 = -C (cuts.c) */
+void lrd_write_problem_as_read(FILE *f, const lrd_problem *pr);
+/* The dual bound of a rounding, d = b.y + sum_i T_i min(0, lambda_min(S_blk[i])) + sum_j u_j min(0, s_j), from the certificate's y and
+ * eigenvalues at Lanczos tolerance tol and the dual slack of the LP block lpk (-1: none, no third sum); sc: scaleObjHis.  Fills *out
+ * (gap = (f_best - d) / max(1, |d|); lp_neg: how many s_j < 0) and lam_min [ncone]; all NaN / 0 when tol <= 0 or the table lacks the
+ * slots.  Non-zero: the backend failed (rounding.c). */
+typedef struct { double by, bound, gap; int lp_neg; } lrd_dual_bound;
+int lrd_rounded_dual_bound(lrd_backend *be, int src, double tol, double sc, int nblk, int ncone, const int *blk, const double *T, int lpk,
+                           int nlp, const double *lp_upper, double f_best, lrd_dual_bound *out, double *lam_min);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

@@ -279,93 +279,6 @@ int lrd_session_solution(lrd_session *s, double tol, lrd_solution **out) {
     return 0;
 }
 
-/* hyperplane rounding of a +-1-structured context, in the file's units (lorads_host.h: lrd_rounding) */
-int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_hyperplanes,
-                         lrd_rounding **out) {
-    *out = NULL;
-    lrd_backend *be = &s->be;
-    const lrd_problem *p = s->prob;
-    int src;
-    const int refused = lrd_session_postsolve(s, be->round_pm1 != NULL, "round a solution",
-                                              "rounding the solution of a sharded deal (world > 1) is", NULL, NULL, &src);
-    if (refused) return refused;
-    if (trials <= 0) return trials < 0 ? 1 : be->round_pm1(be->ctx, src, 0, seed, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
-    const double sc = s->sol.scaleObjHis;
-    size_t ntot = 0, gtot = 0;
-    for (int k = 0; k < p->nblk; ++k) {
-        ntot += (size_t)p->blk[k].n;
-        gtot += (size_t)s->sol.rank[k] * (size_t)trials;
-    }
-    lrd_rounding *r = (lrd_rounding *)calloc(1, sizeof *r);
-    r->nblk = p->nblk; r->trials = trials; r->max_rounds = max_rounds; r->src = src; r->seed = seed; r->scale = sc; r->tol = tol;
-    r->obj = (double *)calloc((size_t)trials, sizeof(double));
-    r->obj0 = (double *)calloc((size_t)trials, sizeof(double));
-    r->cone = (lrd_rounding_cone *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(lrd_rounding_cone));
-    int8_t *sign = (int8_t *)calloc(ntot ? ntot : 1, 1);
-    double *g = with_hyperplanes ? (double *)calloc(gtot ? gtot : 1, sizeof(double)) : NULL;
-    int rc = be->round_pm1(be->ctx, src, trials, seed, max_rounds, r->obj, r->obj0, &r->best, &r->best0, sign, &r->rounds, g);
-    if (rc) {
-        free(sign); free(g);
-        lrd_rounding_free(r);
-        return rc;
-    }
-    for (int t = 0; t < trials; ++t) { r->obj[t] /= sc; r->obj0[t] /= sc; }
-    r->f_best = r->obj[r->best];
-    r->f_best0 = r->obj0[r->best0];
-    size_t at = 0, gat = 0;
-    for (int k = 0; k < p->nblk; ++k) { /* t from the problem: the one constraint on every diagonal (the backend has checked it) */
-        const lrd_block *b = &p->blk[k];
-        lrd_rounding_cone *q = &r->cone[k];
-        const int n = b->n;
-        q->n = n; q->rank = s->sol.rank[k];
-        q->sigma = (int8_t *)calloc((size_t)(n > 0 ? n : 1), 1);
-        q->t = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof(double));
-        q->x = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof(double));
-        for (int i = 0; i < b->nrow; ++i) {
-            const int e = b->a_ptr[i];
-            q->t[b->a_row[e]] = sqrt(p->b[b->row_idx[i]] / b->a_val[e]);
-        }
-        q->T = 0.0;
-        for (int j = 0; j < n; ++j) {
-            q->sigma[j] = sign[at + (size_t)j];
-            q->x[j] = q->sigma[j] * q->t[j];
-            q->T += q->t[j] * q->t[j];
-        }
-        q->lam_min = NAN;
-        if (g) {
-            const size_t len = (size_t)q->rank * (size_t)trials;
-            q->G = (double *)malloc((len ? len : 1) * sizeof(double));
-            memcpy(q->G, g + gat, len * sizeof(double));
-            gat += len;
-        }
-        at += (size_t)n;
-    }
-    free(sign); free(g);
-    r->by = r->bound = r->gap = NAN;
-    if (tol > 0 && be->certificate) { /* d = b.y + sum_k T_k min(0, lambda_min(S_k)) from the certificate's y and eigenvalues */
-        double c[LRD_CERT_N];
-        double *lm = (double *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(double));
-        rc = be->certificate(be->ctx, src, tol, c, lm, NULL, NULL);
-        if (!rc) {
-            r->by = c[3] / sc;
-            double d = r->by;
-            for (int k = 0; k < p->nblk; ++k) {
-                r->cone[k].lam_min = lm[k] / sc;
-                if (r->cone[k].lam_min < 0) d += r->cone[k].T * r->cone[k].lam_min;
-            }
-            r->bound = d;
-            r->gap = (r->f_best - d) / (fabs(d) > 1.0 ? fabs(d) : 1.0);
-        }
-        free(lm);
-        if (rc) { lrd_rounding_free(r); return 1; }
-    }
-    *out = r;
-    return 0;
-}
-int lrd_session_round(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, lrd_rounding **out) {
-    return lrd_session_round_ex(s, trials, seed, max_rounds, tol, 0, out);
-}
-
 int lrd_session_current_rank(lrd_session *s, int k) { return s->have_sol ? s->sol.rank[k] : s->prob->blk[k].rank; }
 
 void lrd_session_close(lrd_session *s) {

@@ -906,6 +906,19 @@ class Session:
         finally:
             self.lib.lrd_solution_free(ptr)
 
+    def _refused(self, rc, what_rc2, what_rc3):
+        """the refusals of a post-solve entry point: rc 2 (what_rc2 takes the backend's name and, behind ": ", the HIP backend's own
+        reason) and rc 3 (a sharded deal)"""
+        if rc == 2:
+            msg = None
+            if self.be is not None and self.be.name == "hip-gfx950":
+                lib, _ = self._hip()
+                lib.lorads_hip_last_error.restype = C.c_char_p
+                msg = (lib.lorads_hip_last_error() or b"").decode()
+            raise NotImplementedError(what_rc2 % (self.be.name if self.be else "attached", (": " + msg) if msg else ""))
+        if rc == 3:
+            raise NotImplementedError(what_rc3)
+
     def _round_ptr(self, trials, seed, local_search_rounds, tol, hyperplanes):
         from .rounding import RoundingStruct
         ptr = C.POINTER(RoundingStruct)()
@@ -914,17 +927,9 @@ class Session:
         self.lib.lrd_rounding_free.argtypes = [C.POINTER(RoundingStruct)]
         rc = self.lib.lrd_session_round_ex(self.h, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds), float(tol),
                                            1 if hyperplanes else 0, C.byref(ptr))
-        if rc == 2:
-            msg = None
-            if self.be is not None and self.be.name == "hip-gfx950":
-                lib, _ = self._hip()
-                lib.lorads_hip_last_error.restype = C.c_char_p
-                msg = lib.lorads_hip_last_error()
-            raise NotImplementedError("the problem cannot be rounded: it is not +-1-structured (no LP block; every constraint "
-                                      "a_i X[p,p] = b_i with b_i / a_i > 0, one per diagonal) or the %s backend cannot round%s"
-                                      % (self.be.name if self.be else "attached", (": " + msg.decode()) if msg else ""))
-        if rc == 3:
-            raise NotImplementedError("rounding the solution of a sharded deal (world > 1) is not supported")
+        self._refused(rc, "the problem cannot be rounded: it is not +-1-structured (no LP block; every constraint "
+                      "a_i X[p,p] = b_i with b_i / a_i > 0, one per diagonal) or the %s backend cannot round%s",
+                      "rounding the solution of a sharded deal (world > 1) is not supported")
         _check(rc, "round")
         return ptr
 
@@ -971,17 +976,10 @@ class Session:
         self.lib.lrd_kcut_free.restype = None
         rc = self.lib.lrd_session_kcut(self.h, int(parts), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds),
                                        float(tol), 1 if vectors else 0, C.byref(ptr))
-        if rc == 2:
-            msg = None
-            if self.be is not None and self.be.name == "hip-gfx950":
-                lib, _ = self._hip()
-                lib.lorads_hip_last_error.restype = C.c_char_p
-                msg = (lib.lorads_hip_last_error() or b"").decode()
-            raise NotImplementedError("the problem cannot be rounded into parts: it is not k-cut-structured (every diagonal fixed by one "
-                                      "constraint a_i X[p,p] = b_i with b_i / a_i > 0; LP columns only in bound rows 2 a X[p,q] + c x_j = b) "
-                                      "or the %s backend cannot round%s" % (self.be.name if self.be else "attached", (": " + msg) if msg else ""))
-        if rc == 3:
-            raise NotImplementedError("rounding the solution of a sharded deal (world > 1) is not supported")
+        self._refused(rc, "the problem cannot be rounded into parts: it is not k-cut-structured (every diagonal fixed by one "
+                      "constraint a_i X[p,p] = b_i with b_i / a_i > 0; LP columns only in bound rows 2 a X[p,q] + c x_j = b) "
+                      "or the %s backend cannot round%s",
+                      "rounding the solution of a sharded deal (world > 1) is not supported")
         _check(rc, "round_kcut")
         return ptr
 
@@ -1022,16 +1020,8 @@ class Session:
         self.lib.lrd_cuts_free.argtypes = [C.POINTER(CutsStruct)]
         self.lib.lrd_cuts_free.restype = None
         rc = self.lib.lrd_session_triangle_cuts(self.h, float(min_violation), int(max_cuts), C.byref(ptr))
-        if rc == 2:
-            msg = None
-            if self.be is not None and self.be.name == "hip-gfx950":
-                lib, _ = self._hip()
-                lib.lorads_hip_last_error.restype = C.c_char_p
-                msg = lib.lorads_hip_last_error()
-            raise NotImplementedError("triangle inequalities cannot be separated: the problem is not +-1-structured or the %s backend "
-                                      "cannot separate%s" % (self.be.name if self.be else "attached", (": " + msg.decode()) if msg else ""))
-        if rc == 3:
-            raise NotImplementedError("the separation of a sharded deal (world > 1) is not supported")
+        self._refused(rc, "triangle inequalities cannot be separated: the problem is not +-1-structured or the %s backend "
+                      "cannot separate%s", "the separation of a sharded deal (world > 1) is not supported")
         _check(rc, "triangle_cuts")
         try:
             return Cuts.from_struct(ptr.contents)

@@ -9,7 +9,7 @@ and the read-back route for the 32-row case: Session.primal_apply on a panel of 
 one JSON line to --out (default profiles/topk_time.jsonl).  Not part of bench.py.
 
 --quick: one call per case, for a `rocprofv3 --kernel-trace --stats` run of its own.  --stats-csv FILE (no GPU work) reads that
-run's kernel_stats.csv and appends, for the last --quick record of --out, calls and total time of the k_topk_* and k_bnd_* kernels
+run's kernel_stats.csv and appends, for the last --quick record of --out, calls and total time of the k_topk_*, k_bnd_* and k_pack_* kernels
 and the scan's pairs per second."""
 import argparse
 import csv
@@ -36,7 +36,7 @@ def kernel_stats(path):
     with open(path) as fh:
         for row in csv.DictReader(fh):
             name = row.get("Name") or row.get("KernelName") or ""
-            hit = re.search(r"\bk_(topk|bnd)_[a-z0-9_]+", name)
+            hit = re.search(r"\bk_(topk|bnd|pack)_[a-z0-9_]+", name)
             if not hit:
                 continue
             d = out.setdefault(hit.group(0), {"calls": 0, "total_ms": 0.0})

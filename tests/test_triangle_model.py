@@ -218,3 +218,62 @@ def test_sign_patterns():
     v = tm.class_values(np.array([a]), np.array([b]), np.array([c]))[:, 0]
     assert abs(v.sum() + 4.0) <= 1e-15
     assert np.allclose(v, [-1 - (x * a + y * b + z * c) for x, y, z in SIGNS.tolist()], rtol=0, atol=1e-15)
+
+
+def test_session_drivers_merge_the_cones_lists_through_a_stub_table():
+    """lrd_session_triangle_cuts and lrd_session_entry_bounds over a table whose two slots return fixed, sorted lists for three
+    cones: the merged list is (violation descending, cone, p, q[, s], class ascending) with violations that tie across cones
+    and is cut off at max_cuts below the total; count stays per cone, passes add up.  No GPU: the merge is the host's."""
+    path = common.generated_instance("blk3x8", make=lambda: instances.blockdiag_maxcut(3, 8, 10, 77))   # (three cones of 8)
+    # per cone (p, q, s, class, violation), sorted as a backend returns them: 0.5 and 0.25 tie across the cones, 0.5 within cone 1
+    cut_lists = [[(0, 1, 2, 3, 0.5), (0, 1, 3, 0, 0.25), (1, 2, 3, 1, 0.125)],
+                 [(0, 1, 2, 1, 0.75), (0, 1, 2, 2, 0.5), (0, 2, 3, 0, 0.5), (2, 3, 4, 0, 0.25)],
+                 [(0, 1, 2, 3, 0.5), (0, 1, 2, 0, 0.25), (4, 5, 6, 2, 0.0625)]]
+    bnd_lists = [[(p, q, cl % 2, v) for p, q, _, cl, v in lst] for lst in cut_lists]  # (p, q, class, violation), sorted too
+    counts, calls = [30, 41, 52], []
+
+    def fill(rows, count, n_violated, cols, kept, passes, np_):
+        count[0] = n_violated
+        for e, row in enumerate(rows):
+            for ptr, val in zip(cols, row):
+                ptr[e] = val
+        kept[0], passes[0] = len(rows), np_
+        return 0
+
+    def stub_cuts(ctx, src, blk, minv, max_cuts, count, p, q, s_, cls, viol, kept, passes):
+        calls.append(("cuts", blk, minv, max_cuts))
+        return fill(cut_lists[blk][:max_cuts], count, counts[blk], (p, q, s_, cls, viol), kept, passes, blk + 1)
+
+    def stub_bounds(ctx, src, blk, lower, upper, minv, max_cuts, count, p, q, cls, viol, kept, passes):
+        calls.append(("bounds", blk, lower, upper, minv, max_cuts))
+        return fill(bnd_lists[blk][:max_cuts], count, counts[blk], (p, q, cls, viol), kept, passes, 1)
+
+    s = host.Session.open(path)   # (the product's host library and a table of stubs alone: no oracle, no backend)
+    s.set_params(verbose=0)
+    s.prepare(1, 0)
+    st = host.BackendStruct()
+    types = dict(host.BackendStruct._fields_)
+    keep = (types["set_mat"](lambda ctx, which, k, ptr: 0), types["triangle_cuts"](stub_cuts),
+            types["entry_bounds"](stub_bounds))   # (alive as long as the table is)
+    st.name = b"stub"
+    st.set_mat, st.triangle_cuts, st.entry_bounds = keep
+    s.attach(st)
+    try:
+        all_cuts = sorted([(k,) + r for k in range(3) for r in cut_lists[k]], key=lambda r: (-r[5],) + r[:5])
+        all_bnds = sorted([(k,) + r for k in range(3) for r in bnd_lists[k]], key=lambda r: (-r[4],) + r[:4])
+        assert [r[0] for r in all_cuts[:6]] == [1, 0, 1, 1, 2, 0] and [r[5] for r in all_cuts[:6]] == [0.75, 0.5, 0.5, 0.5, 0.5, 0.25]
+        for max_cuts in (6, 4, 1, 100):
+            c = s.triangle_cuts(max_cuts=max_cuts, min_violation=0.03125)
+            got = list(zip(c.cone.tolist(), c.p.tolist(), c.q.tolist(), c.s.tolist(), c.cls.tolist(), c.violation.tolist()))
+            assert got == all_cuts[:max_cuts], (max_cuts, got)
+            assert c.count.tolist() == counts and len(c) == min(max_cuts, 10) and c.passes == 6 and c.max_cuts == max_cuts
+            b = s.entry_bounds(max_cuts=max_cuts, lower=-0.5, upper=0.25, min_violation=0.03125)
+            got = list(zip(b.cone.tolist(), b.p.tolist(), b.q.tolist(), b.cls.tolist(), b.violation.tolist()))
+            assert got == all_bnds[:max_cuts], (max_cuts, got)
+            assert b.count.tolist() == counts and len(b) == min(max_cuts, 10) and b.passes == 3 and b.max_cuts == max_cuts
+            assert b.bound.tolist() == [0.25 if cl else -0.5 for cl in b.cls.tolist()]
+        assert calls[:3] == [("cuts", k, 0.03125, 6) for k in range(3)]
+        assert calls[3:6] == [("bounds", k, -0.5, 0.25, 0.03125, 6) for k in range(3)]
+    finally:
+        s.close()
+    del keep
