@@ -327,6 +327,11 @@ int lorads_hip_sync(lorads_hip_ctx *ctx);
  * enqueued ahead, taken by the next lorads_hip_admm_step, discarded (the caller did something other than lorads_hip_update_dual_var
  * and lorads_hip_admm_step with the same rho), blocked by their gate (the step's V-solve resumed: they wrote nothing)} */
 int lorads_hip_spec_front_stats(lorads_hip_ctx *ctx, int64_t out[4]);
+/* the rows per workgroup of the two row-tile gather kernels (k_front_cw, k_spmm_ell) on cone `block`: out = {rows per workgroup,
+ * grid, compute units dealt over}.  LORADS_ROW_DEAL, read at creation: unset or "auto" deals a cone of more than 32 rows per
+ * compute unit evenly, 0 keeps 32 rows per workgroup, 1..32 forces that many for every cone (a test switch: a cone for which that
+ * many rows would give more workgroups than a partial-sum slot holds keeps 32, as `out` then shows).  Leaves a front in flight alone. */
+int lorads_hip_row_deal_stats(lorads_hip_ctx *ctx, int32_t block, int out[3]);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,7 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
     hipEvent_t e0, e1;
     HC(hipEventCreate(&e0)); HC(hipEventCreate(&e1));
     const int grow = nblocks_for((size_t)B.n, TPB / 8), gcw = nblocks_for((size_t)B.nrow, TPB / 64);
+    const RowDeal rd = row_deal_of(c, B); // (the two row-tile gather kernels as the solve launches them)
     for (int it = -3; it < reps; ++it) { // three warm-up launches
         if (it == 0) HC(hipEventRecord(e0, c->stream));
         switch (which) {
@@ -47,10 +48,10 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
         case 1: LAUNCH((k_cw<4, true, 5, true>), gcw, B.nrow, B.a_ptr, B.ca_row, B.ca_val, B.ca_col, U, V, B.r, 1.0, B.w_op,
                        (double *)nullptr, (int)CV_SET, B.row_idx, (double *)nullptr, NOGUARD, B.ca_ell, InitArgs{}, ResArgs{}); break;
         case 2:
-            if (B.cell_w == 8) LAUNCH((k_spmm_ell<8, true, 3, 8>), grow, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
+            if (B.cell_w == 8) LAUNCH((k_spmm_ell<8, true, 3, 8>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
                                       B.cell_con, B.cell_a, (const double *)B.w_op, V, B.r, (int)OP_CG, U, (const double *)nullptr, Q,
                                       part_slot(c, 0), NOGUARD);
-            else LAUNCH((k_spmm_ell<8, true, 3, 16>), grow, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col, B.cell_con,
+            else LAUNCH((k_spmm_ell<8, true, 3, 16>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col, B.cell_con,
                         B.cell_a, (const double *)B.w_op, V, B.r, (int)OP_CG, U, (const double *)nullptr, Q, part_slot(c, 0), NOGUARD);
             break;
         case 30: case 31: { // the one-kernel front (31: without the second visit of the slots), weights of a plain W_ADMM front
@@ -61,8 +62,8 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
             A.csum = c->csum; A.b = c->b; A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_op;
             A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = 1.0; A.wmode = W_ADMM;
             A.contrib = which == 30 ? B.w_contrib : (double *)nullptr;
-            if (B.cell_w == 8) LAUNCH((k_front_cw<3, 8>), grow, B.n, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
-            else LAUNCH((k_front_cw<3, 16>), grow, B.n, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
+            if (B.cell_w == 8) LAUNCH((k_front_cw<3, 8>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
+            else LAUNCH((k_front_cw<3, 16>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
         } break;
         case 32: LAUNCH(k_wsum, nblocks_for((size_t)B.nrow, TPB / 8), B.nrow, B.cs_w, (const double *)B.w_contrib, B.w_op, NOGUARD, InitArgs{}, 0, DS(0.0),
                         c->m, (const double *)c->b, (const double *)c->csum, c->lambda); break;

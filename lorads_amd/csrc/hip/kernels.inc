@@ -775,7 +775,7 @@ __device__ __forceinline__ double cg_wacc(double wa, double alpha, double wp) { 
 __device__ __forceinline__ double cg0_alpha(double rr, double ww) { return rr / (rr + ww); }
 
 template <int LG, bool V2, int NS, int EW, bool CG0 = false>
-__global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,
+__global__ __launch_bounds__(TPB) void k_spmm_ell(int n, int rpw, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,
                                                   const int *__restrict__ adj_con, const double *__restrict__ adj_a,
                                                   const int *__restrict__ ell_col, const int *__restrict__ ell_con,
                                                   const double *__restrict__ ell_a, const double *__restrict__ wgt,
@@ -798,8 +798,9 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__
     constexpr int W = V2 ? 2 : 1;
     constexpr int NH = EW / 8;             // index words per lane
     constexpr int CH = NS <= 5 ? 4 : 2; // neighbour rows gathered per step (a step is skipped when the group has no such slots: 4.5 slots per row on average at the headline; 8 per step was 10.1 us, 4: 9.1 us, 2: 9.4 us)
-    const int row = (blockIdx.x * TPB + threadIdx.x) / LG, lane = threadIdx.x % LG;
-    const bool act = row < n;
+    // rpw rows per workgroup (row_deal; TPB / LG: every lane group holds one): a lane group beyond rpw is a row past n in every sense
+    const int grp = threadIdx.x / LG, row = blockIdx.x * rpw + grp, lane = threadIdx.x % LG;
+    const bool act = grp < rpw && row < n;
     const int rowc = act ? row : 0;
     const size_t base = (size_t)rowc * r;
     const size_t eb = (size_t)rowc * EW + (lane & 7);
@@ -807,7 +808,8 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, const int *__restrict__
     double ac[NH];
 #pragma unroll
     for (int h = 0; h < NH; ++h) { qc[h] = ell_col[eb + 8 * h]; kc[h] = ell_con[eb + 8 * h]; ac[h] = ell_a[eb + 8 * h]; }
-    const int t0 = adj_ptr[rowc], t1 = adj_ptr[rowc + 1]; // (both words exist for every clamped row: no predicated load)
+    const int t0 = adj_ptr[rowc], t1r = adj_ptr[rowc + 1]; // (both words exist for every clamped row: no predicated load)
+    const int t1 = act ? t1r : t0;                         // (an inactive group stays out of row 0's CSR tail)
     double xi[NS][W], rh[NS][W], acc[NS][W];
     Slice<LG, V2, NS>::load(xin + base, r, lane, xi);
     // (OP_CG: an L1 hit, never used; CG0: the row of x)
@@ -990,7 +992,7 @@ __device__ __forceinline__ void front_cw_weights(const FrontCwArgs &A, double rh
 // second visit takes them from there -- 53 % of the rows have no more than four slots, and the second gather of a slot row was a
 // quarter of the kernel's L1 misses (profiles/r03_front_cw_counters.json).  The same lanes write and read a slot's row: no barrier.
 template <int NS, int EW, int KC = 0>
-__global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const double *__restrict__ X, int r,
+__global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A, const double *__restrict__ X, int r,
                                                   const double *__restrict__ xin, double *__restrict__ out,
                                                   double *__restrict__ rhs_out, double *__restrict__ part,
                                                   double *__restrict__ part_b, Guard g, Deferred d) {
@@ -1003,14 +1005,16 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const do
     const double rho = dsv(A.rho), rho_dual = A.dual_on ? dsv(A.rho_dual) : 0.0;
     DefPriv dv{};
     if (d.st) dv = deferred_private(d);
-    const int row = (blockIdx.x * TPB + threadIdx.x) / LG, lane = threadIdx.x % LG, l8 = lane & 7;
-    const bool act = row < n;
+    // rpw rows per workgroup (row_deal): a lane group beyond rpw is a row past n in every sense (the LDS park keeps its 32 places)
+    const int grp = threadIdx.x / LG, row = blockIdx.x * rpw + grp, lane = threadIdx.x % LG, l8 = lane & 7;
+    const bool act = grp < rpw && row < n;
     const int rowc = act ? row : 0;
     const size_t base = (size_t)rowc * r;
     // level 1: the two lists' heads, this lane's slots, the row's own operands
     const int c0 = A.fc_ptr[rowc], c1e = act ? A.fc_ptr[rowc + 1] : c0;
-    const int a0 = A.sl_ptr[rowc], a1 = A.sl_ptr[rowc + 1];
-    const int cnt = act ? a1 - a0 : 0;
+    const int a0 = A.sl_ptr[rowc], a1r = A.sl_ptr[rowc + 1];
+    const int a1 = act ? a1r : a0; // (an inactive group stays out of row 0's CSR tails, in both visits)
+    const int cnt = a1 - a0;
     const size_t eb = (size_t)rowc * EW + l8;
     int qc[NH], kc[NH], dc[NH];
     double ac[NH];
@@ -1120,9 +1124,10 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, FrontCwArgs A, const do
     }
     // ---- second visit of the row's slots: contributions of the constraint values of (r0, X)
     // (A.contrib == null -- measurement only, lorads_hip_ubench -- leaves the visit out: what it costs is the difference)
-    // (rows past n are clamped to row 0: their lanes must not write row 0's tail contributions, which row 0's own lanes write)
+    // (inactive groups are clamped to row 0: their lanes must not write row 0's tail contributions, which row 0's own lanes
+    // write -- a1 = a0 for them, see above)
     const int cnt2 = A.contrib ? cnt : 0;
-    const int a1b = A.contrib && act ? a1 : a0;
+    const int a1b = A.contrib ? a1 : a0;
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
         if ((h == 0 && cnt2 > 0) || cnt2 > 8 * h) {

@@ -721,6 +721,10 @@ struct lorads_hip_ctx {
     bool opt_front_lds = true; // k_front_cw parks the first four slot rows in LDS for its second visit (LORADS_FRONT_LDS=0: gathered again)
     bool opt_front_cw = true; // k_front_cw + k_wsum instead of k_sval + k_spmm2<FRONT> + iteration 0's k_cw (LORADS_FRONT_CW=0: the latter)
     bool opt_fuse_cg0 = true; // CG iteration 0 of a front_cw_ok cone: the update inside k_spmm_ell (LORADS_FUSE_CG0=0: k_cg_update)
+    // rows per workgroup of k_front_cw and k_spmm_ell (row_deal; LORADS_ROW_DEAL, read at creation): -1 the rule, 0 always 32 (the
+    // launches as they were), 1..32 that many for every cone (tests).  row_deal_cus: the compute units the rule deals over (the
+    // device's; LORADS_ROW_DEAL_CUS pretends another count, tests only)
+    int opt_row_deal = -1, row_deal_cus = 0;
     bool pend_dual_virtual = false; // the pending dual update has already been USED (formed on the fly by k_front_cw) but not stored
     // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
     // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
@@ -807,6 +811,18 @@ inline DS ds_tol(const lorads_hip_ctx *c, double v) { return c->par_mode ? DS(c-
 inline DS ds_rho_dual(const lorads_hip_ctx *c, double v) { return c->par_mode ? DS(c->par + 2, v) : DS(v); }
 inline DS ds_maxit(const lorads_hip_ctx *c, int v) { return c->par_mode ? DS(c->par + 3, (double)v) : DS((double)v); }
 inline int nblocks_for(size_t items, int per_block) { return (int)((items + per_block - 1) / per_block); }
+// Rows per workgroup and grid of the two row-tile gather kernels (k_front_cw, k_spmm_ell at 8 lanes per row) on a device of `ncu`
+// compute units.  A grid of ceil(n / 32) workgroups that is no multiple of ncu lands as one generation in which some CUs hold one
+// workgroup more than the rest, and the launch lasts as long as the fullest CU: deal the rows over k ncu workgroups instead, k the
+// number of workgroups the fullest CU holds today.  A cone of up to 32 ncu rows keeps its 32 rows per workgroup.
+struct RowDeal { int rpw, grid; };
+inline RowDeal row_deal(size_t n, int ncu) {
+    const int g0 = nblocks_for(n, 32);
+    if (ncu <= 0 || g0 <= ncu) return RowDeal{32, g0};
+    const size_t k = ((size_t)g0 + ncu - 1) / ncu;
+    const int rpw = (int)std::min<size_t>(32, (n + k * ncu - 1) / (k * ncu));
+    return RowDeal{rpw, nblocks_for(n, rpw)};
+}
 // grid of the L-BFGS stage kernels: every workgroup re-sums the previous stage's partials, so keep them few
 inline int grid_lbfgs(size_t len);
 inline int grid1d(size_t len) {
@@ -903,6 +919,14 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->opt_front_cw = env_on("LORADS_FRONT_CW");
     c->opt_fuse_cg0 = env_on("LORADS_FUSE_CG0");
     c->opt_front_lds = env_on("LORADS_FRONT_LDS");
+    {
+        const char *v = getenv("LORADS_ROW_DEAL");
+        c->opt_row_deal = (!v || !v[0] || v[0] == 'a') ? -1 : std::max(0, std::min(32, atoi(v)));
+        int dev = 0;
+        HC(hipGetDevice(&dev));
+        HC(hipDeviceGetAttribute(&c->row_deal_cus, hipDeviceAttributeMultiprocessorCount, dev));
+        if (getenv("LORADS_ROW_DEAL_CUS")) c->row_deal_cus = std::max(1, atoi(getenv("LORADS_ROW_DEAL_CUS")));
+    }
     c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
     c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
@@ -1852,6 +1876,14 @@ int lorads_hip_presolve_stats(lorads_hip_ctx *c, int64_t stats[2]) {
 int lorads_hip_spec_front_stats(lorads_hip_ctx *c, int64_t out[4]) { // (leaves a front in flight alone: tests read it between steps)
     if (!c || !out) return fail_msg("spec_front_stats: bad argument");
     out[0] = c->n_spec_enq; out[1] = c->n_spec_adopt; out[2] = c->n_spec_discard; out[3] = c->n_spec_blocked;
+    return 0;
+}
+
+int lorads_hip_row_deal_stats(lorads_hip_ctx *c, int32_t k, int out[3]) { // (a statistics entry: leaves a front in flight alone)
+    if (!c || !out) return fail_msg("row_deal_stats: bad argument");
+    if (k < 0 || k >= c->nb) return fail_msg("bad block");
+    const RowDeal rd = row_deal_of(c, c->blk[k]);
+    out[0] = rd.rpw; out[1] = rd.grid; out[2] = c->row_deal_cus;
     return 0;
 }
 

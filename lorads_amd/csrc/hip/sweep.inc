@@ -101,6 +101,18 @@ int spmm_front(lorads_hip_ctx *c, const Block &B, const Pattern &P, const double
                               B.diag_only ? B.w_uv : (double *)nullptr));
     return grid;
 }
+// rows per workgroup and grid of k_front_cw and of k_spmm_ell at 8 lanes per row on cone B: fixed for the context's life (see
+// row_deal and lorads_hip_ctx::opt_row_deal).  The merged lockstep cone keeps 32 rows; so does a forced deal whose grid would not
+// fit a partial-sum slot.
+RowDeal row_deal_of(const lorads_hip_ctx *c, const Block &B) {
+    const size_t n = (size_t)std::max(B.n, 0);
+    if (c->opt_row_deal == 0 || &B == &c->merged) return RowDeal{32, nblocks_for(n, 32)};
+    if (c->opt_row_deal > 0) {
+        const int rpw = nblocks_for(n, c->opt_row_deal) <= c->maxpart ? c->opt_row_deal : 32;
+        return RowDeal{rpw, nblocks_for(n, rpw)};
+    }
+    return row_deal(n, c->row_deal_cus);
+}
 // epilogue(x + sum over (neighbour, constraint) slots of a w_i V_q): the operator's SpMM with the coefficients formed
 // from the constraint weights w
 // cg0 != null: CG iteration 0's update folded in (the CG0 form of k_spmm_ell: 16-byte rows, mode OP_CG, out unused, `part`
@@ -109,25 +121,27 @@ int spmm_cw(lorads_hip_ctx *c, const Block &B, const double *w, const double *X,
             double *out, double *part, Guard g, const Cg0Args *cg0 = nullptr) {
     const Shape sh = shape_for(B.r);
     const int grid = nblocks_for((size_t)B.n, TPB / sh.lg);
+    // k_spmm_ell: rows per workgroup and grid together -- at 8 lanes per row the rows dealt over the compute units, else TPB / lg rows
+    const RowDeal rd = sh.lg == 8 ? row_deal_of(c, B) : RowDeal{TPB / sh.lg, grid};
     if (cg0) {
         if (!B.cell_w || !sh.v2 || mode != OP_CG) { c->launch_err = "CG iteration 0 in the operator: no kernel form for this cone"; return 0; }
         if (B.cell_w == 8) {
-            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
+            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8, true>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
                                              B.cell_col, B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, (double *)nullptr, part, g, *cg0))
         } else {
-            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
+            NS_SWITCH(8, true, sh.ns, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16, true>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a,
                                              B.cell_col, B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, (double *)nullptr, part, g, *cg0))
         }
-        return grid;
+        return rd.grid;
     }
     if (B.cell_w && (mode == OP_CG || mode == OP_RES)) {
         if (B.cell_w == 8)
-            SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
+            SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
                                       B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g));
         else
-            SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
+            SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
                                       B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g));
-        return grid;
+        return rd.grid;
     }
     SHAPE_DISPATCH(sh, LAUNCH((k_spmm<LG_, V2_, NS_, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, w, X, B.r, mode, xin, rhs,
                               0.0, out, part, g, (const double *)nullptr, B.cadj_a));
@@ -585,15 +599,16 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     Block &B = *s.B;
     double *r = c->cr + B.off, *rhs = c->rhs + B.off;
     double *pA = part_slot(c, 18), *pB = part_slot(c, 1);
-    const int grid = nblocks_for((size_t)B.n, TPB / 8);
+    const RowDeal rd = row_deal_of(c, B);
+    const int grid = rd.grid;
     const int ns = (B.r + 15) / 16;
     // (LAUNCH would send a virtual dual update off as its own kernel: this launch is the one that uses it)
     const bool keep = c->pend_dual_virtual;
     c->pend_dual_virtual = false;
     FrontSample fs(c);
-#define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
+#define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, rd.rpw, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
     // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
-#define FCWL(NSV, EWV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4>), grid, sizeof(double2) * 32 * 4 * NSV * 8, B.n, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
+#define FCWL(NSV, EWV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4>), grid, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
     if (c->opt_front_lds && ns <= 3) {
         if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8); else if (ns == 2) FCWL(2, 8); else FCWL(3, 8); }
         else { if (ns == 1) FCWL(1, 16); else if (ns == 2) FCWL(2, 16); else FCWL(3, 16); }
@@ -979,7 +994,7 @@ bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol,
     c->virt_refresh = false;
     c->spec.reset = reset; c->spec.nreset = nreset;
     c->n_front++; // (as the launch would have counted it)
-    front_cw_started(c, s, nblocks_for((size_t)B.n, TPB / 8), tol);
+    front_cw_started(c, s, row_deal_of(c, B).grid, tol);
     return true;
 }
 

@@ -686,6 +686,14 @@ class Session:
         _check(lib.lorads_hip_spec_front_stats(ctx, out), "spec_front_stats")
         return dict(zip(["enqueued", "adopted", "discarded", "blocked"], [int(out[i]) for i in range(4)]))
 
+    def hip_row_deal_stats(self, blk=0):
+        """{rpw, grid, ncu}: rows per workgroup and grid of k_front_cw / k_spmm_ell on cone `blk`, compute units dealt over (LORADS_ROW_DEAL)"""
+        lib, ctx = self._hip()
+        out = (C.c_int * 3)()
+        lib.lorads_hip_row_deal_stats.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int)]
+        _check(lib.lorads_hip_row_deal_stats(ctx, blk, out), "row_deal_stats")
+        return dict(zip(["rpw", "grid", "ncu"], [int(out[i]) for i in range(3)]))
+
     def hip_graph_stats(self):
         """{captured, replayed, held, enabled} of the launch-chain replay (hipGraph) of this context"""
         lib, ctx = self._hip()
