@@ -332,6 +332,11 @@ int lorads_hip_spec_front_stats(lorads_hip_ctx *ctx, int64_t out[4]);
  * compute unit evenly, 0 keeps 32 rows per workgroup, 1..32 forces that many for every cone (a test switch: a cone for which that
  * many rows would give more workgroups than a partial-sum slot holds keeps 32, as `out` then shows).  Leaves a front in flight alone. */
 int lorads_hip_row_deal_stats(lorads_hip_ctx *ctx, int32_t block, int out[3]);
+/* which row outputs of those two kernels are stored through the L2 (write-through) instead of left dirty in it for the end-of-kernel
+ * release: the mask in effect.  LORADS_WT_STORES, read at creation: bit 0 the front's initial residual, 1 its right-hand side, 2 the
+ * slot contributions, 3 x and r of CG iteration 0 inside k_spmm_ell, 4 the average R written there, 5 the output of the plain
+ * k_spmm_ell; 0 = plain stores everywhere; unset = the default.  Results do not depend on it.  Leaves a front in flight alone. */
+int lorads_hip_wt_stores(lorads_hip_ctx *ctx, int *mask);
 
 #ifdef __cplusplus
 }

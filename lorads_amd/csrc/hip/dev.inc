@@ -62,6 +62,7 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
             A.csum = c->csum; A.b = c->b; A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_op;
             A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = 1.0; A.wmode = W_ADMM;
             A.contrib = which == 30 ? B.w_contrib : (double *)nullptr;
+            A.wt = c->opt_wt_stores;
             if (B.cell_w == 8) LAUNCH((k_front_cw<3, 8>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
             else LAUNCH((k_front_cw<3, 16>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
         } break;

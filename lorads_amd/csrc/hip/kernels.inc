@@ -26,6 +26,31 @@ struct Slice {
     }
 };
 
+// Row outputs written THROUGH the L2 (`sc1`; DESIGN.md 4 item 11, LORADS_WT_STORES): a plain store leaves its line dirty in the
+// XCD's L2 and the end-of-kernel release writes all of them back before the next kernel may start; a write-through store sends the
+// line on at once, beside the rest of the kernel.  `wt` is wave-uniform (a bit of a kernel argument: one scalar branch), `off` the
+// element offset from `p`.  The 16-byte form has no builtin with a 64-bit address, so it is one asm store; `s_nop 1` keeps the
+// next instruction off its data registers until the store has read them.  hipcc does not count the asm store in vmcnt, so its later
+// waits wait for more than it thinks, never for less.  No "memory" clobber (it would pin the gathers that follow behind the store):
+// what orders the store against the loads of the same bytes is its data, which is computed from them -- NO KERNEL LOADS, IN THE SAME
+// LAUNCH, BYTES IT STORED THIS WAY: k_front_cw writes out / rhs_out / contrib and reads none of them; the CG0 form of k_spmm_ell
+// reads its rows of x and r before it forms what it stores there, and R is written only; the plain form writes `out` only.
+enum { WT_R0 = 1, WT_RHS = 2, WT_CONTRIB = 4, WT_CG0 = 8, WT_AVG = 16, WT_OUT = 32, WT_ALL = 63,
+       WT_DEFAULT = WT_R0 | WT_RHS | WT_CG0 | WT_AVG }; // (measured at the headline: profiles/r08_write_through_ab.txt)
+__device__ __forceinline__ void store16(double *p, size_t off, double a, double b, bool wt) {
+    if (wt) {
+        typedef double d2v __attribute__((ext_vector_type(2)));
+        const d2v v = {a, b};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p + off), "v"(v));
+    } else {
+        *(double2 *)(p + off) = make_double2(a, b);
+    }
+}
+__device__ __forceinline__ void store8(double *p, size_t off, double a, bool wt) {
+    if (wt) __hip_atomic_store(p + off, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else p[off] = a;
+}
+
 // pair dot of one pattern entry, LG lanes: x_p.y_q + x_q.y_p (p != q) or x_p.y_p; all row loads issued first
 template <int LG, bool V2, int NS>
 __device__ __forceinline__ double pair_dot(const double *__restrict__ X, const double *__restrict__ Y, int p, int q, int r,
@@ -762,6 +787,7 @@ struct Cg0Args {
     CGState *shadow;
     const double *avg_other;      // avg_out != null: R = (avg_other + x) / 2
     double *avg_out;
+    int wt;                       // WT_* bits: which row outputs go through the L2 (store16; the plain form reads WT_OUT from here too)
 };
 // the update of one element, shared by k_cg_update and the CG0 form of k_spmm_ell (same arithmetic, same bits)
 struct CgElem { double x, r; };
@@ -848,24 +874,27 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, int rpw, const int *__r
             }
         }
     }
-    for (int t = t0 + EW; t < t1; t += 4) { // the rare row with more than EW slots: the rest of its CSR list
-        int q[4], e[4];
-        double aa[4];
+    // (slots per trip: four; two in the CG0 form, which holds the rows of x and r besides -- with four, hipcc kept the form at its
+    // four wavefronts per SIMD by waiting for every load of the trip on its own, and the headline has one such row)
+    constexpr int TU = CG0 ? 2 : 4;
+    for (int t = t0 + EW; t < t1; t += TU) { // the rare row with more than EW slots: the rest of its CSR list
+        int q[TU], e[TU];
+        double aa[TU];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < TU; ++u) {
             const int tt = t + u < t1 ? t + u : t1 - 1;
             q[u] = adj_col[tt];
             e[u] = adj_con[tt];
             aa[u] = adj_a[tt];
         }
-        double s4[4], v[4][NS][W];
+        double s4[TU], v[TU][NS][W];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < TU; ++u) {
             s4[u] = aa[u] * wgt[e[u]];
             Slice<LG, V2, NS>::load(X + (size_t)q[u] * r, r, lane, v[u]);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < TU; ++u) {
             const double su = t + u < t1 ? s4[u] : 0.0;
 #pragma unroll
             for (int c = 0; c < NS; ++c)
@@ -896,11 +925,11 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, int rpw, const int *__r
             }
             if (act && j0 < r) {
                 if (open) {
-                    if (V2) *(double2 *)(u.x + base + j0) = make_double2(xo[0], xo[W - 1]);
-                    else u.x[base + j0] = xo[0];
-                    if (u.store_r) {
-                        if (V2) *(double2 *)(u.r + base + j0) = make_double2(ro[0], ro[W - 1]);
-                        else u.r[base + j0] = ro[0];
+                    if (V2) store16(u.x, base + j0, xo[0], xo[W - 1], u.wt & WT_CG0);
+                    else store8(u.x, base + j0, xo[0], u.wt & WT_CG0);
+                    if (u.store_r) { // (its row of r was read at the top: xi)
+                        if (V2) store16(u.r, base + j0, ro[0], ro[W - 1], u.wt & WT_CG0);
+                        else store8(u.r, base + j0, ro[0], u.wt & WT_CG0);
                     }
                 }
                 if (u.avg_out && (open || avg_only)) {
@@ -909,9 +938,9 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, int rpw, const int *__r
                     for (int w = 0; w < W; ++w) ao[w] = open ? xo[w] : rh[c][w];
                     if (V2) {
                         const double2 o = *(const double2 *)(u.avg_other + base + j0);
-                        *(double2 *)(u.avg_out + base + j0) = make_double2(cg_avg(o.x, ao[0]), cg_avg(o.y, ao[W - 1]));
+                        store16(u.avg_out, base + j0, cg_avg(o.x, ao[0]), cg_avg(o.y, ao[W - 1]), u.wt & WT_AVG);
                     } else {
-                        u.avg_out[base + j0] = cg_avg(u.avg_other[base + j0], ao[0]);
+                        store8(u.avg_out, base + j0, cg_avg(u.avg_other[base + j0], ao[0]), u.wt & WT_AVG);
                     }
                 }
             }
@@ -932,8 +961,8 @@ __global__ __launch_bounds__(TPB) void k_spmm_ell(int n, int rpw, const int *__r
             else { v[w] = rh[c][w] - (xi[c][w] + a); local += v[w] * v[w]; }
         }
         if (GATE_OPEN && act && j0 < r) {
-            if (V2) *(double2 *)(out + base + j0) = make_double2(v[0], v[W - 1]);
-            else out[base + j0] = v[0];
+            if (V2) store16(out, base + j0, v[0], v[W - 1], u.wt & WT_OUT);
+            else store8(out, base + j0, v[0], u.wt & WT_OUT);
         }
     }
     const double t = block_sum(act ? local : 0.0, sh);
@@ -971,6 +1000,7 @@ struct FrontCwArgs {
     double *contrib;                  // [number of slots]
     CGState *reset;
     int nreset;
+    int wt;                           // WT_* bits: which outputs go through the L2 (store16 / store8)
 };
 __device__ __forceinline__ void front_cw_weights(const FrontCwArgs &A, double rho, double rho_dual, int i, double a, double &c1, double &c2) {
     const int g = A.row_idx ? A.row_idx[i] : i;
@@ -1118,8 +1148,8 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A,
             local += r0[c][w] * r0[c][w];
         }
         if (live && act && j0 < r) {
-            *(double2 *)(out + base + j0) = make_double2(r0[c][0], r0[c][1]);
-            *(double2 *)(rhs_out + base + j0) = make_double2(vb[0], vb[1]);
+            store16(out, base + j0, r0[c][0], r0[c][1], A.wt & WT_R0);
+            store16(rhs_out, base + j0, vb[0], vb[1], A.wt & WT_RHS);
         }
     }
     // ---- second visit of the row's slots: contributions of the constraint values of (r0, X)
@@ -1159,7 +1189,7 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A,
                     mine = l8 == u0 + u ? dsum : mine;
                 }
             }
-            if (live && l8 + 8 * h < cnt2) A.contrib[dc[h]] = ac[h] * mine;
+            if (live && l8 + 8 * h < cnt2) store8(A.contrib, (size_t)dc[h], ac[h] * mine, A.wt & WT_CONTRIB);
         }
     }
     for (int t = a0 + EW; t < a1b; ++t) {
@@ -1170,7 +1200,7 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A,
 #pragma unroll
             for (int w = 0; w < W; ++w) dsum += r0[c][w] * v[c][w];
         dsum = group_sum<LG>(dsum);
-        if (live && l8 == 0) A.contrib[A.sl_dst[t]] = A.sl_a[t] * dsum;
+        if (live && l8 == 0) store8(A.contrib, (size_t)A.sl_dst[t], A.sl_a[t] * dsum, A.wt & WT_CONTRIB);
     }
     double two[2] = {act ? local : 0.0, act ? local_b : 0.0};
     block_sum_n<2>(two, sh);

@@ -725,6 +725,9 @@ struct lorads_hip_ctx {
     // launches as they were), 1..32 that many for every cone (tests).  row_deal_cus: the compute units the rule deals over (the
     // device's; LORADS_ROW_DEAL_CUS pretends another count, tests only)
     int opt_row_deal = -1, row_deal_cus = 0;
+    // which row outputs of those two kernels are stored through the L2 (WT_* bits, store16 in kernels.inc; LORADS_WT_STORES, read at
+    // creation: a bit mask, 0 = plain stores everywhere)
+    int opt_wt_stores = WT_DEFAULT;
     bool pend_dual_virtual = false; // the pending dual update has already been USED (formed on the fly by k_front_cw) but not stored
     // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
     // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
@@ -927,6 +930,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
         HC(hipDeviceGetAttribute(&c->row_deal_cus, hipDeviceAttributeMultiprocessorCount, dev));
         if (getenv("LORADS_ROW_DEAL_CUS")) c->row_deal_cus = std::max(1, atoi(getenv("LORADS_ROW_DEAL_CUS")));
     }
+    if (getenv("LORADS_WT_STORES") && getenv("LORADS_WT_STORES")[0]) c->opt_wt_stores = atoi(getenv("LORADS_WT_STORES")) & WT_ALL;
     c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
     c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
@@ -1884,6 +1888,12 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *c, int32_t k, int out[3]) { // (a 
     if (k < 0 || k >= c->nb) return fail_msg("bad block");
     const RowDeal rd = row_deal_of(c, c->blk[k]);
     out[0] = rd.rpw; out[1] = rd.grid; out[2] = c->row_deal_cus;
+    return 0;
+}
+
+int lorads_hip_wt_stores(lorads_hip_ctx *c, int *mask) { // (a statistics entry: leaves a front in flight alone)
+    if (!c || !mask) return fail_msg("wt_stores: bad argument");
+    *mask = c->opt_wt_stores;
     return 0;
 }
 

@@ -135,12 +135,14 @@ int spmm_cw(lorads_hip_ctx *c, const Block &B, const double *w, const double *X,
         return rd.grid;
     }
     if (B.cell_w && (mode == OP_CG || mode == OP_RES)) {
+        Cg0Args wo{}; // (the plain form reads its store mask from here and nothing else)
+        wo.wt = c->opt_wt_stores;
         if (B.cell_w == 8)
             SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
-                                      B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g));
+                                      B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g, wo));
         else
             SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 16>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
-                                      B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g));
+                                      B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g, wo));
         return rd.grid;
     }
     SHAPE_DISPATCH(sh, LAUNCH((k_spmm<LG_, V2_, NS_, true>), grid, B.n, B.cadj_ptr, B.cadj_col, B.cadj_con, w, X, B.r, mode, xin, rhs,
@@ -592,6 +594,7 @@ FrontCwArgs front_cw_args(lorads_hip_ctx *c, const Block &B, double rho, int wmo
     A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_uv; A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = ds_rho(c, rho);
     A.wmode = wmode;
     A.contrib = B.w_contrib;
+    A.wt = c->opt_wt_stores;
     return A;
 }
 // ... and its launch for the solve `s` under gate `g`; returns its grid (= the number of partials it leaves in slots 18 and 1)
@@ -766,6 +769,7 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     const int nww = rule0 ? nblocks_for((size_t)B.nrow, TPB / 8) : 0;
     const bool fuse0 = rule0 && c->opt_fuse_cg0 && v2_avg;
     Cg0Args u{};
+    u.wt = c->opt_wt_stores;
     if (fuse0) {
         u.st = s.st; u.part_ww = pW; u.nww = nww; u.x = s.x; u.r = r; u.store_r = store_r;
         u.w_acc = rec ? B.w_uv : (double *)nullptr; u.w_p = B.w_op; u.nw = nw; u.shadow = shadow_of(c, s.st);

@@ -694,6 +694,14 @@ class Session:
         _check(lib.lorads_hip_row_deal_stats(ctx, blk, out), "row_deal_stats")
         return dict(zip(["rpw", "grid", "ncu"], [int(out[i]) for i in range(3)]))
 
+    def hip_wt_stores(self):
+        """the mask of row outputs that k_front_cw / k_spmm_ell store through the L2 in this context (LORADS_WT_STORES)"""
+        lib, ctx = self._hip()
+        out = C.c_int(-1)
+        lib.lorads_hip_wt_stores.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        _check(lib.lorads_hip_wt_stores(ctx, C.byref(out)), "wt_stores")
+        return int(out.value)
+
     def hip_graph_stats(self):
         """{captured, replayed, held, enabled} of the launch-chain replay (hipGraph) of this context"""
         lib, ctx = self._hip()
