@@ -10,11 +10,8 @@
 // the host-side state the captured enqueue left behind.  A speculation miss resumes launch by launch, as before.
 // LORADS_GRAPH=0 switches the replay off (tests compare the two bit for bit).
 struct MutSnap { // the host-side state an enqueue reads and writes
-    InitArgs pend_init; Guard pend_init_g;
-    Deferred pend_chk; Guard pend_chk_g;
-    lorads_hip_ctx::PendDir pend_dir;
-    lorads_hip_ctx::PendSegChk pend_segchk;
-    bool pend_dual, pend_dual_virtual, virt_refresh, avg_folded, final_pending, stage_clean, merged_t_uv;
+    Pending pend; // (saved whole; Pending::restore puts back the part an enqueue changes)
+    bool virt_refresh, avg_folded, final_pending, stage_clean, merged_t_uv;
     EvalFinalArgs final_args;
     double *lambda, *lambda_alt;
     int ls_np, head;
@@ -46,9 +43,8 @@ void graph_cache_free(lorads_hip_ctx *c) {
 }
 MutSnap snap_take(const lorads_hip_ctx *c) {
     MutSnap s;
-    s.pend_init = c->pend_init; s.pend_init_g = c->pend_init_g; s.pend_chk = c->pend_chk; s.pend_chk_g = c->pend_chk_g;
-    s.pend_dir = c->pend_dir; s.pend_segchk = c->pend_segchk;
-    s.pend_dual = c->pend_dual; s.pend_dual_virtual = c->pend_dual_virtual; s.virt_refresh = c->virt_refresh; s.avg_folded = c->avg_folded;
+    s.pend = c->pend;
+    s.virt_refresh = c->virt_refresh; s.avg_folded = c->avg_folded;
     s.final_pending = c->final_pending; s.stage_clean = c->stage_clean; s.merged_t_uv = c->merged.t_uv_valid;
     s.final_args = c->final_args;
     s.lambda = c->lambda; s.lambda_alt = c->lambda_alt;
@@ -60,9 +56,8 @@ MutSnap snap_take(const lorads_hip_ctx *c) {
     return s;
 }
 void snap_put(lorads_hip_ctx *c, const MutSnap &s) {
-    c->pend_init = s.pend_init; c->pend_init_g = s.pend_init_g; c->pend_chk = s.pend_chk; c->pend_chk_g = s.pend_chk_g;
-    c->pend_dir = s.pend_dir; c->pend_segchk = s.pend_segchk;
-    c->pend_dual = s.pend_dual; c->pend_dual_virtual = s.pend_dual_virtual; c->virt_refresh = s.virt_refresh; c->avg_folded = s.avg_folded;
+    c->pend.restore(s.pend);
+    c->virt_refresh = s.virt_refresh; c->avg_folded = s.avg_folded;
     c->final_pending = s.final_pending; c->stage_clean = s.stage_clean; c->merged.t_uv_valid = s.merged_t_uv;
     c->final_args = s.final_args;
     c->lambda = s.lambda; c->lambda_alt = s.lambda_alt;
@@ -73,13 +68,8 @@ void snap_put(lorads_hip_ctx *c, const MutSnap &s) {
         c->blk[k].wj_for = s.wj_for[k];
     }
 }
-// nothing but a dual update may be waiting when a step is replayed: the waiting scalar steps carry values (tolerances) in their
-// arguments, and every entry point that reads results has flushed them anyway
-bool snap_quiet(const MutSnap &s) {
-    return !s.pend_init.st && !s.pend_chk.st && !s.pend_dir.kind && !s.pend_segchk.on && !s.pend_dual_virtual && !s.final_pending;
-}
 void snap_key(const lorads_hip_ctx *c, const MutSnap &s, std::vector<uint64_t> &key) {
-    key.push_back((uint64_t)s.pend_dual | (uint64_t)s.virt_refresh << 1 | (uint64_t)s.avg_folded << 2 | (uint64_t)s.stage_clean << 3 |
+    key.push_back((uint64_t)s.pend.dual_owed_unused() | (uint64_t)s.virt_refresh << 1 | (uint64_t)s.avg_folded << 2 | (uint64_t)s.stage_clean << 3 |
                   (uint64_t)s.merged_t_uv << 4 | (uint64_t)c->has_merged << 5);
     key.push_back((uint64_t)(uintptr_t)s.lambda);
     key.push_back((uint64_t)(uintptr_t)s.lambda_alt);
@@ -104,7 +94,7 @@ bool graph_ok(const lorads_hip_ctx *c) {
 int step_params_mask(const lorads_hip_ctx *c, const double (&v)[4]) {
     int mask = 0;
     for (int k = 0; k < 4; ++k) {
-        if (k == 2 && !c->pend_dual && !c->pend_dual_virtual) continue; // (nobody reads it)
+        if (k == 2 && !c->pend.dual_owed()) continue; // (nobody reads it)
         if (!((c->par_valid >> k) & 1) || memcmp(&v[k], &c->par_h[k], sizeof(double)) != 0) mask |= 1 << k;
     }
     return mask;
@@ -124,7 +114,7 @@ bool graph_this_step(lorads_hip_ctx *c, double rho, double tol, int maxit) {
     return !hot;
 }
 int set_step_params(lorads_hip_ctx *c, double rho, double tol, int maxit) {
-    const double v[4] = {rho, tol, c->pend_dual_rho, (double)maxit};
+    const double v[4] = {rho, tol, c->pend.dual_rho_value(), (double)maxit};
     const int mask = step_params_mask(c, v);
     if (!mask) return 0;
     hipLaunchKernelGGL(k_set_par, dim3(1), dim3(1), 0, c->stream, c->par, v[0], v[1], v[2], v[3], mask);
@@ -139,7 +129,8 @@ int set_step_params(lorads_hip_ctx *c, double rho, double tol, int maxit) {
 template <class F>
 int graph_step(lorads_hip_ctx *c, std::vector<uint64_t> &key, F &&enqueue) {
     const MutSnap before = snap_take(c);
-    if (!snap_quiet(before)) return enqueue();
+    // nothing but a dual update may be waiting when a step is replayed (see Pending; every entry point that reads results has flushed the rest anyway)
+    if (!before.pend.at_rest_for_replay() || before.final_pending) return enqueue();
     if (!c->graphs) c->graphs = new GraphCache();
     snap_key(c, before, key);
     auto it = c->graphs->map.find(key);

@@ -320,7 +320,7 @@ extern "C" int lorads_hip_dual_infeasibility(lorads_hip_ctx *c, double tol, int3
                                              double *lam_min, int32_t *matvecs) {
     spec_touch(c);
     if (!c || !sum_neg || ncv < 2 || tol <= 0) return fail_msg("dual_infeasibility: bad argument");
-    flush_pending(c); // (a dual update still waiting for a carrier: the multipliers must be final here)
+    c->pend.flush(c); // (a dual update still waiting for a carrier: the multipliers must be final here)
     double acc = 0.0;
     std::vector<int> cones;
     std::vector<double> th((size_t)std::max(c->nb, 1), 0.0);

@@ -72,6 +72,7 @@
 #include <thread>
 #include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "lorads_hip.h"
@@ -485,6 +486,102 @@ struct GraphCache; // captured launch chains (graph.inc)
 struct PersistPlan; // the one-launch ADMM iteration of Max-Cut-type cones (persist.inc)
 struct LTeamPlan;   // the one-launch L-BFGS history update + direction of phase 1 (lbfgs_team.inc)
 
+// The one-workgroup scalar steps that wait for a carrier kernel (see InitArgs / Deferred; the table in DESIGN.md 4): whoever can
+// carry one takes it BEFORE its LAUNCH, under the rule named here; any other launch first sends them off as the kernels they
+// replace (flush).  Nothing else in the backend touches this state.  What needs the context is defined in pending.inc.
+class Pending {
+public:
+    // a direction update (k_cg_dir) waiting for the row-local operator that follows it (k_op_diag forms the rows of p itself)
+    struct Dir { int kind = 0; CGState *st = nullptr; double *r = nullptr, *p = nullptr; size_t len = 0; int gv = 0;
+                 const double *rs_part = nullptr; int rs_np = 0; Guard g{}; bool seg = false; int half = 0;
+                 const double *chk_part = nullptr; double chk_tol = 0; int chk_maxit = 0, chk_k = 0; // chk_*: lockstep test riding with the direction
+                 const double *rs_seg = nullptr; }; // rs_seg: lockstep restart's scalars riding with it (chk_tol / chk_maxit / chk_k set too)
+    struct SegChk { bool on = false; int half = 0, k = 0; const double *part = nullptr; double tol = 0; int maxit = 0;
+                    bool ride_res = false; }; // ride_res: the restart's residual pass that follows may take it (see take_on_op_diag)
+    struct SegInit { bool on = false; int half = 0; double tol = 0; Guard front{}; const double *part_rr = nullptr, *part_b = nullptr; };
+    // ---- the two questions about the whole state.  They differ on purpose.  LAUNCH asks the first: whatever flush() sends goes
+    // before a kernel that has not taken it.  The lockstep test is not among it: it is to wait across the update's launch for the
+    // operator kernel behind it, and the lockstep driver sends it where it knows that nothing will take it (flush_segchk).  The
+    // graph asks the second: a waiting start, test or direction holds the step's tolerance by value and a used-but-unstored dual
+    // update belongs to a front already enqueued, so no chain is keyed or replayed over them; an owed dual update is part of the
+    // key instead, and neither a lockstep start nor a separable commit waits where a replayed step begins (the start does not
+    // outlive enqueue_batched, nothing replays with an all-reduce hook).
+    bool must_flush() const { return init.st || chk.st || dir.kind || dual || dual_virtual || sep || seginit.on; }
+    bool at_rest_for_replay() const { return !init.st && !chk.st && !dir.kind && !segchk.on && !dual_virtual; }
+    // a replay puts back the part an enqueue changes (seginit: off at every save and restore, see above).  dual_rho is
+    // update_dual_var's alone, and the separable commit was never part of a snapshot: they stay as they are.
+    void restore(Pending from) { from.dual_rho = dual_rho; from.sep = sep; from.sep_with_obj = sep_with_obj; from.sep_ex = sep_ex; *this = from; }
+    // ---- posting: wait for a carrier (init, check: or, with LORADS_LAZY_SCALARS=0, go out at once as the kernel itself)
+    void post_init(lorads_hip_ctx *c, CGState *st, const double *part_rr, int nrr, const double *part_b, int nb, double tol, Guard front);
+    void post_check(lorads_hip_ctx *c, CGState *st, const double *part, int np, double tol, int maxit, Guard g);
+    void post_dir(const Dir &d) { dir = d; }
+    void post_segchk(const SegChk &t) { segchk = t; }
+    void post_seginit(const SegInit &t) { seginit = t; }
+    void post_dual(double rho) { dual = true; dual_rho = rho; }
+    void post_sep(int with_obj, const SepExtra &ex) { sep = true; sep_with_obj = with_obj; sep_ex = ex; }
+    // ---- the carrying rules: each takes what the kernel launched under gate `g` may carry, or returns "nothing"
+    // The start rides on the solve's own first kernel: skip gate = the solve, need gate = the front's.
+    InitArgs take_init_on(const Guard &g) { return (init.st && !chk.st && g.skip == &init.st->done && g.need == init_g.need) ? std::exchange(init, InitArgs{}) : InitArgs{}; }
+    // The test rides on a kernel of its own solve that carries the solve's own gate (k_op_diag: the k = 0 restart's residual).
+    Deferred take_check_on(const Guard &g) { return take_check(chk.st && !init.st && g.skip == &chk.st->done && g.need == chk_g.need); }
+    // The test rides on a kernel that waits for its solve and skips on nothing (the next front, k_sval, k_cw, k_refresh_w, k_average,
+    // the evaluation's first kernel): no start and no direction may be waiting, they would be sent off in front of the carrier.
+    // One function for two earlier spellings: four sites asked `!g.skip && g.need == &st->done`, four passed `need` alone and
+    // launched under Guard{nullptr, need} -- the same question.  Two of the latter (k_refresh_w, k_average) did not ask for
+    // `!dir.kind`.  They need not: a test and a direction wait together only between solve_iter_tail and the solve_iter_body that
+    // solve_iters runs right behind it, whose operator kernel takes or flushes both; every body posts its test AFTER that launch,
+    // and a tail outside solve_iters (a resume) starts from a flushed state: the host has just read the states.  So wherever
+    // those two sites are reached with a test waiting, dir.kind is 0 and the term changes nothing.
+    Deferred take_check_behind(const Guard &g) { return take_check(chk.st && !init.st && !dir.kind && !g.skip && g.need == &chk.st->done); }
+    // The test rides on k_cg_dir of its own solve, which needs its beta (no direction is waiting: this kernel is it).
+    Deferred take_check_of(const CGState *st) { return take_check(chk.st == st && !init.st); }
+    // k_op_diag: a direction update, the lockstep solves' start or a lockstep test marked for the restart's residual pass
+    DirArgs take_on_op_diag(lorads_hip_ctx *c, int mode, const double *xin, const Guard &g, int rows);
+    // lockstep sweep: iteration k's test, to ride with the direction update behind it (its partials, or null) ...
+    const double *take_segchk_part(int half, int k) {
+        return segchk_is(half, k) ? std::exchange(segchk, SegChk{}).part : nullptr;
+    }
+    bool segchk_rides_res(int half, int k) { return segchk_is(half, k) && (segchk.ride_res = true); } // ... or marked for the restart's residual pass
+    // the separable commit rides on a hand-over that has room for the scalars travelling with it
+    bool take_sep(int max_extra, int *with_obj, SepExtra *ex) {
+        if (!sep || sep_ex.n > max_extra) return false;
+        sep = false; *with_obj = sep_with_obj; *ex = sep_ex;
+        return true;
+    }
+    // ---- the dual update.  `dual`: owed, nobody has used it.  `dual_virtual`: a front has formed its weights from the updated
+    // multipliers on the fly, nobody has stored them.  Never both: update_dual_var flushes before it posts, and the second is only
+    // ever set in exchange for the first.  The owed update rides on the sweep's first front when that kernel is gated on nothing
+    // and no other scalar step waits (a flush would run them behind multipliers they were to see before).  What else the carrier
+    // must be -- a cone that sees every constraint, the weights' mode -- is the site's to ask; the lockstep front also asks for
+    // the last two terms.
+    bool dual_rides(const Guard &front, bool lockstep = false) const {
+        return dual && !front.need && !front.skip && !init.st && !chk.st && !dir.kind && (!lockstep || (!segchk.on && !dual_virtual));
+    }
+    bool dual_owed_unused() const { return dual && !dual_virtual; }
+    bool dual_owed() const { return dual || dual_virtual; } // ... in either form
+    bool dual_owed_at(double rho) const { return dual && memcmp(&dual_rho, &rho, sizeof(double)) == 0; }
+    double dual_rho_value() const { return dual_rho; }
+    double take_dual() { dual = false; return dual_rho; }                     // used and stored by the taker
+    double use_dual() { dual = false; dual_virtual = true; return dual_rho; } // used by the taker, stored later: by k_wsum ...
+    bool take_dual_used(double *rho) { const bool was = set_dual_used(false); if (was) *rho = dual_rho; return was; }
+    bool set_dual_used(bool on) { const bool was = dual_virtual; dual_virtual = on; return was; } // (... see launch_front_cw)
+    bool sep_waits() const { return sep; }
+    // ---- what nobody took: the same kernels, in the same order, as launches of their own (not counted in n_launch)
+    void flush(lorads_hip_ctx *c);
+    void flush_segchk(lorads_hip_ctx *c);
+private:
+    Deferred take_check(bool may) { return may ? std::exchange(chk, Deferred{}) : Deferred{}; }
+    bool segchk_is(int half, int k) const { return segchk.on && segchk.half == half && segchk.k == k; }
+    InitArgs init{}; Guard init_g{};   // a solve's start (flushed as k_cg_init)
+    Deferred chk{}; Guard chk_g{};     // a convergence test (flushed as k_cg_check)
+    Dir dir;                           // (flushed as k_cg_dir / k_cg_dir_seg, behind the tests it carries)
+    SegChk segchk;                     // lockstep sweep: iteration k's test (flush_segchk: k_cg_check_seg)
+    SegInit seginit;                   // lockstep sweep: the solves' start waiting for iteration 0's operator kernel (k_cg_init_seg)
+    bool dual = false, dual_virtual = false; // LORADSUpdateDualVar waiting for the first front of the next sweep (k_dual_update)
+    double dual_rho = 0.0;
+    bool sep = false; int sep_with_obj = 0; SepExtra sep_ex{}; // a separable evaluation's reduced scalars waiting for the hand-over (k_sep_commit)
+};
+
 } // namespace
 
 constexpr size_t LZ_PINNED = 256; // doubles of pinned read-back per Lanczos worker (covers ncv <= 126)
@@ -695,12 +792,8 @@ struct lorads_hip_ctx {
     bool opt_alm_fold_cv = true;             // ... where every constraint has one entry the pattern pass does the constraint pass's work (LORADS_ALM_FOLD_CV=0)
     bool opt_alm_fused_tail = true;          // ... and, behind it, shared passes for A(R R^T), q1, q2 and one closing workgroup (LORADS_ALM_FUSED_TAIL=0)
     bool use_publish = true;
-    // LORADSUpdateDualVar waiting for the first kernel of the next sweep (k_sval of the U-solve's front forms the weights
-    // from the updated multipliers and stores them to lambda_alt, then the two vectors swap); sent off as k_dual_update
-    // by flush_pending if anything else comes first
-    bool pend_dual = false;
-    double pend_dual_rho = 0.0;
-    double *lambda_alt = nullptr;
+    Pending pend;             // the scalar steps that wait for a carrier kernel: the only owner of that state
+    double *lambda_alt = nullptr; // a front that carries the waiting dual update stores the new multipliers here, then the two vectors swap
     bool virt_refresh = false; // the V-solve's front forms its weights as if the refresh after the U-solve had been stored (see enqueue_sweep)
     bool opt_entry_bip = true; // single-entry cones with a bipartite entry graph: k_op_entry_bip x 2 (LORADS_ENTRY_BIP=0: k_op_entry)
     bool opt_fuse_dir = true; // Max-Cut-type cones: the direction update inside the operator kernel (LORADS_FUSE_DIR=0: k_cg_dir)
@@ -728,7 +821,6 @@ struct lorads_hip_ctx {
     // which row outputs of those two kernels are stored through the L2 (WT_* bits, store16 in kernels.inc; LORADS_WT_STORES, read at
     // creation: a bit mask, 0 = plain stores everywhere)
     int opt_wt_stores = WT_DEFAULT;
-    bool pend_dual_virtual = false; // the pending dual update has already been USED (formed on the fly by k_front_cw) but not stored
     // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
     // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
     bool opt_spec_front = true;
@@ -749,20 +841,7 @@ struct lorads_hip_ctx {
     double *scal = nullptr;   // 64 device scalars
     CGState *st = nullptr;    // one per (cone, half)
     CGState *st_shadow = nullptr; // state before a pending convergence test (see Deferred)
-    InitArgs pend_init{};     // a solve's start waiting for the kernel that will carry it (flushed as k_cg_init otherwise)
-    Guard pend_init_g{};
-    Deferred pend_chk{};      // a convergence test waiting likewise (flushed as k_cg_check otherwise)
-    Guard pend_chk_g{};
     bool opt_lazy_scalars = true; // LORADS_LAZY_SCALARS=0: every scalar step as its own launch
-    // a direction update (k_cg_dir) waiting for the row-local operator that follows it (k_op_diag forms the rows of p
-    // itself); sent off as its own launch if anything else comes first
-    struct PendDir { int kind = 0; CGState *st = nullptr; double *r = nullptr, *p = nullptr; size_t len = 0; int gv = 0;
-                     const double *rs_part = nullptr; int rs_np = 0; Guard g{}; bool seg = false; int half = 0;
-                     const double *chk_part = nullptr; double chk_tol = 0; int chk_maxit = 0, chk_k = 0; // chk_*: lockstep test riding with the direction
-                     const double *rs_seg = nullptr; } pend_dir; // rs_seg: lockstep restart's scalars riding with it (chk_tol / chk_maxit / chk_k set too)
-    struct PendSegChk { bool on = false; int half = 0, k = 0; const double *part = nullptr; double tol = 0; int maxit = 0;
-                        bool ride_res = false; } pend_segchk; // ride_res: the restart's residual pass that follows may take it (see op_diag)
-    struct PendSegInit { bool on = false; int half = 0; double tol = 0; Guard front{}; const double *part_rr = nullptr, *part_b = nullptr; } pend_seginit; // lockstep sweep: the solves' start waiting for iteration 0's operator kernel
     bool opt_seg_carry_init = true; // (LORADS_SEG_CARRY_INIT=0: k_cg_init_seg as a launch of its own)
     // separable shards: the evaluation's four scalars summed by the ranks' hosts after the hand-over (lorads_hip_set_scalar_exchange)
     lorads_hip_scalar_exchange_fn sx = nullptr;
@@ -788,9 +867,6 @@ struct lorads_hip_ctx {
     bool sep = false; // lorads_hip_set_separable: this context holds one rank's own constraints; only scalars cross the ranks
     double *sepbuf = nullptr; // 32: scalars on their way through the all-reduce in that mode
     SepExtra sep_extra{};     // scalars the next evaluation's all-reduce also carries (set by the caller, taken by enqueue_eval)
-    bool sep_pending = false; // the reduced scalars of a separable evaluation wait for the hand-over kernel to commit them (k_publish_sep)
-    int sep_with_obj = 0;
-    SepExtra sep_ex{};
     double *gram = nullptr;   // 128: [0..66) products V_a.V_b of the Gram-form L-BFGS direction, [80..91) the coefficients of D
     bool opt_gram = true;     // LORADS_LBFGS_GRAM=0: sharded direction by the sequential recursion, one collective per dot
     bool opt_gram_single = false; // LORADS_LBFGS_GRAM=2: the Gram-form direction on a single GPU as well
@@ -802,7 +878,7 @@ struct lorads_hip_ctx {
     long n_matvec = 0, n_cg_it = 0, n_solves = 0, n_samp = 0, n_samp_spmm = 0, n_resume = 0;
     double ms_samp = 0, ms_samp_spmm = 0;
     std::vector<float> samp_ms; // every timed operator application of the current profiling window
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pend_mv, pend_sp;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> timed_mv, timed_sp; // event pairs of a profiling window, read by drain_events
     std::vector<hipEvent_t> ev_pool; // pre-created (hipEventCreate is too slow for the timed region)
     size_t ev_next = 0;
 };
@@ -1022,7 +1098,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
 
 int lorads_hip_sync(lorads_hip_ctx *c) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1038,7 +1114,7 @@ int lorads_hip_set_allreduce(lorads_hip_ctx *c, lorads_hip_allreduce_fn fn, void
 int lorads_hip_set_scalar_exchange(lorads_hip_ctx *c, lorads_hip_scalar_exchange_fn fn, void *user) {
     spec_touch(c);
     if (!c) return fail_msg("set_scalar_exchange: no context");
-    if (c->sx_pending || c->sep_pending) { // (an evaluation's sums are still on their way: finish that hand-over under the old rule first)
+    if (c->sx_pending || c->pend.sep_waits()) { // (an evaluation's sums are still on their way: finish that hand-over under the old rule first)
         if (read_states(c)) return 1;
     }
     c->sx = fn; c->sx_user = user;
@@ -1046,7 +1122,7 @@ int lorads_hip_set_scalar_exchange(lorads_hip_ctx *c, lorads_hip_scalar_exchange
 }
 int lorads_hip_set_separable(lorads_hip_ctx *c, int32_t on) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     c->sep = on != 0;
     if (c->sep && !c->sepbuf && c->mem.alloc(&c->sepbuf, 32)) return 1;
     return 0;
@@ -1408,7 +1484,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
             ca.part_ls = part_slot(c, 10); ca.nls = nls; ca.pstride = c->maxpart;
             ca.obj1 = part_slot(c, 4); ca.obj2 = part_slot(c, 6); ca.nobj = go;
             ca.rinv = 1.0 / rho; ca.scal = c->scal; ca.q12_tail = c->q12 + 2 * (size_t)c->m;
-            flush_pending(c);
+            c->pend.flush(c);
             flush_final(c);
             ++c->pub_seq;
             LAUNCH(k_alm_close, 1, ca, (const unsigned long long *)c->ctrl, 23, (unsigned long long *)c->h_ctrl_dev, c->h_flag_dev, c->seq_dev);
@@ -1445,7 +1521,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
         c->sep_extra.p[0] = c->scal + 8;
         c->sep_extra.p[1] = c->scal + 9;
         if (enqueue_eval(c, LORADS_HIP_PAIR_RR, nullptr, false)) return 1;
-        flush_pending(c); // (the reduced y.s must be committed before it is read)
+        c->pend.flush(c); // (the reduced y.s must be committed before it is read)
         hipLaunchKernelGGL(k_scalar_op, dim3(1), dim3(1), 0, c->stream, (int)SOP_BETA, c->scal + 9, c->ring_ab + 2 * hd, c->ring_ab + 2 * hd + 1,
                            c->scal + 10);
     } else if (lorads_hip_set_y_as_neg_grad(c) || lorads_hip_alm_update_var(c, tau) || enqueue_alm_grad(c, rho) ||
@@ -1519,15 +1595,14 @@ int lorads_hip_update_dual_var(lorads_hip_ctx *c, double rho) {
     c->ls_np = 0;
     // (a front enqueued ahead of its step has formed exactly ONE dual update on the fly: a second one finds the first stored)
     if (c->spec.live) { if (c->spec.dual_seen) spec_touch(c); else c->spec.dual_seen = true; }
-    // (see pend_dual; with sharded cones only the one-kernel front can take it: it needs no owner pairs, k_wsum stores all of lambda)
+    // (see Pending::post_dual; with sharded cones only the one-kernel front can take it: it needs no owner pairs, k_wsum stores all of lambda)
     // (lockstep sweep of a Max-Cut-type merged cone that sees every constraint: its U front takes it, see enqueue_batched)
     const bool merged_front = c->has_merged && c->opt_seg_carry_dual && c->merged.diag_only && c->merged.rc_w > 0 && c->merged.w_uv &&
                               c->merged.nrow == c->m && c->opt_front_diag && !c->opt_split_front && !shard_vec(c) && !getenv("LORADS_NO_BATCH");
     if (c->opt_lazy_scalars && c->lambda_alt && ((c->nb == 1 && (!shard_vec(c) || front_cw_ok(c, c->blk[0]))) || merged_front ||
                                                  (c->persist && !c->persist->failed && persist_eligible(c)))) {
-        flush_pending(c);
-        c->pend_dual = true;
-        c->pend_dual_rho = rho;
+        c->pend.flush(c);
+        c->pend.post_dual(rho);
         return 0;
     }
     LAUNCH(k_dual_update, nblocks_for((size_t)c->m, TPB), c->m, rho, c->b, c->csum, c->lambda);
@@ -1551,7 +1626,7 @@ static void invalidate_t(lorads_hip_ctx *c) {
 
 int lorads_hip_alm_to_admm(lorads_hip_ctx *c) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     invalidate_t(c);
     HC(hipMemcpyAsync(c->V, c->R, sizeof(double) * c->all_elem, hipMemcpyDeviceToDevice, c->stream));
     HC(hipMemcpyAsync(c->U, c->V, sizeof(double) * c->all_elem, hipMemcpyDeviceToDevice, c->stream));
@@ -1589,7 +1664,7 @@ int lorads_hip_scale_obj(lorads_hip_ctx *c, double s) {
 
 int lorads_hip_set_mat(lorads_hip_ctx *c, int32_t which, int32_t k, const double *cm) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     double *base = mat_base(c, which);
     if (!base || k < 0 || k >= c->nb) return fail_msg("set_mat: bad argument");
     persist_touch(c);
@@ -1607,7 +1682,7 @@ int lorads_hip_set_mat(lorads_hip_ctx *c, int32_t which, int32_t k, const double
 
 int lorads_hip_get_mat(lorads_hip_ctx *c, int32_t which, int32_t k, double *cm) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     double *base = mat_base(c, which);
     if (!base || k < 0 || k >= c->nb) return fail_msg("get_mat: bad argument");
     Block &B = c->blk[k];
@@ -1621,7 +1696,7 @@ int lorads_hip_get_mat(lorads_hip_ctx *c, int32_t which, int32_t k, double *cm) 
 
 int lorads_hip_set_vec(lorads_hip_ctx *c, int32_t which, const double *v) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     c->ls_np = 0;
     double *d = vec_base(c, which);
     if (!d) return fail_msg("set_vec: bad argument");
@@ -1632,7 +1707,7 @@ int lorads_hip_set_vec(lorads_hip_ctx *c, int32_t which, const double *v) {
 
 int lorads_hip_get_vec(lorads_hip_ctx *c, int32_t which, double *v) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     double *d = vec_base(c, which);
     if (!d) return fail_msg("get_vec: bad argument");
     HC(hipMemcpyAsync(v, d, sizeof(double) * (size_t)c->m, hipMemcpyDeviceToHost, c->stream));
@@ -1642,7 +1717,7 @@ int lorads_hip_get_vec(lorads_hip_ctx *c, int32_t which, double *v) {
 
 int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     persist_touch(c);
     // AUG_RANK (data/lorads_solver.c:806-906): keep the old columns, new columns = 1/sqrt(k) on their
     // leading diagonal (lpRandomDiag :776-786), clear L-BFGS history and CG workspaces.  Everything stays in HBM: the new
@@ -1687,7 +1762,7 @@ int lorads_hip_resize_rank(lorads_hip_ctx *c, const int32_t *nr) {
 
 int lorads_hip_profile(lorads_hip_ctx *c, int32_t enable, int32_t every) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
     c->prof = enable;
@@ -1712,7 +1787,7 @@ int lorads_hip_profile_target(lorads_hip_ctx *c, int32_t target) {
 
 int lorads_hip_profile_samples(lorads_hip_ctx *c, double *out, int32_t cap, int32_t *n) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
     *n = (int32_t)c->samp_ms.size();
@@ -1722,7 +1797,7 @@ int lorads_hip_profile_samples(lorads_hip_ctx *c, double *out, int32_t cap, int3
 
 int lorads_hip_profile_read(lorads_hip_ctx *c, double s[8]) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     drain_events(c);
     s[0] = (double)c->n_matvec;
@@ -1742,7 +1817,7 @@ int lorads_hip_time_operator(lorads_hip_ctx *c, int32_t reps, double *ms) {
     spec_touch(c);
     if (c->nb < 1) return fail_msg("time_operator: no cone");
     Block &B = c->blk[0];
-    flush_pending(c);
+    c->pend.flush(c);
     hipEvent_t e0, e1;
     HC(hipEventCreate(&e0)); HC(hipEventCreate(&e1));
     const int prof0 = c->prof;
@@ -1827,7 +1902,7 @@ int lorads_hip_persist_set_tag(lorads_hip_ctx *c, uint32_t tag) {
     spec_touch(c);
     if (!c->persist || !c->persist->valid) return fail_msg("persist_set_tag: no plan of the one-launch ADMM iteration is valid");
     PersistPlan &P = *c->persist;
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     // (granules of earlier launches carry earlier tags: a tag set below them must not meet one of its own values)
     HC(hipMemset(P.gran, 0, sizeof(unsigned long long) * std::max<size_t>(P.gran_words, 1)));
@@ -1858,7 +1933,7 @@ int lorads_hip_lbfgs_team_stats(lorads_hip_ctx *c, int64_t stats[4]) {
 
 int lorads_hip_persist_stamps(lorads_hip_ctx *c, int32_t enable, uint64_t ticks[16]) {
     spec_touch(c);
-    flush_pending(c);
+    c->pend.flush(c);
     HC(hipStreamSynchronize(c->stream));
     for (int i = 0; i < 16; ++i) ticks[i] = 0;
     if (c->persist && c->persist->valid && c->persist->stamps && c->persist_stamps) {

@@ -990,10 +990,9 @@ bool persist_ready(lorads_hip_ctx *c, int maxit) {
 int run_sweep_persist(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_eval) {
     PersistPlan &P = *c->persist;
     // the dual update of the previous iteration rides on the U front (the rows store their constraints' new multipliers in place)
-    const bool dual_on = c->pend_dual && !c->pend_dual_virtual;
-    const double rho_dual = c->pend_dual_rho;
-    if (dual_on) c->pend_dual = false;
-    flush_pending(c);
+    const bool dual_on = c->pend.dual_owed_unused();
+    const double rho_dual = dual_on ? c->pend.take_dual() : c->pend.dual_rho_value();
+    c->pend.flush(c);
     flush_final(c);
     c->avg_folded = false;
     if (P.tag > 0xffffffffu - 4u * PK_TAGS_PER_LAUNCH) { // (tags about to wrap: start over on a clean slate)
@@ -1033,7 +1032,7 @@ int run_sweep_persist(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
     if (samp) { e0 = c->ev_pool[c->ev_next++]; e1 = c->ev_pool[c->ev_next++]; hipEventRecord(e0, c->stream); }
     ++c->n_launch;
     hipLaunchKernelGGL(pk_kernel(P.ns, P.rows), dim3(P.grid), dim3(TPB), P.lds, c->stream, A);
-    if (samp) { hipEventRecord(e1, c->stream); c->pend_mv.push_back({e0, e1}); }
+    if (samp) { hipEventRecord(e1, c->stream); c->timed_mv.push_back({e0, e1}); }
     if (c->shared_gpu_fd >= 0) {
         (void)hipStreamSynchronize(c->stream);
         flock(c->shared_gpu_fd, LOCK_UN);
@@ -1042,7 +1041,7 @@ int run_sweep_persist(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
     for (auto &B : c->blk) { B.t_uv_valid = false; B.wj_for = nullptr; B.w0_ready = false; }
     if (dev_sum) {
         if (allreduce_dev(c, c->sepbuf, 4)) return 1;
-        c->sep_pending = true; c->sep_with_obj = 1; c->sep_ex = SepExtra{};
+        c->pend.post_sep(1, SepExtra{});
         if (enqueue_publish(c, 0, state_words(c))) return 1;
     } else {
         ++c->pub_seq;

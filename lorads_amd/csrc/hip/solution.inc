@@ -167,9 +167,9 @@ int cert_alloc(lorads_hip_ctx *c) {
 void cert_lambda(lorads_hip_ctx *c) {
     if (c->m == 0) return;
     hipMemcpyAsync(c->cert.lam, c->lambda, sizeof(double) * (size_t)c->m, hipMemcpyDeviceToDevice, c->stream);
-    if (c->pend_dual || c->pend_dual_virtual)
+    if (c->pend.dual_owed())
         hipLaunchKernelGGL(k_dual_update, dim3(nblocks_for((size_t)c->m, TPB)), dim3(TPB), 0, c->stream, c->m,
-                           ds_rho_dual(c, c->pend_dual_rho), (const double *)c->b, (const double *)c->csum, c->cert.lam);
+                           ds_rho_dual(c, c->pend.dual_rho_value()), (const double *)c->b, (const double *)c->csum, c->cert.lam);
 }
 
 // S_k = C_k - sum_i lambda_i A_ik into the scratch: the union pattern's values (k_sval, W_DUAL) and, on a cone with dense constraint

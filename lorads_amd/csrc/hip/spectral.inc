@@ -337,7 +337,7 @@ extern "C" int lorads_hip_compress_rank(lorads_hip_ctx *c, int32_t src, const in
                                 nullptr, qoff);
         if (rc) return rc;
     }
-    flush_pending(c);
+    c->pend.flush(c);
     persist_touch(c);
     double *old[3] = {c->R, c->U, c->V};
     DevPool old_mem; // the old arrays live until the kernels below have read them, and go on every way out

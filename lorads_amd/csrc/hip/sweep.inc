@@ -2,31 +2,16 @@
 // evaluation and the result hand-over (included by lorads_hip.hip inside its anonymous namespace).
 // ---- launch helpers
 // (an empty grid -- a cone without constraints, an empty pattern -- is simply nothing to do, not a refused launch)
-// Scalar steps waiting for a carrier kernel (see InitArgs / Deferred): whoever can carry them takes them BEFORE its
-// LAUNCH; any other launch first sends them off as the one-workgroup kernels they replace.
-void flush_pending(lorads_hip_ctx *c);
-#define LAUNCH(kern, grid, ...)                                                                      \
-    do {                                                                                             \
-        const int grid__ = (int)(grid);                                                              \
-        if (c->pend_init.st || c->pend_chk.st || c->pend_dir.kind || c->pend_dual || c->pend_dual_virtual || c->sep_pending || c->pend_seginit.on) flush_pending(c); \
-        if (grid__ > 0) { ++c->n_launch; hipLaunchKernelGGL(kern, dim3(grid__), dim3(TPB), 0, c->stream, __VA_ARGS__); } \
-    } while (0)
+// Scalar steps waiting for a carrier kernel (class Pending): whoever can carry them takes them BEFORE its LAUNCH; any other
+// launch first sends them off as the one-workgroup kernels they replace.
 #define LAUNCH_LDS(kern, grid, lds, ...)                                                             \
     do {                                                                                             \
         const int grid__ = (int)(grid);                                                              \
-        if (c->pend_init.st || c->pend_chk.st || c->pend_dir.kind || c->pend_dual || c->pend_dual_virtual || c->sep_pending || c->pend_seginit.on) flush_pending(c); \
+        if (c->pend.must_flush()) c->pend.flush(c);                                                  \
         if (grid__ > 0) { ++c->n_launch; hipLaunchKernelGGL(kern, dim3(grid__), dim3(TPB), (size_t)(lds), c->stream, __VA_ARGS__); } \
     } while (0)
-inline InitArgs take_init(lorads_hip_ctx *c) {
-    const InitArgs ia = c->pend_init;
-    c->pend_init = InitArgs{};
-    return ia;
-}
-inline Deferred take_check(lorads_hip_ctx *c) {
-    const Deferred d = c->pend_chk;
-    c->pend_chk = Deferred{};
-    return d;
-}
+#define LAUNCH(kern, grid, ...) LAUNCH_LDS(kern, grid, 0, __VA_ARGS__)
+#include "pending.inc"
 
 // (LG, V2, NS) for a rank: 8 lanes x 16-byte loads when r is even and <= 128, else 8/32/64 lanes x 8-byte loads
 struct Shape {
@@ -158,12 +143,9 @@ int cw(lorads_hip_ctx *c, const Block &B, const double *X, const double *Y, doub
     if (B.nrow == 0) return 0;
     const Shape sh = shape_for(B.r);
     const int grid = nblocks_for((size_t)B.nrow, TPB / 64);
-    // a solve's start that is waiting rides on this kernel if it is the solve's own first kernel (same gate)
-    InitArgs ia{};
-    if (c->pend_init.st && !c->pend_chk.st && g.skip == &c->pend_init.st->done && g.need == c->pend_init_g.need) ia = take_init(c);
-    // a waiting convergence test whose solve this kernel waits for rides on it (nothing else pending, same gate)
-    const Deferred d = (!ia.st && c->pend_chk.st && !c->pend_init.st && !c->pend_dir.kind && !g.skip && g.need == &c->pend_chk.st->done)
-                           ? take_check(c) : Deferred{};
+    // a waiting start rides on this kernel if it is the solve's own first, a waiting test if this kernel waits for its solve
+    const InitArgs ia = c->pend.take_init_on(g);
+    const Deferred d = c->pend.take_check_behind(g);
     if (cw_quad(c, B)) { // 4 lanes per entry: a whole fixed-width constraint of 9..16 entries in one trip
         const int ns4 = (B.r + 7) / 8;
         NS_SWITCH(4, true, ns4, LAUNCH((k_cw<LG_, V2_, NS_, true>), grid, B.nrow, B.a_ptr, B.ca_row, B.ca_val, B.ca_col, X, Y, B.r,
@@ -176,7 +158,7 @@ int cw(lorads_hip_ctx *c, const Block &B, const double *X, const double *Y, doub
 }
 // W = C X on the matrix cores (dense objective only)
 int dense_cx(lorads_hip_ctx *c, const Block &B, const double *X, double *W, Guard g, const double *M = nullptr) {
-    flush_pending(c);
+    c->pend.flush(c);
     if (!M) M = B.Cfull; // (the dense objective; else: a dense constraint matrix or a combination of them)
     if (B.ksplit_b <= 0) return 1; // (n_pad is a multiple of 64: never)
     { // C as the MFMA B operand, K split inside the workgroup (see k_dense_cx_b)
@@ -272,35 +254,10 @@ int op_diag(lorads_hip_ctx *c, const Block &B, const double *V, int mode, const 
     // a waiting solve start rides on the solve's first operator application, a waiting convergence test on the
     // residual of the k = 0 restart (both carry the solve's own gate)
     Carry cy{};
-    DirArgs da{};
-    if (c->pend_init.st && !c->pend_chk.st && g.skip == &c->pend_init.st->done && g.need == c->pend_init_g.need) cy.ia = take_init(c);
-    else if (c->pend_chk.st && !c->pend_init.st && g.skip == &c->pend_chk.st->done && g.need == c->pend_chk_g.need) cy.d = take_check(c);
-    // a waiting direction update of the same solve whose output is this application's input: formed here, row by row
-    if (c->pend_dir.kind && !c->pend_init.st && !c->pend_chk.st && mode == OP_CG && xin == c->pend_dir.p &&
-        g.skip == c->pend_dir.g.skip && g.need == c->pend_dir.g.need) {
-        da = DirArgs{c->pend_dir.kind, c->pend_dir.r, c->pend_dir.p, c->pend_dir.st, c->pend_dir.rs_part, c->pend_dir.rs_np,
-                     c->pend_dir.seg ? c->seg_tile_cone : (const int *)nullptr, c->pend_dir.half,
-                     c->pend_dir.seg ? c->pend_dir.chk_part : (const double *)nullptr, (const int4 *)c->seg_tile_info, c->seg_rr_alt, ds_tol(c, c->pend_dir.chk_tol),
-                     ds_maxit(c, c->pend_dir.chk_maxit), c->pend_dir.chk_k + 1,
-                     c->pend_dir.seg ? c->pend_dir.rs_seg : (const double *)nullptr, (const int *)c->seg_row0, TPB / shape_for(B.r).lg};
-        c->pend_dir.kind = 0;
-        c->pend_dir.chk_part = nullptr;
-        c->pend_dir.rs_seg = nullptr;
-    } else if (c->pend_seginit.on && mode == OP_CG && xin == c->cr && !c->pend_init.st && !c->pend_chk.st && !c->pend_dir.kind &&
-               g.need == c->pend_seginit.front.need) {
-        // lockstep sweep: the start of every cone's solve rides on iteration 0's application (DirArgs, kind 0)
-        const auto pi = c->pend_seginit;
-        c->pend_seginit.on = false;
-        da = DirArgs{0, nullptr, nullptr, c->st, nullptr, 0, c->seg_tile_cone, pi.half, nullptr, (const int4 *)c->seg_tile_info, c->seg_rr_alt,
-                     DS(0.0), DS(0.0), 0, nullptr, (const int *)c->seg_row0, TPB / shape_for(B.r).lg,
-                     pi.part_rr, pi.part_b, ds_tol(c, pi.tol), c->phase_done};
-    } else if (c->pend_segchk.on && c->pend_segchk.ride_res && mode == OP_RES && !c->pend_init.st && !c->pend_chk.st && !c->pend_dir.kind) {
-        // lockstep sweep: iteration k's convergence test rides on the restart's residual pass (DirArgs, kind 0)
-        const auto pc = c->pend_segchk;
-        c->pend_segchk.on = false; c->pend_segchk.ride_res = false;
-        da = DirArgs{0, nullptr, nullptr, c->st, nullptr, 0, c->seg_tile_cone, pc.half, pc.part, (const int4 *)c->seg_tile_info, c->seg_rr_alt,
-                     ds_tol(c, pc.tol), ds_maxit(c, pc.maxit), pc.k + 1, nullptr, (const int *)c->seg_row0, TPB / shape_for(B.r).lg};
-    }
+    cy.ia = c->pend.take_init_on(g);
+    if (!cy.ia.st) cy.d = c->pend.take_check_on(g);
+    // a waiting direction update whose output is this application's input is formed here, row by row (see take_on_op_diag)
+    const DirArgs da = c->pend.take_on_op_diag(c, mode, xin, g, TPB / sh.lg);
     SHAPE_DISPATCH(sh, LAUNCH((k_op_diag<LG_, V2_, NS_>), grid, B.n, B.gdiag, V, B.r, mode, xin, rhs, out, part, g, cy, da, dot_out));
     return grid;
 }
@@ -367,8 +324,7 @@ void sval(lorads_hip_ctx *c, const Pattern &P, bool with_c, int mode, const WArg
           int nreset = 0, const double *w2 = nullptr, const int *econ = nullptr) {
     if (P.ne == 0 && !reset) return;
     // a waiting convergence test whose gate is this kernel's gate rides on it (the V-solve's front after a virtual refresh)
-    const Deferred d = (c->pend_chk.st && !c->pend_init.st && !c->pend_dir.kind && !g.skip && g.need == &c->pend_chk.st->done)
-                           ? take_check(c) : Deferred{};
+    const Deferred d = c->pend.take_check_behind(g);
     LAUNCH(k_sval, std::max(1, nblocks_for((size_t)P.ne, TPB)), P.ne, P.e_ptr, econ ? econ : P.e_con, P.e_val,
            with_c ? P.cbase : nullptr, mode, wa, P.S, g, reset, nreset, w2, w2 ? P.S2 : (double *)nullptr, d);
 }
@@ -376,11 +332,9 @@ void sval(lorads_hip_ctx *c, const Pattern &P, bool with_c, int mode, const WArg
 // the constraint weights of iteration 0's operator application from the contributions k_front_cw has left (see there)
 // (part_ww != null: also the partials of ||w||^2, one per workgroup, see Cg0Args)
 int wsum(lorads_hip_ctx *c, Block &B, Guard g, double *part_ww = nullptr) {
-    InitArgs ia{};
-    if (c->pend_init.st && !c->pend_chk.st && g.skip == &c->pend_init.st->done && g.need == c->pend_init_g.need) ia = take_init(c);
+    const InitArgs ia = c->pend.take_init_on(g);
     double rho_dual = 0.0;
-    int dual_on = 0;
-    if (c->pend_dual_virtual) { c->pend_dual_virtual = false; rho_dual = c->pend_dual_rho; dual_on = 1; } // this kernel stores the multipliers
+    const int dual_on = c->pend.take_dual_used(&rho_dual) ? 1 : 0; // this kernel stores the multipliers
     const int grid = nblocks_for((size_t)B.nrow, TPB / 8);
     // (behind an adopted front: the sweep's reset words, see spec_front_adopt)
     CGState *reset = c->spec.reset;
@@ -458,28 +412,28 @@ int apply_operator(lorads_hip_ctx *c, Block &B, const double *V, const double *x
     }
     if (samp) {
         hipEventRecord(e1, c->stream);
-        c->pend_mv.push_back({e0, e1});
-        if (e2) c->pend_sp.push_back({e2, e1});
+        c->timed_mv.push_back({e0, e1});
+        if (e2) c->timed_sp.push_back({e2, e1});
     }
     c->n_matvec++;
     return grid;
 }
 
 void drain_events(lorads_hip_ctx *c) {
-    for (auto &pr : c->pend_mv) {
+    for (auto &pr : c->timed_mv) {
         float ms = 0;
         hipEventSynchronize(pr.second);
         hipEventElapsedTime(&ms, pr.first, pr.second);
         c->ms_samp += ms; c->n_samp++;
         c->samp_ms.push_back(ms);
     }
-    for (auto &pr : c->pend_sp) {
+    for (auto &pr : c->timed_sp) {
         float ms = 0;
         hipEventElapsedTime(&ms, pr.first, pr.second);
         c->ms_samp_spmm += ms; c->n_samp_spmm++;
     }
-    c->pend_mv.clear();
-    c->pend_sp.clear();
+    c->timed_mv.clear();
+    c->timed_sp.clear();
     c->ev_next = 0;
 }
 
@@ -494,60 +448,6 @@ void drain_events(lorads_hip_ctx *c) {
 // solve variable), w_op[p] = p_p . V_p from k_op_diag, and constraint i = a_i e_p e_p^T has the value a_i w_uv[p].
 bool constr_by_recurrence(lorads_hip_ctx *c, const Block &B) {
     return (B.use_cw || (B.diag_only && B.w_uv && B.w_op && B.diag_row)) && !c->opt_exact_refresh && &B != &c->merged;
-}
-
-SegArgs seg_args(lorads_hip_ctx *c, int half, int k = 0);
-int seg_threads(lorads_hip_ctx *c);
-CGState *shadow_of(lorads_hip_ctx *c, CGState *st) { return c->st_shadow + (st - c->st); }
-void flush_pending(lorads_hip_ctx *c) {
-    if (c->sep_pending) { // the reduced scalars of separable shards wait for the hand-over (k_publish_sep); anything else first: their own launch
-        c->sep_pending = false;
-        hipLaunchKernelGGL(k_sep_commit, dim3(1), dim3(1), 0, c->stream, (const double *)c->sepbuf, c->scal, c->sep_with_obj, c->sep_ex);
-    }
-    if (c->pend_dual_virtual) { // k_front_cw has formed its weights from the updated multipliers; nobody has stored them yet
-        c->pend_dual_virtual = false;
-        hipLaunchKernelGGL(k_dual_update, dim3(nblocks_for((size_t)c->m, TPB)), dim3(TPB), 0, c->stream, c->m, ds_rho_dual(c, c->pend_dual_rho), c->b,
-                           c->csum, c->lambda);
-    }
-    if (c->pend_dual) { // first: everything else may read the multipliers
-        c->pend_dual = false;
-        hipLaunchKernelGGL(k_dual_update, dim3(nblocks_for((size_t)c->m, TPB)), dim3(TPB), 0, c->stream, c->m, ds_rho_dual(c, c->pend_dual_rho), c->b,
-                           c->csum, c->lambda);
-    }
-    if (c->pend_seginit.on) { // the lockstep solves' start that no operator kernel has taken
-        const auto pi = c->pend_seginit;
-        c->pend_seginit.on = false;
-        hipLaunchKernelGGL(k_cg_init_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, seg_args(c, pi.half), pi.part_rr, pi.part_b,
-                           ds_tol(c, pi.tol), pi.front);
-    }
-    if (c->pend_init.st) {
-        const InitArgs ia = take_init(c);
-        hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(TPB), 0, c->stream, ia.st, ia.part_rr, ia.nrr, ia.part_b, ia.nb, ia.tol,
-                           c->pend_init_g, ia.shadow);
-    }
-    if (c->pend_chk.st) {
-        const Deferred d = take_check(c);
-        hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(TPB), 0, c->stream, d.st, (int)CHK_ITER, d.part, d.np, d.tol, d.maxit,
-                           c->pend_chk_g);
-    }
-    if (c->pend_dir.kind) { // (after the test: the direction needs its beta)
-        const auto pd = c->pend_dir;
-        c->pend_dir.kind = 0;
-        if (pd.seg) {
-            if (pd.chk_part) // the convergence test that was to ride on the next operator kernel: its own launch after all
-                hipLaunchKernelGGL(k_cg_check_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, seg_args(c, pd.half, pd.chk_k), (int)CHK_ITER,
-                                   pd.chk_part, ds_tol(c, pd.chk_tol), ds_maxit(c, pd.chk_maxit), pd.g);
-            if (pd.rs_seg) // likewise the restart's scalars
-                hipLaunchKernelGGL(k_cg_check_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, seg_args(c, pd.half, pd.chk_k), (int)CHK_RESTART,
-                                   pd.rs_seg, ds_tol(c, pd.chk_tol), ds_maxit(c, pd.chk_maxit), pd.g);
-            c->pend_dir.rs_seg = nullptr;
-            hipLaunchKernelGGL(k_cg_dir_seg, dim3(c->seg_nvt), dim3(TPB), 0, c->stream, seg_args(c, pd.half), pd.kind, (const double *)pd.r,
-                               pd.p, pd.g);
-        }
-        else
-            hipLaunchKernelGGL(k_cg_dir, dim3(pd.gv), dim3(TPB), 0, c->stream, pd.len, pd.st, pd.kind, (const double *)pd.r, pd.p, pd.g,
-                               Deferred{}, pd.rs_part, pd.rs_np);
-    }
 }
 
 // k_cw cones and Max-Cut-type cones with a sparse objective build the right-hand side and the initial residual of a solve in one kernel
@@ -571,7 +471,7 @@ struct FrontSample {
         c->n_front++;
         if (samp) { e0 = c->ev_pool[c->ev_next++]; e1 = c->ev_pool[c->ev_next++]; hipEventRecord(e0, c->stream); }
     }
-    void done() { if (e0) { hipEventRecord(e1, c->stream); c->pend_mv.push_back({e0, e1}); } }
+    void done() { if (e0) { hipEventRecord(e1, c->stream); c->timed_mv.push_back({e0, e1}); } }
 };
 
 // ---- one CG solve, split so that it can be enqueued speculatively and resumed
@@ -606,8 +506,7 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     const int grid = rd.grid;
     const int ns = (B.r + 15) / 16;
     // (LAUNCH would send a virtual dual update off as its own kernel: this launch is the one that uses it)
-    const bool keep = c->pend_dual_virtual;
-    c->pend_dual_virtual = false;
+    const bool keep = c->pend.set_dual_used(false);
     FrontSample fs(c);
 #define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, rd.rpw, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
     // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
@@ -619,23 +518,17 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
 #undef FCWL
 #undef FCW
     fs.done();
-    c->pend_dual_virtual = keep;
+    c->pend.set_dual_used(keep);
     return grid;
 }
 // the host-side state behind a one-kernel front: its launch, or the adoption of one that was enqueued ahead of its step
 void front_cw_started(lorads_hip_ctx *c, const Solve &s, int grid, double tol) {
     s.B->w0_ready = true;
-    if (c->opt_lazy_scalars) {
-        c->pend_init = InitArgs{s.st, shadow_of(c, s.st), part_slot(c, 18), part_slot(c, 1), grid, grid, ds_tol(c, tol)};
-        c->pend_init_g = s.front;
-    } else {
-        LAUNCH(k_cg_init, 1, s.st, part_slot(c, 18), grid, part_slot(c, 1), grid, ds_tol(c, tol), s.front, shadow_of(c, s.st));
-    }
+    c->pend.post_init(c, s.st, part_slot(c, 18), grid, part_slot(c, 1), grid, tol, s.front);
 }
 // may the U front of a fresh sweep take a waiting dual update along?  (see solve_front)
 bool front_carries_dual(const lorads_hip_ctx *c, const Solve &s, int wmode) {
-    return c->pend_dual && wmode == W_ADMM && !s.front.need && !s.front.skip && c->nb == 1 && !c->pend_init.st && !c->pend_chk.st &&
-           !c->pend_dir.kind;
+    return c->pend.dual_rides(s.front) && wmode == W_ADMM && c->nb == 1;
 }
 bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGState *reset, int nreset);
 
@@ -666,14 +559,11 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         // every constraint, and stored by the k_wsum that follows (or by k_dual_update if anything else comes first)
         // (sharded: the cone sees its own constraints only -- the front needs no others -- and k_wsum updates the whole vector)
         if (front_carries_dual(c, s, A.wmode)) {
-            c->pend_dual = false;
-            c->pend_dual_virtual = true;
-            A.rho_dual = ds_rho_dual(c, c->pend_dual_rho);
+            A.rho_dual = ds_rho_dual(c, c->pend.use_dual());
             A.dual_on = 1;
         }
         // a waiting convergence test whose gate is this kernel's gate rides on it (the V-solve's front after a virtual refresh)
-        const Deferred d = (c->pend_chk.st && !c->pend_init.st && !c->pend_dir.kind && !s.front.skip && s.front.need == &c->pend_chk.st->done)
-                               ? take_check(c) : Deferred{};
+        const Deferred d = c->pend.take_check_behind(s.front);
         front_cw_started(c, s, launch_front_cw(c, s, A, s.front, d), tol);
         return;
     }
@@ -694,13 +584,11 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         // a dual update that is still waiting rides on this kernel when it is the ungated first kernel of the sweep of a
         // cone that sees every constraint: the multipliers are read from lambda, the updated ones go to lambda_alt (owner
         // pairs), and the two vectors swap for everything enqueued from here on
-        const bool carry_dual = c->pend_dual && wmode == W_ADMM && !s.front.need && !s.front.skip && B.pu.e_con_own && B.nrow == c->m && B.pu.n_owned == c->m &&
-                                c->nb == 1 && !c->pend_init.st && !c->pend_chk.st && !c->pend_dir.kind;
+        const bool carry_dual = c->pend.dual_rides(s.front) && wmode == W_ADMM && B.pu.e_con_own && B.nrow == c->m && B.pu.n_owned == c->m && c->nb == 1;
         const int *econ = B.pu.e_con;
         if (carry_dual) {
-            c->pend_dual = false;
             wa.lambda_out = c->lambda_alt;
-            wa.rho_dual = ds_rho_dual(c, c->pend_dual_rho);
+            wa.rho_dual = ds_rho_dual(c, c->pend.take_dual());
             econ = B.pu.e_con_own;
         }
         // Max-Cut-type cone with its rows' constraint lists: no coefficient pass, the front forms the diagonal coefficients itself
@@ -708,8 +596,7 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         DiagOnFly of{};
         if (onfly) {
             of.on = true; of.wa = wa; of.wmode = wmode; of.reset = reset; of.nreset = nreset;
-            of.d = (c->pend_chk.st && !c->pend_init.st && !c->pend_dir.kind && !s.front.skip && s.front.need == &c->pend_chk.st->done)
-                       ? take_check(c) : Deferred{};
+            of.d = c->pend.take_check_behind(s.front);
         } else {
             sval(c, B.pu, true, wmode, wa, s.front, reset, nreset, B.use_cw ? B.w_uv : (const double *)nullptr, econ);
         }
@@ -718,12 +605,7 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
         fs.done();
         if (carry_dual) std::swap(c->lambda, c->lambda_alt);
         if (B.diag_only && B.w_uv) B.t_uv_valid = true; // (the front has left the row dots U_p . V_p)
-        if (c->opt_lazy_scalars) { // the solve's start rides on the first kernel of iteration 0 (or goes off on its own)
-            c->pend_init = InitArgs{s.st, shadow_of(c, s.st), pA, pB, nf, nf, ds_tol(c, tol)};
-            c->pend_init_g = s.front;
-        } else {
-            LAUNCH(k_cg_init, 1, s.st, pA, nf, pB, nf, ds_tol(c, tol), s.front, shadow_of(c, s.st));
-        }
+        c->pend.post_init(c, s.st, pA, nf, pB, nf, tol, s.front); // the solve's start rides on the first kernel of iteration 0 (or goes off on its own)
         return;
     }
     sval(c, B.pu, true, W_ADMM, wa, s.front, reset, nreset);
@@ -731,12 +613,7 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
     if (B.dense_c || B.dense_a) dense_part(c, B, s.V, W_ADMM, wa, 1.0, true, s.front);
     const int nb1 = spmm(c, B, B.pu, s.V, OP_RHS, nullptr, nullptr, rho, rhs, pB, s.front, (B.dense_c || B.dense_a) ? B.Wd : nullptr);
     const int na = apply_operator(c, B, s.V, s.x, OP_RES, rhs, r, pA, s.front);
-    if (c->opt_lazy_scalars) { // rides on the first kernel of iteration 0 if that kernel can carry it (k_op_diag, k_cw)
-        c->pend_init = InitArgs{s.st, shadow_of(c, s.st), pA, pB, na, nb1, ds_tol(c, tol)};
-        c->pend_init_g = s.front;
-    } else {
-        LAUNCH(k_cg_init, 1, s.st, pA, na, pB, nb1, ds_tol(c, tol), s.front, shadow_of(c, s.st));
-    }
+    c->pend.post_init(c, s.st, pA, na, pB, nb1, tol, s.front);
 }
 // CG iteration 0 of this cone takes alpha = rr / (rr + ||w||^2) (cg0_alpha, see Cg0Args) when its operator application runs
 // k_wsum: the w that k_wsum leaves must be exactly the w that k_spmm_ell applies -- one cone on the k_front_cw path (not the
@@ -790,12 +667,7 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     B.t_uv_valid = rec; // x (= U or V) moved: the kept values moved with it, or are stale
     if (B.wj_for == s.x) B.wj_for = nullptr; // (... and so are products kept for x as a fixed factor)
     c->merged.t_uv_valid = false;
-    if (c->opt_lazy_scalars) { // the convergence test rides on the next kernel if that kernel can carry it
-        c->pend_chk = Deferred{s.st, shadow_of(c, s.st), pC, nrr, ds_maxit(c, maxit), ds_tol(c, tol), s.front.need};
-        c->pend_chk_g = g;
-    } else {
-        LAUNCH(k_cg_check, 1, s.st, (int)CHK_ITER, pC, nrr, ds_tol(c, tol), ds_maxit(c, maxit), g);
-    }
+    c->pend.post_check(c, s.st, pC, nrr, tol, maxit, g); // the convergence test rides on the next kernel if that kernel can carry it
 }
 // tail of CG iteration k: restart with the true residual when k % 20 == 0 (incl. k = 0), new direction (:195-228)
 // `runs_for_sure`: the host has seen this solve unfinished and nothing is enqueued between that observation and this
@@ -814,8 +686,7 @@ void solve_iter_tail(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
         // speculation miss) must not be taken for fresh on the strength of a kernel that may have been skipped.
         if (!was_valid && !runs_for_sure) B.t_uv_valid = false;
         if (c->opt_lazy_scalars && B.diag_only && c->opt_fuse_dir) { // p = 2 r is formed by the next operator application itself
-            c->pend_dir.kind = DIR_RESTART; c->pend_dir.st = s.st; c->pend_dir.r = r; c->pend_dir.p = p; c->pend_dir.len = s.len;
-            c->pend_dir.gv = s.gv; c->pend_dir.rs_part = pA; c->pend_dir.rs_np = nr; c->pend_dir.g = g; c->pend_dir.seg = false;
+            c->pend.post_dir(Pending::Dir{DIR_RESTART, s.st, r, p, s.len, s.gv, pA, nr, g});
         } else if (c->opt_lazy_scalars) { // the restart's two scalars are written by workgroup 0 of the direction kernel
             LAUNCH(k_cg_dir, s.gv, s.len, s.st, (int)DIR_RESTART, r, p, g, Deferred{}, (const double *)pA, nr);
         } else {
@@ -824,10 +695,9 @@ void solve_iter_tail(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
         }
     } else if (c->opt_lazy_scalars && B.diag_only && c->opt_fuse_dir) {
         // p = r + beta p is formed by the next operator application itself (and the waiting test rides on it too)
-        c->pend_dir.kind = DIR_BETA; c->pend_dir.st = s.st; c->pend_dir.r = r; c->pend_dir.p = p; c->pend_dir.len = s.len;
-        c->pend_dir.gv = s.gv; c->pend_dir.rs_part = nullptr; c->pend_dir.rs_np = 0; c->pend_dir.g = g; c->pend_dir.seg = false;
+        c->pend.post_dir(Pending::Dir{DIR_BETA, s.st, r, p, s.len, s.gv, nullptr, 0, g});
     } else {
-        const Deferred d = (c->pend_chk.st == s.st && !c->pend_init.st) ? take_check(c) : Deferred{};
+        const Deferred d = c->pend.take_check_of(s.st);
         LAUNCH(k_cg_dir, s.gv, s.len, s.st, (int)DIR_BETA, r, p, g, d);
     }
 }
@@ -841,7 +711,7 @@ void solve_iters(lorads_hip_ctx *c, const Solve &s, int k0, int k1, double tol, 
 // constrVal[k] <- A_k(sym(U V^T)) and constrValSum += new - old (lorads_alg_common.c:199-203)
 void refresh_after_solve(lorads_hip_ctx *c, Block &B, const int *need) {
     if (constr_by_recurrence(c, B) && B.t_uv_valid && B.nrow > 0) { // w_uv already is A(sym(U V^T)): bookkeeping only
-        const Deferred d = (c->pend_chk.st && need == &c->pend_chk.st->done && !c->pend_init.st) ? take_check(c) : Deferred{};
+        const Deferred d = c->pend.take_check_behind(Guard{nullptr, need});
         LAUNCH(k_refresh_w, nblocks_for((size_t)B.nrow, TPB), B.nrow, (const double *)B.w_uv, B.cv, B.row_idx, c->csum,
                Guard{nullptr, need}, d, B.diag_only ? (const int *)B.diag_row : (const int *)nullptr,
                B.diag_only ? (const double *)B.diag_a : (const double *)nullptr);
@@ -859,13 +729,14 @@ int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords) {
         word0 = std::min(word0, (size_t)SX_WORD);
         nwords = w1 - word0;
     }
-    const bool sep = c->sep_pending && !c->final_pending && c->sep_ex.n <= 4;
-    if (sep) c->sep_pending = false; // (taken by this hand-over)
-    flush_pending(c);
+    int sep_with_obj = 0;
+    SepExtra ex{};
+    const bool sep = !c->final_pending && c->pend.take_sep(4, &sep_with_obj, &ex); // (taken by this hand-over)
+    c->pend.flush(c);
     ++c->pub_seq;
     if (sep) {
-        LAUNCH(k_publish_sep, 1, (const double *)c->sepbuf, c->scal, c->sep_with_obj, c->sep_ex.n, c->sep_ex.p[0], c->sep_ex.p[1], c->sep_ex.p[2],
-               c->sep_ex.p[3], (const unsigned long long *)c->ctrl + word0, (int)nwords, (unsigned long long *)c->h_ctrl_dev + word0,
+        LAUNCH(k_publish_sep, 1, (const double *)c->sepbuf, c->scal, sep_with_obj, ex.n, ex.p[0], ex.p[1], ex.p[2],
+               ex.p[3], (const unsigned long long *)c->ctrl + word0, (int)nwords, (unsigned long long *)c->h_ctrl_dev + word0,
                c->h_flag_dev, c->seq_dev);
     } else if (c->final_pending) {
         LAUNCH(k_publish_final, 1, c->final_args, (const unsigned long long *)c->ctrl + word0, (int)nwords,
@@ -927,7 +798,7 @@ int wait_publish(lorads_hip_ctx *c) {
 // copy [word0, word0 + nwords) of the control block to its pinned mirror and wait for it
 int publish_and_wait(lorads_hip_ctx *c, size_t word0, size_t nwords) {
     if (!c->use_publish) {
-        flush_pending(c);
+        c->pend.flush(c);
         flush_final(c);
         HC(hipMemcpyAsync(c->h_ctrl + 8 * word0, c->ctrl + 8 * word0, 8 * nwords, hipMemcpyDeviceToHost, c->stream));
         HC(hipStreamSynchronize(c->stream));
@@ -970,7 +841,7 @@ bool spec_front_ok(lorads_hip_ctx *c) {
 }
 void spec_front_enqueue(lorads_hip_ctx *c, double rho) {
     Block &B = c->blk[0];
-    if (!B.t_uv_valid || c->pend_dual || c->pend_dual_virtual) return;
+    if (!B.t_uv_valid || c->pend.dual_owed()) return;
     const Solve s = make_solve(c, 0, 0, nullptr);
     FrontCwArgs A = front_cw_args(c, B, rho, W_ADMM);
     A.dual_on = 1;
@@ -988,13 +859,12 @@ bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol,
     c->spec.live = false;
     Block &B = *s.B;
     const bool ok = s.st == c->st && reset && !c->par_mode && c->spec.epoch == c->spec_epoch && memcmp(&rho, &c->spec.rho, sizeof(double)) == 0 &&
-                    c->spec.dual_seen && c->pend_dual && memcmp(&c->pend_dual_rho, &c->spec.rho_dual, sizeof(double)) == 0 && !c->virt_refresh &&
+                    c->spec.dual_seen && c->pend.dual_owed_at(c->spec.rho_dual) && !c->virt_refresh &&
                     c->spec.wmode == W_ADMM && front_carries_dual(c, s, W_ADMM) && B.t_uv_valid && c->opt_lazy_scalars &&
                     B.spec[0] >= 1; // (iteration 0 is enqueued: its k_wsum is the next launch and takes the reset words)
     if (!ok) { ++c->n_spec_discard; return false; }
     ++c->n_spec_adopt;
-    c->pend_dual = false;
-    c->pend_dual_virtual = true;
+    c->pend.use_dual();
     c->virt_refresh = false;
     c->spec.reset = reset; c->spec.nreset = nreset;
     c->n_front++; // (as the launch would have counted it)
@@ -1004,7 +874,7 @@ bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol,
 
 // the LP block's ADMM update (see k_lp_sweep); st = the block's two stage states
 void enqueue_lp_sweep(lorads_hip_ctx *c, Block &B, double rho, CGState *st, Guard g) {
-    flush_pending(c);
+    c->pend.flush(c);
     LpArgs A;
     A.ncols = B.n; A.nlev = B.lp_nlev; A.lvl_ptr = B.lp_lvl_ptr; A.lvl_cols = B.lp_lvl_cols; A.ptr = B.lp_ptr; A.grow = B.lp_grow;
     A.a = B.lp_a; A.nrm2sq = B.lp_nrm2sq; A.cobj = B.lp_cobj; A.cv = B.lp_cv; A.U = c->U + B.off; A.V = c->V + B.off;
@@ -1111,7 +981,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
         c->avg_folded = false; // the sweep's last update has left R (see solve_iter_body); a waiting test rides on the next kernel
     } else if (pair == LORADS_HIP_PAIR_UV) {
         c->avg_folded = false;
-        const Deferred d = (c->pend_chk.st && need == &c->pend_chk.st->done && !c->pend_init.st) ? take_check(c) : Deferred{};
+        const Deferred d = c->pend.take_check_behind(g);
         LAUNCH(k_average, grid1d(c->all_elem), c->all_elem, c->U, c->V, c->R, g, d);
     }
     Block *S1 = solo(c);
@@ -1135,7 +1005,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
     // that each of them holds one such cone; a deal that leaves some rank two cones takes the general form everywhere)
     if (vec && c->ar_fast_all < 0) {
         double v[2] = {(c->opt_ar_fast && c->nb == 1 && !c->blk[0].dense_c && c->blk[0].nc > 0 && !c->blk[0].is_lp) ? 1.0 : 0.0, 1.0};
-        flush_pending(c);
+        c->pend.flush(c);
         HC(hipStreamSynchronize(c->stream));
         if (c->ar(c->ar_user, v, 2, 0)) return fail_msg("allreduce hook failed");
         c->ar_fast_all = v[0] == v[1] ? 1 : 0;
@@ -1148,7 +1018,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
     for (Block *bp : cones) {
         Block &B = *bp;
         if (D1 == &B && fold_res) {
-            const Deferred d = (c->pend_chk.st && need == &c->pend_chk.st->done && !c->pend_init.st && !c->pend_dir.kind) ? take_check(c) : Deferred{};
+            const Deferred d = c->pend.take_check_behind(g);
             const Shape sh = shape_for(B.r);
             nres = nblocks_for((size_t)B.n, TPB / sh.lg);
             SHAPE_DISPATCH(sh, LAUNCH((k_eval_diag<LG_, V2_, NS_>), nres, B.n, (const double *)(c->U + B.off), (const double *)(c->V + B.off),
@@ -1158,7 +1028,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
         } else if (fold_res && B.use_cw && with_obj && fold_obj && c->opt_fuse_eval && cw_quad(c, B) && B.nc > 0 && !B.dense_c &&
                    nblocks_for((size_t)B.nrow, TPB / 64) <= c->maxpart) {
             // constraint values + residual partials AND the objective partials in one launch (k_eval_cw_obj)
-            const Deferred d = (c->pend_chk.st && need == &c->pend_chk.st->done && !c->pend_init.st && !c->pend_dir.kind) ? take_check(c) : Deferred{};
+            const Deferred d = c->pend.take_check_behind(g);
             nres = nblocks_for((size_t)B.nrow, TPB / 64);
             nobj = std::min(nblocks_for((size_t)B.nc, TPB / 8), 2048);
             const int ns4 = (B.r + 7) / 8, ns = (B.r + 15) / 16;
@@ -1202,7 +1072,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
         const bool obj_from_part = with_obj && cones.size() == 1 && nobj > 0;
         if (!ar_fast)
             LAUNCH(k_stage_tail, 1, obj_from_part ? part_slot(c, 4) : (const double *)nullptr, nobj, c->scal + 2, need, dst + c->m);
-        flush_pending(c);
+        c->pend.flush(c);
         if (allreduce_dev(c, dst, c->m + 2 + (ar_fast ? nobj : 0))) return 1;
         nres = std::max(1, std::min(grid1d((size_t)c->m), 256));
         LAUNCH(k_commit_eval, nres, c->m, dst, c->csum, c->b, c->lambda, part_slot(c, 8), part_slot(c, 9), c->scal,
@@ -1228,10 +1098,10 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
             return 0;
         }
         LAUNCH(k_sep_stage, 1, part_slot(c, 8), part_slot(c, 9), nres, op, nobj, (const double *)c->scal, g, with_obj ? 1 : 0, c->sepbuf, ex);
-        flush_pending(c);
+        c->pend.flush(c);
         if (allreduce_dev(c, c->sepbuf, 4 + ex.n)) return 1;
         // (the commit of the reduced scalars rides on the hand-over that follows; flush_pending sends it off on its own otherwise)
-        c->sep_pending = true; c->sep_with_obj = with_obj ? 1 : 0; c->sep_ex = ex;
+        c->pend.post_sep(with_obj ? 1 : 0, ex);
         return 0;
     }
     if (c->use_publish) {
@@ -1244,7 +1114,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
 }
 
 int read_scalars_at(lorads_hip_ctx *c, const double *dptr, int count, double *out) {
-    flush_pending(c);
+    c->pend.flush(c);
     flush_final(c);
     if (c->launch_err) { const char *e = c->launch_err; c->launch_err = nullptr; hipStreamSynchronize(c->stream); return fail_msg(e); }
     HC(hipMemcpyAsync(c->h_scal + 32, dptr, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, c->stream));
@@ -1309,16 +1179,6 @@ SegArgs seg_args(lorads_hip_ctx *c, int half, int k) {
     sa.rr_alt = c->seg_rr_alt; sa.slot_rd = carry ? (k & 1) : 0; sa.slot_wr = carry ? ((k + 1) & 1) : 0;
     return sa;
 }
-// a convergence test of the lockstep sweep that nothing has carried yet: its own launch
-void flush_segchk(lorads_hip_ctx *c) {
-    if (!c->pend_segchk.on) return;
-    const auto pc = c->pend_segchk;
-    c->pend_segchk.on = false;
-    flush_pending(c);
-    const Guard g{&c->phase_done[pc.half], pc.half ? &c->phase_done[0] : nullptr};
-    hipLaunchKernelGGL(k_cg_check_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, seg_args(c, pc.half, pc.k), (int)CHK_ITER, pc.part, ds_tol(c, pc.tol),
-                       ds_maxit(c, pc.maxit), g);
-}
 void batched_body(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     Block &M = c->merged;
     const double *Vfix = half == 0 ? c->V : c->U;
@@ -1332,12 +1192,10 @@ void batched_body(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     M.t_uv_valid = false;
     for (auto &B0 : c->blk) B0.t_uv_valid = false;
     if (seg_carry(c)) { // the test waits for the next operator kernel (batched_tail), or for flush_segchk
-        c->pend_segchk.on = true; c->pend_segchk.half = half; c->pend_segchk.k = k; c->pend_segchk.part = pC; c->pend_segchk.tol = tol;
-        c->pend_segchk.maxit = maxit;
+        c->pend.post_segchk(Pending::SegChk{true, half, k, pC, tol, maxit});
         return;
     }
-    flush_pending(c);
-    hipLaunchKernelGGL(k_cg_check_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, sa, (int)CHK_ITER, pC, ds_tol(c, tol), ds_maxit(c, maxit), g);
+    SEG_LAUNCH(k_cg_check_seg, sa, (int)CHK_ITER, pC, ds_tol(c, tol), ds_maxit(c, maxit), g);
 }
 void batched_tail(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     Block &M = c->merged;
@@ -1347,35 +1205,26 @@ void batched_tail(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     const SegArgs sa = seg_args(c, half, k);
     // Max-Cut-type merged cone: the direction update is formed by the operator application that follows (k_op_diag, DirArgs)
     const bool fuse = M.diag_only && c->opt_lazy_scalars && c->opt_fuse_dir && c->seg_tile_cone;
-    auto defer_dir = [&](int kind) {
-        c->pend_dir.kind = kind; c->pend_dir.st = c->st; c->pend_dir.r = c->cr; c->pend_dir.p = c->cp; c->pend_dir.len = 0;
-        c->pend_dir.gv = 0; c->pend_dir.rs_part = nullptr; c->pend_dir.rs_np = 0; c->pend_dir.g = g; c->pend_dir.seg = true;
-        c->pend_dir.half = half;
-        c->pend_dir.chk_part = nullptr;
-        c->pend_dir.rs_seg = nullptr;
-        if (kind == DIR_BETA && c->pend_segchk.on && c->pend_segchk.half == half && c->pend_segchk.k == k) { // iteration k's test rides along
-            c->pend_dir.chk_part = c->pend_segchk.part; c->pend_dir.chk_tol = c->pend_segchk.tol; c->pend_dir.chk_maxit = c->pend_segchk.maxit;
-            c->pend_dir.chk_k = k;
-            c->pend_segchk.on = false;
-        }
+    // (iteration k's waiting test rides along with p = r + beta p -- its tolerance and limit are this call's, batched_iters gives an
+    // iteration's body and tail the same -- and a riding restart's two scalars, rs_seg, with p = 2 r)
+    auto defer_dir = [&](int kind, const double *rs_seg = nullptr) {
+        const double *chk_part = kind == DIR_BETA ? c->pend.take_segchk_part(half, k) : (const double *)nullptr;
+        c->pend.post_dir(Pending::Dir{kind, c->st, c->cr, c->cp, 0, 0, nullptr, 0, g, true, half, chk_part, tol, maxit, k, rs_seg});
     };
-    if (k % 20 != 0 && !fuse) flush_segchk(c);
+    if (k % 20 != 0 && !fuse) c->pend.flush_segchk(c);
     if (k % 20 == 0) {
         // (the restart recomputes the residual of the cones that are still running: their test comes first -- on the residual pass
         // itself when the test was waiting for an operator kernel anyway, and the restart's two scalars on the operator that follows)
         const bool ride = fuse && seg_carry(c) && c->opt_seg_carry_restart && c->seg_row0;
-        if (ride && c->pend_segchk.on && c->pend_segchk.half == half && c->pend_segchk.k == k) c->pend_segchk.ride_res = true;
-        else flush_segchk(c);
+        if (!(ride && c->pend.segchk_rides_res(half, k))) c->pend.flush_segchk(c);
         // (riding: the residual's partials go to a slot of their own -- the operator kernel that sums them writes slot 0, p.Ap, itself)
         double *p_res = ride ? part_slot(c, 19) : part_slot(c, 0);
         apply_operator(c, M, Vfix, x, OP_RES, c->rhs, c->cr, p_res, g);
-        if (c->pend_segchk.on) { c->pend_segchk.ride_res = false; flush_segchk(c); } // (not taken: cannot happen on this path; kept in order of safety, not of arithmetic)
+        c->pend.flush_segchk(c); // (not taken: cannot happen on this path; kept in order of safety, not of arithmetic)
         if (ride) {
-            defer_dir(DIR_RESTART);
-            c->pend_dir.rs_seg = p_res; c->pend_dir.chk_tol = tol; c->pend_dir.chk_maxit = maxit; c->pend_dir.chk_k = k;
+            defer_dir(DIR_RESTART, p_res);
         } else {
-            flush_pending(c);
-            hipLaunchKernelGGL(k_cg_check_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, sa, (int)CHK_RESTART, part_slot(c, 0), ds_tol(c, tol), ds_maxit(c, maxit), g);
+            SEG_LAUNCH(k_cg_check_seg, sa, (int)CHK_RESTART, part_slot(c, 0), ds_tol(c, tol), ds_maxit(c, maxit), g);
             if (fuse) defer_dir(DIR_RESTART);
             else LAUNCH(k_cg_dir_seg, c->seg_nvt, sa, (int)DIR_RESTART, c->cr, c->cp, g);
         }
@@ -1389,7 +1238,7 @@ void batched_iters(lorads_hip_ctx *c, int half, int k0, int k1, double tol, int 
         if (k > k0) batched_tail(c, half, k - 1, tol, maxit);
         batched_body(c, half, k, tol, maxit);
     }
-    flush_segchk(c); // (the last enqueued iteration's test: the hand-over, the other phase and a resume read the states)
+    c->pend.flush_segchk(c); // (the last enqueued iteration's test: the hand-over, the other phase and a resume read the states)
 }
 // returns the number of lockstep iterations enqueued so far for `phase` (for a later resume)
 void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, double tol, int maxit, int launched[2],
@@ -1425,12 +1274,10 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
                 of.on = true; of.wa = wa; of.wmode = (half == 1 && virt) ? W_ADMM_VS : W_ADMM;
                 // a dual update that is still waiting rides on the sweep's ungated first kernel, as on a single cone's front (solve_front):
                 // every constraint sits in one row of the merged cone, the updated multipliers go to lambda_alt and the vectors swap
-                const bool carry_dual = c->pend_dual && half == 0 && !front.need && M.nrow == c->m && c->m > 0 && c->lambda_alt && c->opt_seg_carry_dual &&
-                                        !c->pend_init.st && !c->pend_chk.st && !c->pend_dir.kind && !c->pend_segchk.on && !c->pend_dual_virtual;
+                const bool carry_dual = c->pend.dual_rides(front, true) && half == 0 && M.nrow == c->m && c->m > 0 && c->lambda_alt && c->opt_seg_carry_dual;
                 if (carry_dual) {
-                    c->pend_dual = false;
                     of.wa.lambda_out = c->lambda_alt;
-                    of.wa.rho_dual = ds_rho_dual(c, c->pend_dual_rho);
+                    of.wa.rho_dual = ds_rho_dual(c, c->pend.take_dual());
                 }
                 spmm_front(c, M, M.pu, Vfix, x, rho, c->rhs, c->cr, p_rr0, part_slot(c, 1), front, of);
                 if (carry_dual) std::swap(c->lambda, c->lambda_alt);
@@ -1439,12 +1286,8 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
                 spmm(c, M, M.pu, Vfix, OP_RHS, nullptr, nullptr, rho, c->rhs, part_slot(c, 1), front);
                 apply_operator(c, M, Vfix, x, OP_RES, c->rhs, c->cr, p_rr0, front);
             }
-            flush_pending(c);
-            if (carry_init) {
-                c->pend_seginit.on = true; c->pend_seginit.half = half; c->pend_seginit.tol = tol; c->pend_seginit.front = front;
-                c->pend_seginit.part_rr = p_rr0; c->pend_seginit.part_b = part_slot(c, 1);
-            } else
-                hipLaunchKernelGGL(k_cg_init_seg, dim3(1), dim3(seg_threads(c)), 0, c->stream, seg_args(c, half), p_rr0, part_slot(c, 1), ds_tol(c, tol), front);
+            if (carry_init) { c->pend.flush(c); c->pend.post_seginit(Pending::SegInit{true, half, tol, front, p_rr0, part_slot(c, 1)}); }
+            else SEG_LAUNCH(k_cg_init_seg, seg_args(c, half), p_rr0, part_slot(c, 1), ds_tol(c, tol), front);
             batched_iters(c, half, 0, k1, tol, maxit);
             launched[half] = k1;
         }
