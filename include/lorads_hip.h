@@ -327,6 +327,10 @@ int lorads_hip_sync(lorads_hip_ctx *ctx);
  * enqueued ahead, taken by the next lorads_hip_admm_step, discarded (the caller did something other than lorads_hip_update_dual_var
  * and lorads_hip_admm_step with the same rho), blocked by their gate (the step's V-solve resumed: they wrote nothing)} */
 int lorads_hip_spec_front_stats(lorads_hip_ctx *ctx, int64_t out[4]);
+/* a step's result hand-over rides on the launch of that front as one more workgroup where the front follows the evaluation's own
+ * hand-over (LORADS_HANDOVER_ON_FRONT=0, read at creation: always a launch of its own, the front behind it): out = {hand-overs
+ * carried on a front, hand-overs launched alone}.  Results do not depend on it.  Leaves a front in flight alone. */
+int lorads_hip_handover_stats(lorads_hip_ctx *ctx, int64_t out[2]);
 /* the rows per workgroup of the two row-tile gather kernels (k_front_cw, k_spmm_ell) on cone `block`: out = {rows per workgroup,
  * grid, compute units dealt over}.  LORADS_ROW_DEAL, read at creation: unset or "auto" deals a cone of more than 32 rows per
  * compute unit evenly, 0 keeps 32 rows per workgroup, 1..32 forces that many for every cone (a test switch: a cone for which that

@@ -1017,26 +1017,103 @@ __device__ __forceinline__ void front_cw_weights(const FrontCwArgs &A, double rh
     c1 = a * m1;
     c2 = a * wu;
 }
+// The closing sums of an evaluation (gated like the evaluation itself) and the result hand-over behind them, one workgroup: the
+// body of k_publish_final (see k_publish for the hand-over itself) and of workgroup 0 of k_front_cw's hand-over form.  sh: 12 doubles.
+struct EvalFinalArgs {
+    const double *part_v, *part_d, *obj_part;
+    int np, nobj;
+    double *out;
+    Guard g;
+};
+__device__ __forceinline__ void publish_final(EvalFinalArgs fa, const unsigned long long *src, int nwords, unsigned long long *dst,
+                                              unsigned long long *flag, unsigned long long *seq_dev, double *sh) {
+    const unsigned long long seq = *seq_dev + 1; // (requested with everything else at the top)
+    // the control block's words (written by earlier kernels) are requested at the top, beside the gate and the partial sums:
+    // only the three scalars formed here change, and they go to the host mirror straight from registers -- no fence and
+    // re-read between the sums and the hand-over.  (fa.out is words 0..2 of src: the evaluation's scalars.)
+    constexpr int PW = 4;
+    unsigned long long pre[PW];
+#pragma unroll
+    for (int k = 0; k < PW; ++k) {
+        const int i = threadIdx.x + k * TPB;
+        pre[k] = __builtin_nontemporal_load(src + (i < nwords ? i : 0));
+    }
+    const bool live = !blocked(fa.g);
+    const double *const pp[3] = {fa.part_v, fa.part_d, fa.obj_part ? fa.obj_part : fa.part_v};
+    const int nn[3] = {fa.np, fa.np, fa.obj_part ? fa.nobj : 0};
+    double t3[3];
+    private_partials_n<3>(pp, nn, t3); // (the three sets of loads fly together)
+    block_sum_n<3>(t3, sh);
+    const double v = t3[0], d = t3[1], o = t3[2];
+    if (live && threadIdx.x == 0) { fa.out[0] = v; fa.out[1] = d; if (fa.obj_part) fa.out[2] = o; }
+    const bool own = (const double *)src == fa.out; // the words being handed over start at the evaluation's scalars
+#pragma unroll
+    for (int k = 0; k < PW; ++k) {
+        const int i = threadIdx.x + k * TPB;
+        if (i >= nwords) continue;
+        unsigned long long w = pre[k];
+        if (live && own) {
+            if (i == 0) w = (unsigned long long)__double_as_longlong(v);
+            else if (i == 1) w = (unsigned long long)__double_as_longlong(d);
+            else if (i == 2 && fa.obj_part) w = (unsigned long long)__double_as_longlong(o);
+        }
+        dst[i] = w;
+    }
+    if (!own || nwords > PW * TPB) { // (a hand-over that does not start at the scalars, or a very long one: the plain way)
+        __threadfence();
+        __syncthreads();
+        for (int i = threadIdx.x; i < nwords; i += TPB) dst[i] = __builtin_nontemporal_load(src + i);
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *seq_dev = seq;
+        __atomic_store_n(flag, seq, __ATOMIC_RELEASE);
+        __threadfence_system();
+    }
+}
+// what the hand-over form of k_front_cw (HO) hands to publish_final: it travels beside the front's own arguments
+struct HandoverArgs {
+    EvalFinalArgs fa;
+    const unsigned long long *src;
+    unsigned long long *dst;
+    int nwords;
+    unsigned long long *flag, *seq_dev;
+};
+struct FrontCwHoArgs : FrontCwArgs { HandoverArgs ho; };
 // KC = 4 (round 3; LORADS_FRONT_LDS=0: KC = 0): the rows of the first four slots, gathered for the A part, are parked in LDS
 // (32 rows x 4 slots x NS x 128 bytes per workgroup: 48 KB at NS = 3, three workgroups per CU as the registers allow anyway) and the
 // second visit takes them from there -- 53 % of the rows have no more than four slots, and the second gather of a slot row was a
 // quarter of the kernel's L1 misses (profiles/r03_front_cw_counters.json).  The same lanes write and read a slot's row: no barrier.
-template <int NS, int EW, int KC = 0>
-__global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A, const double *__restrict__ X, int r,
+// HO (the hand-over form: the next step's U front enqueued where the step's hand-over stood, see spec_front_enqueue): the grid has
+// one workgroup more.  Workgroup 0 is the hand-over of k_publish_final (publish_final under its own gate in A.ho.fa) and returns:
+// it is dispatched first, so the host sees the flag at the head of the front.  Workgroup b > 0 is row workgroup b - 1.  Nobody waits
+// for anybody: the row workgroups read nothing the hand-over writes (the three scalars, the mirror, seq_dev) and write scratch alone.
+template <int NS, int EW, int KC = 0, bool HO = false>
+__global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::conditional_t<HO, FrontCwHoArgs, FrontCwArgs> A,
+                                                  const double *__restrict__ X, int r,
                                                   const double *__restrict__ xin, double *__restrict__ out,
                                                   double *__restrict__ rhs_out, double *__restrict__ part,
                                                   double *__restrict__ part_b, Guard g, Deferred d) {
     constexpr int LG = 8, W = 2, NH = EW / 8;
     using SL = Slice<LG, true, NS>;
-    __shared__ double sh[8];
+    __shared__ double sh[HO ? 12 : 8];
     extern __shared__ __attribute__((aligned(16))) double2 slotc[]; // [32 rows][KC slots][NS][8 lanes]
-    if (A.reset && blockIdx.x == 0 && threadIdx.x < A.nreset) A.reset[threadIdx.x].done = 0;
+    unsigned wg = blockIdx.x; // the row workgroup
+    if constexpr (HO) {
+        if (blockIdx.x == 0) {
+            publish_final(A.ho.fa, A.ho.src, A.ho.nwords, A.ho.dst, A.ho.flag, A.ho.seq_dev, sh);
+            return;
+        }
+        wg = blockIdx.x - 1;
+    }
+    if (A.reset && wg == 0 && threadIdx.x < A.nreset) A.reset[threadIdx.x].done = 0;
     const Gate gt = gate_load(g);
     const double rho = dsv(A.rho), rho_dual = A.dual_on ? dsv(A.rho_dual) : 0.0;
     DefPriv dv{};
     if (d.st) dv = deferred_private(d);
     // rpw rows per workgroup (row_deal): a lane group beyond rpw is a row past n in every sense (the LDS park keeps its 32 places)
-    const int grp = threadIdx.x / LG, row = blockIdx.x * rpw + grp, lane = threadIdx.x % LG, l8 = lane & 7;
+    const int grp = threadIdx.x / LG, row = wg * rpw + grp, lane = threadIdx.x % LG, l8 = lane & 7;
     const bool act = grp < rpw && row < n;
     const int rowc = act ? row : 0;
     const size_t base = (size_t)rowc * r;
@@ -1204,7 +1281,7 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, FrontCwArgs A,
     }
     double two[2] = {act ? local : 0.0, act ? local_b : 0.0};
     block_sum_n<2>(two, sh);
-    if (live && threadIdx.x == 0) { part[blockIdx.x] = two[0]; part_b[blockIdx.x] = two[1]; }
+    if (live && threadIdx.x == 0) { part[wg] = two[0]; part_b[wg] = two[1]; }
 }
 
 // w_i = sum of the contributions k_front_cw left for constraint i's slots: constraint-major, fixed width cw (padding holds 0),
@@ -2335,60 +2412,12 @@ __global__ __launch_bounds__(TPB) void k_publish(const unsigned long long *__res
 }
 
 // k_eval_final and k_publish in one launch: the closing sums of an evaluation (gated like the evaluation itself) are
-// written to the device scalars and the control block then goes to the host mirror in the same workgroup
-struct EvalFinalArgs {
-    const double *part_v, *part_d, *obj_part;
-    int np, nobj;
-    double *out;
-    Guard g;
-};
+// written to the device scalars and the control block then goes to the host mirror in the same workgroup (publish_final, above
+// k_front_cw, whose hand-over form runs the same body in a workgroup of its own)
 __global__ __launch_bounds__(TPB) void k_publish_final(EvalFinalArgs fa, const unsigned long long *src, int nwords,
                                                        unsigned long long *dst, unsigned long long *flag, unsigned long long *seq_dev) {
     __shared__ double sh[12];
-    const unsigned long long seq = *seq_dev + 1; // (requested with everything else at the top)
-    // the control block's words (written by earlier kernels) are requested at the top, beside the gate and the partial sums:
-    // only the three scalars formed here change, and they go to the host mirror straight from registers -- no fence and
-    // re-read between the sums and the hand-over.  (fa.out is words 0..2 of src: the evaluation's scalars.)
-    constexpr int PW = 4;
-    unsigned long long pre[PW];
-#pragma unroll
-    for (int k = 0; k < PW; ++k) {
-        const int i = threadIdx.x + k * TPB;
-        pre[k] = __builtin_nontemporal_load(src + (i < nwords ? i : 0));
-    }
-    const bool live = !blocked(fa.g);
-    const double *const pp[3] = {fa.part_v, fa.part_d, fa.obj_part ? fa.obj_part : fa.part_v};
-    const int nn[3] = {fa.np, fa.np, fa.obj_part ? fa.nobj : 0};
-    double t3[3];
-    private_partials_n<3>(pp, nn, t3); // (the three sets of loads fly together)
-    block_sum_n<3>(t3, sh);
-    const double v = t3[0], d = t3[1], o = t3[2];
-    if (live && threadIdx.x == 0) { fa.out[0] = v; fa.out[1] = d; if (fa.obj_part) fa.out[2] = o; }
-    const bool own = (const double *)src == fa.out; // the words being handed over start at the evaluation's scalars
-#pragma unroll
-    for (int k = 0; k < PW; ++k) {
-        const int i = threadIdx.x + k * TPB;
-        if (i >= nwords) continue;
-        unsigned long long w = pre[k];
-        if (live && own) {
-            if (i == 0) w = (unsigned long long)__double_as_longlong(v);
-            else if (i == 1) w = (unsigned long long)__double_as_longlong(d);
-            else if (i == 2 && fa.obj_part) w = (unsigned long long)__double_as_longlong(o);
-        }
-        dst[i] = w;
-    }
-    if (!own || nwords > PW * TPB) { // (a hand-over that does not start at the scalars, or a very long one: the plain way)
-        __threadfence();
-        __syncthreads();
-        for (int i = threadIdx.x; i < nwords; i += TPB) dst[i] = __builtin_nontemporal_load(src + i);
-    }
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *seq_dev = seq;
-        __atomic_store_n(flag, seq, __ATOMIC_RELEASE);
-        __threadfence_system();
-    }
+    publish_final(fa, src, nwords, dst, flag, seq_dev, sh);
 }
 // the hand-over that follows the all-reduce of separable shards: k_sep_commit (the reduced scalars into the control block) and
 // k_publish in one launch -- the sharded iteration's chain is one kernel shorter

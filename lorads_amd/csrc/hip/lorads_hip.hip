@@ -835,6 +835,10 @@ struct lorads_hip_ctx {
     } spec;
     unsigned long long spec_epoch = 0; // bumped by spec_touch: every C-ABI entry but update_dual_var, admm_step and the statistics' own
     long long n_spec_enq = 0, n_spec_adopt = 0, n_spec_discard = 0, n_spec_blocked = 0;
+    // ... and that front's launch carries the step's hand-over as one more workgroup instead of following k_publish_final (sweep.inc:
+    // enqueue_publish; k_front_cw's hand-over form).  LORADS_HANDOVER_ON_FRONT=0: two launches (read at creation)
+    bool opt_handover_on_front = true;
+    long long n_handover_front = 0, n_handover_alone = 0; // hand-overs carried on a front / launched as kernels of their own
     bool opt_exact_refresh = false, opt_split_front = false; // test knobs (read at creation): see constr_by_recurrence, fused_front
     bool final_pending = false;              // an evaluation's closing sums wait for the next hand-over (k_publish_final)
     EvalFinalArgs final_args;
@@ -1008,6 +1012,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     }
     if (getenv("LORADS_WT_STORES") && getenv("LORADS_WT_STORES")[0]) c->opt_wt_stores = atoi(getenv("LORADS_WT_STORES")) & WT_ALL;
     c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
+    c->opt_handover_on_front = env_on("LORADS_HANDOVER_ON_FRONT");
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
     c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
     c->opt_tile_update = env_on("LORADS_TILE_UPDATE");
@@ -1955,6 +1960,12 @@ int lorads_hip_presolve_stats(lorads_hip_ctx *c, int64_t stats[2]) {
 int lorads_hip_spec_front_stats(lorads_hip_ctx *c, int64_t out[4]) { // (leaves a front in flight alone: tests read it between steps)
     if (!c || !out) return fail_msg("spec_front_stats: bad argument");
     out[0] = c->n_spec_enq; out[1] = c->n_spec_adopt; out[2] = c->n_spec_discard; out[3] = c->n_spec_blocked;
+    return 0;
+}
+
+int lorads_hip_handover_stats(lorads_hip_ctx *c, int64_t out[2]) { // (a statistics entry: leaves a front in flight alone)
+    if (!c || !out) return fail_msg("handover_stats: bad argument");
+    out[0] = c->n_handover_front; out[1] = c->n_handover_alone;
     return 0;
 }
 

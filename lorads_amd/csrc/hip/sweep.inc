@@ -498,7 +498,8 @@ FrontCwArgs front_cw_args(lorads_hip_ctx *c, const Block &B, double rho, int wmo
     return A;
 }
 // ... and its launch for the solve `s` under gate `g`; returns its grid (= the number of partials it leaves in slots 18 and 1)
-int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Guard g, Deferred d) {
+// `ho`: the hand-over form -- one workgroup more, which hands the step's results over as k_publish_final would (not among the partials)
+int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Guard g, Deferred d, const HandoverArgs *ho = nullptr) {
     Block &B = *s.B;
     double *r = c->cr + B.off, *rhs = c->rhs + B.off;
     double *pA = part_slot(c, 18), *pB = part_slot(c, 1);
@@ -508,13 +509,18 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     // (LAUNCH would send a virtual dual update off as its own kernel: this launch is the one that uses it)
     const bool keep = c->pend.set_dual_used(false);
     FrontSample fs(c);
-#define FCW(EWV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV>), grid, B.n, rd.rpw, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
+    FrontCwHoArgs AH{};
+    if (ho) { static_cast<FrontCwArgs &>(AH) = A; AH.ho = *ho; }
+#define FCW(EWV, HO, AV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV, 0, HO>), grid + HO, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
     // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
-#define FCWL(NSV, EWV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4>), grid, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, A, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
-    if (c->opt_front_lds && ns <= 3) {
-        if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8); else if (ns == 2) FCWL(2, 8); else FCWL(3, 8); }
-        else { if (ns == 1) FCWL(1, 16); else if (ns == 2) FCWL(2, 16); else FCWL(3, 16); }
-    } else if (B.cell_w == 8) { FCW(8) } else { FCW(16) }
+#define FCWL(NSV, EWV, HO, AV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4, HO>), grid + HO, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
+#define FRONT(HO, AV)                                                                                                    \
+    if (c->opt_front_lds && ns <= 3) {                                                                                   \
+        if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8, HO, AV); else if (ns == 2) FCWL(2, 8, HO, AV); else FCWL(3, 8, HO, AV); }     \
+        else { if (ns == 1) FCWL(1, 16, HO, AV); else if (ns == 2) FCWL(2, 16, HO, AV); else FCWL(3, 16, HO, AV); }                \
+    } else if (B.cell_w == 8) { FCW(8, HO, AV) } else { FCW(16, HO, AV) }
+    if (ho) { FRONT(true, AH) } else { FRONT(false, A) }
+#undef FRONT
 #undef FCWL
 #undef FCW
     fs.done();
@@ -721,9 +727,13 @@ void refresh_after_solve(lorads_hip_ctx *c, Block &B, const int *need) {
 }
 
 void flush_final(lorads_hip_ctx *c);
+bool spec_front_enqueue(lorads_hip_ctx *c, double rho, const HandoverArgs *ho = nullptr);
 // hand [word0, word0 + nwords) of the control block over to its pinned mirror: the kernel that copies the words and publishes the
 // next sequence number (the last kernel of every launch chain that is replayed as a graph) ...
-int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords) {
+// `front_rho`: the next step's U front may be enqueued behind this hand-over (run_sweep), at that rho.  Where the hand-over is the
+// evaluation's (k_publish_final) over the usual words, that front's launch carries it as one more workgroup
+// (LORADS_HANDOVER_ON_FRONT=0: never) and *front_carried says so; every other hand-over is a launch of its own, as ever.
+int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords, const double *front_rho = nullptr, bool *front_carried = nullptr) {
     if (c->sx_pending && (word0 > SX_WORD || word0 + nwords < SX_WORD + 4)) { // the staged local sums travel with this hand-over
         const size_t w1 = std::max(word0 + nwords, (size_t)SX_WORD + 4);
         word0 = std::min(word0, (size_t)SX_WORD);
@@ -739,13 +749,22 @@ int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords) {
                ex.p[3], (const unsigned long long *)c->ctrl + word0, (int)nwords, (unsigned long long *)c->h_ctrl_dev + word0,
                c->h_flag_dev, c->seq_dev);
     } else if (c->final_pending) {
-        LAUNCH(k_publish_final, 1, c->final_args, (const unsigned long long *)c->ctrl + word0, (int)nwords,
-               (unsigned long long *)c->h_ctrl_dev + word0, c->h_flag_dev, c->seq_dev);
+        const HandoverArgs H{c->final_args, (const unsigned long long *)c->ctrl + word0, (unsigned long long *)c->h_ctrl_dev + word0,
+                             (int)nwords, c->h_flag_dev, c->seq_dev};
+        const bool own = (const double *)H.src == H.fa.out; // (as k_publish_final sees it)
+        if (front_rho && c->opt_handover_on_front && own && spec_front_enqueue(c, *front_rho, &H)) {
+            *front_carried = true;
+            c->final_pending = false;
+            ++c->n_handover_front;
+            return 0;
+        }
+        LAUNCH(k_publish_final, 1, H.fa, H.src, H.nwords, H.dst, H.flag, H.seq_dev);
         c->final_pending = false;
     } else {
         LAUNCH(k_publish, 1, (const unsigned long long *)c->ctrl + word0, (int)nwords, (unsigned long long *)c->h_ctrl_dev + word0,
                c->h_flag_dev, c->seq_dev);
     }
+    ++c->n_handover_alone;
     return 0;
 }
 // separable shards with a scalar exchange: the hand-over has brought this rank's LOCAL sums of the evaluation; the ranks' hosts sum
@@ -839,19 +858,22 @@ bool spec_front_ok(lorads_hip_ctx *c) {
     if (c->prof && c->prof_every < (1 << 20)) return false; // (a window that times launches between events: nothing runs differently in it)
     return front_cw_ok(c, c->blk[0]) && !c->blk[0].is_lp;
 }
-void spec_front_enqueue(lorads_hip_ctx *c, double rho) {
+// `ho`: this step's hand-over, not launched yet, rides on the front's launch (see enqueue_publish).  Returns whether a front went off.
+bool spec_front_enqueue(lorads_hip_ctx *c, double rho, const HandoverArgs *ho) {
     Block &B = c->blk[0];
-    if (!B.t_uv_valid || c->pend.dual_owed()) return;
+    if (!B.t_uv_valid || c->pend.dual_owed()) return false;
     const Solve s = make_solve(c, 0, 0, nullptr);
     FrontCwArgs A = front_cw_args(c, B, rho, W_ADMM);
     A.dual_on = 1;
     A.rho_dual = ds_rho_dual(c, rho);
     // gated like the evaluation: if this step's V-solve missed its speculation the resume still needs cr and rhs, and a blocked
     // front writes nothing.  No reset words: they would shut the very gate it waits at (the k_wsum behind it takes them).
-    launch_front_cw(c, s, A, Guard{nullptr, &c->st[2 * c->nb - 1].done}, Deferred{});
+    // (with the hand-over on board: its workgroup has its own gate, the evaluation's, and publishes whether or not the rows write)
+    launch_front_cw(c, s, A, Guard{nullptr, &c->st[2 * c->nb - 1].done}, Deferred{}, ho);
     c->spec.live = true; c->spec.dual_seen = false;
     c->spec.rho = rho; c->spec.rho_dual = rho; c->spec.wmode = W_ADMM; c->spec.epoch = c->spec_epoch;
     ++c->n_spec_enq;
+    return true;
 }
 // stage 0 of a fresh sweep: take the front that is already there instead of launching one?
 bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGState *reset, int nreset) {
@@ -1382,7 +1404,7 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
     // (no cross-rank sum inside the sweep: with sharded cones the lockstep form works unchanged)
     if (c->has_merged && !getenv("LORADS_NO_BATCH")) { spec_touch(c); return run_sweep_batched(c, rho, tol, maxit, with_eval); }
     int first = 0, resume = -1;
-    bool first_pass = true, any_missed = false;
+    bool first_pass = true, any_missed = false, front_carried = false; // (front_carried: the hand-over went with the next step's U front)
     const bool graph = graph_this_step(c, rho, tol, maxit);
     if (graph && set_step_params(c, rho, tol, maxit)) return 1;
     ParMode pm(c, graph);
@@ -1401,13 +1423,14 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
             if (first_pass && 2 * c->nb - 1 > TPB) HC(hipMemsetAsync(c->st, 0, sizeof(CGState) * (size_t)(2 * c->nb), c->stream));
             enqueue_sweep(c, first, resume, rho, tol, maxit, with_eval);
             if (eval_now && enqueue_eval(c, LORADS_HIP_PAIR_UV, c->nb ? &c->st[2 * c->nb - 1].done : nullptr)) return 1;
-            return c->use_publish ? enqueue_publish(c, 0, state_words(c)) : 0;
+            if (!c->use_publish) return 0;
+            return enqueue_publish(c, 0, state_words(c), spec && first_pass ? &rho : nullptr, &front_carried);
         };
         if (graph && first_pass) {
             std::vector<uint64_t> key{1, (uint64_t)with_eval, (uint64_t)maxit, (uint64_t)((c->n_sweeps % 32) == 31)};
             if (graph_step(c, key, enq)) return 1;
         } else if (enq()) return 1;
-        if (spec && first_pass) spec_front_enqueue(c, rho);
+        if (spec && first_pass && !front_carried) spec_front_enqueue(c, rho);
         if (c->use_publish ? wait_publish(c) : read_states(c)) return 1;
         if (eval_now && c->ar) any_missed = c->h_scal[5] > 0.5;
         const int stg = first_unfinished(c, first);

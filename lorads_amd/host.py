@@ -686,6 +686,15 @@ class Session:
         _check(lib.lorads_hip_spec_front_stats(ctx, out), "spec_front_stats")
         return dict(zip(["enqueued", "adopted", "discarded", "blocked"], [int(out[i]) for i in range(4)]))
 
+    def hip_handover_stats(self):
+        """{on_front, alone}: result hand-overs carried on the launch of the next step's U front / launched as kernels of their own
+        (LORADS_HANDOVER_ON_FRONT)"""
+        lib, ctx = self._hip()
+        out = (C.c_int64 * 2)()
+        lib.lorads_hip_handover_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_handover_stats(ctx, out), "handover_stats")
+        return dict(zip(["on_front", "alone"], [int(out[i]) for i in range(2)]))
+
     def hip_row_deal_stats(self, blk=0):
         """{rpw, grid, ncu}: rows per workgroup and grid of k_front_cw / k_spmm_ell on cone `blk`, compute units dealt over (LORADS_ROW_DEAL)"""
         lib, ctx = self._hip()

@@ -43,6 +43,14 @@ for k, v in sorted(agg.items(), key=lambda x: -x[1][1]):
     print("%-30s calls %5d  total %9.1f us  avg %7.2f us  med %7.2f us  %5.1f%%" %
           (k, v[0], v[1] / 1e3, v[1] / v[0] / 1e3, statistics.median(v[2]) / 1e3, 100 * v[1] / tot))
 print("sum of kernel time %.3f ms, busy fraction %.2f" % (tot / 1e6, tot / (t1 - t0)))
+# the solve fronts by the kernel in front of them: the U front stands behind the step's hand-over (k_publish_final) or, where its
+# launch carries that hand-over as one more workgroup, behind the evaluation itself; the V front behind k_spmm_ell
+by_pred = collections.OrderedDict()
+for prev, r in zip(adm, adm[1:]):
+    if short(r["Kernel_Name"]) == "k_front_cw":
+        by_pred.setdefault(short(prev["Kernel_Name"]), []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+for k, v in by_pred.items():
+    print("k_front_cw behind %-22s calls %5d  med %7.2f us" % (k, len(v), statistics.median(v) / 1e3))
 gaps = [int(adm[i + 1]["Start_Timestamp"]) - int(adm[i]["End_Timestamp"]) for i in range(len(adm) - 1)]
 print("gaps: median %.2f us  mean %.2f us  max %.1f us  (>20us: %d)" %
       (statistics.median(gaps) / 1e3, sum(gaps) / len(gaps) / 1e3, max(gaps) / 1e3, sum(1 for g in gaps if g > 20000)))
