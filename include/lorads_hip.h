@@ -341,6 +341,13 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *ctx, int32_t block, int out[3]);
  * slot contributions, 3 x and r of CG iteration 0 inside k_spmm_ell, 4 the average R written there, 5 the output of the plain
  * k_spmm_ell; 0 = plain stores everywhere; unset = the default.  Results do not depend on it.  Leaves a front in flight alone. */
 int lorads_hip_wt_stores(lorads_hip_ctx *ctx, int *mask);
+/* what the dense-coefficient GEMM (k_dense_cx_b: a dense objective, dense constraint matrices) launches for cone `block` at its
+ * current device rank: out = {n padded to 64, K split over workgroups (slabs that k_sum_slabs adds when > 1), number of launches L,
+ * then (first column, column tiles of 16 on the matrix cores, single columns on plain FMAs) for each of the L <= 4 launches}, zeros
+ * behind them and for a cone without dense storage.  LORADS_DENSE_REM=0, read at creation, gives the single columns a tile of
+ * their own.  out[15]: the factor array whose products A_j Y with the dense constraint matrices are kept at this moment (0 none,
+ * 1 U, 2 V, 3 another array): whoever overwrites that array has to drop them.  Leaves a front in flight alone. */
+int lorads_hip_dense_plan(lorads_hip_ctx *ctx, int32_t block, int64_t out[16]);
 
 #ifdef __cplusplus
 }

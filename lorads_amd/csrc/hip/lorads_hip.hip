@@ -1200,7 +1200,10 @@ int lorads_hip_alm_cal_grad(lorads_hip_ctx *c, double rho, double *lag) {
 int lorads_hip_lbfgs_direction(lorads_hip_ctx *c, int32_t inner) {
     spec_touch(c);
     c->merged.t_uv_valid = false;
-    for (auto &B : c->blk) B.t_uv_valid = false; // U is overwritten by the direction D
+    // U is overwritten by the direction D: pair values kept for (U, V) and dense products kept for the U array (it is the fixed
+    // factor of a sweep's last solve) are those of the old U.  The fused front and step write D through this function (the one-launch
+    // direction of lbfgs_team.inc never runs for a cone with dense storage).
+    for (auto &B : c->blk) { B.t_uv_valid = false; B.wj_for = nullptr; }
     const size_t n = c->all_elem;
     const int gv = c->ar ? grid1d(n) : grid_lbfgs(n);
     double *D = c->U;
@@ -1980,6 +1983,23 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *c, int32_t k, int out[3]) { // (a 
 int lorads_hip_wt_stores(lorads_hip_ctx *c, int *mask) { // (a statistics entry: leaves a front in flight alone)
     if (!c || !mask) return fail_msg("wt_stores: bad argument");
     *mask = c->opt_wt_stores;
+    return 0;
+}
+
+int lorads_hip_dense_plan(lorads_hip_ctx *c, int32_t k, int64_t out[16]) { // (a statistics entry: leaves a front in flight alone)
+    if (!c || !out) return fail_msg("dense_plan: bad argument");
+    if (k < 0 || k >= c->nb) return fail_msg("bad block");
+    for (int i = 0; i < 16; ++i) out[i] = 0;
+    const Block &B = c->blk[k];
+    if (!B.dense_c && !B.dense_a) return 0;
+    out[0] = B.npad; out[1] = B.ksplit_b;
+    for (int col0 = 0; col0 < B.r && out[2] < 4; col0 += 128) { // (dense_cx's launch loop; rank <= 512: at most four launches)
+        const DenseTiles tl = dense_tiles(B.r, col0, c->opt_dense_rem);
+        int64_t *o = out + 3 + 3 * out[2]++;
+        o[0] = col0; o[1] = tl.nt; o[2] = tl.rem;
+    }
+    // which factor the kept products W_j = A_j Y (dense_cache_fill) belong to right now
+    out[15] = !B.wj_for ? 0 : B.wj_for == c->U + B.off ? 1 : B.wj_for == c->V + B.off ? 2 : 3;
     return 0;
 }
 

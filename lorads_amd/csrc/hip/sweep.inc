@@ -156,6 +156,15 @@ int cw(lorads_hip_ctx *c, const Block &B, const double *X, const double *Y, doub
                               w_out, cv, mode, B.row_idx, vec, g, B.ca_ell, ia, ra, d));
     return grid;
 }
+// the tiles of one k_dense_cx_b launch that starts at column col0 of a rank-r factor: up to 8 column tiles of 16 on the matrix cores;
+// a last tile that would hold 1..4 columns is not given to them: those columns run on plain FMAs (REM)
+struct DenseTiles { int nt, rem; };
+static inline DenseTiles dense_tiles(int r, int col0, bool use_rem) {
+    const int cols = std::min(r - col0, 128);
+    DenseTiles t{(cols + 15) / 16, 0};
+    if (cols % 16 >= 1 && cols % 16 <= 4 && t.nt >= 2 && use_rem) { t.rem = cols % 16; t.nt -= 1; }
+    return t;
+}
 // W = C X on the matrix cores (dense objective only)
 int dense_cx(lorads_hip_ctx *c, const Block &B, const double *X, double *W, Guard g, const double *M = nullptr) {
     c->pend.flush(c);
@@ -165,10 +174,8 @@ int dense_cx(lorads_hip_ctx *c, const Block &B, const double *X, double *W, Guar
         const int gx = B.npad / 32, ks = B.ksplit_b, krange = B.npad / ks;
         double *dst = ks == 1 ? W : B.Wpart;
         for (int col0 = 0; col0 < B.r; col0 += 128) { // (up to 8 column tiles of 16 per launch)
-            const int cols = std::min(B.r - col0, 128);
-            int nt = (cols + 15) / 16, rem = 0;
-            // a last tile that would hold 1..4 columns is not given to the matrix cores: those columns run on plain FMAs (REM)
-            if (cols % 16 >= 1 && cols % 16 <= 4 && nt >= 2 && c->opt_dense_rem) { rem = cols % 16; nt -= 1; }
+            const DenseTiles tl = dense_tiles(B.r, col0, c->opt_dense_rem);
+            const int nt = tl.nt, rem = tl.rem;
 #define DCXB(NTV, RV) hipLaunchKernelGGL((k_dense_cx_b<NTV, 4, RV>), dim3(gx, ks), dim3(TPB), 0, c->stream, B.n, B.npad, krange, M, X, B.r, dst, g, col0)
 #define DCXR(NTV)                                  \
     switch (rem) {                                 \

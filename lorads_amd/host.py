@@ -711,6 +711,18 @@ class Session:
         _check(lib.lorads_hip_wt_stores(ctx, C.byref(out)), "wt_stores")
         return int(out.value)
 
+    def hip_dense_plan(self, blk=0):
+        """{npad, ksplit, launches: [(col0, nt, rem), ...]}: what the dense-coefficient GEMM (k_dense_cx_b) launches for cone `blk` at
+        its current device rank -- n padded to 64, the K split over workgroups, and per launch its first column, its column tiles of
+        16 and its single columns (LORADS_DENSE_REM).  Zeros and no launch for a cone without dense storage.  kept: the factor whose
+        products with the dense constraint matrices are kept at this moment ("", "U", "V" or "other")."""
+        lib, ctx = self._hip()
+        out = (C.c_int64 * 16)()
+        lib.lorads_hip_dense_plan.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_dense_plan(ctx, blk, out), "dense_plan")
+        return dict(npad=int(out[0]), ksplit=int(out[1]), launches=[tuple(int(out[3 + 3 * i + j]) for j in range(3)) for i in range(int(out[2]))],
+                    kept=("", "U", "V", "other")[int(out[15])])
+
     def hip_graph_stats(self):
         """{captured, replayed, held, enabled} of the launch-chain replay (hipGraph) of this context"""
         lib, ctx = self._hip()

@@ -204,6 +204,13 @@ class AdmmModel:
         self.cv = [self.cone_auv(k, self.U[k], self.V[k]) for k in range(self.nb)]
         self.csum = np.sum(self.cv, axis=0) if self.nb else np.zeros(self.m, dtype=self.dtype)
 
+    def scale_obj(self, s):
+        """objScale_dualvar (data/lorads_solver.c:1040-1052): C and the multipliers times s; factors and constraint sums stay"""
+        s = self.dtype(s)
+        for cn in self.cones:
+            cn.c_val = cn.c_val * s
+        self.lam = self.lam * s
+
     def sweep(self, rho, tol, maxit):
         """admm_update_var: returns (CG iterations over all solves, [(cone, half, iterations, history), ...])"""
         rho = self.dtype(rho)

@@ -104,10 +104,11 @@ def _mats(be, which, nb):
     return [be.get_mat(which, k) for k in range(nb)]
 
 
-def run_case(name, env=None, params=None, schedule=SMALL, hist=2, ranks=None, separable=None, hook=False, path="fused"):
-    """runs the schedule on the model and on the device; returns (facts of the session, worst errors by group, bound, records)"""
+def run_case(name, env=None, params=None, schedule=SMALL, hist=2, ranks=None, separable=None, hook=False, path="fused", file=None):
+    """runs the schedule on the model and on the device; returns (facts of the session, worst errors by group, bound, records).
+    file: the instance's file where `name` is no named one."""
     env, params = env or {}, params or {}
-    file = _path(name)
+    file = file or _path(name)
     rho = schedule["rho"]
     with _environment(env):
         s = common.hip_session(file, separable=separable, lbfgs_len=hist, **params)
@@ -175,7 +176,8 @@ def run_case(name, env=None, params=None, schedule=SMALL, hist=2, ranks=None, se
             facts = dict(team=dict(st, launches=st["launches"] - team0), kinds=[s.hip_operator_kind(k) for k in range(nb)],
                          images=[s.hip_block_image(k) for k in range(nb)], ranks=[sh[1] for sh in shapes], iters=len(recs),
                          dir_launches=dir_launches, dir_calls=dir_calls, step_launches=step_launches, calls=list(calls),
-                         fallbacks=fallbacks, elements=sum(a * b for a, b in shapes), hist=hist, lp=[cn.is_lp for cn in model.cones], m=s.m)
+                         fallbacks=fallbacks, elements=sum(a * b for a, b in shapes), hist=hist, lp=[cn.is_lp for cn in model.cones], m=s.m,
+                         dense=[s.hip_dense_plan(k) for k in range(nb)])
             print(name, env, path, "history", hist, "ranks", facts["ranks"], "iterations", len(recs), "e64 %.1e" % max(e64[:len(recs)]),
                   "bound %.1e" % bound, "worst", {k: "%.1e" % v for k, v in worst.items()}, "team", facts["team"],
                   "launches/direction", dir_launches, "launches/step", step_launches,

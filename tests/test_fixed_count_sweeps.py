@@ -155,7 +155,8 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
         facts = dict(kinds=[s.hip_operator_kind(k) for k in range(s.nblk)], images=[s.hip_block_image(k) for k in range(s.nblk)],
                      persist=s.hip_persist_stats()["iterations"] - p0, launches=s.hip_launch_count() - n0, calls=len(calls),
                      ranks=[s.block_shape(k)[1] for k in range(s.nblk)], stops=stops, counts=counts, persist_calls=persist_calls,
-                     stats=s.hip_persist_stats(), plan=s.hip_persist_plan())
+                     stats=s.hip_persist_stats(), plan=s.hip_persist_plan(), dense=[s.hip_dense_plan(k) for k in range(s.nblk)],
+                     graph=s.hip_graph_stats())
         if stamps:
             word = s.hip_persist_stamps(False)[15]
             facts["l2"] = (word >> 1) & 3 if word & 1 else None  # bit 0: granules through the XCD's L2, bit 1: factor rows too
