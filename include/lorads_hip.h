@@ -193,6 +193,35 @@ int lorads_hip_round_kcut(lorads_hip_ctx *ctx, int32_t src, int32_t parts, int32
                           double *obj, double *obj0, int32_t *best, int32_t *best0, uint8_t *label, int32_t *rounds, double *vectors,
                           double *t, double *lp_upper);
 
+/* Stable sets read off the factors of a theta-structured context, with a (1, 2)-swap search (no reference
+ * counterpart).  Qualifies: at least one SDP cone, at most one LP block, no dense constraint matrices; per SDP cone exactly one trace
+ * row -- a I over all n rows with a > 0 and b > 0, touching no other cone: T_k = b / a; every other constraint without an LP entry an
+ * edge row: one off-diagonal entry (p, q) of one cone, b = 0 (the edge rows are the cone's graph G_k); every constraint with an LP
+ * entry a bound row as lorads_hip_round_kcut takes it.  C is arbitrary.  For a stable set S of G_k the point X(S) = T_k 1_S 1_S^T / |S|
+ * is feasible; f_k = <C_k, X(S)> (the theta files: -|S|).  Per cone k and trial t a priority per vertex: trial 0 takes |F_p|^2, trial
+ * t >= 1 takes F_p . g_t with g_t lorads_hip_round_pm1's hyperplane t of that seed and F the factor lorads_hip_certificate takes (src),
+ * the projections one product on the FP64 matrix cores.  The trial's set is the lexicographically first maximal stable set in the
+ * order (priority descending, index ascending); then at most max_rounds rounds of the (1, 2)-swap search (0: none): the member of
+ * least index that has two non-adjacent neighbours with no other member next to them leaves, the lexicographically first such pair
+ * joins, and the vertices left without a member next to them are completed greedily in the trial's order; the round that finds no
+ * such member is the last and is counted.  One workgroup owns one trial.  Values in device terms (C scaled by scaleObjHis).
+ * Read-only on the solver's state; the same state and arguments give the same bits.
+ *   obj [trials]            sum_k f_k after the search       obj0 [trials] (may be NULL)  of the greedy sets
+ *   best / best0            argmin of obj / obj0 (lowest index on ties; may be NULL)
+ *   member [sum_k n_k]      the best trial's sets after the search, 1: in the set, SDP cone after SDP cone (may be NULL)
+ *   sizes [cones x trials]  |S| after the search, cone after cone, per trial (may be NULL)
+ *   rounds                  the largest number of search rounds a trial ran (may be NULL)
+ *   scores                  per SDP cone trials x n_k priorities (trial, then vertex), cone after cone (may be NULL)
+ *   T [cones + LP columns]  T_k of the SDP cones, then u_j = (|2 a| T_k / 2 + |b|) / |c| of the LP columns' bound rows: x_j <= u_j at
+ *                           every feasible point, since |X_pq| <= (X_pp + X_qq) / 2 <= T_k / 2 (may be NULL)
+ * trials = 0 checks applicability only (T is still filled).  There is no limit on n or on a vertex's degree.  Returns 1 on a bad
+ * argument (src, trials outside [0, 65536], max_rounds < 0, obj NULL with trials > 0) or a failed allocation (the context stays
+ * usable), 2 when the context does not qualify (lorads_hip_last_error names the first offending constraint, cone or column), 3 when
+ * it is sharded -- all before any device work. */
+int lorads_hip_round_stable(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
+                            double *obj0, int32_t *best, int32_t *best0, uint8_t *member, int32_t *sizes, int32_t *rounds,
+                            double *scores, double *T);
+
 /* Spectrum and rank reduction of the solution factors (no reference counterpart).  Per SDP cone k (the LP block
  * has no factor and is passed over) F_k is the factor lorads_hip_certificate takes (src) at the cone's own rank rl_k, G_k = F_k^T F_k =
  * Q_k Lambda_k Q_k^T with lambda_1 >= lambda_2 >= ... (ties: lower original index first): the non-zero eigenvalues of X_k = F_k F_k^T.

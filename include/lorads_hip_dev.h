@@ -89,6 +89,10 @@ int lorads_hip_launch_count(lorads_hip_ctx *ctx, int64_t *n);
  * stats = {device allocations, device bytes, pinned allocations, pinned bytes} */
 int lorads_hip_memory_stats(int64_t stats[4]);
 
+/* the sets of trial `trial` of this context's last lorads_hip_round_stable call, as that call's `member` (its states stay in the
+ * feature's scratch until the next call): a test compares every trial with the model, not the best one alone */
+int lorads_hip_stable_trial(lorads_hip_ctx *ctx, int32_t trial, uint8_t *member);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,78 @@ __global__ __launch_bounds__(TPB) void k_kcut_field(int nrows, const int *__rest
     if (wv == 0 && valid) part[(size_t)t * RND_STRIPS + strip] = ((sh[0][lane] + sh[0][64 + lane]) + sh[0][128 + lane]) + sh[0][192 + lane];
 }
 
+// ---- the constraint data as the applicability checks read it (shared with stable.inc)
+// every stored entry, constraint by constraint: (block, row, column, coefficient); b; the LP block's objective
+struct ConEnt { int k, p, q; double a; };
+struct ConData {
+    std::vector<std::vector<ConEnt>> con;
+    std::vector<double> b, cobj;
+};
+int read_constraints(lorads_hip_ctx *c, ConData &D) {
+    D.con.assign((size_t)c->m, {});
+    D.b.assign((size_t)c->m, 0.0);
+    D.cobj.clear();
+    if (c->m) HC(hipMemcpyAsync(D.b.data(), c->b, sizeof(double) * D.b.size(), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        if (B.is_lp) { // (read_constraint_image below synchronises for this copy too)
+            D.cobj.resize((size_t)B.n);
+            if (B.n) HC(hipMemcpyAsync(D.cobj.data(), B.lp_cobj, sizeof(double) * D.cobj.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        ConImage m;
+        if (read_constraint_image(c, k, m)) return 1;
+        for (int i = 0; i < B.nrow; ++i)
+            for (int s = m.ap[i]; s < m.ap[i + 1]; ++s) D.con[(size_t)m.ri[i]].push_back({k, m.er[m.ae[s]], m.ec[m.ae[s]], m.av[s]});
+    }
+    return 0;
+}
+// what holds before any constraint is looked at: at most one LP block, a cone, no dense constraint matrices ("" or the reason)
+std::string blocks_admit_bound_rows(const lorads_hip_ctx *c, int *lpk) {
+    char msg[256];
+    int nlp = 0, nsdp = 0;
+    *lpk = -1;
+    for (int k = 0; k < c->nb; ++k) {
+        if (c->blk[k].is_lp) { ++nlp; *lpk = k; } else ++nsdp;
+    }
+    if (nlp > 1) return "more than one LP block";
+    if (nsdp == 0) return "no cone";
+    for (int k = 0; k < c->nb; ++k)
+        if (c->blk[k].dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); return msg; }
+    return "";
+}
+// entries of constraint E in the LP block lpk
+inline int lp_entries(const std::vector<ConEnt> &E, int lpk) {
+    int lp = 0;
+    for (const ConEnt &e : E) lp += e.k == lpk;
+    return lp;
+}
+// A constraint with an LP entry as the bound row 2 a X_pq + c x_j = b (what lrd_session_write_bounded appends): one off-diagonal
+// cone entry and one LP column, neither coefficient zero.  "" and the row, or the reason it is none.
+struct BoundRow { int i, k, p, q, j; double a, cc; };
+std::string bound_row(int i, const std::vector<ConEnt> &E, int lpk, BoundRow &r) {
+    char msg[256];
+    int lp = 0, sdp = 0;
+    const ConEnt *el = nullptr, *es = nullptr;
+    for (const ConEnt &e : E) {
+        if (e.k == lpk) { ++lp; el = &e; } else { ++sdp; es = &e; }
+    }
+    if (lp != 1) { snprintf(msg, sizeof msg, "constraint %d has %d LP entries", i + 1, lp); return msg; }
+    if (sdp != 1) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and %d cone entries", i + 1, sdp); return msg; }
+    if (es->p == es->q) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and a diagonal entry", i + 1); return msg; }
+    if (el->a == 0.0 || es->a == 0.0) { snprintf(msg, sizeof msg, "constraint %d has a zero coefficient", i + 1); return msg; }
+    r = {i, es->k, es->p, es->q, el->p, es->a, el->a};
+    return "";
+}
+// every LP column in exactly one bound row and without an objective ("" or the reason)
+std::string lp_columns_only_bound(const std::vector<int> &col_use, const std::vector<double> &cobj) {
+    char msg[256];
+    for (size_t j = 0; j < col_use.size(); ++j) {
+        if (col_use[j] != 1) { snprintf(msg, sizeof msg, "LP column %d occurs in %d constraints", (int)j + 1, col_use[j]); return msg; }
+        if (cobj[j] != 0.0) { snprintf(msg, sizeof msg, "LP column %d has an objective coefficient", (int)j + 1); return msg; }
+    }
+    return "";
+}
+
 // Applicability (once per context: the constraint data never changes).  Without an LP block it is rnd_check's answer and t; with one
 // the constraint data is read back and checked here, and t and the bounds u_j of the LP columns are kept.
 int kcut_check(lorads_hip_ctx *c) {
@@ -155,11 +227,9 @@ int kcut_check(lorads_hip_ctx *c) {
     X.why.clear();
     X.t = nullptr;
     X.lp_u.clear();
-    int nlp = 0, lpk = -1, nsdp = 0;
-    for (int k = 0; k < c->nb; ++k) {
-        if (c->blk[k].is_lp) { ++nlp; lpk = k; } else ++nsdp;
-    }
-    if (nlp == 0) {
+    int lpk = -1;
+    const std::string blocks = blocks_admit_bound_rows(c, &lpk);
+    if (lpk < 0) {
         X.qualifies = Rn.qualifies;
         X.why = Rn.why;
         X.t = Rn.t;
@@ -167,42 +237,23 @@ int kcut_check(lorads_hip_ctx *c) {
         return 0;
     }
     char msg[256];
-    if (nlp > 1) X.why = "more than one LP block";
-    else if (nsdp == 0) X.why = "no cone";
-    for (int k = 0; k < c->nb && X.why.empty(); ++k)
-        if (c->blk[k].dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); X.why = msg; }
+    X.why = blocks;
     if (!X.why.empty()) { X.checked = true; return 0; }
-    // every stored entry, constraint by constraint: (block, row, column, coefficient)
-    struct Ent { int k, p, q; double a; };
-    std::vector<std::vector<Ent>> con((size_t)c->m);
-    std::vector<double> b((size_t)c->m), th((size_t)Rn.t_off[c->nb], 0.0), cobj;
-    if (c->m) HC(hipMemcpyAsync(b.data(), c->b, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        if (B.is_lp) { // (read_constraint_image below synchronises for this copy too)
-            cobj.resize((size_t)B.n);
-            if (B.n) HC(hipMemcpyAsync(cobj.data(), B.lp_cobj, sizeof(double) * cobj.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        ConImage m;
-        if (read_constraint_image(c, k, m)) return 1;
-        for (int i = 0; i < B.nrow; ++i)
-            for (int s = m.ap[i]; s < m.ap[i + 1]; ++s) con[(size_t)m.ri[i]].push_back({k, m.er[m.ae[s]], m.ec[m.ae[s]], m.av[s]});
-    }
+    ConData D;
+    if (read_constraints(c, D)) return 1;
+    const std::vector<double> &b = D.b;
+    std::vector<double> th((size_t)Rn.t_off[c->nb], 0.0);
     const int nl = c->blk[lpk].n;
     std::vector<int> col_use((size_t)nl, 0);
     std::vector<std::vector<int>> cover((size_t)c->nb);
     for (int k = 0; k < c->nb; ++k) cover[k].assign((size_t)c->blk[k].n, 0);
     X.lp_u.assign((size_t)nl, 0.0);
-    struct Row { int i, k, p, q, j; double a, cc; };
-    std::vector<Row> brow;
+    std::vector<BoundRow> brow;
     for (int i = 0; i < c->m && X.why.empty(); ++i) {
-        const std::vector<Ent> &E = con[(size_t)i];
-        int lp = 0, sdp = 0;
-        const Ent *el = nullptr, *es = nullptr;
-        for (const Ent &e : E) {
-            if (e.k == lpk) { ++lp; el = &e; } else { ++sdp; es = &e; }
-        }
-        if (lp == 0) {
+        const std::vector<ConEnt> &E = D.con[(size_t)i];
+        if (lp_entries(E, lpk) == 0) {
+            const int sdp = (int)E.size();
+            const ConEnt *es = sdp ? &E.back() : nullptr;
             if (sdp != 1) { snprintf(msg, sizeof msg, "constraint %d has %d stored entries", i + 1, sdp); X.why = msg; break; }
             if (es->p != es->q) { snprintf(msg, sizeof msg, "constraint %d is not on a diagonal", i + 1); X.why = msg; break; }
             const double ratio = b[(size_t)i] / es->a;
@@ -214,12 +265,11 @@ int kcut_check(lorads_hip_ctx *c) {
             cover[es->k][es->p]++;
             th[(size_t)Rn.t_off[es->k] + es->p] = std::sqrt(ratio);
         } else {
-            if (lp != 1) { snprintf(msg, sizeof msg, "constraint %d has %d LP entries", i + 1, lp); X.why = msg; break; }
-            if (sdp != 1) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and %d cone entries", i + 1, sdp); X.why = msg; break; }
-            if (es->p == es->q) { snprintf(msg, sizeof msg, "constraint %d has an LP entry and a diagonal entry", i + 1); X.why = msg; break; }
-            if (el->a == 0.0 || es->a == 0.0) { snprintf(msg, sizeof msg, "constraint %d has a zero coefficient", i + 1); X.why = msg; break; }
-            col_use[(size_t)el->p]++;
-            brow.push_back({i, es->k, es->p, es->q, el->p, es->a, el->a});
+            BoundRow r;
+            X.why = bound_row(i, E, lpk, r);
+            if (!X.why.empty()) break;
+            col_use[(size_t)r.j]++;
+            brow.push_back(r);
         }
     }
     for (int k = 0; k < c->nb && X.why.empty(); ++k) {
@@ -230,13 +280,10 @@ int kcut_check(lorads_hip_ctx *c) {
                 X.why = msg;
             }
     }
-    for (int j = 0; j < nl && X.why.empty(); ++j) {
-        if (col_use[(size_t)j] != 1) { snprintf(msg, sizeof msg, "LP column %d occurs in %d constraints", j + 1, col_use[(size_t)j]); X.why = msg; }
-        else if (cobj[(size_t)j] != 0.0) { snprintf(msg, sizeof msg, "LP column %d has an objective coefficient", j + 1); X.why = msg; }
-    }
+    if (X.why.empty()) X.why = lp_columns_only_bound(col_use, D.cobj);
     X.qualifies = X.why.empty();
     if (X.qualifies) {
-        for (const Row &r : brow) // x_j = (b - 2 a X_pq) / c and |X_pq| <= t_p t_q
+        for (const BoundRow &r : brow) // x_j = (b - 2 a X_pq) / c and |X_pq| <= t_p t_q
             X.lp_u[(size_t)r.j] = (std::fabs(b[(size_t)r.i]) + 2.0 * std::fabs(r.a) * th[(size_t)Rn.t_off[r.k] + r.p] * th[(size_t)Rn.t_off[r.k] + r.q]) /
                                   std::fabs(r.cc);
         if (X.mem.upload(&X.t_own, th)) return 1;

@@ -654,6 +654,26 @@ struct KCutScratch {
     void release() { mem.release(); *this = KCutScratch{}; }
 };
 
+// scratch of the stable-set rounding (stable.inc): allocated on its first call, never read by the solve.  Per cone the graph of its
+// edge rows (CSR, both directions, ascending), G 8 K sum(rank), one state byte per (trial, vertex) of every cone, and per chunk of
+// trials the scores (8 n) and the search's lists (4 n) of the cone at hand.
+struct StableScratch {
+    bool checked = false, qualifies = false;
+    std::string why;                          // the first reason the context does not qualify
+    std::vector<int> v_off;                   // [nb + 1] first vertex of every SDP cone in the stacked vertex arrays (an LP block has none)
+    std::vector<long long> e_off;             // [nb + 1] first adjacency entry of every SDP cone in g_col
+    std::vector<double> T;                    // [nb] T_k = b / a of the cone's trace row (LP block: 0)
+    std::vector<double> lp_u;                 // [LP columns] u_j = (|2 a| T / 2 + |b|) / |c| of the column's bound row
+    int *g_ptr = nullptr, *g_col = nullptr;   // cone k: g_ptr + v_off[k] + k (n + 1 entries, relative to the cone's own columns), g_col + e_off[k]
+    DevBuf<double> G, sc, f, f0;              // the directions; the chunk's scores [trial][vertex]; obj, obj0
+    DevBuf<unsigned char> st;                 // states, cone k at v_off[k] * K, trial t of it n bytes further per trial
+    DevBuf<int> own, size, nround;            // the chunk's lists (the one member next to a vertex); |S| per (cone, trial); rounds per trial
+    int *ctl = nullptr;                       // [0] best before, [1] best after the search
+    int K = 0;                                // trials of the last call (lorads_hip_stable_trial reads its states)
+    DevPool mem;
+    void release() { mem.release(); *this = StableScratch{}; }
+};
+
 // scratch of the spectrum / rank reduction (spectral.inc): allocated on its first call, never read by the solve
 struct SpecCone { int rl, m; long long g_off, e_off, q_off; }; // one cone of a k_spec_jacobi launch: orders, places in SpecScratch::W
 struct SpecScratch {
@@ -728,6 +748,7 @@ struct lorads_hip_ctx {
     CertScratch cert;                 // solution export (solution.inc)
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
     KCutScratch kcut;                 // rounding into k parts (kcut.inc)
+    StableScratch stable;             // stable-set rounding (stable.inc)
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
@@ -1093,6 +1114,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->bounds.release();
     c->topk.release();
     c->kcut.release();
+    c->stable.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -2029,6 +2051,7 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "solution.inc"
 #include "rounding.inc"
 #include "kcut.inc"
+#include "stable.inc"
 #include "spectral.inc"
 #include "primal.inc"
 #include "select.inc"

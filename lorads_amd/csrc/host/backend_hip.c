@@ -62,6 +62,8 @@ typedef struct {
                       int32_t *, double *, double *, double *); /* optional */
     int (*primal_topk)(lorads_hip_ctx *, int32_t, int32_t, int32_t, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t,
                        const int64_t *, const int32_t *, int32_t *, double *, int32_t *); /* optional */
+    int (*round_stable)(lorads_hip_ctx *, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, uint8_t *,
+                        int32_t *, int32_t *, double *, double *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -138,6 +140,12 @@ static int b_kcut(void *cx, int src, int parts, int trials, uint64_t seed, int m
                   int *best0, uint8_t *label, int *rounds, double *vec, double *t, double *lpu) {
     return report(H, H->round_kcut(H->ctx, src, parts, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, label,
                                    (int32_t *)rounds, vec, t, lpu), "round_kcut");
+}
+/* stable sets: codes 2 (not theta-structured) and 3 (sharded) pass through with the library's reason on stderr */
+static int b_stable(void *cx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                    uint8_t *member, int *sizes, int *rounds, double *scores, double *T) {
+    return report(H, H->round_stable(H->ctx, src, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, member,
+                                     (int32_t *)sizes, (int32_t *)rounds, scores, T), "round_stable");
 }
 /* top-k search: codes 2 (the LP block) and 3 (sharded) pass through */
 static int b_topk(void *cx, int src, int blk, int nq, const int *row, int lo, int hi, int k, int smallest, int diag, const int64_t *sptr,
@@ -216,6 +224,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->entry_bounds) = dlsym(h->dl, "lorads_hip_entry_bounds");
     *(void **)(&h->round_kcut) = dlsym(h->dl, "lorads_hip_round_kcut");
     *(void **)(&h->primal_topk) = dlsym(h->dl, "lorads_hip_primal_topk");
+    *(void **)(&h->round_stable) = dlsym(h->dl, "lorads_hip_round_stable");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -267,5 +276,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->entry_bounds) out->entry_bounds = b_bounds;
     if (h->round_kcut) out->round_kcut = b_kcut;
     if (h->primal_topk) out->primal_topk = b_topk;
+    if (h->round_stable) out->round_stable = b_stable;
     return 0;
 }

@@ -164,6 +164,11 @@ typedef struct lrd_backend {
      * get_slack: S of block blk as lower-triangle triplets; NULL arrays return the count alone. */
     int (*certificate)(void *ctx, int src, double tol, double *out, double *lam_min, double *residual, double *y);
     int (*get_slack)(void *ctx, int blk, int64_t *nnz, int *row, int *col, double *val);
+    /* OPTIONAL (in front of round_pm1: the table's mirror is checked to hold round_pm1, round_kcut and the primal pair side by side):
+     * stable sets of a theta-structured context read off the factors + the (1, 2)-swap search, read-only on the state
+     * (include/lorads_hip.h: lorads_hip_round_stable, the same arguments and return codes; values in the backend's terms) */
+    int (*round_stable)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                        uint8_t *member, int *sizes, int *rounds, double *scores, double *T);
     /* OPTIONAL: hyperplane rounding + 1-flip local search of a +-1-structured context, read-only on the state (include/lorads_hip.h:
      * lorads_hip_round_pm1, the same arguments and return codes; values in the backend's terms) */
     int (*round_pm1)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
@@ -536,6 +541,42 @@ int lrd_session_kcut(lrd_session *s, int parts, int trials, uint64_t seed, int m
 void lrd_kcut_free(lrd_kcut *r);
 /* plain-text file, a pure function of the struct (kcut.c) */
 int lrd_kcut_write(const char *path, const lrd_kcut *r);
+
+/* ---- stable sets of theta-structured problems (stable.c).  Everything in the file's units.  Every SDP cone has
+ * one trace row a tr(X_k) = b (T_k = b / a) and edge rows X_pq = 0, the cone's graph; LP columns only in bound rows as above.  For a
+ * stable set S of the graph X(S) = T_k 1_S 1_S^T / |S| is feasible; f = sum_k <C_k, X(S_k)> (the theta files: -|S|); the dual bound
+ * d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) <= the optimum <= f. */
+typedef struct {
+    int blk;           /* the cone's block in the file, 0-based */
+    int n, rank;       /* rank: the cone's own current rank (the directions' dimension) */
+    int size;          /* |S| of the best trial after the search */
+    int *member;       /* [size] the set, 0-based, ascending */
+    int *sizes;        /* [trials] |S| of every trial after the search */
+    double T;
+    double lam_min;    /* lambda_min(S_k) (NaN without a bound) */
+    double *scores;    /* trials x n priorities (trial, then vertex) in the backend's terms, only when asked for (else NULL) */
+} lrd_stable_cone;
+typedef struct {
+    int nblk;           /* SDP cones */
+    int trials, max_rounds, rounds;
+    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where F came from */
+    uint64_t seed;
+    double scale;       /* scaleObjHis the backend's values were divided by */
+    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
+    double f_best, f_best0;
+    double *obj, *obj0; /* [trials] f after the search / of the greedy sets */
+    int nlp, lp_neg;    /* LP columns; how many of them have a dual slack s_j < 0 (0 without a bound) */
+    double *lp_upper;   /* [nlp] u_j */
+    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
+    double tol;         /* Lanczos tolerance of lambda_min */
+    lrd_stable_cone *cone; /* [nblk], file order */
+} lrd_stable;
+/* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
+ * lacks the slot, 3 when it is sharded.  with_scores: also fill every cone's scores. */
+int lrd_session_round_stable(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_scores, lrd_stable **out);
+void lrd_stable_free(lrd_stable *r);
+/* plain-text file, a pure function of the struct (stable.c) */
+int lrd_stable_write(const char *path, const lrd_stable *r);
 
 /* ---- internal: what the post-solve drivers and writers above share (not part of the interface)
  * Two adjacent runs [0, at) and [at, at + got) of a list kept as ncol parallel columns, each sorted by `before(list, a, b)` (is entry a

@@ -48,6 +48,9 @@ int main(int argc, char **argv) {
     int kcut_parts = 0, kcut_trials = 1024, kcut_ls = 100; /* rounding of a k-cut-structured problem into k parts (ours as well) */
     unsigned long long kcut_seed = 0;
     const char *kcut_file = NULL, *kcut_other = NULL; /* kcut_other: some --kcut* option other than --kcutParts was given */
+    int stable_trials = 0, stable_ls = 100; /* stable sets of a theta-structured problem read off the factors (ours as well) */
+    unsigned long long stable_seed = 0;
+    const char *stable_file = NULL, *stable_other = NULL; /* stable_other: some --stable* option other than --stableTrials was given */
     const char *topk_in = NULL, *topk_out = NULL, *topk_other = NULL; /* the k best entries per row of the primal (ours as well);
                                                                        * topk_other: some --topk* option other than --topkFile was given */
     int topk_k = 0, topk_smallest = 0, topk_diag = 0, topk_constrained = 0;
@@ -159,6 +162,25 @@ int main(int argc, char **argv) {
             }
             continue;
         }
+        if (!strcmp(argv[i], "--stableFile")) { stable_other = argv[i]; stable_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--stableTrials") || !strcmp(argv[i], "--stableSeed") || !strcmp(argv[i], "--stableLocalSearch")) {
+            char *end = NULL;
+            const char w = argv[i][8]; /* T, S or L */
+            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
+            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'T' && (v < 1 || v > 65536)) ||
+                (w == 'L' && v > 65536)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            if (w == 'T') stable_trials = (int)v;
+            else {
+                stable_other = argv[i];
+                if (w == 'S') stable_seed = v;
+                else stable_ls = (int)v;
+            }
+            continue;
+        }
         if (!strcmp(argv[i], "--compressTol") || !strcmp(argv[i], "--compressRank")) {
             char *end = NULL;
             const int is_tol = argv[i][10] == 'T';
@@ -206,6 +228,11 @@ int main(int argc, char **argv) {
     }
     if (kcut_parts > 0 && (long)kcut_parts * kcut_trials > (1L << 20)) {
         fprintf(stderr, "bad value of --kcutParts and --kcutTrials: %d x %d is above 2^20\n", kcut_parts, kcut_trials);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (stable_other && stable_trials == 0) {
+        fprintf(stderr, "%s needs --stableTrials\n", stable_other);
         lrd_session_close(s);
         return 2;
     }
@@ -293,6 +320,15 @@ int main(int argc, char **argv) {
         lrd_kcut *none = NULL;
         if (lrd_session_kcut(s, kcut_parts, 0, kcut_seed, kcut_ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --kcutParts needs a k-cut-structured problem (see above); nothing was solved\n");
+            lrd_topk_free(topk);
+            lrd_session_close(s);
+            return 2;
+        }
+    }
+    if (stable_trials > 0) { /* applicability before any solving */
+        lrd_stable *none = NULL;
+        if (lrd_session_round_stable(s, 0, stable_seed, stable_ls, 0.0, 0, &none)) {
+            fprintf(stderr, "lorads: --stableTrials needs a theta-structured problem (see above); nothing was solved\n");
             lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
@@ -451,6 +487,20 @@ int main(int argc, char **argv) {
         printf("Rounding into %d parts (%d trials, seed %llu%s%s): best f %.10e, dual bound d %.10e, gap %.6e, %d local-search rounds\n",
                x->parts, x->trials, kcut_seed, kcut_file ? ", " : "", kcut_file ? kcut_file : "", x->f_best, x->bound, x->gap, x->rounds);
         lrd_kcut_free(x);
+    }
+    if (stable_trials > 0) {
+        lrd_stable *x = NULL;
+        if (lrd_session_round_stable(s, stable_trials, (uint64_t)stable_seed, stable_ls, 1e-8, 0, &x) ||
+            (stable_file && lrd_stable_write(stable_file, x))) {
+            fprintf(stderr, "lorads: the stable-set rounding failed%s%s\n", stable_file ? " or cannot write " : "", stable_file ? stable_file : "");
+            lrd_stable_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Stable sets (%d trials, seed %llu%s%s): size", x->trials, stable_seed, stable_file ? ", " : "", stable_file ? stable_file : "");
+        for (int k = 0; k < x->nblk; ++k) printf(" %d", x->cone[k].size);
+        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->f_best, x->bound, x->gap, x->rounds);
+        lrd_stable_free(x);
     }
     lrd_session_close(s);
     return 0;

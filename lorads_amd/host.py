@@ -60,6 +60,8 @@ class BackendStruct(C.Structure):
         ("alm_step", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, _dp)),
         ("certificate", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp)),
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
+        ("round_stable", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
+                                     C.POINTER(C.c_uint8), _ip, _ip, _dp, _dp)),
         ("round_pm1", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
                                   C.POINTER(C.c_int8), _ip, _dp)),
         ("round_kcut", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
@@ -391,6 +393,54 @@ class Backend:
             return rc, None
         return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, label=label[:ntot], rounds=rounds.value,
                        t=t[:ntot], lp_upper=lpu[:nlp], vectors=vec[:glen] if glen else None)
+
+    def has_round_stable(self):
+        return bool(self._s.round_stable)
+
+    def round_stable(self, src, trials, seed=0, max_rounds=0, want_scores=False):
+        """the table's slot as it is (values in the backend's terms): returns (code, dict) with obj, obj0, best, best0, member (0/1
+        per vertex, SDP cone after SDP cone), sizes (cones x trials), rounds, T (per SDP cone), lp_upper and -- want_scores -- scores
+        (per SDP cone an n x trials array); code != 0 is the slot's refusal (the dict is then None).  trials = 0 checks
+        applicability and still gives T and lp_upper."""
+        ses = self._session
+        lp = ses._lp_blocks()
+        ns = [ses.block_shape(k)[0] for k in range(ses.nblk) if not lp[k]]
+        ntot, ncone = sum(ns), len(ns)
+        nlp = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if lp[k])
+        K = max(int(trials), 0)
+        ok = K <= 65536
+        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
+        member, Tu = np.zeros(max(ntot, 1), dtype=np.uint8), np.zeros(max(ncone + nlp, 1))
+        sizes = np.zeros(max(ncone * K, 1) if ok else 1, dtype=np.int32)
+        slen = ntot * K if want_scores and ok else 0
+        sc = np.zeros(max(slen, 1))
+        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self._s.round_stable(self._s.ctx, int(src), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
+                                  obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
+                                  member.ctypes.data_as(C.POINTER(C.c_uint8)), sizes.ctypes.data_as(_ip), C.byref(rounds),
+                                  sc.ctypes.data_as(_dp) if slen else None, Tu.ctypes.data_as(_dp))
+        if rc:
+            return rc, None
+        scores, at = None, 0
+        if slen:
+            scores = []
+            for n in ns:
+                scores.append(sc[at * K:(at + n) * K].reshape(K, n).T.copy())
+                at += n
+        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, member=member[:ntot],
+                       sizes=sizes[:ncone * K].reshape(ncone, K), rounds=rounds.value, T=Tu[:ncone], lp_upper=Tu[ncone:ncone + nlp],
+                       scores=scores)
+
+    def stable_trial(self, trial):
+        """the sets of one trial of the last round_stable call on this table's HIP context (0/1 per vertex, SDP cone after SDP cone)"""
+        ses = self._session
+        lib, ctx = ses._hip()
+        lp = ses._lp_blocks()
+        ntot = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if not lp[k])
+        member = np.zeros(max(ntot, 1), dtype=np.uint8)
+        lib.lorads_hip_stable_trial.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]
+        _check(lib.lorads_hip_stable_trial(ctx, int(trial), member.ctypes.data_as(C.POINTER(C.c_uint8))), "stable_trial")
+        return member[:ntot]
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -1045,6 +1095,54 @@ class Session:
             _check(self.lib.lrd_kcut_write(os.fsencode(path), ptr), "kcut_write")
         finally:
             self.lib.lrd_kcut_free(ptr)
+
+    def _stable_ptr(self, trials, seed, local_search_rounds, tol, scores):
+        from .stable import StableStruct
+        trials, local_search_rounds = int(trials), int(local_search_rounds)
+        if not 0 <= trials <= 65536:
+            raise ValueError("round_stable: trials %d is outside [0, 65536]" % trials)
+        if local_search_rounds < 0:
+            raise ValueError("round_stable: local_search_rounds %d is negative" % local_search_rounds)
+        ptr = C.POINTER(StableStruct)()
+        self.lib.lrd_session_round_stable.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
+                                                      C.POINTER(C.POINTER(StableStruct))]
+        self.lib.lrd_stable_free.argtypes = [C.POINTER(StableStruct)]
+        self.lib.lrd_stable_free.restype = None
+        rc = self.lib.lrd_session_round_stable(self.h, trials, int(seed) & 0xFFFFFFFFFFFFFFFF, local_search_rounds, float(tol),
+                                               1 if scores else 0, C.byref(ptr))
+        self._refused(rc, "no stable set can be read off the solution: the problem is not theta-structured (per cone one trace row "
+                      "a tr(X) = b with a, b > 0, every other constraint an edge row X[p,q] = 0; LP columns only in bound rows "
+                      "2 a X[p,q] + c x_j = b) or the %s backend cannot round%s",
+                      "rounding the solution of a sharded deal (world > 1) is not supported")
+        _check(rc, "round_stable")
+        return ptr
+
+    def round_stable(self, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, scores=False):
+        """Stable sets of a theta-structured problem's graphs read off the current point, on the device (lorads_amd.stable.StableSet,
+        file units): per trial the greedy set in the order of the vertices' priorities (trial 0: X_pp; trial t: F_p . g_t) and a
+        (1, 2)-swap search, f = sum <C, X(S)> with X(S) = T 1_S 1_S^T / |S| before and after the search, the best trial's members
+        and sizes per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) at Lanczos
+        tolerance tol (tol <= 0: NaN): for the theta files |S| <= alpha <= floor(-d).  trials = 0 checks applicability alone
+        (None).  Read-only on the solver's state."""
+        from .stable import StableSet
+        if trials == 0:
+            self._stable_ptr(0, seed, local_search_rounds, tol, False)
+            return None
+        ptr = self._stable_ptr(trials, seed, local_search_rounds, tol, scores)
+        try:
+            return StableSet.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_stable_free(ptr)
+
+    def write_stable(self, path, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
+        """the stable-set file of the command line's --stableFile (the same C writer: the same bytes)"""
+        from .stable import StableStruct
+        ptr = self._stable_ptr(trials, seed, local_search_rounds, tol, False)
+        try:
+            self.lib.lrd_stable_write.argtypes = [C.c_char_p, C.POINTER(StableStruct)]
+            _check(self.lib.lrd_stable_write(os.fsencode(path), ptr), "stable_write")
+        finally:
+            self.lib.lrd_stable_free(ptr)
 
     def triangle_cuts(self, max_cuts=1000, min_violation=1e-3):
         """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device
