@@ -222,6 +222,37 @@ int lorads_hip_round_stable(lorads_hip_ctx *ctx, int32_t src, int32_t trials, ui
                             double *obj0, int32_t *best, int32_t *best0, uint8_t *member, int32_t *sizes, int32_t *rounds,
                             double *scores, double *T);
 
+/* Balanced partitions read off the factors of a bisection-structured context, with a repair step and a swap search (DESIGN.md section
+ * 19; no reference counterpart).  Qualifies: no LP block; per cone k the diagonal rows of lorads_hip_round_pm1 -- one a_i X_k[p,p] = b_i
+ * with b_i / a_i > 0 per diagonal position --, all t_p = sqrt(b_i / a_i) bit-equal (t_k), and exactly one sum row: every position of
+ * the cone's lower triangle, all values bit-equal to one a != 0, no entry on another cone, and |q - d_k^2| <= 1e-9 max(1, q) for
+ * q = b / (a t_k^2) and an integer 0 <= d_k <= n_k with d_k = n_k (mod 2).  The sum row may sit in the sparse structures or in the dense
+ * store.  C is arbitrary.  x = t_k sigma with sum(sigma) = +-d_k is feasible; f = sum_k x_k^T C_k x_k.  Per cone k and trial t:
+ *   signs    lorads_hip_round_pm1's hyperplane t of that seed and its sign bits; D = sum_p sigma_p
+ *   repair   |D - target| / 2 flips, target = +d_k where D >= 0, else -d_k: each flips the vertex of least Delta_p = -4 x_p h_p on the
+ *            side in excess (h_p = sum_{q != p} C_pq x_q over p's stored row list in its stored order), the lowest index on ties
+ *   search   at most max_rounds rounds (0: none).  Order A: p = argmin over sigma = +1 of Delta_p, q = argmin over sigma = -1 of
+ *            Delta_q + 8 C_pq x_p x_q, Delta_A their sum; order B the same from the -1 side; the round takes A unless Delta_B < Delta_A
+ *            and swaps the pair where Delta < -2^-40 (tau_p + tau_q), tau_p = 4 t_k^2 sum_{q != p} |C_pq|.  A round that does not swap
+ *            is the last and is counted.  sum(sigma) is untouched and every swap lowers f by exactly its Delta.
+ * One workgroup owns one (cone, trial); the result of a trial does not depend on `trials`.  Values in device terms (C scaled by
+ * scaleObjHis).  Read-only on the solver's state; the same state and arguments give the same bits.
+ *   obj [trials]               f after the search          obj0 [trials] (may be NULL)  f after the repair
+ *   best / best0               argmin of obj / obj0 (lowest index on ties; may be NULL)
+ *   sign [sum_k n_k]           the best trial's signs after the search, cone after cone (may be NULL)
+ *   imbalance [cones x trials] D of the hyperplane's signs, before the repair, cone after cone, per trial (may be NULL)
+ *   rounds                     the largest number of search rounds a trial ran on a cone (may be NULL)
+ *   hyperplanes                as lorads_hip_round_pm1's (may be NULL)
+ *   t [cones], diff [cones]    t_k and d_k (may be NULL)
+ * trials = 0 checks applicability only (t and diff are still filled).  Returns 1 on a bad argument (src, trials outside [0, 65536],
+ * max_rounds < 0, obj NULL with trials > 0) or a failed allocation (the context stays usable), 2 when the context does not qualify
+ * (lorads_hip_last_error names the first offending constraint or cone), 3 when it is sharded -- all before any device work.
+ * LORADS_BISECT_LDS=0 at the context's creation keeps a trial's state in device memory at every size (the path of cones too large
+ * for the LDS); the results are the same bits. */
+int lorads_hip_round_bisect(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
+                            double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *imbalance, int32_t *rounds,
+                            double *hyperplanes, double *t, int32_t *diff);
+
 /* Spectrum and rank reduction of the solution factors (no reference counterpart).  Per SDP cone k (the LP block
  * has no factor and is passed over) F_k is the factor lorads_hip_certificate takes (src) at the cone's own rank rl_k, G_k = F_k^T F_k =
  * Q_k Lambda_k Q_k^T with lambda_1 >= lambda_2 >= ... (ties: lower original index first): the non-zero eigenvalues of X_k = F_k F_k^T.

@@ -93,6 +93,10 @@ int lorads_hip_memory_stats(int64_t stats[4]);
  * feature's scratch until the next call): a test compares every trial with the model, not the best one alone */
 int lorads_hip_stable_trial(lorads_hip_ctx *ctx, int32_t trial, uint8_t *member);
 
+/* the signs of trial `trial` of this context's last lorads_hip_round_bisect call, as that call's `sign` (they stay in the feature's
+ * scratch until the next call): a test compares every trial with the model, not the best one alone */
+int lorads_hip_bisect_trial(lorads_hip_ctx *ctx, int32_t trial, int8_t *sign);
+
 #ifdef __cplusplus
 }
 #endif

@@ -674,6 +674,25 @@ struct StableScratch {
     void release() { mem.release(); *this = StableScratch{}; }
 };
 
+// scratch of the bisection rounding (bisect.inc): allocated on its first call, never read by the solve.  G 8 K sum(rank), the sign
+// words of the hyperplanes (n K / 8 bytes), one sign byte per (trial, vertex) of every cone, and -- only where a trial's state does
+// not fit the LDS -- per chunk of trials the fields h (8 n) of the cone at hand.
+struct BisectScratch {
+    bool checked = false, qualifies = false;
+    std::string why;                          // the first reason the context does not qualify
+    std::vector<int> v_off;                   // [nb + 1] first vertex of every cone in the stacked vertex arrays
+    std::vector<double> t;                    // [nb] t_k, the one value of sqrt(b_i / a_i) of the cone's diagonal rows
+    std::vector<int> d;                       // [nb] d_k, the size difference the cone's sum row prescribes
+    DevBuf<double> G, f, f0, h;               // the hyperplanes; obj, obj0; the chunk's fields [trial][vertex] (the slab path)
+    DevBuf<unsigned long long> sgn;           // sign words of the hyperplanes, cone k at v_off[k] * W (rounding.inc's layout)
+    DevBuf<signed char> x;                    // signs after the search, cone k at v_off[k] * K, trial t of it n bytes further per trial
+    DevBuf<int> imb, nround;                  // sum of the hyperplane's signs per (cone, trial); rounds per trial
+    int *ctl = nullptr;                       // [0] best before, [1] best after the search
+    int K = 0;                                // trials of the last call (lorads_hip_bisect_trial reads its signs)
+    DevPool mem;
+    void release() { mem.release(); *this = BisectScratch{}; }
+};
+
 // scratch of the spectrum / rank reduction (spectral.inc): allocated on its first call, never read by the solve
 struct SpecCone { int rl, m; long long g_off, e_off, q_off; }; // one cone of a k_spec_jacobi launch: orders, places in SpecScratch::W
 struct SpecScratch {
@@ -749,6 +768,7 @@ struct lorads_hip_ctx {
     RoundScratch rnd;                 // +-1 rounding (rounding.inc)
     KCutScratch kcut;                 // rounding into k parts (kcut.inc)
     StableScratch stable;             // stable-set rounding (stable.inc)
+    BisectScratch bisect;             // bisection rounding (bisect.inc)
     SpecScratch spectral;             // spectrum and rank reduction of the factors (spectral.inc)
     PrimalScratch primal;             // entries of X = F F^T and its products (primal.inc)
     CutScratch cuts;                  // separation of the triangle inequalities (cuts.inc)
@@ -826,6 +846,7 @@ struct lorads_hip_ctx {
     bool opt_presolve_check = false; // LORADS_PRESOLVE_CHECK=1: build every device pattern on the host too and compare
     size_t dev_presolve_min = (size_t)1 << 15; // stored entries below which a pattern is built on the host (LORADS_DEV_PRESOLVE_MIN)
     long long n_dev_patterns = 0, n_checked_patterns = 0;
+    bool opt_bisect_lds = true;  // bisection rounding: a trial's state in the LDS where it fits (LORADS_BISECT_LDS=0: the device-memory slab at every size, the path of cones too large for the LDS)
     bool opt_dense_cache = true; // dense constraint matrices: A_j V kept for the length of a CG solve (LORADS_DENSE_CACHE=0: nd + 1 GEMMs per application)
     bool opt_front_diag = true; // Max-Cut-type cones: the front forms its diagonal coefficients itself, no k_sval (LORADS_FRONT_DIAG=0)
     bool opt_eval_diag = true; // Max-Cut-type cones: k_eval_diag instead of k_average + k_pairdots + k_cv_res (LORADS_EVAL_DIAG=0)
@@ -1040,6 +1061,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->opt_eval_diag = env_on("LORADS_EVAL_DIAG");
     c->opt_front_diag = env_on("LORADS_FRONT_DIAG");
     c->opt_dense_cache = env_on("LORADS_DENSE_CACHE");
+    c->opt_bisect_lds = env_on("LORADS_BISECT_LDS");
     c->opt_fuse_eval = env_on("LORADS_FUSE_EVAL");
     c->opt_dense_rem = env_on("LORADS_DENSE_REM");
     c->opt_exact_refresh = env_set("LORADS_EXACT_REFRESH");
@@ -1115,6 +1137,7 @@ void lorads_hip_destroy(lorads_hip_ctx *c) { // (safe on a context at any stage 
     c->topk.release();
     c->kcut.release();
     c->stable.release();
+    c->bisect.release();
     c->factor_mem.release();
     c->mem.release();
     if (c->shared_gpu_fd >= 0) close(c->shared_gpu_fd);
@@ -2052,6 +2075,7 @@ int lorads_hip_algorithmic_bytes(lorads_hip_ctx *c, int32_t k, double *mv, doubl
 #include "rounding.inc"
 #include "kcut.inc"
 #include "stable.inc"
+#include "bisect.inc"
 #include "spectral.inc"
 #include "primal.inc"
 #include "select.inc"

@@ -1,5 +1,5 @@
 // postsolve.inc -- what the post-solve entry points share, included by lorads_hip.hip after lanczos.inc and before the first of them:
-// solution.inc, rounding.inc, kcut.inc, stable.inc, spectral.inc, primal.inc, cuts.inc, bounds.inc and topk.inc (DESIGN.md sections 10 to 18).  All of them read the solution
+// solution.inc, rounding.inc, kcut.inc, stable.inc, bisect.inc, spectral.inc, primal.inc, cuts.inc, bounds.inc and topk.inc (DESIGN.md sections 10 to 19).  All of them read the solution
 // factors and none is run by a solve.
 //   FactorView / factor_view, factor_ld   which arrays make up F for a `src`, and F's elements on the device
 //   mfma_strip_tile, mfma_fm_tile         the two FP64 matrix-core tile bodies, with the operand layout written down once

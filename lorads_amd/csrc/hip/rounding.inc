@@ -184,6 +184,20 @@ int read_constraint_image(lorads_hip_ctx *c, int k, ConImage &m) {
     return 0;
 }
 
+// Constraint gi's one stored entry a at (p, q) as the diagonal row a X[p,p] = b with b / a > 0 (shared with bisect.inc): "" and
+// *t = sqrt(b / a), or the reason it is none (*t is then left as it was)
+std::string diag_row(int gi, int p, int q, double a, double b, double *t) {
+    char msg[256];
+    if (p != q) { snprintf(msg, sizeof msg, "constraint %d is not on a diagonal", gi + 1); return msg; }
+    const double ratio = b / a;
+    if (!(ratio > 0) || !std::isfinite(ratio)) {
+        snprintf(msg, sizeof msg, "constraint %d has b / a = %g (not positive)", gi + 1, ratio);
+        return msg;
+    }
+    *t = std::sqrt(ratio);
+    return "";
+}
+
 // applicability (once per context: the constraint data never changes); t of every cone to the device
 int rnd_check(lorads_hip_ctx *c) {
     RoundScratch &X = c->rnd;
@@ -212,15 +226,9 @@ int rnd_check(lorads_hip_ctx *c) {
             per_con[gi] += cnt;
             if (cnt != 1) { snprintf(msg, sizeof msg, "constraint %d has %d entries on cone %d", gi + 1, cnt, k + 1); X.why = msg; break; }
             const int e = ae[ap[i]], p = er[e];
-            if (er[e] != ec[e]) { snprintf(msg, sizeof msg, "constraint %d is not on a diagonal", gi + 1); X.why = msg; break; }
-            const double ratio = b[gi] / av[ap[i]];
-            if (!(ratio > 0) || !std::isfinite(ratio)) {
-                snprintf(msg, sizeof msg, "constraint %d has b / a = %g (not positive)", gi + 1, ratio);
-                X.why = msg;
-                break;
-            }
+            X.why = diag_row(gi, er[e], ec[e], av[ap[i]], b[gi], &th[X.t_off[k] + p]);
+            if (!X.why.empty()) break;
             cover[p]++;
-            th[X.t_off[k] + p] = std::sqrt(ratio);
         }
         for (int p = 0; p < B.n && X.why.empty(); ++p)
             if (cover[p] != 1) {

@@ -64,6 +64,8 @@ typedef struct {
                        const int64_t *, const int32_t *, int32_t *, double *, int32_t *); /* optional */
     int (*round_stable)(lorads_hip_ctx *, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, uint8_t *,
                         int32_t *, int32_t *, double *, double *); /* optional */
+    int (*round_bisect)(lorads_hip_ctx *, int32_t, int32_t, uint64_t, int32_t, double *, double *, int32_t *, int32_t *, int8_t *,
+                        int32_t *, int32_t *, double *, double *, int32_t *); /* optional */
 } hipbe;
 
 #define H ((hipbe *)cx)
@@ -147,6 +149,12 @@ static int b_stable(void *cx, int src, int trials, uint64_t seed, int max_rounds
     return report(H, H->round_stable(H->ctx, src, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, member,
                                      (int32_t *)sizes, (int32_t *)rounds, scores, T), "round_stable");
 }
+/* balanced partitions: codes 2 (not bisection-structured) and 3 (sharded) pass through with the library's reason on stderr */
+static int b_bisect(void *cx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                    int8_t *sign, int *imbalance, int *rounds, double *hyperplanes, double *t, int *diff) {
+    return report(H, H->round_bisect(H->ctx, src, trials, seed, max_rounds, obj, obj0, (int32_t *)best, (int32_t *)best0, sign,
+                                     (int32_t *)imbalance, (int32_t *)rounds, hyperplanes, t, (int32_t *)diff), "round_bisect");
+}
 /* top-k search: codes 2 (the LP block) and 3 (sharded) pass through */
 static int b_topk(void *cx, int src, int blk, int nq, const int *row, int lo, int hi, int k, int smallest, int diag, const int64_t *sptr,
                   const int *scol, int *idx, double *val, int *found) {
@@ -225,6 +233,7 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     *(void **)(&h->round_kcut) = dlsym(h->dl, "lorads_hip_round_kcut");
     *(void **)(&h->primal_topk) = dlsym(h->dl, "lorads_hip_primal_topk");
     *(void **)(&h->round_stable) = dlsym(h->dl, "lorads_hip_round_stable");
+    *(void **)(&h->round_bisect) = dlsym(h->dl, "lorads_hip_round_bisect");
     lorads_hip_block *hb = (lorads_hip_block *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof *hb);
     for (int k = 0; k < p->nblk; ++k) {
         const lrd_block *b = &p->blk[k];
@@ -277,5 +286,6 @@ int lrd_hip_backend_create(const lrd_problem *p, int lbfgs_len, const char *libp
     if (h->round_kcut) out->round_kcut = b_kcut;
     if (h->primal_topk) out->primal_topk = b_topk;
     if (h->round_stable) out->round_stable = b_stable;
+    if (h->round_bisect) out->round_bisect = b_bisect;
     return 0;
 }

@@ -163,6 +163,12 @@ typedef struct lrd_backend {
      * certificate used: a dual update still waiting inside the backend applied, not stored) may be NULL.
      * get_slack: S of block blk as lower-triangle triplets; NULL arrays return the count alone. */
     int (*certificate)(void *ctx, int src, double tol, double *out, double *lam_min, double *residual, double *y);
+    /* OPTIONAL (between the export pair: the table's mirror is checked to hold get_slack, round_stable, round_pm1, round_kcut and the
+     * primal pair side by side): balanced partitions of a bisection-structured context read off the factors + repair + swap search,
+     * read-only on the state (include/lorads_hip.h: lorads_hip_round_bisect, the same arguments and return codes; values in the
+     * backend's terms) */
+    int (*round_bisect)(void *ctx, int src, int trials, uint64_t seed, int max_rounds, double *obj, double *obj0, int *best, int *best0,
+                        int8_t *sign, int *imbalance, int *rounds, double *hyperplanes, double *t, int *diff);
     int (*get_slack)(void *ctx, int blk, int64_t *nnz, int *row, int *col, double *val);
     /* OPTIONAL (in front of round_pm1: the table's mirror is checked to hold round_pm1, round_kcut and the primal pair side by side):
      * stable sets of a theta-structured context read off the factors + the (1, 2)-swap search, read-only on the state
@@ -577,6 +583,41 @@ int lrd_session_round_stable(lrd_session *s, int trials, uint64_t seed, int max_
 void lrd_stable_free(lrd_stable *r);
 /* plain-text file, a pure function of the struct (stable.c) */
 int lrd_stable_write(const char *path, const lrd_stable *r);
+
+/* ---- balanced partitions of bisection-structured problems (bisect.c).  Everything in the file's units.  Every
+ * cone has the +-1 diagonal rows with one value t of sqrt(b_i / a_i) and one sum row a <11^T, X_k> = b with b / (a t^2) = d^2: for
+ * signs with sum(sigma) = +-d the point x = t sigma is feasible, the parts have (n + d) / 2 and (n - d) / 2 vertices, and
+ * f = sum_k x_k^T C_k x_k; the dual bound d = b.y + sum_k n_k t_k^2 min(0, lambda_min(S_k)) <= the optimum <= f. */
+typedef struct {
+    int n, rank;       /* rank: the cone's own current rank (the hyperplanes' dimension) */
+    int diff;          /* d_k */
+    int plus, minus;   /* vertices with sigma = +1 / -1 in the best trial: (n + d) / 2 and (n - d) / 2 in either order */
+    int8_t *sigma;     /* [n] the best trial's signs after the search */
+    int *imbalance;    /* [trials] sum of the hyperplane's signs, before the repair */
+    double t;
+    double lam_min;    /* lambda_min(S_k) (NaN without a bound) */
+    double *G;         /* rank x trials hyperplanes, only when asked for (else NULL) */
+} lrd_bisection_cone;
+typedef struct {
+    int nblk;           /* cones */
+    int trials, max_rounds, rounds;
+    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where F came from */
+    uint64_t seed;
+    double scale;       /* scaleObjHis the backend's values were divided by */
+    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
+    double f_best, f_best0;
+    double *obj, *obj0; /* [trials] f after the search / after the repair */
+    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
+    double tol;         /* Lanczos tolerance of lambda_min */
+    lrd_bisection_cone *cone; /* [nblk], file order */
+} lrd_bisection;
+/* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
+ * lacks the slot, 3 when it is sharded.  with_hyperplanes: also fill every cone's G. */
+int lrd_session_round_bisect(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_hyperplanes,
+                             lrd_bisection **out);
+void lrd_bisection_free(lrd_bisection *r);
+/* plain-text file, a pure function of the struct (bisect.c) */
+int lrd_bisection_write(const char *path, const lrd_bisection *r);
 
 /* ---- internal: what the post-solve drivers and writers above share (not part of the interface)
  * Two adjacent runs [0, at) and [at, at + got) of a list kept as ncol parallel columns, each sorted by `before(list, a, b)` (is entry a

@@ -51,6 +51,9 @@ int main(int argc, char **argv) {
     int stable_trials = 0, stable_ls = 100; /* stable sets of a theta-structured problem read off the factors (ours as well) */
     unsigned long long stable_seed = 0;
     const char *stable_file = NULL, *stable_other = NULL; /* stable_other: some --stable* option other than --stableTrials was given */
+    int bisect_trials = 0, bisect_ls = 1000; /* balanced partitions of a bisection-structured problem read off the factors (ours as well) */
+    unsigned long long bisect_seed = 0;
+    const char *bisect_file = NULL, *bisect_other = NULL; /* bisect_other: some --bisect* option other than --bisectTrials was given */
     const char *topk_in = NULL, *topk_out = NULL, *topk_other = NULL; /* the k best entries per row of the primal (ours as well);
                                                                        * topk_other: some --topk* option other than --topkFile was given */
     int topk_k = 0, topk_smallest = 0, topk_diag = 0, topk_constrained = 0;
@@ -181,6 +184,25 @@ int main(int argc, char **argv) {
             }
             continue;
         }
+        if (!strcmp(argv[i], "--bisectFile")) { bisect_other = argv[i]; bisect_file = argv[i + 1]; continue; }
+        if (!strcmp(argv[i], "--bisectTrials") || !strcmp(argv[i], "--bisectSeed") || !strcmp(argv[i], "--bisectLocalSearch")) {
+            char *end = NULL;
+            const char w = argv[i][8]; /* T, S or L */
+            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
+            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'T' && (v < 1 || v > 65536)) ||
+                (w == 'L' && v > 65536)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            if (w == 'T') bisect_trials = (int)v;
+            else {
+                bisect_other = argv[i];
+                if (w == 'S') bisect_seed = v;
+                else bisect_ls = (int)v;
+            }
+            continue;
+        }
         if (!strcmp(argv[i], "--compressTol") || !strcmp(argv[i], "--compressRank")) {
             char *end = NULL;
             const int is_tol = argv[i][10] == 'T';
@@ -233,6 +255,11 @@ int main(int argc, char **argv) {
     }
     if (stable_other && stable_trials == 0) {
         fprintf(stderr, "%s needs --stableTrials\n", stable_other);
+        lrd_session_close(s);
+        return 2;
+    }
+    if (bisect_other && bisect_trials == 0) {
+        fprintf(stderr, "%s needs --bisectTrials\n", bisect_other);
         lrd_session_close(s);
         return 2;
     }
@@ -329,6 +356,15 @@ int main(int argc, char **argv) {
         lrd_stable *none = NULL;
         if (lrd_session_round_stable(s, 0, stable_seed, stable_ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --stableTrials needs a theta-structured problem (see above); nothing was solved\n");
+            lrd_topk_free(topk);
+            lrd_session_close(s);
+            return 2;
+        }
+    }
+    if (bisect_trials > 0) { /* applicability before any solving */
+        lrd_bisection *none = NULL;
+        if (lrd_session_round_bisect(s, 0, bisect_seed, bisect_ls, 0.0, 0, &none)) {
+            fprintf(stderr, "lorads: --bisectTrials needs a bisection-structured problem (see above); nothing was solved\n");
             lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
@@ -501,6 +537,20 @@ int main(int argc, char **argv) {
         for (int k = 0; k < x->nblk; ++k) printf(" %d", x->cone[k].size);
         printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->f_best, x->bound, x->gap, x->rounds);
         lrd_stable_free(x);
+    }
+    if (bisect_trials > 0) {
+        lrd_bisection *x = NULL;
+        if (lrd_session_round_bisect(s, bisect_trials, (uint64_t)bisect_seed, bisect_ls, 1e-8, 0, &x) ||
+            (bisect_file && lrd_bisection_write(bisect_file, x))) {
+            fprintf(stderr, "lorads: the bisection rounding failed%s%s\n", bisect_file ? " or cannot write " : "", bisect_file ? bisect_file : "");
+            lrd_bisection_free(x);
+            lrd_session_close(s);
+            return 4;
+        }
+        printf("Bisection (%d trials, seed %llu%s%s): parts", x->trials, bisect_seed, bisect_file ? ", " : "", bisect_file ? bisect_file : "");
+        for (int k = 0; k < x->nblk; ++k) printf(" %d+%d", x->cone[k].plus, x->cone[k].minus);
+        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->f_best, x->bound, x->gap, x->rounds);
+        lrd_bisection_free(x);
     }
     lrd_session_close(s);
     return 0;

@@ -59,6 +59,8 @@ class BackendStruct(C.Structure):
         ("alm_front", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_int, _dp)),
         ("alm_step", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int, _dp)),
         ("certificate", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, _dp, _dp, _dp, _dp)),
+        ("round_bisect", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
+                                     C.POINTER(C.c_int8), _ip, _ip, _dp, _dp, _ip)),
         ("get_slack", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _dp)),
         ("round_stable", C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp, _dp, _ip, _ip,
                                      C.POINTER(C.c_uint8), _ip, _ip, _dp, _dp)),
@@ -441,6 +443,52 @@ class Backend:
         lib.lorads_hip_stable_trial.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]
         _check(lib.lorads_hip_stable_trial(ctx, int(trial), member.ctypes.data_as(C.POINTER(C.c_uint8))), "stable_trial")
         return member[:ntot]
+
+    def has_round_bisect(self):
+        return bool(self._s.round_bisect)
+
+    def round_bisect(self, src, trials, seed=0, max_rounds=0, want_hyperplanes=False):
+        """the table's slot as it is (values in the backend's terms): returns (code, dict) with obj, obj0, best, best0, sign (cone
+        after cone), imbalance (cones x trials), rounds, t and diff (per cone) and -- want_hyperplanes -- hyperplanes (per cone a
+        rank x trials array); code != 0 is the slot's refusal (the dict is then None).  trials = 0 checks applicability and still
+        gives t and diff."""
+        ses = self._session
+        ns = [ses.block_shape(k)[0] for k in range(ses.nblk)]
+        rk = [ses.block_shape(k)[1] for k in range(ses.nblk)]
+        ntot, ncone = sum(ns), len(ns)
+        K = max(int(trials), 0)
+        ok = K <= 65536
+        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
+        sign, t, diff = np.zeros(max(ntot, 1), dtype=np.int8), np.zeros(max(ncone, 1)), np.zeros(max(ncone, 1), dtype=np.int32)
+        imb = np.zeros(max(ncone * K, 1) if ok else 1, dtype=np.int32)
+        glen = sum(rk) * K if want_hyperplanes and ok else 0
+        g = np.zeros(max(glen, 1))
+        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = self._s.round_bisect(self._s.ctx, int(src), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
+                                  obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
+                                  sign.ctypes.data_as(C.POINTER(C.c_int8)), imb.ctypes.data_as(_ip), C.byref(rounds),
+                                  g.ctypes.data_as(_dp) if glen else None, t.ctypes.data_as(_dp), diff.ctypes.data_as(_ip))
+        if rc:
+            return rc, None
+        planes, at = None, 0
+        if glen:
+            planes = []
+            for r in rk:
+                planes.append(g[at:at + r * K].reshape(r, K).copy())
+                at += r * K
+        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, sign=sign[:ntot],
+                       imbalance=imb[:ncone * K].reshape(ncone, K), rounds=rounds.value, t=t[:ncone], diff=diff[:ncone],
+                       hyperplanes=planes)
+
+    def bisect_trial(self, trial):
+        """the signs of one trial of the last round_bisect call on this table's HIP context (cone after cone)"""
+        ses = self._session
+        lib, ctx = ses._hip()
+        ntot = sum(ses.block_shape(k)[0] for k in range(ses.nblk))
+        sign = np.zeros(max(ntot, 1), dtype=np.int8)
+        lib.lorads_hip_bisect_trial.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int8)]
+        _check(lib.lorads_hip_bisect_trial(ctx, int(trial), sign.ctypes.data_as(C.POINTER(C.c_int8))), "bisect_trial")
+        return sign[:ntot]
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -1143,6 +1191,53 @@ class Session:
             _check(self.lib.lrd_stable_write(os.fsencode(path), ptr), "stable_write")
         finally:
             self.lib.lrd_stable_free(ptr)
+
+    def _bisection_ptr(self, trials, seed, local_search_rounds, tol, hyperplanes):
+        from .bisection import BisectionStruct
+        trials, local_search_rounds = int(trials), int(local_search_rounds)
+        if not 0 <= trials <= 65536:
+            raise ValueError("round_bisection: trials %d is outside [0, 65536]" % trials)
+        if local_search_rounds < 0:
+            raise ValueError("round_bisection: local_search_rounds %d is negative" % local_search_rounds)
+        ptr = C.POINTER(BisectionStruct)()
+        self.lib.lrd_session_round_bisect.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
+                                                      C.POINTER(C.POINTER(BisectionStruct))]
+        self.lib.lrd_bisection_free.argtypes = [C.POINTER(BisectionStruct)]
+        self.lib.lrd_bisection_free.restype = None
+        rc = self.lib.lrd_session_round_bisect(self.h, trials, int(seed) & 0xFFFFFFFFFFFFFFFF, local_search_rounds, float(tol),
+                                               1 if hyperplanes else 0, C.byref(ptr))
+        self._refused(rc, "no balanced partition can be read off the solution: the problem is not bisection-structured (no LP block; "
+                      "per cone one constraint a X[p,p] = b on every diagonal with one value of b / a > 0, and one sum row "
+                      "a <11^T, X> = b with b / (a t^2) = d^2, d = n (mod 2)) or the %s backend cannot round%s",
+                      "rounding the solution of a sharded deal (world > 1) is not supported")
+        _check(rc, "round_bisection")
+        return ptr
+
+    def round_bisection(self, trials=1024, seed=0, local_search_rounds=1000, tol=1e-8, hyperplanes=False):
+        """Balanced partitions of a bisection-structured problem read off the current point, on the device
+        (lorads_amd.bisection.Bisection, file units): per trial the +-1 rounding's hyperplane signs, the repair to
+        sum(sigma) = +-d, and a swap search that keeps the balance; f = sum x^T C x after the repair and after the search, the
+        best trial's signs and part sizes per cone, and the dual bound d = b.y + sum_k n_k t_k^2 min(0, lambda_min(S_k)) at Lanczos
+        tolerance tol (tol <= 0: NaN).  trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
+        from .bisection import Bisection
+        if trials == 0:
+            self._bisection_ptr(0, seed, local_search_rounds, tol, False)
+            return None
+        ptr = self._bisection_ptr(trials, seed, local_search_rounds, tol, hyperplanes)
+        try:
+            return Bisection.from_struct(ptr.contents)
+        finally:
+            self.lib.lrd_bisection_free(ptr)
+
+    def write_bisection(self, path, trials=1024, seed=0, local_search_rounds=1000, tol=1e-8):
+        """the bisection file of the command line's --bisectFile (the same C writer: the same bytes)"""
+        from .bisection import BisectionStruct
+        ptr = self._bisection_ptr(trials, seed, local_search_rounds, tol, False)
+        try:
+            self.lib.lrd_bisection_write.argtypes = [C.c_char_p, C.POINTER(BisectionStruct)]
+            _check(self.lib.lrd_bisection_write(os.fsencode(path), ptr), "bisection_write")
+        finally:
+            self.lib.lrd_bisection_free(ptr)
 
     def triangle_cuts(self, max_cuts=1000, min_violation=1e-3):
         """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device

@@ -134,6 +134,45 @@ def maxcut_negative_ratio(n, n_edges, seed):
     return dict(m=n, blocks=[n], b=b, entries=p["entries"])
 
 
+def _with_sum_row(prob, diff):
+    """prob (one cone, the +-1 diagonal rows) plus the sum row <11^T, X> = diff^2 as its last constraint: every position of the upper
+    triangle with the value 1"""
+    n, m = prob["blocks"][0], prob["m"]
+    ent = list(prob["entries"])
+    for i in range(n):
+        for j in range(i, n):
+            ent.append((m + 1, 1, i + 1, j + 1, 1.0))
+    return dict(m=m + 1, blocks=[n], b=np.concatenate([prob["b"], [float(diff * diff)]]), entries=ent)
+
+
+def bisection(n, n_edges, seed, diff=0, weights=None):
+    """min <L/4, X> s.t. X_ii = 1, <11^T, X> = diff^2: the relaxation of the smallest cut with parts of (n + diff) / 2 and
+    (n - diff) / 2 vertices (diff = 0: Min-Bisection).  F0 = -L/4 (=> C = L/4, x^T C x the cut's weight for x in {+-1}^n), F_i = e_i e_i^T
+    with b = 1, and the sum row last.  diff must have n's parity."""
+    if not 0 <= diff <= n or (n - diff) % 2:
+        raise ValueError("diff must lie in [0, n] and have n's parity")
+    p = maxcut(n, n_edges, seed, weights)
+    ent = [(mat, blk, i, j, -v if mat == 0 else v) for mat, blk, i, j, v in p["entries"]]
+    return _with_sum_row(dict(m=n, blocks=[n], b=p["b"], entries=ent), diff)
+
+
+def clique_pair(m, seed):
+    """Min-Bisection of two cliques K_m joined by a perfect matching, the vertex labels shuffled by the seed: the smallest bisection
+    separates the cliques and cuts the m matching edges, and the relaxation is tight (n lambda_2(L) / 4 = m for m >= 2)"""
+    rng = np.random.default_rng(seed)
+    n = 2 * m
+    lab = rng.permutation(n)
+    edges = [(a, b) for a in range(m) for b in range(a + 1, m)]
+    edges += [(m + a, m + b) for a, b in edges]
+    edges += [(a, m + a) for a in range(m)]
+    ent = [(0, 1, i + 1, i + 1, -m / 4.0) for i in range(n)]  # every vertex has degree m
+    for a, b in sorted((min(lab[a], lab[b]), max(lab[a], lab[b])) for a, b in edges):
+        ent.append((0, 1, int(a) + 1, int(b) + 1, 0.25))
+    for i in range(n):
+        ent.append((i + 1, 1, i + 1, i + 1, 1.0))
+    return _with_sum_row(dict(m=n, blocks=[n], b=np.ones(n), entries=ent), 0)
+
+
 def theta(n, n_edges, seed):
     """Lovasz theta: max <J, X> s.t. tr X = 1, X_ij = 0 on edges.  m = n_edges + 1."""
     rng = np.random.default_rng(seed)
@@ -475,6 +514,12 @@ NAMED = {
     "kpartite4x6": lambda: kpartite(4, 6),
     "maxcut_uncovered60": lambda: maxcut_uncovered(60, 120, 123),
     "maxcut_negratio60": lambda: maxcut_negative_ratio(60, 120, 124),
+    # bisection-structured contexts of the balanced rounding: the sum row in the sparse structures (n < 32), in
+    # the dense store, a prescribed size difference, and the two-clique graphs whose relaxation is tight
+    "bisect24": lambda: bisection(24, 80, 241),
+    "bisect40d4": lambda: bisection(40, 160, 401, diff=4),
+    "cliquepair12": lambda: clique_pair(12, 121),
+    "cliquepair16": lambda: clique_pair(16, 161),
     # timing / log-level instances
     "maxcut800": lambda: maxcut(800, 19176, 8001),         # cfg2 G1-like
     "maxcut4000": lambda: maxcut(4000, 24000, 4000),       # cfg3a-mini
