@@ -401,6 +401,13 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *ctx, int32_t block, int out[3]);
  * slot contributions, 3 x and r of CG iteration 0 inside k_spmm_ell, 4 the average R written there, 5 the output of the plain
  * k_spmm_ell; 0 = plain stores everywhere; unset = the default.  Results do not depend on it.  Leaves a front in flight alone. */
 int lorads_hip_wt_stores(lorads_hip_ctx *ctx, int *mask);
+/* the cuts in the solve front's chain of dependent loads (k_front_cw): LORADS_FRONT_CHAIN, read at creation: bit 0 the neighbour
+ * rows loaded without the mask of the slice beyond r (masked once in the epilogue), bit 1 the row's own operands requested late;
+ * 0 = the front without them; unset = the default (both).  *mask is the context's mask.  The cuts belong to the form of the front
+ * with the LDS park (r <= 48, LORADS_FRONT_LDS on); other cones launch the uncut kernel whatever the mask says: *effective (may
+ * be null) is the mask if some cone of the context launches the cut form, else 0.  Results do not depend on either, bit for
+ * bit.  Leaves a front in flight alone. */
+int lorads_hip_front_chain(lorads_hip_ctx *ctx, int *mask, int *effective);
 /* what the dense-coefficient GEMM (k_dense_cx_b: a dense objective, dense constraint matrices) launches for cone `block` at its
  * current device rank: out = {n padded to 64, K split over workgroups (slabs that k_sum_slabs adds when > 1), number of launches L,
  * then (first column, column tiles of 16 on the matrix cores, single columns on plain FMAs) for each of the L <= 4 launches}, zeros

@@ -54,17 +54,22 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
             else LAUNCH((k_spmm_ell<8, true, 3, 16>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col, B.cell_con,
                         B.cell_a, (const double *)B.w_op, V, B.r, (int)OP_CG, U, (const double *)nullptr, Q, part_slot(c, 0), NOGUARD);
             break;
-        case 30: case 31: { // the one-kernel front (31: without the second visit of the slots), weights of a plain W_ADMM front
+        case 30: case 31: case 33: case 34: {
+            // the one-kernel front as the solve launches it at rank 40 (slots 0..3 parked in LDS), weights of a plain W_ADMM front
+            // (31: without the second visit of the slots; 33 / 34: the same two with every bit of LORADS_FRONT_CHAIN)
             if (!B.front_cw) return fail_msg("ubench: cone without the one-kernel front's data");
             FrontCwArgs A{};
             A.fc_ptr = B.fc_ptr; A.fc_col = B.fc_col; A.fc_val = B.fc_val; A.sl_ptr = B.cadj_ptr; A.sl_col = B.cadj_col; A.sl_con = B.cadj_con;
             A.sl_a = B.cadj_a; A.ell_col = B.cell_col; A.ell_con = B.cell_con; A.ell_a = B.cell_a; A.ell_dst = B.cell_dst; A.sl_dst = B.cadj_dst;
             A.csum = c->csum; A.b = c->b; A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_op;
             A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = 1.0; A.wmode = W_ADMM;
-            A.contrib = which == 30 ? B.w_contrib : (double *)nullptr;
+            A.contrib = (which == 30 || which == 33) ? B.w_contrib : (double *)nullptr;
             A.wt = c->opt_wt_stores;
-            if (B.cell_w == 8) LAUNCH((k_front_cw<3, 8>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
-            else LAUNCH((k_front_cw<3, 16>), rd.grid, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{});
+            const size_t lds = sizeof(double2) * 32 * 4 * 3 * 8;
+#define UB_FRONT(EWV, FCV) LAUNCH_LDS((k_front_cw<3, EWV, 4, false, FCV>), rd.grid, lds, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{})
+            if (which < 33) { if (B.cell_w == 8) UB_FRONT(8, 0); else UB_FRONT(16, 0); }
+            else { if (B.cell_w == 8) UB_FRONT(8, FC_ALL); else UB_FRONT(16, FC_ALL); }
+#undef UB_FRONT
         } break;
         case 32: LAUNCH(k_wsum, nblocks_for((size_t)B.nrow, TPB / 8), B.nrow, B.cs_w, (const double *)B.w_contrib, B.w_op, NOGUARD, InitArgs{}, 0, DS(0.0),
                         c->m, (const double *)c->b, (const double *)c->csum, c->lambda); break;

@@ -24,6 +24,17 @@ struct Slice {
             }
         }
     }
+    // the same loads without the mask: a slice beyond r holds the row's first columns.  For callers that mask the slice's results.
+    __device__ static __forceinline__ void load_raw(const double *__restrict__ row, int r, int lane, double (&v)[NS][W]) {
+        static_assert(V2, "the 16-byte form only");
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {
+            const int j = (lane + c * LG) * W;
+            const double2 t = *(const double2 *)(row + (j < r ? j : 0));
+            v[c][0] = t.x;
+            v[c][1] = t.y;
+        }
+    }
 };
 
 // Row outputs written THROUGH the L2 (`sc1`; DESIGN.md 4 item 11, LORADS_WT_STORES): a plain store leaves its line dirty in the
@@ -1079,6 +1090,10 @@ struct HandoverArgs {
     unsigned long long *dst;
     int nwords;
     unsigned long long *flag, *seq_dev;
+    // workgroups ahead of the row workgroups: always 1, and an argument on purpose.  With the constant hipcc schedules the row body
+    // of the hand-over form apart from the plain form's (154 against 158 VGPRs at <3, 16, 4>, ten more `s_waitcnt vmcnt(0)`, loads
+    // of the late-operand form waited for one by one) and the U front runs 0.7 us longer (profiles/r11_front_chain_ab.txt)
+    int lead;
 };
 struct FrontCwHoArgs : FrontCwArgs { HandoverArgs ho; };
 // KC = 4 (round 3; LORADS_FRONT_LDS=0: KC = 0): the rows of the first four slots, gathered for the A part, are parked in LDS
@@ -1089,23 +1104,64 @@ struct FrontCwHoArgs : FrontCwArgs { HandoverArgs ho; };
 // one workgroup more.  Workgroup 0 is the hand-over of k_publish_final (publish_final under its own gate in A.ho.fa) and returns:
 // it is dispatched first, so the host sees the flag at the head of the front.  Workgroup b > 0 is row workgroup b - 1.  Nobody waits
 // for anybody: the row workgroups read nothing the hand-over writes (the three scalars, the mirror, seq_dev) and write scratch alone.
-template <int NS, int EW, int KC = 0, bool HO = false>
+// FC (LORADS_FRONT_CHAIN; either bit leaves the arithmetic as it is: the same products added in the same order):
+//   FC_RAW   the neighbour rows are loaded without the mask of the slice beyond r (Slice::load_raw: no v_cndmask per loaded
+//            register, no masked copy beside the loaded one); that slice of the right-hand side and of r0 is masked once, in the
+//            epilogue, so every sum gets the same +0.0 from it as before
+//   FC_LATE  the row's own operands (X_p, xin_p: nothing reads them before the epilogue) are requested behind the first slot batch
+//            and arrive under the waits of the batches that follow -- 8 NS registers free while the objective is walked
+enum { FC_RAW = 1, FC_LATE = 2, FC_ALL = 3, FC_DEFAULT = FC_ALL }; // (measured at the headline: profiles/r11_front_chain_ab.txt)
+template <int NB, class SL, bool RAW = false, int NS, int W>
+__device__ __forceinline__ void front_gather(const double *__restrict__ X, int r, int lane, int q, int u0, double (&v)[NB][NS][W]) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        if constexpr (RAW) SL::load_raw(X + (size_t)__shfl(q, u0 + u, 8) * r, r, lane, v[u]);
+        else SL::load(X + (size_t)__shfl(q, u0 + u, 8) * r, r, lane, v[u]);
+    }
+}
+template <int NB, int NS, int W>
+__device__ __forceinline__ void front_fma2(double k1, double k2, int u0, const double (&v)[NB][NS][W], double (&acc)[NS][W], double (&acc2)[NS][W]) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        const double s1 = __shfl(k1, u0 + u, 8), s2 = __shfl(k2, u0 + u, 8);
+#pragma unroll
+        for (int c = 0; c < NS; ++c)
+#pragma unroll
+            for (int w = 0; w < W; ++w) { acc[c][w] += s1 * v[u][c][w]; acc2[c][w] += s2 * v[u][c][w]; }
+    }
+}
+// lane u0 + u of the group keeps r0 . v[u] in `mine`
+template <int NB, int NS, int W>
+__device__ __forceinline__ void front_dots(const double (&r0)[NS][W], const double (&v)[NB][NS][W], int u0, int l8, double &mine) {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+        double dsum = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; ++c)
+#pragma unroll
+            for (int w = 0; w < W; ++w) dsum += r0[c][w] * v[u][c][w];
+        dsum = group_sum<8>(dsum);
+        mine = l8 == u0 + u ? dsum : mine;
+    }
+}
+template <int NS, int EW, int KC = 0, bool HO = false, int FC = 0>
 __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::conditional_t<HO, FrontCwHoArgs, FrontCwArgs> A,
                                                   const double *__restrict__ X, int r,
                                                   const double *__restrict__ xin, double *__restrict__ out,
                                                   double *__restrict__ rhs_out, double *__restrict__ part,
                                                   double *__restrict__ part_b, Guard g, Deferred d) {
     constexpr int LG = 8, W = 2, NH = EW / 8;
+    constexpr bool RAW = (FC & FC_RAW) != 0, LATE = (FC & FC_LATE) != 0;
     using SL = Slice<LG, true, NS>;
     __shared__ double sh[HO ? 12 : 8];
     extern __shared__ __attribute__((aligned(16))) double2 slotc[]; // [32 rows][KC slots][NS][8 lanes]
     unsigned wg = blockIdx.x; // the row workgroup
     if constexpr (HO) {
-        if (blockIdx.x == 0) {
-            publish_final(A.ho.fa, A.ho.src, A.ho.nwords, A.ho.dst, A.ho.flag, A.ho.seq_dev, sh);
+        if (blockIdx.x < (unsigned)A.ho.lead) { // (lead = 1, see HandoverArgs)
+            if (blockIdx.x == 0) publish_final(A.ho.fa, A.ho.src, A.ho.nwords, A.ho.dst, A.ho.flag, A.ho.seq_dev, sh);
             return;
         }
-        wg = blockIdx.x - 1;
+        wg = blockIdx.x - A.ho.lead;
     }
     if (A.reset && wg == 0 && threadIdx.x < A.nreset) A.reset[threadIdx.x].done = 0;
     const Gate gt = gate_load(g);
@@ -1131,8 +1187,10 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::condition
     int qn = A.fc_col[tc];
     double svn = A.fc_val[tc];
     double xi[NS][W], rh[NS][W];
-    SL::load(X + base, r, lane, xi);
-    SL::load(xin + base, r, lane, rh);
+    if constexpr (!LATE) {
+        SL::load(X + base, r, lane, xi);
+        SL::load(xin + base, r, lane, rh);
+    }
     // level 2 (beside the first neighbour rows): this lane's slot coefficients from the m-vectors
     double k1[NH], k2[NH];
 #pragma unroll
@@ -1159,8 +1217,7 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::condition
         for (int u0 = 0; u0 < 8; u0 += 4) {
             if (u0 == 0 || t + u0 < c1e) {
                 double v[4][NS][W];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) SL::load(X + (size_t)__shfl(q, u0 + u, 8) * r, r, lane, v[u]);
+                front_gather<4, SL, RAW>(X, r, lane, q, u0, v);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const double a1c = __shfl(sv, u0 + u, 8);
@@ -1173,37 +1230,44 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::condition
         }
     }
     // ---- the A part: the row's slots, two coefficients per slot
+    { // slots 0..3 (every row: padding names the row itself, coefficient 0)
+        double v[4][NS][W];
+        front_gather<4, SL, RAW>(X, r, lane, qc[0], 0, v);
+        if constexpr (LATE) {
+            SL::load(X + base, r, lane, xi);
+            SL::load(xin + base, r, lane, rh);
+        }
+        if constexpr (KC > 0) { // park the rows for the second visit
 #pragma unroll
-    for (int h = 0; h < NH; ++h) {
-        if (h == 0 || cnt > 8 * h) {
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int c = 0; c < NS; ++c)
+                    slotc[(((threadIdx.x >> 3) * KC + u) * NS + c) * 8 + l8] = make_double2(v[u][c][0], v[u][c][1]);
+        }
+        front_fma2<4>(k1[0], k2[0], 0, v, acc, acc2);
+    }
+    if (cnt > 4) { // slots 4..7
+        double v[4][NS][W];
+        front_gather<4, SL, RAW>(X, r, lane, qc[0], 4, v);
+        front_fma2<4>(k1[0], k2[0], 4, v, acc, acc2);
+    }
+#pragma unroll
+    for (int h = 1; h < NH; ++h) {
+        if (cnt > 8 * h) {
 #pragma unroll
             for (int u0 = 0; u0 < 8; u0 += 4) {
                 if (u0 > 0 && cnt <= 8 * h + u0) continue;
                 double v[4][NS][W];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) SL::load(X + (size_t)__shfl(qc[h], u0 + u, 8) * r, r, lane, v[u]);
-                if (KC > 0 && h == 0 && u0 < KC) { // park the rows for the second visit
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int c = 0; c < NS; ++c)
-                            slotc[(((threadIdx.x >> 3) * KC + u0 + u) * NS + c) * 8 + l8] = make_double2(v[u][c][0], v[u][c][1]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double s1 = __shfl(k1[h], u0 + u, 8), s2 = __shfl(k2[h], u0 + u, 8);
-#pragma unroll
-                    for (int c = 0; c < NS; ++c)
-#pragma unroll
-                        for (int w = 0; w < W; ++w) { acc[c][w] += s1 * v[u][c][w]; acc2[c][w] += s2 * v[u][c][w]; }
-                }
+                front_gather<4, SL, RAW>(X, r, lane, qc[h], u0, v);
+                front_fma2<4>(k1[h], k2[h], u0, v, acc, acc2);
             }
         }
     }
     for (int t = a0 + EW; t < a1; ++t) { // the rare row with more than EW slots: the rest of its CSR list, one slot at a time
         double s1, s2, v[NS][W];
         front_cw_weights(A, rho, rho_dual, A.sl_con[t], A.sl_a[t], s1, s2);
-        SL::load(X + (size_t)A.sl_col[t] * r, r, lane, v);
+        if constexpr (RAW) SL::load_raw(X + (size_t)A.sl_col[t] * r, r, lane, v);
+        else SL::load(X + (size_t)A.sl_col[t] * r, r, lane, v);
 #pragma unroll
         for (int c = 0; c < NS; ++c)
 #pragma unroll
@@ -1220,8 +1284,12 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::condition
 #pragma unroll
         for (int w = 0; w < W; ++w) {
             vb[w] = xi[c][w] - acc[c][w] / rho;
-            local_b += fabs(vb[w]);
             r0[c][w] = vb[w] - (rh[c][w] + acc2[c][w]);
+            if constexpr (RAW) { // (the neighbour rows came unmasked: a slice beyond r is masked here, once)
+                vb[w] = j0 < r ? vb[w] : 0.0;
+                r0[c][w] = j0 < r ? r0[c][w] : 0.0;
+            }
+            local_b += fabs(vb[w]);
             local += r0[c][w] * r0[c][w];
         }
         if (live && act && j0 < r) {
@@ -1235,36 +1303,43 @@ __global__ __launch_bounds__(TPB) void k_front_cw(int n, int rpw, std::condition
     // write -- a1 = a0 for them, see above)
     const int cnt2 = A.contrib ? cnt : 0;
     const int a1b = A.contrib ? a1 : a0;
+    if (cnt2 > 0) { // slots 0..7 (a lane's contribution does not depend on the order its neighbours' are formed in)
+        double mine = 0.0;
+        if constexpr (KC > 0) { // slots 0..3 parked by the first visit
+            double v[4][NS][W];
 #pragma unroll
-    for (int h = 0; h < NH; ++h) {
-        if ((h == 0 && cnt2 > 0) || cnt2 > 8 * h) {
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int c = 0; c < NS; ++c) {
+                    const double2 t = slotc[(((threadIdx.x >> 3) * KC + u) * NS + c) * 8 + l8];
+                    v[u][c][0] = t.x; v[u][c][1] = t.y;
+                }
+            front_dots<4>(r0, v, 0, l8, mine);
+            if (cnt2 > 4) {
+                front_gather<4, SL, RAW>(X, r, lane, qc[0], 4, v);
+                front_dots<4>(r0, v, 4, l8, mine);
+            }
+        } else {
+#pragma unroll
+            for (int u0 = 0; u0 < 8; u0 += 4) {
+                if (u0 > 0 && cnt2 <= u0) continue;
+                double v[4][NS][W];
+                front_gather<4, SL, RAW>(X, r, lane, qc[0], u0, v);
+                front_dots<4>(r0, v, u0, l8, mine);
+            }
+        }
+        if (live && l8 < cnt2) store8(A.contrib, (size_t)dc[0], ac[0] * mine, A.wt & WT_CONTRIB);
+    }
+#pragma unroll
+    for (int h = 1; h < NH; ++h) {
+        if (cnt2 > 8 * h) {
             double mine = 0.0;
 #pragma unroll
             for (int u0 = 0; u0 < 8; u0 += 4) {
                 if (u0 > 0 && cnt2 <= 8 * h + u0) continue;
                 double v[4][NS][W];
-                if (KC > 0 && h == 0 && u0 < KC) { // parked by the first visit
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int c = 0; c < NS; ++c) {
-                            const double2 t = slotc[(((threadIdx.x >> 3) * KC + u0 + u) * NS + c) * 8 + l8];
-                            v[u][c][0] = t.x; v[u][c][1] = t.y;
-                        }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) SL::load(X + (size_t)__shfl(qc[h], u0 + u, 8) * r, r, lane, v[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    double dsum = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NS; ++c)
-#pragma unroll
-                        for (int w = 0; w < W; ++w) dsum += r0[c][w] * v[u][c][w];
-                    dsum = group_sum<LG>(dsum);
-                    mine = l8 == u0 + u ? dsum : mine;
-                }
+                front_gather<4, SL, RAW>(X, r, lane, qc[h], u0, v);
+                front_dots<4>(r0, v, u0, l8, mine);
             }
             if (live && l8 + 8 * h < cnt2) store8(A.contrib, (size_t)dc[h], ac[h] * mine, A.wt & WT_CONTRIB);
         }

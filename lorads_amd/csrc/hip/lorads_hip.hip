@@ -863,6 +863,9 @@ struct lorads_hip_ctx {
     // which row outputs of those two kernels are stored through the L2 (WT_* bits, store16 in kernels.inc; LORADS_WT_STORES, read at
     // creation: a bit mask, 0 = plain stores everywhere)
     int opt_wt_stores = WT_DEFAULT;
+    // the cuts in the solve front's chain of dependent loads (FC_* bits, k_front_cw; LORADS_FRONT_CHAIN, read at creation: a bit
+    // mask, 0 = the front without them)
+    int opt_front_chain = FC_DEFAULT;
     // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
     // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
     bool opt_spec_front = true;
@@ -1053,6 +1056,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
         if (getenv("LORADS_ROW_DEAL_CUS")) c->row_deal_cus = std::max(1, atoi(getenv("LORADS_ROW_DEAL_CUS")));
     }
     if (getenv("LORADS_WT_STORES") && getenv("LORADS_WT_STORES")[0]) c->opt_wt_stores = atoi(getenv("LORADS_WT_STORES")) & WT_ALL;
+    if (getenv("LORADS_FRONT_CHAIN") && getenv("LORADS_FRONT_CHAIN")[0]) c->opt_front_chain = atoi(getenv("LORADS_FRONT_CHAIN")) & FC_ALL;
     c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
     c->opt_handover_on_front = env_on("LORADS_HANDOVER_ON_FRONT");
     if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
@@ -2028,6 +2032,17 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *c, int32_t k, int out[3]) { // (a 
 int lorads_hip_wt_stores(lorads_hip_ctx *c, int *mask) { // (a statistics entry: leaves a front in flight alone)
     if (!c || !mask) return fail_msg("wt_stores: bad argument");
     *mask = c->opt_wt_stores;
+    return 0;
+}
+
+int lorads_hip_front_chain(lorads_hip_ctx *c, int *mask, int *eff) { // (a statistics entry: leaves a front in flight alone)
+    if (!c || !mask) return fail_msg("front_chain: bad argument");
+    *mask = c->opt_front_chain;
+    if (eff) { // what launch_front_cw launches: the cuts belong to the form with the LDS park
+        *eff = 0;
+        for (const Block &B : c->blk)
+            if (B.front_cw && c->opt_front_lds && (B.r + 15) / 16 <= 3) *eff = c->opt_front_chain;
+    }
     return 0;
 }
 

@@ -517,10 +517,21 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     const bool keep = c->pend.set_dual_used(false);
     FrontSample fs(c);
     FrontCwHoArgs AH{};
-    if (ho) { static_cast<FrontCwArgs &>(AH) = A; AH.ho = *ho; }
-#define FCW(EWV, HO, AV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV, 0, HO>), grid + HO, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
+    // (the hand-over form: `lead` workgroups ahead of the row workgroups, in the grid and in the kernel's argument alike)
+    const int lead = ho ? 1 : 0;
+    if (ho) { static_cast<FrontCwArgs &>(AH) = A; AH.ho = *ho; AH.ho.lead = lead; }
+    // (LORADS_FRONT_CHAIN: the cuts belong to the form with the LDS park, the one they were measured on -- see k_front_cw)
+    const int fc = c->opt_front_chain & FC_ALL;
+#define FC_SWITCH(...)                                             \
+    do { switch (fc) {                                             \
+    case 0: { constexpr int FC_ = 0; __VA_ARGS__; } break;         \
+    case 1: { constexpr int FC_ = 1; __VA_ARGS__; } break;         \
+    case 2: { constexpr int FC_ = 2; __VA_ARGS__; } break;         \
+    default: { constexpr int FC_ = 3; __VA_ARGS__; } break;        \
+    } } while (0)
+#define FCW(EWV, HO, AV) NS_SWITCH(8, true, ns, LAUNCH((k_front_cw<NS_, EWV, 0, HO>), grid + lead, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
     // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
-#define FCWL(NSV, EWV, HO, AV) LAUNCH_LDS((k_front_cw<NSV, EWV, 4, HO>), grid + HO, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d)
+#define FCWL(NSV, EWV, HO, AV) FC_SWITCH(LAUNCH_LDS((k_front_cw<NSV, EWV, 4, HO, FC_>), grid + lead, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
 #define FRONT(HO, AV)                                                                                                    \
     if (c->opt_front_lds && ns <= 3) {                                                                                   \
         if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8, HO, AV); else if (ns == 2) FCWL(2, 8, HO, AV); else FCWL(3, 8, HO, AV); }     \
@@ -530,6 +541,7 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
 #undef FRONT
 #undef FCWL
 #undef FCW
+#undef FC_SWITCH
     fs.done();
     c->pend.set_dual_used(keep);
     return grid;
@@ -757,7 +769,7 @@ int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords, const double
                c->h_flag_dev, c->seq_dev);
     } else if (c->final_pending) {
         const HandoverArgs H{c->final_args, (const unsigned long long *)c->ctrl + word0, (unsigned long long *)c->h_ctrl_dev + word0,
-                             (int)nwords, c->h_flag_dev, c->seq_dev};
+                             (int)nwords, c->h_flag_dev, c->seq_dev, 0}; // (lead: set by launch_front_cw with the grid)
         const bool own = (const double *)H.src == H.fa.out; // (as k_publish_final sees it)
         if (front_rho && c->opt_handover_on_front && own && spec_front_enqueue(c, *front_rho, &H)) {
             *front_carried = true;

@@ -809,6 +809,15 @@ class Session:
         _check(lib.lorads_hip_wt_stores(ctx, C.byref(out)), "wt_stores")
         return int(out.value)
 
+    def hip_front_chain(self, effective=False):
+        """the mask of cuts in the solve front's chain of dependent loads in this context (LORADS_FRONT_CHAIN); effective: 0
+        unless some cone launches the form of the front that takes them (the LDS park: r <= 48, LORADS_FRONT_LDS on)"""
+        lib, ctx = self._hip()
+        out, eff = C.c_int(-1), C.c_int(-1)
+        lib.lorads_hip_front_chain.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _check(lib.lorads_hip_front_chain(ctx, C.byref(out), C.byref(eff)), "front_chain")
+        return int(eff.value if effective else out.value)
+
     def hip_dense_plan(self, blk=0):
         """{npad, ksplit, launches: [(col0, nt, rem), ...]}: what the dense-coefficient GEMM (k_dense_cx_b) launches for cone `blk` at
         its current device rank -- n padded to 64, the K split over workgroups, and per launch its first column, its column tiles of
