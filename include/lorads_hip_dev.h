@@ -46,6 +46,11 @@ int lorads_hip_operator_kind(lorads_hip_ctx *ctx, int32_t blk, int32_t *kind);
  * constraint-wise operator, Gram form available, one-kernel front available, fixed width of the slot list, rows of either colour
  * of a bipartite entry graph (0: not bipartite) packed as colour-0 count} */
 int lorads_hip_block_image(lorads_hip_ctx *ctx, int32_t blk, int64_t image[16]);
+/* the data layout of block blk's constraint-wise operator (all 0 where the cone has none): out = {fixed width of the constraint
+ * entry list that k_cw reads (0: the constraint CSR), slots per constraint of the contribution array that k_wsum sums (0: the
+ * one-kernel front is not built), fixed width of the slot list (0: k_spmm<CW> walks the CSR slot list), rows with more slots than
+ * that width (their tails run on the CSR list)} */
+int lorads_hip_cw_layout(lorads_hip_ctx *ctx, int32_t blk, int64_t out[4]);
 /* replay of captured launch chains (hipGraph; LORADS_GRAPH=0 switches it off): stats = {chains captured, chains replayed,
  * chains held now, 1 if the replay is enabled for this context} */
 int lorads_hip_graph_stats(lorads_hip_ctx *ctx, int64_t stats[4]);

@@ -449,6 +449,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                 if (M.upload(&B.cell_col, ecol) || M.upload(&B.cell_con, econ) || M.upload(&B.cell_a, eav)) return 1;
                 B.cell_w = ew;
             }
+            for (int i = 0; i < B.n; ++i) B.cell_over += (ptr[i + 1] - ptr[i]) > B.cell_w;
             if (B.cell_w && !B.dense_c && !getenv("LORADS_NO_FRONT_CW_DATA")) {
                 // k_front_cw: the objective's own adjacency (both orientations, duplicates summed, neighbours ascending) ...
                 std::vector<std::pair<int, int>> posC(B.nc), uniqC;

@@ -450,6 +450,7 @@ struct Block {
     double *cadj_a = nullptr;
     int cadj_ptr_host_n = 0;                  // number of slots in the CSR list (cadj_col / cadj_con / cadj_a)
     int cell_w = 0;                           // > 0: the slot list also in fixed width (8 or 16 per row) for k_spmm_ell
+    int cell_over = 0;                        // rows with more slots than cell_w (their tail runs on the CSR list); counted at build
     int *cell_col = nullptr, *cell_con = nullptr;
     double *cell_a = nullptr;
     double *w_uv = nullptr, *w_op = nullptr; // A(sym(U V^T)) kept for re-use (valid <=> t_uv_valid); operator scratch
@@ -1919,6 +1920,17 @@ int lorads_hip_block_image(lorads_hip_ctx *c, int32_t k, int64_t im[16]) {
     const int64_t v[16] = {B.n, B.rl, B.nrow, B.na, B.nc, B.pa.ne, B.pu.ne, B.dense_c, B.dense_a ? B.nd : 0, B.diag_only, B.entry_only,
                            B.use_cw, B.has_gram, B.front_cw, B.cell_w, B.bip_n[0]};
     for (int i = 0; i < 16; ++i) im[i] = v[i];
+    return 0;
+}
+
+int lorads_hip_cw_layout(lorads_hip_ctx *c, int32_t k, int64_t out[4]) {
+    spec_touch(c);
+    if (k < 0 || k >= c->nb) return fail_msg("bad block");
+    const Block &B = c->blk[k];
+    out[0] = B.ca_ell;
+    out[1] = B.cs_w;
+    out[2] = B.cell_w;
+    out[3] = B.cell_over;
     return 0;
 }
 

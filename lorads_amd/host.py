@@ -776,6 +776,14 @@ class Session:
                 "has_gram", "front_cw", "slot_width", "bip_rows0"]
         return dict(zip(keys, [int(out[i]) for i in range(16)]))
 
+    def hip_cw_layout(self, blk=0):
+        """{ca_ell, cs_w, cell_w, rows_over}: the layout of cone blk's constraint-wise operator (see lorads_hip_dev.h)"""
+        lib, ctx = self._hip()
+        out = (C.c_int64 * 4)()
+        lib.lorads_hip_cw_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        _check(lib.lorads_hip_cw_layout(ctx, blk, out), "cw_layout")
+        return dict(zip(["ca_ell", "cs_w", "cell_w", "rows_over"], [int(out[i]) for i in range(4)]))
+
     def hip_spec_front_stats(self):
         """{enqueued, adopted, discarded, blocked} of the next step's U front enqueued behind a step's hand-over (LORADS_SPEC_FRONT)"""
         lib, ctx = self._hip()

@@ -265,6 +265,41 @@ def randsparse(n, m, seed, c_edges=None, n_diag=2, n_off=8, r0=5, dense_c=False)
     return dict(m=m, blocks=[n], b=b, entries=ent)
 
 
+def randsparse_sizes(n, sizes, seed, c_edges, r0=3):
+    """randsparse's objective; constraint k has sizes[k] = (n_diag, n_off) entries, values N(0,1)/sqrt(n_diag + n_off) (unscaled,
+    a constraint of 256 entries next to one of 1 leaves the CG too ill-conditioned for a float64 model to serve as a yardstick);
+    b = A(R0 R0^T) as in randsparse"""
+    base = randsparse(n, 0, seed, c_edges=c_edges, r0=r0)
+    rng = np.random.default_rng(seed + 7)
+    R0 = np.random.default_rng(seed + 1).standard_normal((n, r0)) / math.sqrt(n)
+    ent, b = list(base["entries"]), []
+    for k, (nd, no) in enumerate(sizes):
+        d = sorted(rng.choice(n, size=nd, replace=False).tolist()) if nd else []
+        seen = set()
+        while len(seen) < no:
+            i, j = rng.integers(0, n, size=2).tolist()
+            if i != j:
+                seen.add((min(i, j), max(i, j)))
+        vals = rng.standard_normal(nd + no) / math.sqrt(nd + no)
+        acc = 0.0
+        for t, i in enumerate(d):
+            ent.append((k + 1, 1, i + 1, i + 1, float(vals[t])))
+            acc += vals[t] * float(R0[i] @ R0[i])
+        for t, (i, j) in enumerate(sorted(seen)):
+            v = float(vals[nd + t])
+            ent.append((k + 1, 1, i + 1, j + 1, v))
+            acc += 2.0 * v * float(R0[i] @ R0[j])
+        b.append(acc)
+    return dict(m=len(sizes), blocks=[n], b=np.array(b), entries=ent)
+
+
+# (n_diag, n_off) per constraint: 1 .. 40 entries (k_cw takes 16 / 4 / 2 entries per trip at 8 / 32 / 64 lanes per entry, so the sizes
+# 1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 40 straddle one, two and three trips), and up to 256
+SIZES_1_40 = [(1, 0), (0, 1), (2, 0), (1, 1), (0, 3), (2, 3), (1, 6), (0, 8), (2, 7), (0, 15), (1, 15), (0, 17), (2, 29), (0, 32), (1, 32),
+              (0, 33), (3, 37)]
+SIZES_1_256 = SIZES_1_40 + [(0, 63), (0, 64), (1, 64), (0, 127), (0, 129), (5, 251)]
+
+
 def prescribed_slack(S):
     """Max-Cut-type instance (X_ii = 1, one constraint per row) whose objective is the off-diagonal part of the symmetric matrix S:
     with the multipliers lambda = -diag(S) the slack C - sum_i lambda_i e_i e_i^T is S itself, entry for entry and without rounding
@@ -497,6 +532,15 @@ NAMED = {
     "hub16": lambda: with_hub_rows(randsparse(810, 400, 2103, c_edges=1600, n_diag=2, n_off=8, r0=3), 3, 60, 2104),
     # ... and one with ten times as many constraints as rows: the constraint values outnumber the operator kernel's threads
     "wide60": lambda: randsparse(60, 600, 2105, c_edges=120, n_diag=1, n_off=2, r0=2),
+    # constraints of unequal size (tests/test_unequal_constraints.py): k_cw on the constraint CSR; three trips of k_wsum (mixsz130,
+    # mixsz300); a few huge constraints, so the older front under the constraint-wise operator (bigsz200); the constraint-wise
+    # operator without a switch (m >= 256: mixsz300, and theta64x300 with a dense C); two such cones next to a Max-Cut cone (mixblk3)
+    "mixsz130": lambda: randsparse_sizes(130, SIZES_1_40 * 2, 2201, 260),
+    "bigsz200": lambda: randsparse_sizes(200, SIZES_1_256, 2203, 400),
+    "mixsz300": lambda: randsparse_sizes(300, (SIZES_1_40 * 16)[:260], 2205, 900),
+    "theta64x300": lambda: theta(64, 300, 3),
+    "mixblk3": lambda: block_diag([randsparse_sizes(90, SIZES_1_40, 2207, 180),
+                                   randsparse_sizes(70, SIZES_1_40[:12] + [(0, 1)] * 6, 2208, 140), maxcut(50, 80, 5)]),
     # Max-Cut cones of unequal size (and therefore unequal rank, data/lorads_solver.c:290-319), separable: one team of workgroups each
     "blkmix5": lambda: block_diag([maxcut(90, 140, 71), maxcut(120, 250, 72), maxcut(150, 400, 73), maxcut(260, 900, 74), maxcut(200, 500, 75)]),
     "densec300": lambda: randsparse(300, 60, 778, n_diag=2, n_off=4, r0=3, dense_c=True),  # dense C -> MFMA C.X path

@@ -177,7 +177,7 @@ def run_case(name, env=None, params=None, schedule=SMALL, hist=2, ranks=None, se
                          images=[s.hip_block_image(k) for k in range(nb)], ranks=[sh[1] for sh in shapes], iters=len(recs),
                          dir_launches=dir_launches, dir_calls=dir_calls, step_launches=step_launches, calls=list(calls),
                          fallbacks=fallbacks, elements=sum(a * b for a, b in shapes), hist=hist, lp=[cn.is_lp for cn in model.cones], m=s.m,
-                         dense=[s.hip_dense_plan(k) for k in range(nb)])
+                         dense=[s.hip_dense_plan(k) for k in range(nb)], layouts=[s.hip_cw_layout(k) for k in range(nb)])
             print(name, env, path, "history", hist, "ranks", facts["ranks"], "iterations", len(recs), "e64 %.1e" % max(e64[:len(recs)]),
                   "bound %.1e" % bound, "worst", {k: "%.1e" % v for k, v in worst.items()}, "team", facts["team"],
                   "launches/direction", dir_launches, "launches/step", step_launches,

@@ -46,6 +46,32 @@ HEADLINE = [("step", 1, 0.0), ("sweep", 2, 0.0), ("step", 2, 0.0)]
 RANKS = [("sweep", 2, 0.0), ("step", 1, 0.0)]
 
 
+def find_stop(model, name, i, js, maxit, fixed, stops):
+    """the tolerance of schedule entry i whose stops are asked for by the tuple js, from the model alone: (tol, maxit); the
+    iteration it stops at is appended to `stops` (None: no such tolerance, and the sweep runs maxit iterations at tolerance 0)"""
+    if fixed:
+        # the stop is looked for among the first 40 iterations; with every solve stopped by then, maxit plays no part
+        js = tuple(j for j in js if j not in stops) + js
+        found = stopping_tol(model, RHO, js, maxit, probe_maxit=40) or stopping_tol(model, RHO, js, maxit, ratio=1.25, probe_maxit=40)
+        stops.append(found[1] if found else None)
+        assert found, (name, i, "no tolerance that stops every solve early", js)
+        return found[0], maxit
+    pref = js + tuple(j for j in range(1, 16) if j not in js)
+    found = None
+    # a stop not taken yet first; a solve that never nears the tolerance runs to maxit, so a smaller maxit leaves fewer
+    # residuals to keep clear of
+    for js in (tuple(j for j in pref if j not in stops), pref):
+        for mx in (maxit, 21, 12, 8, 6, 4):
+            found = stopping_tol(model, RHO, js, mx) or stopping_tol(model, RHO, js, mx, ratio=1.25)
+            if found:
+                maxit = mx
+                break
+        if found:
+            break
+    stops.append(found[1] if found else None)
+    return (found[0] if found else 0.0), maxit
+
+
 def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=None, hook=False, seed=5, path=None, tag=None,
              stamps=False, spread=False):
     """runs the schedule on the device and the model; returns (session facts, worst errors by group).
@@ -86,28 +112,8 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
             kind, maxit, tol = entry[:3]
             fixed = len(entry) > 3 and entry[3] == "fixed"
             pnow = s.hip_persist_stats()["iterations"]
-            if isinstance(tol, tuple) and fixed:
-                # the stop is looked for among the first 40 iterations; with every solve stopped by then, maxit plays no part
-                js = tuple(j for j in tol if j not in stops) + tol
-                found = stopping_tol(model, RHO, js, maxit, probe_maxit=40) or stopping_tol(model, RHO, js, maxit, ratio=1.25, probe_maxit=40)
-                tol = found[0] if found else 0.0
-                stops.append(found[1] if found else None)
-                assert found, (name, i, "no tolerance that stops every solve early", js)
-            elif isinstance(tol, tuple):
-                pref = tol + tuple(j for j in range(1, 16) if j not in tol)
-                found = None
-                # a stop not taken yet first; a solve that never nears the tolerance runs to maxit, so a smaller maxit leaves fewer
-                # residuals to keep clear of
-                for js in (tuple(j for j in pref if j not in stops), pref):
-                    for mx in (maxit, 21, 12, 8, 6, 4):
-                        found = stopping_tol(model, RHO, js, mx) or stopping_tol(model, RHO, js, mx, ratio=1.25)
-                        if found:
-                            maxit = mx
-                            break
-                    if found:
-                        break
-                tol = found[0] if found else 0.0
-                stops.append(found[1] if found else None)
+            if isinstance(tol, tuple):
+                tol, maxit = find_stop(model, name, i, tol, maxit, fixed, stops)
             if kind == "sweep":
                 its = be.admm_update_var(RHO, tol, maxit)
                 mits, _ = model.sweep(RHO, tol, maxit)
@@ -156,7 +162,7 @@ def run_case(name, env=None, params=None, schedule=FULL, ranks=None, separable=N
                      persist=s.hip_persist_stats()["iterations"] - p0, launches=s.hip_launch_count() - n0, calls=len(calls),
                      ranks=[s.block_shape(k)[1] for k in range(s.nblk)], stops=stops, counts=counts, persist_calls=persist_calls,
                      stats=s.hip_persist_stats(), plan=s.hip_persist_plan(), dense=[s.hip_dense_plan(k) for k in range(s.nblk)],
-                     graph=s.hip_graph_stats())
+                     graph=s.hip_graph_stats(), layouts=[s.hip_cw_layout(k) for k in range(s.nblk)])
         if stamps:
             word = s.hip_persist_stamps(False)[15]
             facts["l2"] = (word >> 1) & 3 if word & 1 else None  # bit 0: granules through the XCD's L2, bit 1: factor rows too
