@@ -11,8 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-INT_KEYS = ("trials", "seed", "max_rounds", "rounds", "src", "best", "best0")
-FLOAT_KEYS = ("scale", "f_best", "f_best0", "by", "bound", "gap", "tol")
+from ._rounded import FLOAT_KEYS, INT_KEYS, RoundHeadStruct, _arr, head_of, read_head
 
 
 class BisectionConeStruct(C.Structure):
@@ -24,15 +23,7 @@ class BisectionConeStruct(C.Structure):
 
 class BisectionStruct(C.Structure):
     """lrd_bisection (csrc/host/lorads_host.h)"""
-    _fields_ = [("nblk", C.c_int), ("trials", C.c_int), ("max_rounds", C.c_int), ("rounds", C.c_int), ("src", C.c_int),
-                ("seed", C.c_uint64), ("scale", C.c_double), ("best", C.c_int), ("best0", C.c_int),
-                ("f_best", C.c_double), ("f_best0", C.c_double), ("obj", C.POINTER(C.c_double)), ("obj0", C.POINTER(C.c_double)),
-                ("by", C.c_double), ("bound", C.c_double), ("gap", C.c_double), ("tol", C.c_double),
-                ("cone", C.POINTER(BisectionConeStruct))]
-
-
-def _arr(ptr, n, dtype=np.float64):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n > 0 and ptr else np.zeros(0, dtype=dtype)
+    _fields_ = [("head", RoundHeadStruct), ("nblk", C.c_int), ("cone", C.POINTER(BisectionConeStruct))]
 
 
 class BisectionCone:
@@ -60,30 +51,19 @@ class Bisection:
 
     @classmethod
     def from_struct(cls, st):
-        cones = []
+        cones, K = [], st.head.trials
         for k in range(st.nblk):
             q = st.cone[k]
-            G = _arr(q.G, q.rank * st.trials).reshape(q.rank, st.trials) if q.G else None
+            G = _arr(q.G, q.rank * K).reshape(q.rank, K) if q.G else None
             cones.append(BisectionCone(q.n, q.rank, q.diff, q.plus, q.minus, _arr(q.sigma, q.n, np.int8), q.t,
-                                       _arr(q.imbalance, st.trials, np.int32), q.lam_min, G))
-        sc = {k: getattr(st, k) for k in INT_KEYS + FLOAT_KEYS}
-        return cls(cones, _arr(st.obj, st.trials), _arr(st.obj0, st.trials), **sc)
+                                       _arr(q.imbalance, K, np.int32), q.lam_min, G))
+        obj, obj0, sc = head_of(st, INT_KEYS + FLOAT_KEYS)
+        return cls(cones, obj, obj0, **sc)
 
 
 def read_bisection(path):
     """Parse a bisection file (Session.write_bisection / lorads --bisectFile) into a Bisection (signs, sizes, objectives, scalars)."""
-    with open(path) as f:
-        lines = f.read().split("\n")
-    if lines[0] != "lorads-bisection 1":
-        raise ValueError("%s: not a lorads bisection file" % path)
-    pos = 1
-    sc = {}
-    for key in INT_KEYS + FLOAT_KEYS:
-        t = lines[pos].split()
-        pos += 1
-        if len(t) != 2 or t[0] != key:
-            raise ValueError("%s: expected %s, found %r" % (path, key, t))
-        sc[key] = int(t[1]) if key in INT_KEYS else float(t[1])
+    lines, pos, sc = read_head(path, "lorads-bisection 1", "bisection", INT_KEYS)
     cones = []
     while pos < len(lines) and lines[pos].startswith("cone "):
         t = lines[pos].split()

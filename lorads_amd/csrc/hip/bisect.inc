@@ -11,7 +11,9 @@
 // Per cone and trial the +-1 rounding's hyperplane and sign bits (k_rnd_gauss with parts = 1, k_rnd_sign: a trial depends on
 // (seed, cone, trial) alone), then one workgroup owns one (cone, trial): the repair to sum(sigma) = +-d_k, f, the swap search,
 // f again.  No workgroup waits for another.  Everything is read-only on the solver's state, as in rounding.inc: F is formed on the
-// fly, the scratch is the feature's own (BisectScratch), launches go straight to the stream, every sum has one fixed order.
+// fly, the scratch is the feature's own (BisectScratch), launches go straight to the stream, every sum has one fixed order.  The driver
+// around the search kernel is rounding.inc's (round_begin, round_reserve, round_vectors, round_signs, trial_chunks, round_finish,
+// round_stored_trial).
 //
 // C comes from cbase through the union pattern's adjacency (kcut.inc's kcut_walk), never from adj_sval: with the sum row in the
 // sparse structures a constraint touches every slot, so no slot's adj_sval is C.  A dense-C cone reads its row of Cfull.
@@ -318,36 +320,23 @@ int bis_check(lorads_hip_ctx *c) {
 // does a trial's state of a cone of n rows live in the LDS (LORADS_BISECT_LDS=0 at creation: never, the slab path at every size)
 inline bool bis_in_lds(const lorads_hip_ctx *c, int n) { return c->opt_bisect_lds && (size_t)BIS_RED * 8 + 9 * (size_t)n <= BIS_LDS_BYTES; }
 
+const RoundFeature FT_BISECT{"round_bisect", "bisection-structured", bis_check, false};
+
 } // namespace
 
 // the signs of trial `trial` of the context's last lorads_hip_round_bisect call, cone after cone
 extern "C" int lorads_hip_bisect_trial(lorads_hip_ctx *c, int32_t trial, int8_t *sign) {
     if (!c || !sign) return fail_msg("bisect_trial: bad argument");
-    BisectScratch &X = c->bisect;
-    if (X.K == 0 || trial < 0 || trial >= X.K) return fail_msg("bisect_trial: trial " + std::to_string(trial) + " is outside the last call's");
-    for (int k = 0; k < c->nb; ++k) {
-        const int n = c->blk[k].n;
-        if (n) HC(hipMemcpyAsync(sign + X.v_off[k], X.x + (size_t)X.v_off[k] * X.K + (size_t)trial * n, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    }
-    HC(hipStreamSynchronize(c->stream));
-    for (int p = 0; p < X.v_off[c->nb]; ++p) sign[p] = (sign[p] & 1) ? 1 : -1;
-    return 0;
+    const BisectScratch &X = c->bisect;
+    return round_stored_trial(c, "bisect_trial", X.trial, X.v_off, (const int8_t *)X.x.p, trial, sign,
+                              [](int8_t s) { return (int8_t)((s & 1) ? 1 : -1); });
 }
 
 extern "C" int lorads_hip_round_bisect(lorads_hip_ctx *c, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                                        double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *imbalance, int32_t *rounds,
                                        double *hyperplanes, double *t, int32_t *diff) {
-    spec_touch(c);
-    if (postsolve_args(c, src, nullptr, "round_bisect", true)) return 1;
-    if (trials < 0 || trials > RND_MAXK) return fail_msg("round_bisect: trials " + std::to_string(trials) + " is outside [0, 65536]");
-    if (max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_bisect: bad argument");
-    if (postsolve_sharded(c, "round_bisect", "cannot be rounded")) return 3;
-    if (bis_check(c)) return 1;
+    if (const int rc = round_begin(c, FT_BISECT, c ? &c->bisect : nullptr, src, nullptr, trials, max_rounds, obj)) return rc;
     BisectScratch &X = c->bisect;
-    if (!X.qualifies) {
-        fail_msg("round_bisect: the context is not bisection-structured: " + X.why);
-        return 2;
-    }
     for (int k = 0; k < c->nb; ++k) {
         if (t) t[k] = X.t[k];
         if (diff) diff[k] = X.d[k];
@@ -355,51 +344,32 @@ extern "C" int lorads_hip_round_bisect(lorads_hip_ctx *c, int32_t src, int32_t t
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64, ntot = X.v_off[c->nb];
     int nmax = 1;
-    size_t g = 0;
     bool slab = false;
-    for (auto &B : c->blk) { g += (size_t)B.rl * K; nmax = std::max(nmax, B.n); slab = slab || !bis_in_lds(c, B.n); }
-    const int CH = (int)std::min<size_t>((size_t)K, std::max<size_t>(16, BIS_CHUNK_ELEMS / nmax));
-    if (X.G.grow(X.mem, g) || X.sgn.grow(X.mem, (size_t)ntot * W) || X.x.grow(X.mem, (size_t)ntot * K) || X.f.grow(X.mem, (size_t)K) ||
-        X.f0.grow(X.mem, (size_t)K) || X.imb.grow(X.mem, (size_t)c->nb * K) || X.nround.grow(X.mem, (size_t)K) ||
-        (slab && X.h.grow(X.mem, (size_t)CH * nmax)))
+    for (auto &B : c->blk) { nmax = std::max(nmax, B.n); slab = slab || !bis_in_lds(c, B.n); }
+    const int CH = trial_chunk(c, K, nmax, BIS_CHUNK_ELEMS, 1);
+    TrialScratch &R = X.trial;
+    if (X.sgn.grow(X.mem, (size_t)ntot * W) || X.x.grow(X.mem, (size_t)ntot * K) || X.imb.grow(X.mem, (size_t)c->nb * K) ||
+        (slab && X.h.grow(X.mem, (size_t)CH * nmax)) || round_reserve(c, R, X.mem, K, 1, false))
         return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
-    X.K = K;
-    size_t goff = 0;
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        double *G = X.G + goff;
-        round_gauss(c, k, K, 1, seed, G);
-        const FactorView F = factor_view(c, src, k);
-        const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
-        hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, F.U, F.V, F.uv,
-                           (const double *)G, X.sgn + (size_t)X.v_off[k] * W);
-        goff += (size_t)B.rl * K;
-        const bool lds = bis_in_lds(c, B.n);
-        const size_t shm = (size_t)BIS_RED * 8 + (lds ? (((size_t)9 * B.n + 15) & ~(size_t)15) : 0);
-        const BisCone bc{B.n, B.pu.adj_ptr, B.pu.adj_col, B.pu.adj_e, B.pu.cbase, B.dense_c ? B.Cfull : nullptr, B.npad, X.t[k]};
-        for (int t0 = 0; t0 < K; t0 += CH) {
-            const int t1 = std::min(K, t0 + CH);
-            hipLaunchKernelGGL(k_bis_search, dim3(t1 - t0), dim3(TPB), shm, c->stream, bc, X.d[k], K, t0, k, (int)(k == 0), (int)max_rounds,
-                               (int)lds, (const unsigned long long *)(X.sgn + (size_t)X.v_off[k] * W), X.x + (size_t)X.v_off[k] * K, X.h.p,
-                               X.f.p, X.f0.p, X.imb.p, X.nround.p);
-        }
-        HC(hipGetLastError());
-    }
-    if (hyperplanes && goff) HC(hipMemcpyAsync(hyperplanes, X.G.p, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0.p, X.ctl);
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f.p, X.ctl + 1);
-    int bb[2] = {0, 0};
-    std::vector<int> nr((size_t)K);
-    HC(hipMemcpyAsync(bb, X.ctl, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(obj, X.f.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    if (obj0) HC(hipMemcpyAsync(obj0, X.f0.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (round_vectors(c, R, K, 1, seed, false, hyperplanes, [&](int k, const double *G) {
+            const Block &B = c->blk[k];
+            round_signs(c, src, k, K, W, G, X.sgn + (size_t)X.v_off[k] * W);
+            const bool lds = bis_in_lds(c, B.n);
+            const size_t shm = (size_t)BIS_RED * 8 + (lds ? (((size_t)9 * B.n + 15) & ~(size_t)15) : 0);
+            const BisCone bc{B.n, B.pu.adj_ptr, B.pu.adj_col, B.pu.adj_e, B.pu.cbase, B.dense_c ? B.Cfull : nullptr, B.npad, X.t[k]};
+            trial_chunks(K, CH, [&](int t0, int t1) {
+                hipLaunchKernelGGL(k_bis_search, dim3(t1 - t0), dim3(TPB), shm, c->stream, bc, X.d[k], K, t0, k, (int)(k == 0), (int)max_rounds,
+                                   (int)lds, (const unsigned long long *)(X.sgn + (size_t)X.v_off[k] * W), X.x + (size_t)X.v_off[k] * K, X.h.p,
+                                   R.f.p, R.f0.p, X.imb.p, R.nround.p);
+                return 0;
+            });
+            HC(hipGetLastError());
+            return 0;
+        }))
+        return 1;
     if (imbalance) HC(hipMemcpyAsync(imbalance, X.imb.p, sizeof(int) * (size_t)c->nb * K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(nr.data(), X.nround.p, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    if (best) *best = bb[1];
-    if (best0) *best0 = bb[0];
-    if (rounds) *rounds = *std::max_element(nr.begin(), nr.end());
-    if (sign) return lorads_hip_bisect_trial(c, bb[1], sign);
+    int bt = 0;
+    if (round_finish(c, K, R, R.f.p, -1, RoundOut{obj, obj0, best, best0, rounds}, &bt)) return 1;
+    if (sign) return lorads_hip_bisect_trial(c, bt, sign);
     return 0;
 }

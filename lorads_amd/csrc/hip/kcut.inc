@@ -12,12 +12,10 @@
 // Labels: one byte per (row, trial) in blocks of 64 trials, lab[(w * n + p) * 64 + lane]: a wavefront of the field pass (lane = trial)
 // reads a neighbour's 64 labels as one 64-byte segment.  Everything is read-only on the solver's state, as in rounding.inc: R is formed
 // on the fly, the scratch is the feature's own (KCutScratch), launches go straight to the stream, every sum has one fixed order.
-// The driver around the field kernel is rounding.inc's (round_reserve, round_gauss, round_drive).
+// The driver around the label and field kernels is rounding.inc's (round_begin, round_reserve, round_vectors, round_drive).
 
 namespace {
 
-constexpr int KCUT_MAXPARTS = 64;
-constexpr int KCUT_MAXPROD = 1 << 20;  // trials x parts
 constexpr int KCUT_CH = 16;            // parts whose sums h_a a walk of the row list holds at once (LDS, one column per thread)
 
 // the whole score chain of one part over the rl columns in fours, ascending: mfma_fm_tile's steps -- the same operands (A's element
@@ -293,25 +291,15 @@ int kcut_check(lorads_hip_ctx *c) {
     return 0;
 }
 
+const RoundFeature FT_KCUT{"round_kcut", "k-cut-structured", kcut_check, false};
+
 } // namespace
 
 extern "C" int lorads_hip_round_kcut(lorads_hip_ctx *c, int32_t src, int32_t parts, int32_t trials, uint64_t seed, int32_t max_rounds,
                                      double *obj, double *obj0, int32_t *best, int32_t *best0, uint8_t *label, int32_t *rounds,
                                      double *vectors, double *t, double *lp_upper) {
-    spec_touch(c);
-    if (postsolve_args(c, src, nullptr, "round_kcut", true)) return 1;
-    if (parts < 2 || parts > KCUT_MAXPARTS) return fail_msg("round_kcut: parts " + std::to_string(parts) + " is outside [2, 64]");
-    if (trials < 0 || trials > RND_MAXK) return fail_msg("round_kcut: trials " + std::to_string(trials) + " is outside [0, 65536]");
-    if ((int64_t)trials * parts > KCUT_MAXPROD)
-        return fail_msg("round_kcut: trials x parts = " + std::to_string((int64_t)trials * parts) + " is above 2^20");
-    if (max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_kcut: bad argument");
-    if (postsolve_sharded(c, "round_kcut", "cannot be rounded")) return 3;
-    if (kcut_check(c)) return 1;
+    if (const int rc = round_begin(c, FT_KCUT, c ? &c->kcut : nullptr, src, &parts, trials, max_rounds, obj)) return rc;
     KCutScratch &X = c->kcut;
-    if (!X.qualifies) {
-        fail_msg("round_kcut: the context is not k-cut-structured: " + X.why);
-        return 2;
-    }
     const std::vector<int> &off = c->rnd.t_off;
     if (t) { // t of the SDP cones, cone after cone
         size_t at = 0;
@@ -328,21 +316,17 @@ extern "C" int lorads_hip_round_kcut(lorads_hip_ctx *c, int32_t src, int32_t par
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64;
     TrialScratch &T = X.trial;
-    if (round_reserve(c, T, X.mem, K, parts) || X.lab.grow(X.mem, (size_t)off[c->nb] * W * 64) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    if (round_reserve(c, T, X.mem, K, parts, true) || X.lab.grow(X.mem, (size_t)off[c->nb] * W * 64) || (max_rounds > 0 && rnd_colour(c))) return 1;
     // vectors and labels
-    size_t goff = 0;
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        if (B.is_lp) continue;
-        double *G = T.G + goff;
-        round_gauss(c, k, K, parts, seed, G);
-        const FactorView F = factor_view(c, src, k);
-        const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * W * 4;
-        if (B.n) hipLaunchKernelGGL(k_kcut_label, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, parts,
-                                    F.U, F.V, F.uv, (const double *)G, X.lab + (size_t)off[k] * W * 64);
-        goff += (size_t)B.rl * K * parts;
-    }
-    if (vectors && goff) HC(hipMemcpyAsync(vectors, T.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    if (round_vectors(c, T, K, parts, seed, false, vectors, [&](int k, const double *G) {
+            const Block &B = c->blk[k];
+            const FactorView F = factor_view(c, src, k);
+            const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * W * 4;
+            if (B.n) hipLaunchKernelGGL(k_kcut_label, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, parts,
+                                        F.U, F.V, F.uv, G, X.lab + (size_t)off[k] * W * 64);
+            return 0;
+        }))
+        return 1;
     auto field = [&](int k, const int *rows, int nrows) {
         const Block &B = c->blk[k];
         hipLaunchKernelGGL(k_kcut_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K, parts,

@@ -620,17 +620,26 @@ struct CertScratch {
     void release() { mem.release(); *this = CertScratch{}; }
 };
 
-// what the two roundings' shared driver (rounding.inc: round_drive) works on, for K trials: the Gaussian vectors, the field partials
-// (8 x 256 K), f after / before the search (16 K), and ctl: [0] the search's change flag, [1] best before, [2] best after the search
+// What a rounding call of K trials owns, whichever feature makes it (rounding.inc: round_reserve .. round_finish): the Gaussian
+// vectors, f after / before the search (16 K), ctl -- [0] the field-pass search's change flag, [1] best before, [2] best after the
+// search --, and K of the last call (the stored-trial readers ask it).  The field-pass features (+-1, k parts) grow `part`, the field
+// partials (8 x 256 K); the one-trial-per-workgroup features (stable sets, bisections) grow `nround`, the rounds each trial ran.
 struct TrialScratch {
     DevBuf<double> G, part, f, f0;
+    DevBuf<int> nround;
     int *ctl = nullptr;
+    int K = 0;
+};
+
+// what every rounding's applicability check (rnd_check, kcut_check, stb_check, bis_check) leaves: once per context
+struct Applies {
+    bool checked = false, qualifies = false;
+    std::string why;                          // the first reason the context does not qualify
 };
 
 // scratch of the rounding (rounding.inc): allocated on its first call, never read by the solve
-struct RoundScratch {
-    bool checked = false, qualifies = false, coloured = false;
-    std::string why;                          // the first reason the context does not qualify
+struct RoundScratch : Applies {
+    bool coloured = false;
     std::vector<int> t_off;                   // [nb + 1] first row of every cone in the stacked row arrays
     double *t = nullptr;                      // t_p = sqrt(b_i / a_i), cone k at t_off[k]
     std::vector<std::vector<int>> cls_ptr;    // per cone: colour class -> its range of the class-sorted row list
@@ -643,9 +652,7 @@ struct RoundScratch {
 
 // scratch of the rounding into k parts (kcut.inc): allocated on its first call, never read by the solve.  Labels n K bytes rounded up to
 // blocks of 64 trials, G 8 k K sum(rank).  The colouring and, without an LP block, t are RoundScratch's.
-struct KCutScratch {
-    bool checked = false, qualifies = false;
-    std::string why;                          // the first reason the context does not qualify
+struct KCutScratch : Applies {
     const double *t = nullptr;                // t_p, cone k at RoundScratch::t_off[k]: RoundScratch's, or t_own on a context with an LP block
     double *t_own = nullptr;
     std::vector<double> lp_u;                 // [LP columns] u_j = (|b| + 2 |a| t_p t_q) / |c| of the column's bound row
@@ -658,19 +665,16 @@ struct KCutScratch {
 // scratch of the stable-set rounding (stable.inc): allocated on its first call, never read by the solve.  Per cone the graph of its
 // edge rows (CSR, both directions, ascending), G 8 K sum(rank), one state byte per (trial, vertex) of every cone, and per chunk of
 // trials the scores (8 n) and the search's lists (4 n) of the cone at hand.
-struct StableScratch {
-    bool checked = false, qualifies = false;
-    std::string why;                          // the first reason the context does not qualify
+struct StableScratch : Applies {
     std::vector<int> v_off;                   // [nb + 1] first vertex of every SDP cone in the stacked vertex arrays (an LP block has none)
     std::vector<long long> e_off;             // [nb + 1] first adjacency entry of every SDP cone in g_col
     std::vector<double> T;                    // [nb] T_k = b / a of the cone's trace row (LP block: 0)
     std::vector<double> lp_u;                 // [LP columns] u_j = (|2 a| T / 2 + |b|) / |c| of the column's bound row
     int *g_ptr = nullptr, *g_col = nullptr;   // cone k: g_ptr + v_off[k] + k (n + 1 entries, relative to the cone's own columns), g_col + e_off[k]
-    DevBuf<double> G, sc, f, f0;              // the directions; the chunk's scores [trial][vertex]; obj, obj0
+    TrialScratch trial;                       // (G: the directions, rank x K per cone; K: lorads_hip_stable_trial reads the states of its call)
+    DevBuf<double> sc;                        // the chunk's scores [trial][vertex]
     DevBuf<unsigned char> st;                 // states, cone k at v_off[k] * K, trial t of it n bytes further per trial
-    DevBuf<int> own, size, nround;            // the chunk's lists (the one member next to a vertex); |S| per (cone, trial); rounds per trial
-    int *ctl = nullptr;                       // [0] best before, [1] best after the search
-    int K = 0;                                // trials of the last call (lorads_hip_stable_trial reads its states)
+    DevBuf<int> own, size;                    // the chunk's lists (the one member next to a vertex); |S| per (cone, trial)
     DevPool mem;
     void release() { mem.release(); *this = StableScratch{}; }
 };
@@ -678,18 +682,15 @@ struct StableScratch {
 // scratch of the bisection rounding (bisect.inc): allocated on its first call, never read by the solve.  G 8 K sum(rank), the sign
 // words of the hyperplanes (n K / 8 bytes), one sign byte per (trial, vertex) of every cone, and -- only where a trial's state does
 // not fit the LDS -- per chunk of trials the fields h (8 n) of the cone at hand.
-struct BisectScratch {
-    bool checked = false, qualifies = false;
-    std::string why;                          // the first reason the context does not qualify
+struct BisectScratch : Applies {
     std::vector<int> v_off;                   // [nb + 1] first vertex of every cone in the stacked vertex arrays
     std::vector<double> t;                    // [nb] t_k, the one value of sqrt(b_i / a_i) of the cone's diagonal rows
     std::vector<int> d;                       // [nb] d_k, the size difference the cone's sum row prescribes
-    DevBuf<double> G, f, f0, h;               // the hyperplanes; obj, obj0; the chunk's fields [trial][vertex] (the slab path)
+    TrialScratch trial;                       // (G: the hyperplanes, rank x K per cone; K: lorads_hip_bisect_trial reads the signs of its call)
+    DevBuf<double> h;                         // the chunk's fields [trial][vertex] (the slab path)
     DevBuf<unsigned long long> sgn;           // sign words of the hyperplanes, cone k at v_off[k] * W (rounding.inc's layout)
     DevBuf<signed char> x;                    // signs after the search, cone k at v_off[k] * K, trial t of it n bytes further per trial
-    DevBuf<int> imb, nround;                  // sum of the hyperplane's signs per (cone, trial); rounds per trial
-    int *ctl = nullptr;                       // [0] best before, [1] best after the search
-    int K = 0;                                // trials of the last call (lorads_hip_bisect_trial reads its signs)
+    DevBuf<int> imb;                          // sum of the hyperplane's signs per (cone, trial)
     DevPool mem;
     void release() { mem.release(); *this = BisectScratch{}; }
 };
@@ -847,6 +848,7 @@ struct lorads_hip_ctx {
     bool opt_presolve_check = false; // LORADS_PRESOLVE_CHECK=1: build every device pattern on the host too and compare
     size_t dev_presolve_min = (size_t)1 << 15; // stored entries below which a pattern is built on the host (LORADS_DEV_PRESOLVE_MIN)
     long long n_dev_patterns = 0, n_checked_patterns = 0;
+    int opt_trial_chunk = 0;     // stable-set and bisection rounding: at most this many trials per chunk (LORADS_TRIAL_CHUNK=n, tests only: the chunk loop at sizes a test can afford; 0: the chunk rule alone)
     bool opt_bisect_lds = true;  // bisection rounding: a trial's state in the LDS where it fits (LORADS_BISECT_LDS=0: the device-memory slab at every size, the path of cones too large for the LDS)
     bool opt_dense_cache = true; // dense constraint matrices: A_j V kept for the length of a CG solve (LORADS_DENSE_CACHE=0: nd + 1 GEMMs per application)
     bool opt_front_diag = true; // Max-Cut-type cones: the front forms its diagonal coefficients itself, no k_sval (LORADS_FRONT_DIAG=0)
@@ -1067,6 +1069,7 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->opt_front_diag = env_on("LORADS_FRONT_DIAG");
     c->opt_dense_cache = env_on("LORADS_DENSE_CACHE");
     c->opt_bisect_lds = env_on("LORADS_BISECT_LDS");
+    if (getenv("LORADS_TRIAL_CHUNK")) c->opt_trial_chunk = std::max(0, atoi(getenv("LORADS_TRIAL_CHUNK")));
     c->opt_fuse_eval = env_on("LORADS_FUSE_EVAL");
     c->opt_dense_rem = env_on("LORADS_DENSE_REM");
     c->opt_exact_refresh = env_set("LORADS_EXACT_REFRESH");

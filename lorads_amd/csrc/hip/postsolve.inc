@@ -7,6 +7,8 @@
 //   mfma_chain, packed_dot                the prefetching chain of MFMA steps over a row's columns; on two rows of a packed factor
 //   k_pack_factor / pack_factor           F (and t) zero-padded to whole tiles of rows and whole steps of 4 columns
 //   postsolve_args, postsolve_sharded     the argument checks and the sharded refusal, in the calling feature's words
+// The four roundings share more than this file: the driver of a rounding call -- round_begin, round_reserve, round_vectors, round_signs,
+// round_drive, trial_chunk(s), round_finish, round_stored_trial -- is in rounding.inc, behind the kernels it launches.
 // (DevBuf, the grown scratch buffer of their scratch structs, sits with those structs in lorads_hip.hip: they are members of the
 // context, which is defined long before this file is read.)
 

@@ -11,12 +11,14 @@
 // from U and V as the export forms it, the scratch is the feature's own (RoundScratch), launches go straight to the stream (never
 // through LAUNCH, which would flush a waiting dual update), and every sum is reduced per workgroup and then in a fixed order.
 //
-// Shared with kcut.inc (the rounding into k parts, DESIGN.md section 16): the Gaussian kernel k_rnd_gauss, read_constraint_image,
-// round_reserve and round_drive -- evaluate, best, the search rounds, evaluate, best, read-back -- around a feature's own field kernel.
+// Shared with kcut.inc, stable.inc and bisect.inc (DESIGN.md sections 16, 18, 19): the Gaussian kernel k_rnd_gauss, the sign kernel,
+// read_constraint_image, and the driver of a rounding call below the checks -- round_begin .. round_stored_trial.
 
 namespace {
 
 constexpr int RND_MAXK = 65536;   // trials per call
+constexpr int KCUT_MAXPARTS = 64;      // parts of the rounding into k parts (kcut.inc; round_begin checks both)
+constexpr int KCUT_MAXPROD = 1 << 20;  // its trials x parts
 constexpr int RND_STRIPS = 256;   // row strips of the field pass: per-trial partials per cone (fixed: f's summation order is K's own)
 constexpr int RND_RPW = 8;        // rows per wavefront of the sign pass (one load of G's column serves them all)
 
@@ -297,14 +299,52 @@ int rnd_colour(lorads_hip_ctx *c) {
     return 0;
 }
 
-// the driver's buffers for K trials of `parts` vectors per cone (grown on demand, freed with the feature's pool `mem`)
-int round_reserve(lorads_hip_ctx *c, TrialScratch &T, DevPool &mem, int K, int parts) {
+// ---- the driver of a rounding call, shared by the four roundings (kcut.inc, stable.inc, bisect.inc): round_begin, round_reserve,
+// round_vectors, round_signs, round_drive (the field-pass features) or trial_chunks (the one-trial-per-workgroup features), round_finish,
+// round_stored_trial.  A feature supplies its check, its kernels and its per-cone outputs.
+
+// what a feature calls itself: in its messages, the structure it asks for, and its once-per-context check.  (Plain functions only:
+// hipcc gives the captureless lambdas of several namespace-scope initialisers one name on the host, and all of them call the first.)
+struct RoundFeature {
+    const char *name, *structured;
+    int (*check)(lorads_hip_ctx *);
+    bool terse;   // a bad `trials` is "bad argument" like every other bad argument (round_pm1), not a sentence of its own
+};
+
+// The head of every lorads_hip_round_*: 0 to go on, else the entry point's return code with the message set -- 1 a bad argument or a
+// failed check, 3 a sharded context, 2 a context that lacks the feature's structure.  A: what the feature's check leaves (NULL with
+// a NULL context, which is refused before it is looked at).  `parts`: round_kcut's (its range and the product's are looked at where
+// that entry point always did), NULL for a feature without parts.
+int round_begin(lorads_hip_ctx *c, const RoundFeature &ft, const Applies *A, int32_t src, const int32_t *parts, int32_t trials,
+                int32_t max_rounds, const double *obj) {
+    const std::string who = ft.name;
+    spec_touch(c);
+    if (postsolve_args(c, src, nullptr, ft.name, true)) return 1;
+    if (parts && (*parts < 2 || *parts > KCUT_MAXPARTS)) return fail_msg(who + ": parts " + std::to_string(*parts) + " is outside [2, 64]");
+    if (trials < 0 || trials > RND_MAXK)
+        return fail_msg(ft.terse ? who + ": bad argument" : who + ": trials " + std::to_string(trials) + " is outside [0, 65536]");
+    if (parts && (int64_t)trials * *parts > KCUT_MAXPROD)
+        return fail_msg(who + ": trials x parts = " + std::to_string((int64_t)trials * *parts) + " is above 2^20");
+    if (max_rounds < 0 || (trials > 0 && !obj)) return fail_msg(who + ": bad argument");
+    if (postsolve_sharded(c, ft.name, "cannot be rounded")) return 3;
+    if (ft.check(c)) return 1;
+    if (!A->qualifies) {
+        fail_msg(who + ": the context is not " + ft.structured + ": " + A->why);
+        return 2;
+    }
+    return 0;
+}
+
+// the driver's buffers for K trials of `parts` vectors per cone (grown on demand, freed with the feature's pool `mem`): the field
+// partials for a field-pass feature, the rounds per trial otherwise.  T.K <- K: call it behind the feature's own allocations.
+int round_reserve(lorads_hip_ctx *c, TrialScratch &T, DevPool &mem, int K, int parts, bool field_pass) {
     size_t g = 0;
     for (auto &B : c->blk)
         if (!B.is_lp) g += (size_t)B.rl * K * parts;
-    if (T.G.grow(mem, g) || T.part.grow(mem, (size_t)K * RND_STRIPS)) return 1;
+    if (T.G.grow(mem, g) || (field_pass ? T.part.grow(mem, (size_t)K * RND_STRIPS) : T.nround.grow(mem, (size_t)K))) return 1;
     if (T.f.grow(mem, (size_t)K) || T.f0.grow(mem, (size_t)K)) return 1;
     if (!T.ctl && mem.alloc(&T.ctl, 4)) return 1;
+    T.K = K;
     return 0;
 }
 
@@ -312,6 +352,46 @@ int round_reserve(lorads_hip_ctx *c, TrialScratch &T, DevPool &mem, int K, int p
 void round_gauss(lorads_hip_ctx *c, int k, int K, int parts, uint64_t seed, double *G) {
     const size_t glen = (size_t)c->blk[k].rl * K * parts;
     if (glen) hipLaunchKernelGGL(k_rnd_gauss, dim3(std::min(grid1d(glen), 1024)), dim3(TPB), 0, c->stream, c->blk[k].rl, K, parts, k, seed, G);
+}
+
+// Every cone's vectors, cone after cone in T.G, each followed by `each(k, G)`: what the feature launches on cone k's vectors (0, or 1
+// with the message set).  LP blocks are passed over, and with skip_empty the cones without a row.  `out` (may be NULL) <- all of them.
+template <typename Each>
+int round_vectors(lorads_hip_ctx *c, TrialScratch &T, int K, int parts, uint64_t seed, bool skip_empty, double *out, Each each) {
+    size_t goff = 0;
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        if (B.is_lp || (skip_empty && B.n == 0)) continue;
+        double *G = T.G + goff;
+        round_gauss(c, k, K, parts, seed, G);
+        if (each(k, (const double *)G)) return 1;
+        goff += (size_t)B.rl * K * parts;
+    }
+    if (out && goff) HC(hipMemcpyAsync(out, T.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// cone k's sign words of the hyperplanes G, W words of 64 trials per row, at sgn
+void round_signs(lorads_hip_ctx *c, int32_t src, int k, int K, int W, const double *G, unsigned long long *sgn) {
+    const Block &B = c->blk[k];
+    const FactorView F = factor_view(c, src, k);
+    const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
+    hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, F.U, F.V, F.uv, G, sgn);
+}
+
+// Trials per chunk of a one-trial-per-workgroup feature whose chunk holds `elems` (trial, vertex) pairs of the largest cone (nmax
+// rows): elems / nmax rounded down to a multiple of `multiple`, at least 16, at most K -- and at most LORADS_TRIAL_CHUNK, rounded up
+// to the multiple, where a test sets it.  trial_chunks walks the chunks [t0, t1) of K trials (body: 0, or 1 with the message set).
+inline int trial_chunk(const lorads_hip_ctx *c, int K, int nmax, size_t elems, int multiple) {
+    size_t ch = std::max<size_t>(16, elems / nmax / multiple * multiple);
+    if (c->opt_trial_chunk > 0) ch = std::min(ch, ((size_t)c->opt_trial_chunk + multiple - 1) / multiple * multiple);
+    return (int)std::min<size_t>((size_t)K, ch);
+}
+template <typename Body>
+int trial_chunks(int K, int CH, Body body) {
+    for (int t0 = 0; t0 < K; t0 += CH)
+        if (body(t0, std::min(K, t0 + CH))) return 1;
+    return 0;
 }
 
 // workgroups along x of a field pass over nrows rows (rows == null: all of a cone's, the evaluation: f's summation order is K's own)
@@ -325,11 +405,32 @@ struct RoundOut {
     int32_t *best, *best0, *rounds;
 };
 
-// What the two roundings do with their trials once the signs / labels stand.  `field(k, rows, nrows)` launches the feature's field
-// kernel for cone k over nrows rows (rows == null: all of them, the evaluation; otherwise a colour class of the search), leaving its
-// partials in T.part and its change flag in T.ctl[0].  LP blocks are passed over.  f0 of every trial (every cone's field pass, its
-// strips added per trial in cone order) and its best; the local search, one host synchronisation per round (the flag decides whether
-// another round runs); f and its best again; obj, obj0, best, best0 and rounds to `o`.  *trial <- the best trial after the search.
+// The tail of every rounding: the best of f0 and of f (the lowest index on ties), then obj, obj0, best, best0 and rounds to `o`, behind
+// one synchronisation that also covers the copies the feature enqueued before it.  rounds = host_rounds, what the host counted (the
+// field-pass features), or with host_rounds < 0 the maximum of T.nround (the one-trial-per-workgroup features).  *trial <- the best
+// trial after the search.
+int round_finish(lorads_hip_ctx *c, int K, TrialScratch &T, const double *f, int host_rounds, const RoundOut &o, int *trial) {
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)T.f0, T.ctl + 1);
+    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, f, T.ctl + 2);
+    int bb[2] = {0, 0};
+    std::vector<int> nr(host_rounds < 0 ? (size_t)K : 0);
+    HC(hipMemcpyAsync(bb, T.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
+    HC(hipMemcpyAsync(o.obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (o.obj0) HC(hipMemcpyAsync(o.obj0, T.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (host_rounds < 0) HC(hipMemcpyAsync(nr.data(), T.nround.p, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HC(hipStreamSynchronize(c->stream));
+    if (o.best) *o.best = bb[1];
+    if (o.best0) *o.best0 = bb[0];
+    if (o.rounds) *o.rounds = host_rounds < 0 ? *std::max_element(nr.begin(), nr.end()) : host_rounds;
+    *trial = bb[1];
+    return 0;
+}
+
+// What the two field-pass roundings do with their trials once the signs / labels stand.  `field(k, rows, nrows)` launches the feature's
+// field kernel for cone k over nrows rows (rows == null: all of them, the evaluation; otherwise a colour class of the search), leaving
+// its partials in T.part and its change flag in T.ctl[0].  LP blocks are passed over.  f0 of every trial (every cone's field pass, its
+// strips added per trial in cone order); the local search, one host synchronisation per round (the flag decides whether another round
+// runs); f; then round_finish.
 template <typename Field>
 int round_drive(lorads_hip_ctx *c, int K, int max_rounds, TrialScratch &T, Field field, const RoundOut &o, int *trial) {
     const RoundScratch &Rn = c->rnd;
@@ -344,7 +445,6 @@ int round_drive(lorads_hip_ctx *c, int K, int max_rounds, TrialScratch &T, Field
         }
     };
     eval(T.f0);
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)T.f0, T.ctl + 1);
     int nr = 0;
     for (int round = 0; round < max_rounds; ++round) {
         HC(hipMemsetAsync(T.ctl, 0, sizeof(int), c->stream));
@@ -359,56 +459,44 @@ int round_drive(lorads_hip_ctx *c, int K, int max_rounds, TrialScratch &T, Field
         nr = round + 1;
         if (!flag) break;
     }
-    double *f = T.f0;
-    if (nr > 0) {
-        eval(T.f);
-        f = T.f;
+    if (nr > 0) eval(T.f);
+    return round_finish(c, K, T, nr > 0 ? T.f : T.f0, nr, o, trial);
+}
+
+// The bytes of trial `trial` of the last call of a one-trial-per-workgroup feature, cone after cone, each decoded by `decode`: cone k's
+// trials stand at store + v_off[k] * K, n bytes each (v_off: [nb + 1], a block without vertices has none).
+template <typename Byte, typename Decode>
+int round_stored_trial(lorads_hip_ctx *c, const char *who, const TrialScratch &T, const std::vector<int> &v_off, const Byte *store, int32_t trial,
+                       Byte *out, Decode decode) {
+    if (T.K == 0 || trial < 0 || trial >= T.K) return fail_msg(std::string(who) + ": trial " + std::to_string(trial) + " is outside the last call's");
+    for (int k = 0; k < c->nb; ++k) {
+        const size_t n = (size_t)(v_off[k + 1] - v_off[k]);
+        if (n) HC(hipMemcpyAsync(out + v_off[k], store + (size_t)v_off[k] * T.K + (size_t)trial * n, n, hipMemcpyDeviceToHost, c->stream));
     }
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)f, T.ctl + 2);
-    int bb[2] = {0, 0};
-    HC(hipMemcpyAsync(bb, T.ctl + 1, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(o.obj, f, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    if (o.obj0) HC(hipMemcpyAsync(o.obj0, T.f0, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
     HC(hipStreamSynchronize(c->stream));
-    if (o.best) *o.best = bb[1];
-    if (o.best0) *o.best0 = bb[0];
-    if (o.rounds) *o.rounds = nr;
-    *trial = bb[1];
+    for (int p = 0; p < v_off[c->nb]; ++p) out[p] = decode(out[p]);
     return 0;
 }
+
+const RoundFeature FT_PM1{"round_pm1", "+-1-structured", rnd_check, true};
 
 } // namespace
 
 extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                                     double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds,
                                     double *hyperplanes) {
-    spec_touch(c);
-    if (postsolve_args(c, src, nullptr, "round_pm1", true)) return 1;
-    if (trials < 0 || trials > RND_MAXK || max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_pm1: bad argument");
-    if (postsolve_sharded(c, "round_pm1", "cannot be rounded")) return 3;
-    if (rnd_check(c)) return 1;
+    if (const int rc = round_begin(c, FT_PM1, c ? &c->rnd : nullptr, src, nullptr, trials, max_rounds, obj)) return rc;
     RoundScratch &X = c->rnd;
-    if (!X.qualifies) {
-        fail_msg("round_pm1: the context is not +-1-structured: " + X.why);
-        return 2;
-    }
     if (trials == 0) return 0;
     const int K = trials, W = (K + 63) / 64;
     TrialScratch &T = X.trial;
-    if (round_reserve(c, T, X.mem, K, 1) || X.sgn.grow(X.mem, (size_t)X.t_off[c->nb] * W) || (max_rounds > 0 && rnd_colour(c))) return 1;
+    if (round_reserve(c, T, X.mem, K, 1, true) || X.sgn.grow(X.mem, (size_t)X.t_off[c->nb] * W) || (max_rounds > 0 && rnd_colour(c))) return 1;
     // hyperplanes and sign words
-    size_t goff = 0;
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        double *G = T.G + goff;
-        round_gauss(c, k, K, 1, seed, G);
-        const FactorView F = factor_view(c, src, k);
-        const size_t waves = (size_t)nblocks_for((size_t)B.n, RND_RPW) * W;
-        hipLaunchKernelGGL(k_rnd_sign, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, W, F.U, F.V, F.uv,
-                           (const double *)G, X.sgn + (size_t)X.t_off[k] * W);
-        goff += (size_t)B.rl * K;
-    }
-    if (hyperplanes && goff) HC(hipMemcpyAsync(hyperplanes, T.G, sizeof(double) * goff, hipMemcpyDeviceToHost, c->stream));
+    if (round_vectors(c, T, K, 1, seed, false, hyperplanes, [&](int k, const double *G) {
+            round_signs(c, src, k, K, W, G, X.sgn + (size_t)X.t_off[k] * W);
+            return 0;
+        }))
+        return 1;
     auto field = [&](int k, const int *rows, int nrows) {
         const Block &B = c->blk[k];
         hipLaunchKernelGGL(k_rnd_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K,

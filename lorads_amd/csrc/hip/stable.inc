@@ -11,7 +11,8 @@
 // owns one trial: the greedy set (the lexicographically first maximal stable set in the order priority descending, index ascending,
 // as a parallel fixed point), f, the (1, 2)-swap search with the greedy completion behind every swap, f again.  No workgroup waits
 // for another.  Everything is read-only on the solver's state, as in rounding.inc: F is formed on the fly, the scratch is the
-// feature's own (StableScratch), launches go straight to the stream, every sum has one fixed order.
+// feature's own (StableScratch), launches go straight to the stream, every sum has one fixed order.  The driver around the kernels is
+// rounding.inc's (round_begin, round_reserve, round_vectors, trial_chunks, round_finish, round_stored_trial).
 
 namespace {
 
@@ -315,38 +316,23 @@ inline int stb_cone_index(const lorads_hip_ctx *c, int k) {
     return kc;
 }
 
+const RoundFeature FT_STABLE{"round_stable", "theta-structured", stb_check, false};
+
 } // namespace
 
 // the members of trial `trial` of the context's last lorads_hip_round_stable call (1: in the set), SDP cone after SDP cone
 extern "C" int lorads_hip_stable_trial(lorads_hip_ctx *c, int32_t trial, uint8_t *member) {
     if (!c || !member) return fail_msg("stable_trial: bad argument");
-    StableScratch &X = c->stable;
-    if (X.K == 0 || trial < 0 || trial >= X.K) return fail_msg("stable_trial: trial " + std::to_string(trial) + " is outside the last call's");
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        if (B.is_lp || B.n == 0) continue;
-        HC(hipMemcpyAsync(member + X.v_off[k], X.st + (size_t)X.v_off[k] * X.K + (size_t)trial * B.n, (size_t)B.n, hipMemcpyDeviceToHost,
-                          c->stream));
-    }
-    HC(hipStreamSynchronize(c->stream));
-    for (int p = 0; p < X.v_off[c->nb]; ++p) member[p] = member[p] == STB_IN;
-    return 0;
+    const StableScratch &X = c->stable;
+    return round_stored_trial(c, "stable_trial", X.trial, X.v_off, (const uint8_t *)X.st.p, trial, member,
+                              [](uint8_t s) { return (uint8_t)(s == STB_IN); });
 }
 
 extern "C" int lorads_hip_round_stable(lorads_hip_ctx *c, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                                        double *obj0, int32_t *best, int32_t *best0, uint8_t *member, int32_t *sizes, int32_t *rounds,
                                        double *scores, double *T) {
-    spec_touch(c);
-    if (postsolve_args(c, src, nullptr, "round_stable", true)) return 1;
-    if (trials < 0 || trials > RND_MAXK) return fail_msg("round_stable: trials " + std::to_string(trials) + " is outside [0, 65536]");
-    if (max_rounds < 0 || (trials > 0 && !obj)) return fail_msg("round_stable: bad argument");
-    if (postsolve_sharded(c, "round_stable", "cannot be rounded")) return 3;
-    if (stb_check(c)) return 1;
+    if (const int rc = round_begin(c, FT_STABLE, c ? &c->stable : nullptr, src, nullptr, trials, max_rounds, obj)) return rc;
     StableScratch &X = c->stable;
-    if (!X.qualifies) {
-        fail_msg("round_stable: the context is not theta-structured: " + X.why);
-        return 2;
-    }
     int ncone = 0;
     for (int k = 0; k < c->nb; ++k) ncone += !c->blk[k].is_lp;
     if (T) { // T_k of the SDP cones, then u_j of the LP columns
@@ -358,62 +344,47 @@ extern "C" int lorads_hip_round_stable(lorads_hip_ctx *c, int32_t src, int32_t t
     if (trials == 0) return 0;
     const int K = trials, ntot = X.v_off[c->nb];
     int nmax = 1;
-    size_t g = 0;
     for (auto &B : c->blk)
-        if (!B.is_lp) { g += (size_t)B.rl * K; nmax = std::max(nmax, B.n); }
-    const int CH = (int)std::min<size_t>((size_t)K, std::max<size_t>(16, (STB_CHUNK_ELEMS / nmax) & ~(size_t)15));
-    if (X.G.grow(X.mem, g) || X.sc.grow(X.mem, (size_t)CH * nmax) || X.own.grow(X.mem, (size_t)CH * nmax) || X.f.grow(X.mem, (size_t)K) ||
-        X.f0.grow(X.mem, (size_t)K) || X.st.grow(X.mem, (size_t)ntot * K) || X.size.grow(X.mem, (size_t)ncone * K) ||
-        X.nround.grow(X.mem, (size_t)K))
+        if (!B.is_lp) nmax = std::max(nmax, B.n);
+    const int CH = trial_chunk(c, K, nmax, STB_CHUNK_ELEMS, 16);
+    TrialScratch &R = X.trial;
+    if (X.sc.grow(X.mem, (size_t)CH * nmax) || X.own.grow(X.mem, (size_t)CH * nmax) || X.st.grow(X.mem, (size_t)ntot * K) ||
+        X.size.grow(X.mem, (size_t)ncone * K) || round_reserve(c, R, X.mem, K, 1, false))
         return 1;
-    if (!X.ctl && X.mem.alloc(&X.ctl, 4)) return 1;
-    X.K = K;
-    size_t goff = 0;
     bool first = true;
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        if (B.is_lp || B.n == 0) continue;
-        const int kc = stb_cone_index(c, k);
-        double *G = X.G + goff;
-        round_gauss(c, k, K, 1, seed, G);
-        goff += (size_t)B.rl * K;
-        const FactorView F = factor_view(c, src, k);
-        const int *gp = X.g_ptr + X.v_off[k] + kc, *gc = X.g_col + X.e_off[k];
-        for (int t0 = 0; t0 < K; t0 += CH) {
-            const int t1 = std::min(K, t0 + CH);
-            const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * nblocks_for((size_t)(t1 - t0), 16);
-            hipLaunchKernelGGL(k_stb_proj, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, t0, t1, F.U, F.V,
-                               F.uv, (const double *)G, X.sc.p);
-            if (t0 == 0)
-                hipLaunchKernelGGL(k_stb_norm, dim3(nblocks_for((size_t)B.n, TPB)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, F.U, F.V, F.uv,
-                                   X.sc.p);
-            hipLaunchKernelGGL(k_stb_search, dim3(t1 - t0), dim3(TPB), 0, c->stream, B.n, K, t0, kc, (int)first, (int)max_rounds, gp, gc,
-                               (const double *)X.sc.p, X.st + (size_t)X.v_off[k] * K, X.own.p, (const int *)B.pu.adj_ptr,
-                               (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.cbase,
-                               (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad, X.T[k], X.f.p, X.f0.p, X.size.p, X.nround.p);
-            HC(hipGetLastError());
-            if (scores) { // (the copy is in stream order: the next chunk's kernels write behind it)
-                HC(hipMemcpyAsync(scores + (size_t)X.v_off[k] * K + (size_t)t0 * B.n, X.sc.p, sizeof(double) * (size_t)(t1 - t0) * B.n,
-                                  hipMemcpyDeviceToHost, c->stream));
-                HC(hipStreamSynchronize(c->stream));
-            }
-        }
-        first = false;
-    }
+    if (round_vectors(c, R, K, 1, seed, true, nullptr, [&](int k, const double *G) {
+            const Block &B = c->blk[k];
+            const int kc = stb_cone_index(c, k);
+            const FactorView F = factor_view(c, src, k);
+            const int *gp = X.g_ptr + X.v_off[k] + kc, *gc = X.g_col + X.e_off[k];
+            if (trial_chunks(K, CH, [&](int t0, int t1) {
+                    const size_t waves = (size_t)nblocks_for((size_t)B.n, 16) * nblocks_for((size_t)(t1 - t0), 16);
+                    hipLaunchKernelGGL(k_stb_proj, dim3(nblocks_for(waves, TPB / 64)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, K, t0, t1, F.U,
+                                       F.V, F.uv, G, X.sc.p);
+                    if (t0 == 0)
+                        hipLaunchKernelGGL(k_stb_norm, dim3(nblocks_for((size_t)B.n, TPB)), dim3(TPB), 0, c->stream, B.n, B.rl, B.r, F.U, F.V,
+                                           F.uv, X.sc.p);
+                    hipLaunchKernelGGL(k_stb_search, dim3(t1 - t0), dim3(TPB), 0, c->stream, B.n, K, t0, kc, (int)first, (int)max_rounds, gp, gc,
+                                       (const double *)X.sc.p, X.st + (size_t)X.v_off[k] * K, X.own.p, (const int *)B.pu.adj_ptr,
+                                       (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.cbase,
+                                       (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad, X.T[k], R.f.p, R.f0.p, X.size.p, R.nround.p);
+                    HC(hipGetLastError());
+                    if (scores) { // (the copy is in stream order: the next chunk's kernels write behind it)
+                        HC(hipMemcpyAsync(scores + (size_t)X.v_off[k] * K + (size_t)t0 * B.n, X.sc.p, sizeof(double) * (size_t)(t1 - t0) * B.n,
+                                          hipMemcpyDeviceToHost, c->stream));
+                        HC(hipStreamSynchronize(c->stream));
+                    }
+                    return 0;
+                }))
+                return 1;
+            first = false;
+            return 0;
+        }))
+        return 1;
     if (first) return fail_msg("round_stable: no cone has a vertex");
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f0.p, X.ctl);
-    hipLaunchKernelGGL(k_rnd_best, dim3(1), dim3(TPB), 0, c->stream, K, (const double *)X.f.p, X.ctl + 1);
-    int bb[2] = {0, 0};
-    std::vector<int> nr((size_t)K);
-    HC(hipMemcpyAsync(bb, X.ctl, sizeof(int) * 2, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(obj, X.f.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    if (obj0) HC(hipMemcpyAsync(obj0, X.f0.p, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
     if (sizes) HC(hipMemcpyAsync(sizes, X.size.p, sizeof(int) * (size_t)ncone * K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipMemcpyAsync(nr.data(), X.nround.p, sizeof(int) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-    HC(hipStreamSynchronize(c->stream));
-    if (best) *best = bb[1];
-    if (best0) *best0 = bb[0];
-    if (rounds) *rounds = *std::max_element(nr.begin(), nr.end());
-    if (member) return lorads_hip_stable_trial(c, bb[1], member);
+    int bt = 0;
+    if (round_finish(c, K, R, R.f.p, -1, RoundOut{obj, obj0, best, best0, rounds}, &bt)) return 1;
+    if (member) return lorads_hip_stable_trial(c, bt, member);
     return 0;
 }

@@ -358,16 +358,21 @@ typedef struct {
     double lam_min;    /* lambda_min(S_k) (NaN without a bound) */
     double *G;         /* rank x trials (row-major), only when asked for (else NULL) */
 } lrd_rounding_cone;
+/* what the results of the four roundings (lrd_rounding, lrd_kcut, lrd_stable, lrd_bisection) begin with */
 typedef struct {
-    int nblk, trials, max_rounds, rounds;
-    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where R came from */
+    int trials, max_rounds, rounds;
+    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where the factor came from */
     uint64_t seed;
     double scale;       /* scaleObjHis the backend's values were divided by */
     int best, best0;    /* argmin of obj / obj0, lowest index on ties */
     double f_best, f_best0;
-    double *obj, *obj0; /* [trials] f after / before the local search */
+    double *obj, *obj0; /* [trials] f after / before the search */
     double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
     double tol;         /* Lanczos tolerance of lambda_min */
+} lrd_round_head;
+typedef struct {
+    lrd_round_head head;
+    int nblk;
     lrd_rounding_cone *cone; /* [nblk], file order */
 } lrd_rounding;
 /* trials = 0: applicability alone (*out stays NULL).  Returns 2 when the context does not qualify or the table lacks the slot, 3 when
@@ -527,18 +532,11 @@ typedef struct {
     double *G;         /* parts x rank x trials (part, then column, then trial), only when asked for (else NULL) */
 } lrd_kcut_cone;
 typedef struct {
+    lrd_round_head head;
     int nblk;           /* SDP cones */
-    int parts, trials, max_rounds, rounds;
-    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where R came from */
-    uint64_t seed;
-    double scale;       /* scaleObjHis the backend's values were divided by */
-    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
-    double f_best, f_best0;
-    double *obj, *obj0; /* [trials] f after / before the local search */
+    int parts;
     int nlp, lp_neg;    /* LP columns; how many of them have a dual slack s_j < 0 (0 without a bound) */
     double *lp_upper;   /* [nlp] u_j */
-    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
-    double tol;         /* Lanczos tolerance of lambda_min */
     lrd_kcut_cone *cone; /* [nblk], file order */
 } lrd_kcut;
 /* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
@@ -563,18 +561,10 @@ typedef struct {
     double *scores;    /* trials x n priorities (trial, then vertex) in the backend's terms, only when asked for (else NULL) */
 } lrd_stable_cone;
 typedef struct {
+    lrd_round_head head; /* (obj0: f of the greedy sets) */
     int nblk;           /* SDP cones */
-    int trials, max_rounds, rounds;
-    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where F came from */
-    uint64_t seed;
-    double scale;       /* scaleObjHis the backend's values were divided by */
-    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
-    double f_best, f_best0;
-    double *obj, *obj0; /* [trials] f after the search / of the greedy sets */
     int nlp, lp_neg;    /* LP columns; how many of them have a dual slack s_j < 0 (0 without a bound) */
     double *lp_upper;   /* [nlp] u_j */
-    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
-    double tol;         /* Lanczos tolerance of lambda_min */
     lrd_stable_cone *cone; /* [nblk], file order */
 } lrd_stable;
 /* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
@@ -599,16 +589,8 @@ typedef struct {
     double *G;         /* rank x trials hyperplanes, only when asked for (else NULL) */
 } lrd_bisection_cone;
 typedef struct {
+    lrd_round_head head; /* (obj0: f after the repair) */
     int nblk;           /* cones */
-    int trials, max_rounds, rounds;
-    int src;            /* LRD_PAIR_UV or LRD_PAIR_RR: where F came from */
-    uint64_t seed;
-    double scale;       /* scaleObjHis the backend's values were divided by */
-    int best, best0;    /* argmin of obj / obj0, lowest index on ties */
-    double f_best, f_best0;
-    double *obj, *obj0; /* [trials] f after the search / after the repair */
-    double by, bound, gap; /* b.y, d, (f_best - d) / max(1, |d|); NaN when tol <= 0 */
-    double tol;         /* Lanczos tolerance of lambda_min */
     lrd_bisection_cone *cone; /* [nblk], file order */
 } lrd_bisection;
 /* trials = 0: applicability alone (*out stays NULL).  Returns 1 on a bad argument, 2 when the context does not qualify or the table
@@ -635,6 +617,20 @@ void lrd_write_problem_as_read(FILE *f, const lrd_problem *pr);
 typedef struct { double by, bound, gap; int lp_neg; } lrd_dual_bound;
 int lrd_rounded_dual_bound(lrd_backend *be, int src, double tol, double sc, int nblk, int ncone, const int *blk, const double *T, int lpk,
                            int nlp, const double *lp_upper, double f_best, lrd_dual_bound *out, double *lam_min);
+/* What the four roundings' drivers and writers do with their lrd_round_head (rounding.c).  lrd_zalloc: calloc of at least one element.
+ * lrd_round_begin: lrd_session_postsolve in a rounding's words (have_slot: the table has the feature's slot; cannot: what it cannot do
+ * without).  _init: the call's arguments and zeroed obj, obj0; _scale: both divided by scale, f_best and f_best0 picked; _bound:
+ * lrd_rounded_dual_bound at the head's src, tol, scale and f_best into by, bound, gap, *lp_neg (may be NULL) and lam_min; _free: obj and
+ * obj0.  _write: opens path and writes "<magic>\n", the integer lines -- `first` (lines of the feature's own, may be NULL), trials
+ * .. best0, `last` -- and the seven %.17g lines scale .. tol; the open file, or NULL where it cannot be opened. */
+void *lrd_zalloc(size_t n, size_t size);
+int lrd_round_begin(lrd_session *s, int have_slot, const char *cannot, lrd_solver **v, lrd_backend **be, int *src);
+void lrd_round_head_init(lrd_round_head *h, int trials, uint64_t seed, int max_rounds, int src, double scale, double tol);
+void lrd_round_head_scale(lrd_round_head *h);
+int lrd_round_head_bound(lrd_round_head *h, lrd_backend *be, int nblk, int ncone, const int *blk, const double *T, int lpk, int nlp,
+                         const double *lp_upper, int *lp_neg, double *lam_min);
+void lrd_round_head_free(lrd_round_head *h);
+FILE *lrd_round_head_write(const char *path, const char *magic, const lrd_round_head *h, const char *first, const char *last);
 
 /* scalar helpers of the line search (lorads_alm.c:102-228) */
 int lrd_cubic_roots(double a, double b, double c, double d, double res[3]);

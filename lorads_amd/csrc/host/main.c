@@ -31,9 +31,16 @@ int main(int argc, char **argv) {
     lrd_session *s = lrd_session_open(argv[1]);
     if (!s) return 1;
     const char *solution_file = NULL; /* ours, not the reference's: taken before the parameter block sees the options */
-    const char *round_file = NULL;    /* hyperplane rounding of a +-1-structured problem (ours as well) */
-    int round_trials = 0, round_ls = 100;
-    unsigned long long round_seed = 0;
+    /* The four roundings (ours as well): hyperplane rounding of a +-1-structured problem, rounding of a k-cut-structured problem into
+     * k parts, stable sets of a theta-structured problem, balanced partitions of a bisection-structured problem.  Each has the options
+     * --<prefix>Trials, Seed, LocalSearch and File; `gate` is the option the family's others need (--round* has none), `other` the last
+     * of those others given.  strict = 0 is --round* as it always parsed: trials from 0, an empty value reads as 0, and a refusal
+     * leaves the session open. */
+    enum { RND, KCUT, STB, BIS };
+    struct { const char *prefix, *gate; int strict, trials, ls; unsigned long long seed; const char *file, *other; } ro[4] = {
+        {"round", NULL, 0, 0, 100, 0, NULL, NULL}, {"kcut", "--kcutParts", 1, 1024, 100, 0, NULL, NULL},
+        {"stable", "--stableTrials", 1, 0, 100, 0, NULL, NULL}, {"bisect", "--bisectTrials", 1, 0, 1000, 0, NULL, NULL}};
+    int kcut_parts = 0;
     int compress = 0, compress_cap = 0; /* rank reduction of the solution (ours as well): after the solve, before the file and the rounding */
     double compress_tol = 1e-12;
     const char *entries_in = NULL, *entries_out = NULL; /* entries of the primal at the positions of a query file (ours as well) */
@@ -45,15 +52,6 @@ int main(int argc, char **argv) {
     int bounds_max = -1;              /* separation of entry bounds lower <= X_pq <= upper (ours as well) */
     double bounds_lower = 0.0, bounds_upper = HUGE_VAL, bounds_minv = 1e-3;
     const char *bounds_file = NULL, *bounds_other = NULL; /* bounds_other: some --bounds* option other than --boundsMax was given */
-    int kcut_parts = 0, kcut_trials = 1024, kcut_ls = 100; /* rounding of a k-cut-structured problem into k parts (ours as well) */
-    unsigned long long kcut_seed = 0;
-    const char *kcut_file = NULL, *kcut_other = NULL; /* kcut_other: some --kcut* option other than --kcutParts was given */
-    int stable_trials = 0, stable_ls = 100; /* stable sets of a theta-structured problem read off the factors (ours as well) */
-    unsigned long long stable_seed = 0;
-    const char *stable_file = NULL, *stable_other = NULL; /* stable_other: some --stable* option other than --stableTrials was given */
-    int bisect_trials = 0, bisect_ls = 1000; /* balanced partitions of a bisection-structured problem read off the factors (ours as well) */
-    unsigned long long bisect_seed = 0;
-    const char *bisect_file = NULL, *bisect_other = NULL; /* bisect_other: some --bisect* option other than --bisectTrials was given */
     const char *topk_in = NULL, *topk_out = NULL, *topk_other = NULL; /* the k best entries per row of the primal (ours as well);
                                                                        * topk_other: some --topk* option other than --topkFile was given */
     int topk_k = 0, topk_smallest = 0, topk_diag = 0, topk_constrained = 0;
@@ -75,7 +73,6 @@ int main(int argc, char **argv) {
             solution_file = argv[i + 1];
             continue;
         }
-        if (!strcmp(argv[i], "--roundFile")) { round_file = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--entriesFile")) { entries_in = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--entriesOut")) { entries_out = argv[i + 1]; continue; }
         if (!strcmp(argv[i], "--cutsFile")) { cuts_file = argv[i + 1]; continue; }
@@ -132,75 +129,33 @@ int main(int argc, char **argv) {
             }
             continue;
         }
-        if (!strcmp(argv[i], "--roundTrials") || !strcmp(argv[i], "--roundSeed") || !strcmp(argv[i], "--roundLocalSearch")) {
-            char *end = NULL;
-            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
-            if (!end || *end || argv[i + 1][0] == '-' || (argv[i][7] != 'S' && v > 65536)) {
-                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
-                return 2;
-            }
-            if (argv[i][7] == 'T') round_trials = (int)v;
-            else if (argv[i][7] == 'S') round_seed = v;
-            else round_ls = (int)v;
-            continue;
+        int fam = -1;
+        const char *opt = "";
+        for (int f = 0; f < 4 && fam < 0 && !strncmp(argv[i], "--", 2); ++f) {
+            const size_t len = strlen(ro[f].prefix);
+            if (strncmp(argv[i] + 2, ro[f].prefix, len)) continue;
+            opt = argv[i] + 2 + len;
+            if (!strcmp(opt, "Trials") || !strcmp(opt, "Seed") || !strcmp(opt, "LocalSearch") || !strcmp(opt, "File") ||
+                (f == KCUT && !strcmp(opt, "Parts")))
+                fam = f;
         }
-        if (!strcmp(argv[i], "--kcutFile")) { kcut_other = argv[i]; kcut_file = argv[i + 1]; continue; }
-        if (!strcmp(argv[i], "--kcutParts") || !strcmp(argv[i], "--kcutTrials") || !strcmp(argv[i], "--kcutSeed") ||
-            !strcmp(argv[i], "--kcutLocalSearch")) {
+        if (fam >= 0) {
+            const char w = opt[0]; /* T, S, L, F or P */
+            if (ro[fam].gate && strcmp(argv[i], ro[fam].gate)) ro[fam].other = argv[i];
+            if (w == 'F') { ro[fam].file = argv[i + 1]; continue; }
             char *end = NULL;
-            const char w = argv[i][6]; /* P, T, S or L */
             const unsigned long long v = strtoull(argv[i + 1], &end, 10);
-            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'P' && (v < 2 || v > 64)) ||
-                (w == 'T' && (v < 1 || v > 65536)) || (w == 'L' && v > 65536)) {
+            int bad = !end || *end || argv[i + 1][0] == '-' || (w != 'S' && w != 'P' && v > 65536);
+            if (ro[fam].strict) bad = bad || end == argv[i + 1] || (w == 'T' && v < 1) || (w == 'P' && (v < 2 || v > 64));
+            if (bad) {
                 fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
-                lrd_session_close(s);
+                if (ro[fam].strict) lrd_session_close(s);
                 return 2;
             }
             if (w == 'P') kcut_parts = (int)v;
-            else {
-                kcut_other = argv[i];
-                if (w == 'T') kcut_trials = (int)v;
-                else if (w == 'S') kcut_seed = v;
-                else kcut_ls = (int)v;
-            }
-            continue;
-        }
-        if (!strcmp(argv[i], "--stableFile")) { stable_other = argv[i]; stable_file = argv[i + 1]; continue; }
-        if (!strcmp(argv[i], "--stableTrials") || !strcmp(argv[i], "--stableSeed") || !strcmp(argv[i], "--stableLocalSearch")) {
-            char *end = NULL;
-            const char w = argv[i][8]; /* T, S or L */
-            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
-            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'T' && (v < 1 || v > 65536)) ||
-                (w == 'L' && v > 65536)) {
-                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
-                lrd_session_close(s);
-                return 2;
-            }
-            if (w == 'T') stable_trials = (int)v;
-            else {
-                stable_other = argv[i];
-                if (w == 'S') stable_seed = v;
-                else stable_ls = (int)v;
-            }
-            continue;
-        }
-        if (!strcmp(argv[i], "--bisectFile")) { bisect_other = argv[i]; bisect_file = argv[i + 1]; continue; }
-        if (!strcmp(argv[i], "--bisectTrials") || !strcmp(argv[i], "--bisectSeed") || !strcmp(argv[i], "--bisectLocalSearch")) {
-            char *end = NULL;
-            const char w = argv[i][8]; /* T, S or L */
-            const unsigned long long v = strtoull(argv[i + 1], &end, 10);
-            if (!end || end == argv[i + 1] || *end || argv[i + 1][0] == '-' || (w == 'T' && (v < 1 || v > 65536)) ||
-                (w == 'L' && v > 65536)) {
-                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
-                lrd_session_close(s);
-                return 2;
-            }
-            if (w == 'T') bisect_trials = (int)v;
-            else {
-                bisect_other = argv[i];
-                if (w == 'S') bisect_seed = v;
-                else bisect_ls = (int)v;
-            }
+            else if (w == 'T') ro[fam].trials = (int)v;
+            else if (w == 'S') ro[fam].seed = v;
+            else ro[fam].ls = (int)v;
             continue;
         }
         if (!strcmp(argv[i], "--compressTol") || !strcmp(argv[i], "--compressRank")) {
@@ -243,25 +198,17 @@ int main(int argc, char **argv) {
         lrd_session_close(s);
         return 2;
     }
-    if (kcut_other && kcut_parts == 0) {
-        fprintf(stderr, "%s needs --kcutParts\n", kcut_other);
-        lrd_session_close(s);
-        return 2;
-    }
-    if (kcut_parts > 0 && (long)kcut_parts * kcut_trials > (1L << 20)) {
-        fprintf(stderr, "bad value of --kcutParts and --kcutTrials: %d x %d is above 2^20\n", kcut_parts, kcut_trials);
-        lrd_session_close(s);
-        return 2;
-    }
-    if (stable_other && stable_trials == 0) {
-        fprintf(stderr, "%s needs --stableTrials\n", stable_other);
-        lrd_session_close(s);
-        return 2;
-    }
-    if (bisect_other && bisect_trials == 0) {
-        fprintf(stderr, "%s needs --bisectTrials\n", bisect_other);
-        lrd_session_close(s);
-        return 2;
+    for (int f = KCUT; f <= BIS; ++f) {
+        if (ro[f].other && (f == KCUT ? kcut_parts : ro[f].trials) == 0) {
+            fprintf(stderr, "%s needs %s\n", ro[f].other, ro[f].gate);
+            lrd_session_close(s);
+            return 2;
+        }
+        if (f == KCUT && kcut_parts > 0 && (long)kcut_parts * ro[KCUT].trials > (1L << 20)) {
+            fprintf(stderr, "bad value of --kcutParts and --kcutTrials: %d x %d is above 2^20\n", kcut_parts, ro[KCUT].trials);
+            lrd_session_close(s);
+            return 2;
+        }
     }
     if (topk_other && !topk_in) {
         fprintf(stderr, "%s needs --topkFile\n", topk_other);
@@ -332,12 +279,12 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (lrd_session_attach(s, &be)) return 1;
-    if (round_trials > 0 || cuts_max > 0) { /* applicability before any solving */
+    if (ro[RND].trials > 0 || cuts_max > 0) { /* applicability before any solving */
         lrd_rounding *none = NULL;
-        const int rrc = lrd_session_round(s, 0, round_seed, round_ls, 0.0, &none);
+        const int rrc = lrd_session_round(s, 0, ro[RND].seed, ro[RND].ls, 0.0, &none);
         if (rrc) {
             fprintf(stderr, "lorads: %s needs a +-1-structured problem (see above); nothing was solved\n",
-                    round_trials > 0 ? "--roundTrials" : "--cutsMax");
+                    ro[RND].trials > 0 ? "--roundTrials" : "--cutsMax");
             lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
@@ -345,25 +292,25 @@ int main(int argc, char **argv) {
     }
     if (kcut_parts > 0) { /* applicability before any solving */
         lrd_kcut *none = NULL;
-        if (lrd_session_kcut(s, kcut_parts, 0, kcut_seed, kcut_ls, 0.0, 0, &none)) {
+        if (lrd_session_kcut(s, kcut_parts, 0, ro[KCUT].seed, ro[KCUT].ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --kcutParts needs a k-cut-structured problem (see above); nothing was solved\n");
             lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
         }
     }
-    if (stable_trials > 0) { /* applicability before any solving */
+    if (ro[STB].trials > 0) { /* applicability before any solving */
         lrd_stable *none = NULL;
-        if (lrd_session_round_stable(s, 0, stable_seed, stable_ls, 0.0, 0, &none)) {
+        if (lrd_session_round_stable(s, 0, ro[STB].seed, ro[STB].ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --stableTrials needs a theta-structured problem (see above); nothing was solved\n");
             lrd_topk_free(topk);
             lrd_session_close(s);
             return 2;
         }
     }
-    if (bisect_trials > 0) { /* applicability before any solving */
+    if (ro[BIS].trials > 0) { /* applicability before any solving */
         lrd_bisection *none = NULL;
-        if (lrd_session_round_bisect(s, 0, bisect_seed, bisect_ls, 0.0, 0, &none)) {
+        if (lrd_session_round_bisect(s, 0, ro[BIS].seed, ro[BIS].ls, 0.0, 0, &none)) {
             fprintf(stderr, "lorads: --bisectTrials needs a bisection-structured problem (see above); nothing was solved\n");
             lrd_topk_free(topk);
             lrd_session_close(s);
@@ -495,61 +442,61 @@ int main(int argc, char **argv) {
         printf("\t err6 <X, S> rel.                : %.6e\n", x->err6);
         lrd_solution_free(x);
     }
-    if (round_trials > 0) {
+    if (ro[RND].trials > 0) {
         lrd_rounding *x = NULL;
-        if (lrd_session_round(s, round_trials, (uint64_t)round_seed, round_ls, 1e-8, &x) ||
-            (round_file && lrd_rounding_write(round_file, x))) {
-            fprintf(stderr, "lorads: the rounding failed%s%s\n", round_file ? " or cannot write " : "", round_file ? round_file : "");
+        if (lrd_session_round(s, ro[RND].trials, (uint64_t)ro[RND].seed, ro[RND].ls, 1e-8, &x) ||
+            (ro[RND].file && lrd_rounding_write(ro[RND].file, x))) {
+            fprintf(stderr, "lorads: the rounding failed%s%s\n", ro[RND].file ? " or cannot write " : "", ro[RND].file ? ro[RND].file : "");
             lrd_rounding_free(x);
             lrd_session_close(s);
             return 4;
         }
-        printf("Hyperplane rounding (%d trials, seed %llu, %d local-search rounds%s%s):\n", x->trials, round_seed, x->rounds,
-               round_file ? ", " : "", round_file ? round_file : "");
-        printf("\t best trial                      : %d (before the local search: %d)\n", x->best, x->best0);
-        printf("\t f = x^T C x before local search : %.10e\n\t f = x^T C x after local search  : %.10e\n", x->f_best0, x->f_best);
-        printf("\t dual bound d                    : %.10e\n\t gap (f - d) / max(1, |d|)       : %.6e\n", x->bound, x->gap);
+        printf("Hyperplane rounding (%d trials, seed %llu, %d local-search rounds%s%s):\n", x->head.trials, ro[RND].seed, x->head.rounds,
+               ro[RND].file ? ", " : "", ro[RND].file ? ro[RND].file : "");
+        printf("\t best trial                      : %d (before the local search: %d)\n", x->head.best, x->head.best0);
+        printf("\t f = x^T C x before local search : %.10e\n\t f = x^T C x after local search  : %.10e\n", x->head.f_best0, x->head.f_best);
+        printf("\t dual bound d                    : %.10e\n\t gap (f - d) / max(1, |d|)       : %.6e\n", x->head.bound, x->head.gap);
         lrd_rounding_free(x);
     }
     if (kcut_parts > 0) {
         lrd_kcut *x = NULL;
-        if (lrd_session_kcut(s, kcut_parts, kcut_trials, (uint64_t)kcut_seed, kcut_ls, 1e-8, 0, &x) ||
-            (kcut_file && lrd_kcut_write(kcut_file, x))) {
-            fprintf(stderr, "lorads: the rounding into parts failed%s%s\n", kcut_file ? " or cannot write " : "", kcut_file ? kcut_file : "");
+        if (lrd_session_kcut(s, kcut_parts, ro[KCUT].trials, (uint64_t)ro[KCUT].seed, ro[KCUT].ls, 1e-8, 0, &x) ||
+            (ro[KCUT].file && lrd_kcut_write(ro[KCUT].file, x))) {
+            fprintf(stderr, "lorads: the rounding into parts failed%s%s\n", ro[KCUT].file ? " or cannot write " : "", ro[KCUT].file ? ro[KCUT].file : "");
             lrd_kcut_free(x);
             lrd_session_close(s);
             return 4;
         }
         printf("Rounding into %d parts (%d trials, seed %llu%s%s): best f %.10e, dual bound d %.10e, gap %.6e, %d local-search rounds\n",
-               x->parts, x->trials, kcut_seed, kcut_file ? ", " : "", kcut_file ? kcut_file : "", x->f_best, x->bound, x->gap, x->rounds);
+               x->parts, x->head.trials, ro[KCUT].seed, ro[KCUT].file ? ", " : "", ro[KCUT].file ? ro[KCUT].file : "", x->head.f_best, x->head.bound, x->head.gap, x->head.rounds);
         lrd_kcut_free(x);
     }
-    if (stable_trials > 0) {
+    if (ro[STB].trials > 0) {
         lrd_stable *x = NULL;
-        if (lrd_session_round_stable(s, stable_trials, (uint64_t)stable_seed, stable_ls, 1e-8, 0, &x) ||
-            (stable_file && lrd_stable_write(stable_file, x))) {
-            fprintf(stderr, "lorads: the stable-set rounding failed%s%s\n", stable_file ? " or cannot write " : "", stable_file ? stable_file : "");
+        if (lrd_session_round_stable(s, ro[STB].trials, (uint64_t)ro[STB].seed, ro[STB].ls, 1e-8, 0, &x) ||
+            (ro[STB].file && lrd_stable_write(ro[STB].file, x))) {
+            fprintf(stderr, "lorads: the stable-set rounding failed%s%s\n", ro[STB].file ? " or cannot write " : "", ro[STB].file ? ro[STB].file : "");
             lrd_stable_free(x);
             lrd_session_close(s);
             return 4;
         }
-        printf("Stable sets (%d trials, seed %llu%s%s): size", x->trials, stable_seed, stable_file ? ", " : "", stable_file ? stable_file : "");
+        printf("Stable sets (%d trials, seed %llu%s%s): size", x->head.trials, ro[STB].seed, ro[STB].file ? ", " : "", ro[STB].file ? ro[STB].file : "");
         for (int k = 0; k < x->nblk; ++k) printf(" %d", x->cone[k].size);
-        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->f_best, x->bound, x->gap, x->rounds);
+        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->head.f_best, x->head.bound, x->head.gap, x->head.rounds);
         lrd_stable_free(x);
     }
-    if (bisect_trials > 0) {
+    if (ro[BIS].trials > 0) {
         lrd_bisection *x = NULL;
-        if (lrd_session_round_bisect(s, bisect_trials, (uint64_t)bisect_seed, bisect_ls, 1e-8, 0, &x) ||
-            (bisect_file && lrd_bisection_write(bisect_file, x))) {
-            fprintf(stderr, "lorads: the bisection rounding failed%s%s\n", bisect_file ? " or cannot write " : "", bisect_file ? bisect_file : "");
+        if (lrd_session_round_bisect(s, ro[BIS].trials, (uint64_t)ro[BIS].seed, ro[BIS].ls, 1e-8, 0, &x) ||
+            (ro[BIS].file && lrd_bisection_write(ro[BIS].file, x))) {
+            fprintf(stderr, "lorads: the bisection rounding failed%s%s\n", ro[BIS].file ? " or cannot write " : "", ro[BIS].file ? ro[BIS].file : "");
             lrd_bisection_free(x);
             lrd_session_close(s);
             return 4;
         }
-        printf("Bisection (%d trials, seed %llu%s%s): parts", x->trials, bisect_seed, bisect_file ? ", " : "", bisect_file ? bisect_file : "");
+        printf("Bisection (%d trials, seed %llu%s%s): parts", x->head.trials, ro[BIS].seed, ro[BIS].file ? ", " : "", ro[BIS].file ? ro[BIS].file : "");
         for (int k = 0; k < x->nblk; ++k) printf(" %d+%d", x->cone[k].plus, x->cone[k].minus);
-        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->f_best, x->bound, x->gap, x->rounds);
+        printf(", best f %.10e, dual bound d %.10e, gap %.6e, %d search rounds\n", x->head.f_best, x->head.bound, x->head.gap, x->head.rounds);
         lrd_bisection_free(x);
     }
     lrd_session_close(s);

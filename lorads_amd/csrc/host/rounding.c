@@ -1,5 +1,6 @@
-/* rounding.c -- hyperplane rounding of a +-1-structured session (lorads_host.h: lrd_session_round_ex), the dual
- * bound it shares with the rounding into k parts (lrd_rounded_dual_bound; kcut.c), and the plain-text rounding file
+/* rounding.c -- what the four roundings (this file, kcut.c, stable.c, bisect.c) do with the head of their results (lrd_round_head:
+ * lrd_round_begin, lrd_round_head_*) and their dual bound (lrd_rounded_dual_bound); hyperplane rounding of a +-1-structured session
+ * (lorads_host.h: lrd_session_round_ex) and the plain-text rounding file
  * (lrd_rounding_write), a pure function of the struct so that the command line and the Python session write the same bytes and the
  * format can be checked without a GPU.
  *
@@ -24,9 +25,42 @@ void lrd_rounding_free(lrd_rounding *r) {
         free(q->sigma); free(q->t); free(q->x); free(q->G);
     }
     free(r->cone);
-    free(r->obj);
-    free(r->obj0);
+    lrd_round_head_free(&r->head);
     free(r);
+}
+
+void *lrd_zalloc(size_t n, size_t size) { return calloc(n ? n : 1, size); }
+
+int lrd_round_begin(lrd_session *s, int have_slot, const char *cannot, lrd_solver **v, lrd_backend **be, int *src) {
+    return lrd_session_postsolve(s, have_slot, cannot, "rounding the solution of a sharded deal (world > 1) is", v, be, src);
+}
+
+void lrd_round_head_init(lrd_round_head *h, int trials, uint64_t seed, int max_rounds, int src, double scale, double tol) {
+    h->trials = trials; h->max_rounds = max_rounds; h->src = src; h->seed = seed; h->scale = scale; h->tol = tol;
+    h->obj = (double *)lrd_zalloc((size_t)trials, sizeof(double));
+    h->obj0 = (double *)lrd_zalloc((size_t)trials, sizeof(double));
+}
+
+void lrd_round_head_scale(lrd_round_head *h) {
+    for (int t = 0; t < h->trials; ++t) { h->obj[t] /= h->scale; h->obj0[t] /= h->scale; }
+    h->f_best = h->obj[h->best];
+    h->f_best0 = h->obj0[h->best0];
+}
+
+void lrd_round_head_free(lrd_round_head *h) {
+    free(h->obj);
+    free(h->obj0);
+}
+
+FILE *lrd_round_head_write(const char *path, const char *magic, const lrd_round_head *h, const char *first, const char *last) {
+    FILE *f = fopen(path, "w");
+    if (!f) return NULL;
+    fprintf(f, "%s\n%s", magic, first ? first : "");
+    fprintf(f, "trials %d\nseed %" PRIu64 "\nmax_rounds %d\nrounds %d\nsrc %d\nbest %d\nbest0 %d\n%s", h->trials, h->seed,
+            h->max_rounds, h->rounds, h->src, h->best, h->best0, last ? last : "");
+    fprintf(f, "scale %.17g\nf_best %.17g\nf_best0 %.17g\nby %.17g\nbound %.17g\ngap %.17g\ntol %.17g\n", h->scale, h->f_best,
+            h->f_best0, h->by, h->bound, h->gap, h->tol);
+    return f;
 }
 
 int lrd_rounded_dual_bound(lrd_backend *be, int src, double tol, double sc, int nblk, int ncone, const int *blk, const double *T, int lpk,
@@ -65,6 +99,15 @@ int lrd_rounded_dual_bound(lrd_backend *be, int src, double tol, double sc, int 
     return rc;
 }
 
+int lrd_round_head_bound(lrd_round_head *h, lrd_backend *be, int nblk, int ncone, const int *blk, const double *T, int lpk, int nlp,
+                         const double *lp_upper, int *lp_neg, double *lam_min) {
+    lrd_dual_bound db;
+    const int rc = lrd_rounded_dual_bound(be, h->src, h->tol, h->scale, nblk, ncone, blk, T, lpk, nlp, lp_upper, h->f_best, &db, lam_min);
+    h->by = db.by; h->bound = db.bound; h->gap = db.gap;
+    if (lp_neg) *lp_neg = db.lp_neg;
+    return rc;
+}
+
 /* hyperplane rounding of a +-1-structured context, in the file's units (lorads_host.h: lrd_rounding) */
 int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_rounds, double tol, int with_hyperplanes,
                          lrd_rounding **out) {
@@ -72,8 +115,7 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
     lrd_backend *be = lrd_session_backend(s);
     lrd_solver *v = NULL;
     int src;
-    const int refused = lrd_session_postsolve(s, be && be->round_pm1 != NULL, "round a solution",
-                                              "rounding the solution of a sharded deal (world > 1) is", &v, NULL, &src);
+    const int refused = lrd_round_begin(s, be && be->round_pm1 != NULL, "round a solution", &v, NULL, &src);
     if (refused) return refused;
     const lrd_problem *p = lrd_session_problem(s);
     if (trials <= 0) return trials < 0 ? 1 : be->round_pm1(be->ctx, src, 0, seed, 0, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
@@ -84,21 +126,19 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
         gtot += (size_t)v->rank[k] * (size_t)trials;
     }
     lrd_rounding *r = (lrd_rounding *)calloc(1, sizeof *r);
-    r->nblk = p->nblk; r->trials = trials; r->max_rounds = max_rounds; r->src = src; r->seed = seed; r->scale = sc; r->tol = tol;
-    r->obj = (double *)calloc((size_t)trials, sizeof(double));
-    r->obj0 = (double *)calloc((size_t)trials, sizeof(double));
+    lrd_round_head *h = &r->head;
+    lrd_round_head_init(h, trials, seed, max_rounds, src, sc, tol);
+    r->nblk = p->nblk;
     r->cone = (lrd_rounding_cone *)calloc((size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(lrd_rounding_cone));
     int8_t *sign = (int8_t *)calloc(ntot ? ntot : 1, 1);
     double *g = with_hyperplanes ? (double *)calloc(gtot ? gtot : 1, sizeof(double)) : NULL;
-    int rc = be->round_pm1(be->ctx, src, trials, seed, max_rounds, r->obj, r->obj0, &r->best, &r->best0, sign, &r->rounds, g);
+    int rc = be->round_pm1(be->ctx, src, trials, seed, max_rounds, h->obj, h->obj0, &h->best, &h->best0, sign, &h->rounds, g);
     if (rc) {
         free(sign); free(g);
         lrd_rounding_free(r);
         return rc;
     }
-    for (int t = 0; t < trials; ++t) { r->obj[t] /= sc; r->obj0[t] /= sc; }
-    r->f_best = r->obj[r->best];
-    r->f_best0 = r->obj0[r->best0];
+    lrd_round_head_scale(h);
     size_t at = 0, gat = 0;
     for (int k = 0; k < p->nblk; ++k) { /* t from the problem: the one constraint on every diagonal (the backend has checked it) */
         const lrd_block *b = &p->blk[k];
@@ -129,9 +169,7 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
     free(sign); free(g);
     double *T = (double *)calloc(2 * (size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(double)), *lm = T + (p->nblk > 0 ? p->nblk : 1);
     for (int k = 0; k < p->nblk; ++k) T[k] = r->cone[k].T;
-    lrd_dual_bound db;
-    rc = lrd_rounded_dual_bound(be, src, tol, sc, p->nblk, p->nblk, NULL, T, -1, 0, NULL, r->f_best, &db, lm);
-    r->by = db.by; r->bound = db.bound; r->gap = db.gap;
+    rc = lrd_round_head_bound(h, be, p->nblk, p->nblk, NULL, T, -1, 0, NULL, NULL, lm);
     for (int k = 0; k < p->nblk; ++k) r->cone[k].lam_min = lm[k];
     free(T);
     if (rc) { lrd_rounding_free(r); return 1; }
@@ -145,13 +183,8 @@ int lrd_session_round(lrd_session *s, int trials, uint64_t seed, int max_rounds,
 
 int lrd_rounding_write(const char *path, const lrd_rounding *r) {
     if (!path || !r) return 1;
-    FILE *f = fopen(path, "w");
+    FILE *f = lrd_round_head_write(path, "lorads-rounding 1", &r->head, NULL, NULL);
     if (!f) return 2;
-    fprintf(f, "lorads-rounding 1\n");
-    fprintf(f, "trials %d\nseed %" PRIu64 "\nmax_rounds %d\nrounds %d\nsrc %d\nbest %d\nbest0 %d\n", r->trials, r->seed,
-            r->max_rounds, r->rounds, r->src, r->best, r->best0);
-    fprintf(f, "scale %.17g\nf_best %.17g\nf_best0 %.17g\nby %.17g\nbound %.17g\ngap %.17g\ntol %.17g\n", r->scale, r->f_best,
-            r->f_best0, r->by, r->bound, r->gap, r->tol);
     for (int k = 0; k < r->nblk; ++k) {
         const lrd_rounding_cone *q = &r->cone[k];
         fprintf(f, "cone %d %d\n", k + 1, q->n);

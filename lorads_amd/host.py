@@ -10,6 +10,7 @@ The product attaches ONLY the HIP table (`Session.attach_hip`), which raises if 
 missing -- there is no CPU fallback here.
 """
 import ctypes as C
+import importlib
 import os
 
 import numpy as np
@@ -368,6 +369,26 @@ class Backend:
         k = kept.value
         return 0, cnt.value, p[:k], q[:k], cls[:k], v[:k], passes.value
 
+    def _round_slot(self, fn, src, lead, trials, seed, max_rounds, outs, rest):
+        """a round_* slot of the table as it is: fn(ctx, src, *lead, trials, seed, max_rounds, obj, obj0, &best, &best0, *outs, &rounds,
+        *rest).  Returns (code, what every rounding returns: obj, obj0, best, best0, rounds)."""
+        K = max(int(trials), 0)
+        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
+        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
+        rc = fn(self._s.ctx, int(src), *lead, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds), obj.ctypes.data_as(_dp),
+                obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0), *outs, C.byref(rounds), *rest)
+        return rc, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, rounds=rounds.value)
+
+    def _stored_trial(self, name, trial, ntot, dtype):
+        """one trial of the last round_stable / round_bisect call on this table's HIP context: lorads_hip_<name>, one byte per vertex"""
+        lib, ctx = self._session._hip()
+        out = np.zeros(max(ntot, 1), dtype=dtype)
+        ptr = C.POINTER(np.ctypeslib.as_ctypes_type(dtype))
+        fn = getattr(lib, "lorads_hip_" + name)
+        fn.argtypes = [C.c_void_p, C.c_int, ptr]
+        _check(fn(ctx, int(trial), out.ctypes.data_as(ptr)), name)
+        return out[:ntot]
+
     def has_round_kcut(self):
         return bool(self._s.round_kcut)
 
@@ -382,19 +403,14 @@ class Backend:
         nlp = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if lp[k])
         K = max(int(trials), 0)
         ok = 2 <= parts <= 64 and K * parts <= (1 << 20)
-        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
         label, t, lpu = np.zeros(max(ntot, 1), dtype=np.uint8), np.zeros(max(ntot, 1)), np.zeros(max(nlp, 1))
         glen = sum(ses.block_shape(k)[1] for k in sdp) * K * parts if want_vectors and ok else 0
         vec = np.zeros(max(glen, 1))
-        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
-        rc = self._s.round_kcut(self._s.ctx, int(src), int(parts), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
-                                obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
-                                label.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(rounds), vec.ctypes.data_as(_dp) if glen else None,
-                                t.ctypes.data_as(_dp), lpu.ctypes.data_as(_dp))
+        rc, d = self._round_slot(self._s.round_kcut, src, [int(parts)], trials, seed, max_rounds, [label.ctypes.data_as(C.POINTER(C.c_uint8))],
+                                 [vec.ctypes.data_as(_dp) if glen else None, t.ctypes.data_as(_dp), lpu.ctypes.data_as(_dp)])
         if rc:
             return rc, None
-        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, label=label[:ntot], rounds=rounds.value,
-                       t=t[:ntot], lp_upper=lpu[:nlp], vectors=vec[:glen] if glen else None)
+        return 0, dict(d, label=label[:ntot], t=t[:ntot], lp_upper=lpu[:nlp], vectors=vec[:glen] if glen else None)
 
     def has_round_stable(self):
         return bool(self._s.round_stable)
@@ -411,16 +427,13 @@ class Backend:
         nlp = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if lp[k])
         K = max(int(trials), 0)
         ok = K <= 65536
-        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
         member, Tu = np.zeros(max(ntot, 1), dtype=np.uint8), np.zeros(max(ncone + nlp, 1))
         sizes = np.zeros(max(ncone * K, 1) if ok else 1, dtype=np.int32)
         slen = ntot * K if want_scores and ok else 0
         sc = np.zeros(max(slen, 1))
-        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
-        rc = self._s.round_stable(self._s.ctx, int(src), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
-                                  obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
-                                  member.ctypes.data_as(C.POINTER(C.c_uint8)), sizes.ctypes.data_as(_ip), C.byref(rounds),
-                                  sc.ctypes.data_as(_dp) if slen else None, Tu.ctypes.data_as(_dp))
+        rc, d = self._round_slot(self._s.round_stable, src, [], trials, seed, max_rounds,
+                                 [member.ctypes.data_as(C.POINTER(C.c_uint8)), sizes.ctypes.data_as(_ip)],
+                                 [sc.ctypes.data_as(_dp) if slen else None, Tu.ctypes.data_as(_dp)])
         if rc:
             return rc, None
         scores, at = None, 0
@@ -429,20 +442,14 @@ class Backend:
             for n in ns:
                 scores.append(sc[at * K:(at + n) * K].reshape(K, n).T.copy())
                 at += n
-        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, member=member[:ntot],
-                       sizes=sizes[:ncone * K].reshape(ncone, K), rounds=rounds.value, T=Tu[:ncone], lp_upper=Tu[ncone:ncone + nlp],
+        return 0, dict(d, member=member[:ntot], sizes=sizes[:ncone * K].reshape(ncone, K), T=Tu[:ncone], lp_upper=Tu[ncone:ncone + nlp],
                        scores=scores)
 
     def stable_trial(self, trial):
         """the sets of one trial of the last round_stable call on this table's HIP context (0/1 per vertex, SDP cone after SDP cone)"""
         ses = self._session
-        lib, ctx = ses._hip()
         lp = ses._lp_blocks()
-        ntot = sum(ses.block_shape(k)[0] for k in range(ses.nblk) if not lp[k])
-        member = np.zeros(max(ntot, 1), dtype=np.uint8)
-        lib.lorads_hip_stable_trial.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]
-        _check(lib.lorads_hip_stable_trial(ctx, int(trial), member.ctypes.data_as(C.POINTER(C.c_uint8))), "stable_trial")
-        return member[:ntot]
+        return self._stored_trial("stable_trial", trial, sum(ses.block_shape(k)[0] for k in range(ses.nblk) if not lp[k]), np.uint8)
 
     def has_round_bisect(self):
         return bool(self._s.round_bisect)
@@ -458,16 +465,13 @@ class Backend:
         ntot, ncone = sum(ns), len(ns)
         K = max(int(trials), 0)
         ok = K <= 65536
-        obj, obj0 = np.zeros(max(K, 1)), np.zeros(max(K, 1))
         sign, t, diff = np.zeros(max(ntot, 1), dtype=np.int8), np.zeros(max(ncone, 1)), np.zeros(max(ncone, 1), dtype=np.int32)
         imb = np.zeros(max(ncone * K, 1) if ok else 1, dtype=np.int32)
         glen = sum(rk) * K if want_hyperplanes and ok else 0
         g = np.zeros(max(glen, 1))
-        best, best0, rounds = C.c_int(0), C.c_int(0), C.c_int(0)
-        rc = self._s.round_bisect(self._s.ctx, int(src), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_rounds),
-                                  obj.ctypes.data_as(_dp), obj0.ctypes.data_as(_dp), C.byref(best), C.byref(best0),
-                                  sign.ctypes.data_as(C.POINTER(C.c_int8)), imb.ctypes.data_as(_ip), C.byref(rounds),
-                                  g.ctypes.data_as(_dp) if glen else None, t.ctypes.data_as(_dp), diff.ctypes.data_as(_ip))
+        rc, d = self._round_slot(self._s.round_bisect, src, [], trials, seed, max_rounds,
+                                 [sign.ctypes.data_as(C.POINTER(C.c_int8)), imb.ctypes.data_as(_ip)],
+                                 [g.ctypes.data_as(_dp) if glen else None, t.ctypes.data_as(_dp), diff.ctypes.data_as(_ip)])
         if rc:
             return rc, None
         planes, at = None, 0
@@ -476,19 +480,12 @@ class Backend:
             for r in rk:
                 planes.append(g[at:at + r * K].reshape(r, K).copy())
                 at += r * K
-        return 0, dict(obj=obj[:K], obj0=obj0[:K], best=best.value, best0=best0.value, sign=sign[:ntot],
-                       imbalance=imb[:ncone * K].reshape(ncone, K), rounds=rounds.value, t=t[:ncone], diff=diff[:ncone],
-                       hyperplanes=planes)
+        return 0, dict(d, sign=sign[:ntot], imbalance=imb[:ncone * K].reshape(ncone, K), t=t[:ncone], diff=diff[:ncone], hyperplanes=planes)
 
     def bisect_trial(self, trial):
         """the signs of one trial of the last round_bisect call on this table's HIP context (cone after cone)"""
         ses = self._session
-        lib, ctx = ses._hip()
-        ntot = sum(ses.block_shape(k)[0] for k in range(ses.nblk))
-        sign = np.zeros(max(ntot, 1), dtype=np.int8)
-        lib.lorads_hip_bisect_trial.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int8)]
-        _check(lib.lorads_hip_bisect_trial(ctx, int(trial), sign.ctypes.data_as(C.POINTER(C.c_int8))), "bisect_trial")
-        return sign[:ntot]
+        return self._stored_trial("bisect_trial", trial, sum(ses.block_shape(k)[0] for k in range(ses.nblk)), np.int8)
 
     def set_mat(self, which, blk, a):
         """a: (n, r) array, any layout; sent column-major like the reference's matElem."""
@@ -562,6 +559,31 @@ def host_lib():
 
 RESULT_KEYS = ["pObj", "dObj", "constrVio1", "pdGap", "alm_outer", "alm_inner", "alm_rho", "admm_iter", "cg_iter",
                "admm_rho", "t_alm", "t_admm", "status", "admm_iters_first", "cg_iters_first", "constrVioInf"]
+
+
+# The four roundings of a Session (Session._rounded): the module of the result, its ctypes struct and result class, the host library's
+# driver, free and writer, the name in ValueError and backend-error texts, whether the arguments are range-checked here, and what a
+# refusal (code 2) says before " or the <name> backend cannot round".
+_ROUNDINGS = {
+    "pm1": dict(module="rounding", struct="RoundingStruct", result="Rounding", run="lrd_session_round_ex", free="lrd_rounding_free",
+                write="lrd_rounding_write", name="round", checked=False,
+                refusal="the problem cannot be rounded: it is not +-1-structured (no LP block; every constraint "
+                        "a_i X[p,p] = b_i with b_i / a_i > 0, one per diagonal)"),
+    "kcut": dict(module="kcut", struct="KCutStruct", result="KCut", run="lrd_session_kcut", free="lrd_kcut_free", write="lrd_kcut_write",
+                 name="round_kcut", checked=True,
+                 refusal="the problem cannot be rounded into parts: it is not k-cut-structured (every diagonal fixed by one "
+                         "constraint a_i X[p,p] = b_i with b_i / a_i > 0; LP columns only in bound rows 2 a X[p,q] + c x_j = b)"),
+    "stable": dict(module="stable", struct="StableStruct", result="StableSet", run="lrd_session_round_stable", free="lrd_stable_free",
+                   write="lrd_stable_write", name="round_stable", checked=True,
+                   refusal="no stable set can be read off the solution: the problem is not theta-structured (per cone one trace row "
+                           "a tr(X) = b with a, b > 0, every other constraint an edge row X[p,q] = 0; LP columns only in bound rows "
+                           "2 a X[p,q] + c x_j = b)"),
+    "bisection": dict(module="bisection", struct="BisectionStruct", result="Bisection", run="lrd_session_round_bisect",
+                      free="lrd_bisection_free", write="lrd_bisection_write", name="round_bisection", checked=True,
+                      refusal="no balanced partition can be read off the solution: the problem is not bisection-structured (no LP block; "
+                              "per cone one constraint a X[p,p] = b on every diagonal with one value of b / a > 0, and one sum row "
+                              "a <11^T, X> = b with b / (a t^2) = d^2, d = n (mod 2))"),
+}
 
 
 class Session:
@@ -1071,69 +1093,55 @@ class Session:
         if rc == 3:
             raise NotImplementedError(what_rc3)
 
-    def _round_ptr(self, trials, seed, local_search_rounds, tol, hyperplanes):
-        from .rounding import RoundingStruct
-        ptr = C.POINTER(RoundingStruct)()
-        self.lib.lrd_session_round_ex.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
-                                                  C.POINTER(C.POINTER(RoundingStruct))]
-        self.lib.lrd_rounding_free.argtypes = [C.POINTER(RoundingStruct)]
-        rc = self.lib.lrd_session_round_ex(self.h, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds), float(tol),
-                                           1 if hyperplanes else 0, C.byref(ptr))
-        self._refused(rc, "the problem cannot be rounded: it is not +-1-structured (no LP block; every constraint "
-                      "a_i X[p,p] = b_i with b_i / a_i > 0, one per diagonal) or the %s backend cannot round%s",
+    def _rounded(self, key, path, trials, seed, local_search_rounds, tol, extra=False, parts=None):
+        """One call of the rounding `key` of _ROUNDINGS: its result object (path None; None for trials = 0, which checks
+        applicability alone) or, through the C writer, its file at `path`.  extra: also the hyperplanes / vectors / scores."""
+        R = _ROUNDINGS[key]
+        mod = importlib.import_module("." + R["module"], __package__)
+        st = getattr(mod, R["struct"])
+        who = R["name"]
+        if R["checked"]:
+            trials, local_search_rounds = int(trials), int(local_search_rounds)
+            if parts is not None:
+                parts = int(parts)
+                if not 2 <= parts <= 64:
+                    raise ValueError("%s: parts %d is outside [2, 64]" % (who, parts))
+            if not 0 <= trials <= 65536:
+                raise ValueError("%s: trials %d is outside [0, 65536]" % (who, trials))
+            if parts is not None and trials * parts > 1 << 20:
+                raise ValueError("%s: trials x parts = %d is above 2^20" % (who, trials * parts))
+            if local_search_rounds < 0:
+                raise ValueError("%s: local_search_rounds %d is negative" % (who, local_search_rounds))
+        run, free, write = (getattr(self.lib, R[f]) for f in ("run", "free", "write"))
+        lead = [] if parts is None else [int(parts)]
+        run.argtypes = [C.c_void_p] + [C.c_int] * len(lead) + [C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int, C.POINTER(C.POINTER(st))]
+        free.argtypes, free.restype = [C.POINTER(st)], None
+        ptr = C.POINTER(st)()
+        rc = run(self.h, *lead, int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds), float(tol),
+                 1 if extra and trials != 0 else 0, C.byref(ptr))
+        self._refused(rc, R["refusal"] + " or the %s backend cannot round%s",
                       "rounding the solution of a sharded deal (world > 1) is not supported")
-        _check(rc, "round")
-        return ptr
+        _check(rc, who)
+        if path is None and trials == 0:
+            return None
+        try:
+            if path is None:
+                return getattr(mod, R["result"]).from_struct(ptr.contents)
+            write.argtypes = [C.c_char_p, C.POINTER(st)]
+            _check(write(os.fsencode(path), ptr), R["write"][4:])
+        finally:
+            free(ptr)
 
     def round_pm1(self, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, hyperplanes=False):
         """Goemans-Williamson hyperplane rounding of the current point with a 1-flip local search, on the device
         (lorads_amd.rounding.Rounding, file units): per trial f = x^T C x before and after the search, the best trial's signs and
         x = sigma o t per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) at Lanczos tolerance tol (tol <= 0:
         NaN).  trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
-        from .rounding import Rounding
-        if trials == 0:
-            self._round_ptr(0, seed, local_search_rounds, tol, False)
-            return None
-        ptr = self._round_ptr(trials, seed, local_search_rounds, tol, hyperplanes)
-        try:
-            return Rounding.from_struct(ptr.contents)
-        finally:
-            self.lib.lrd_rounding_free(ptr)
+        return self._rounded("pm1", None, trials, seed, local_search_rounds, tol, hyperplanes)
 
     def write_rounding(self, path, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
         """the rounding file of the command line's --roundFile (the same C writer: the same bytes)"""
-        from .rounding import RoundingStruct
-        ptr = self._round_ptr(trials, seed, local_search_rounds, tol, False)
-        try:
-            self.lib.lrd_rounding_write.argtypes = [C.c_char_p, C.POINTER(RoundingStruct)]
-            _check(self.lib.lrd_rounding_write(os.fsencode(path), ptr), "rounding_write")
-        finally:
-            self.lib.lrd_rounding_free(ptr)
-
-    def _kcut_ptr(self, parts, trials, seed, local_search_rounds, tol, vectors):
-        from .kcut import KCutStruct
-        parts, trials, local_search_rounds = int(parts), int(trials), int(local_search_rounds)
-        if not 2 <= parts <= 64:
-            raise ValueError("round_kcut: parts %d is outside [2, 64]" % parts)
-        if not 0 <= trials <= 65536:
-            raise ValueError("round_kcut: trials %d is outside [0, 65536]" % trials)
-        if trials * parts > 1 << 20:
-            raise ValueError("round_kcut: trials x parts = %d is above 2^20" % (trials * parts))
-        if local_search_rounds < 0:
-            raise ValueError("round_kcut: local_search_rounds %d is negative" % local_search_rounds)
-        ptr = C.POINTER(KCutStruct)()
-        self.lib.lrd_session_kcut.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
-                                              C.POINTER(C.POINTER(KCutStruct))]
-        self.lib.lrd_kcut_free.argtypes = [C.POINTER(KCutStruct)]
-        self.lib.lrd_kcut_free.restype = None
-        rc = self.lib.lrd_session_kcut(self.h, int(parts), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(local_search_rounds),
-                                       float(tol), 1 if vectors else 0, C.byref(ptr))
-        self._refused(rc, "the problem cannot be rounded into parts: it is not k-cut-structured (every diagonal fixed by one "
-                      "constraint a_i X[p,p] = b_i with b_i / a_i > 0; LP columns only in bound rows 2 a X[p,q] + c x_j = b) "
-                      "or the %s backend cannot round%s",
-                      "rounding the solution of a sharded deal (world > 1) is not supported")
-        _check(rc, "round_kcut")
-        return ptr
+        self._rounded("pm1", path, trials, seed, local_search_rounds, tol)
 
     def round_kcut(self, parts, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, vectors=False):
         """Frieze-Jerrum rounding of the current point into `parts` parts with a 1-move local search, on the device
@@ -1141,46 +1149,11 @@ class Session:
         part sizes per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) at Lanczos
         tolerance tol (tol <= 0: NaN).  Works on +-1-structured problems and on what write_bounded makes of them.  trials = 0
         checks applicability alone (None).  Read-only on the solver's state."""
-        from .kcut import KCut
-        if trials == 0:
-            self._kcut_ptr(parts, 0, seed, local_search_rounds, tol, False)
-            return None
-        ptr = self._kcut_ptr(parts, trials, seed, local_search_rounds, tol, vectors)
-        try:
-            return KCut.from_struct(ptr.contents)
-        finally:
-            self.lib.lrd_kcut_free(ptr)
+        return self._rounded("kcut", None, trials, seed, local_search_rounds, tol, vectors, parts)
 
     def write_kcut(self, path, parts, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
         """the k-cut file of the command line's --kcutFile (the same C writer: the same bytes)"""
-        from .kcut import KCutStruct
-        ptr = self._kcut_ptr(parts, trials, seed, local_search_rounds, tol, False)
-        try:
-            self.lib.lrd_kcut_write.argtypes = [C.c_char_p, C.POINTER(KCutStruct)]
-            _check(self.lib.lrd_kcut_write(os.fsencode(path), ptr), "kcut_write")
-        finally:
-            self.lib.lrd_kcut_free(ptr)
-
-    def _stable_ptr(self, trials, seed, local_search_rounds, tol, scores):
-        from .stable import StableStruct
-        trials, local_search_rounds = int(trials), int(local_search_rounds)
-        if not 0 <= trials <= 65536:
-            raise ValueError("round_stable: trials %d is outside [0, 65536]" % trials)
-        if local_search_rounds < 0:
-            raise ValueError("round_stable: local_search_rounds %d is negative" % local_search_rounds)
-        ptr = C.POINTER(StableStruct)()
-        self.lib.lrd_session_round_stable.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
-                                                      C.POINTER(C.POINTER(StableStruct))]
-        self.lib.lrd_stable_free.argtypes = [C.POINTER(StableStruct)]
-        self.lib.lrd_stable_free.restype = None
-        rc = self.lib.lrd_session_round_stable(self.h, trials, int(seed) & 0xFFFFFFFFFFFFFFFF, local_search_rounds, float(tol),
-                                               1 if scores else 0, C.byref(ptr))
-        self._refused(rc, "no stable set can be read off the solution: the problem is not theta-structured (per cone one trace row "
-                      "a tr(X) = b with a, b > 0, every other constraint an edge row X[p,q] = 0; LP columns only in bound rows "
-                      "2 a X[p,q] + c x_j = b) or the %s backend cannot round%s",
-                      "rounding the solution of a sharded deal (world > 1) is not supported")
-        _check(rc, "round_stable")
-        return ptr
+        self._rounded("kcut", path, trials, seed, local_search_rounds, tol, parts=parts)
 
     def round_stable(self, trials=1024, seed=0, local_search_rounds=100, tol=1e-8, scores=False):
         """Stable sets of a theta-structured problem's graphs read off the current point, on the device (lorads_amd.stable.StableSet,
@@ -1189,46 +1162,11 @@ class Session:
         and sizes per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) + sum_j u_j min(0, s_j) at Lanczos
         tolerance tol (tol <= 0: NaN): for the theta files |S| <= alpha <= floor(-d).  trials = 0 checks applicability alone
         (None).  Read-only on the solver's state."""
-        from .stable import StableSet
-        if trials == 0:
-            self._stable_ptr(0, seed, local_search_rounds, tol, False)
-            return None
-        ptr = self._stable_ptr(trials, seed, local_search_rounds, tol, scores)
-        try:
-            return StableSet.from_struct(ptr.contents)
-        finally:
-            self.lib.lrd_stable_free(ptr)
+        return self._rounded("stable", None, trials, seed, local_search_rounds, tol, scores)
 
     def write_stable(self, path, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
         """the stable-set file of the command line's --stableFile (the same C writer: the same bytes)"""
-        from .stable import StableStruct
-        ptr = self._stable_ptr(trials, seed, local_search_rounds, tol, False)
-        try:
-            self.lib.lrd_stable_write.argtypes = [C.c_char_p, C.POINTER(StableStruct)]
-            _check(self.lib.lrd_stable_write(os.fsencode(path), ptr), "stable_write")
-        finally:
-            self.lib.lrd_stable_free(ptr)
-
-    def _bisection_ptr(self, trials, seed, local_search_rounds, tol, hyperplanes):
-        from .bisection import BisectionStruct
-        trials, local_search_rounds = int(trials), int(local_search_rounds)
-        if not 0 <= trials <= 65536:
-            raise ValueError("round_bisection: trials %d is outside [0, 65536]" % trials)
-        if local_search_rounds < 0:
-            raise ValueError("round_bisection: local_search_rounds %d is negative" % local_search_rounds)
-        ptr = C.POINTER(BisectionStruct)()
-        self.lib.lrd_session_round_bisect.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_double, C.c_int,
-                                                      C.POINTER(C.POINTER(BisectionStruct))]
-        self.lib.lrd_bisection_free.argtypes = [C.POINTER(BisectionStruct)]
-        self.lib.lrd_bisection_free.restype = None
-        rc = self.lib.lrd_session_round_bisect(self.h, trials, int(seed) & 0xFFFFFFFFFFFFFFFF, local_search_rounds, float(tol),
-                                               1 if hyperplanes else 0, C.byref(ptr))
-        self._refused(rc, "no balanced partition can be read off the solution: the problem is not bisection-structured (no LP block; "
-                      "per cone one constraint a X[p,p] = b on every diagonal with one value of b / a > 0, and one sum row "
-                      "a <11^T, X> = b with b / (a t^2) = d^2, d = n (mod 2)) or the %s backend cannot round%s",
-                      "rounding the solution of a sharded deal (world > 1) is not supported")
-        _check(rc, "round_bisection")
-        return ptr
+        self._rounded("stable", path, trials, seed, local_search_rounds, tol)
 
     def round_bisection(self, trials=1024, seed=0, local_search_rounds=1000, tol=1e-8, hyperplanes=False):
         """Balanced partitions of a bisection-structured problem read off the current point, on the device
@@ -1236,25 +1174,11 @@ class Session:
         sum(sigma) = +-d, and a swap search that keeps the balance; f = sum x^T C x after the repair and after the search, the
         best trial's signs and part sizes per cone, and the dual bound d = b.y + sum_k n_k t_k^2 min(0, lambda_min(S_k)) at Lanczos
         tolerance tol (tol <= 0: NaN).  trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
-        from .bisection import Bisection
-        if trials == 0:
-            self._bisection_ptr(0, seed, local_search_rounds, tol, False)
-            return None
-        ptr = self._bisection_ptr(trials, seed, local_search_rounds, tol, hyperplanes)
-        try:
-            return Bisection.from_struct(ptr.contents)
-        finally:
-            self.lib.lrd_bisection_free(ptr)
+        return self._rounded("bisection", None, trials, seed, local_search_rounds, tol, hyperplanes)
 
     def write_bisection(self, path, trials=1024, seed=0, local_search_rounds=1000, tol=1e-8):
         """the bisection file of the command line's --bisectFile (the same C writer: the same bytes)"""
-        from .bisection import BisectionStruct
-        ptr = self._bisection_ptr(trials, seed, local_search_rounds, tol, False)
-        try:
-            self.lib.lrd_bisection_write.argtypes = [C.c_char_p, C.POINTER(BisectionStruct)]
-            _check(self.lib.lrd_bisection_write(os.fsencode(path), ptr), "bisection_write")
-        finally:
-            self.lib.lrd_bisection_free(ptr)
+        self._rounded("bisection", path, trials, seed, local_search_rounds, tol)
 
     def triangle_cuts(self, max_cuts=1000, min_violation=1e-3):
         """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device

@@ -11,9 +11,10 @@ import ctypes as C
 
 import numpy as np
 
-INT_KEYS = ("parts", "trials", "seed", "max_rounds", "rounds", "src", "best", "best0", "lp_columns", "lp_negative")
-FLOAT_KEYS = ("scale", "f_best", "f_best0", "by", "bound", "gap", "tol")
-_STRUCT_NAME = {"lp_columns": "nlp", "lp_negative": "lp_neg"}
+from . import _rounded
+from ._rounded import FLOAT_KEYS, RoundHeadStruct, _arr, fill_head, head_of, read_head
+
+INT_KEYS = ("parts",) + _rounded.INT_KEYS + ("lp_columns", "lp_negative")
 
 
 class KCutConeStruct(C.Structure):
@@ -24,16 +25,8 @@ class KCutConeStruct(C.Structure):
 
 class KCutStruct(C.Structure):
     """lrd_kcut (csrc/host/lorads_host.h)"""
-    _fields_ = [("nblk", C.c_int), ("parts", C.c_int), ("trials", C.c_int), ("max_rounds", C.c_int), ("rounds", C.c_int),
-                ("src", C.c_int), ("seed", C.c_uint64), ("scale", C.c_double), ("best", C.c_int), ("best0", C.c_int),
-                ("f_best", C.c_double), ("f_best0", C.c_double), ("obj", C.POINTER(C.c_double)), ("obj0", C.POINTER(C.c_double)),
-                ("nlp", C.c_int), ("lp_neg", C.c_int), ("lp_upper", C.POINTER(C.c_double)),
-                ("by", C.c_double), ("bound", C.c_double), ("gap", C.c_double), ("tol", C.c_double),
-                ("cone", C.POINTER(KCutConeStruct))]
-
-
-def _arr(ptr, n, dtype=np.float64):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n > 0 and ptr else np.zeros(0, dtype=dtype)
+    _fields_ = [("head", RoundHeadStruct), ("nblk", C.c_int), ("parts", C.c_int), ("nlp", C.c_int), ("lp_neg", C.c_int),
+                ("lp_upper", C.POINTER(C.c_double)), ("cone", C.POINTER(KCutConeStruct))]
 
 
 class KCutCone:
@@ -61,20 +54,19 @@ class KCut:
 
     @classmethod
     def from_struct(cls, st):
-        cones = []
+        cones, K = [], st.head.trials
         for k in range(st.nblk):
             q = st.cone[k]
-            G = _arr(q.G, st.parts * q.rank * st.trials).reshape(st.parts, q.rank, st.trials) if q.G else None
+            G = _arr(q.G, st.parts * q.rank * K).reshape(st.parts, q.rank, K) if q.G else None
             cones.append(KCutCone(q.blk, q.n, q.rank, _arr(q.label, q.n, np.uint8), _arr(q.size, st.parts, np.int64), _arr(q.t, q.n),
                                   q.T, q.lam_min, G))
-        sc = {k: getattr(st, _STRUCT_NAME.get(k, k)) for k in INT_KEYS + FLOAT_KEYS}
-        return cls(cones, _arr(st.obj, st.trials), _arr(st.obj0, st.trials), _arr(st.lp_upper, st.nlp), **sc)
+        obj, obj0, sc = head_of(st, INT_KEYS + FLOAT_KEYS)
+        return cls(cones, obj, obj0, _arr(st.lp_upper, st.nlp), **sc)
 
     def to_struct(self):
         """an lrd_kcut that holds what the file holds (for lrd_kcut_write); keeps its arrays alive on the struct"""
         st = KCutStruct()
-        for k in INT_KEYS + FLOAT_KEYS:
-            setattr(st, _STRUCT_NAME.get(k, k), getattr(self, k))
+        fill_head(st, self, INT_KEYS + FLOAT_KEYS)
         st.nblk = len(self.cones)
         arr = (KCutConeStruct * max(1, st.nblk))()
         keep = [arr]
@@ -92,18 +84,7 @@ class KCut:
 
 def read_kcut(path):
     """Parse a k-cut file (Session.write_kcut / lorads --kcutFile) into a KCut (labels, part sizes and scalars only)."""
-    with open(path) as f:
-        lines = f.read().split("\n")
-    if lines[0] != "lorads-kcut 1":
-        raise ValueError("%s: not a lorads k-cut file" % path)
-    pos = 1
-    sc = {}
-    for key in INT_KEYS + FLOAT_KEYS:
-        t = lines[pos].split()
-        pos += 1
-        if len(t) != 2 or t[0] != key:
-            raise ValueError("%s: expected %s, found %r" % (path, key, t))
-        sc[key] = int(t[1]) if key in INT_KEYS else float(t[1])
+    lines, pos, sc = read_head(path, "lorads-kcut 1", "k-cut", INT_KEYS)
     cones = []
     while pos < len(lines) and lines[pos].strip():
         t = lines[pos].split()

@@ -10,8 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-INT_KEYS = ("trials", "seed", "max_rounds", "rounds", "src", "best", "best0")
-FLOAT_KEYS = ("scale", "f_best", "f_best0", "by", "bound", "gap", "tol")
+from ._rounded import FLOAT_KEYS, INT_KEYS, RoundHeadStruct, _arr, head_of, read_head
 
 
 class RoundingConeStruct(C.Structure):
@@ -22,15 +21,7 @@ class RoundingConeStruct(C.Structure):
 
 class RoundingStruct(C.Structure):
     """lrd_rounding (csrc/host/lorads_host.h)"""
-    _fields_ = [("nblk", C.c_int), ("trials", C.c_int), ("max_rounds", C.c_int), ("rounds", C.c_int), ("src", C.c_int),
-                ("seed", C.c_uint64), ("scale", C.c_double), ("best", C.c_int), ("best0", C.c_int),
-                ("f_best", C.c_double), ("f_best0", C.c_double), ("obj", C.POINTER(C.c_double)), ("obj0", C.POINTER(C.c_double)),
-                ("by", C.c_double), ("bound", C.c_double), ("gap", C.c_double), ("tol", C.c_double),
-                ("cone", C.POINTER(RoundingConeStruct))]
-
-
-def _arr(ptr, n, dtype=np.float64):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n > 0 and ptr else np.zeros(0, dtype=dtype)
+    _fields_ = [("head", RoundHeadStruct), ("nblk", C.c_int), ("cone", C.POINTER(RoundingConeStruct))]
 
 
 class RoundingCone:
@@ -57,29 +48,18 @@ class Rounding:
 
     @classmethod
     def from_struct(cls, st):
-        cones = []
+        cones, K = [], st.head.trials
         for k in range(st.nblk):
             q = st.cone[k]
-            G = _arr(q.G, q.rank * st.trials).reshape(q.rank, st.trials) if q.G else None
+            G = _arr(q.G, q.rank * K).reshape(q.rank, K) if q.G else None
             cones.append(RoundingCone(q.n, q.rank, _arr(q.sigma, q.n, np.int8), _arr(q.t, q.n), _arr(q.x, q.n), q.T, q.lam_min, G))
-        sc = {k: getattr(st, k) for k in INT_KEYS + FLOAT_KEYS}
-        return cls(cones, _arr(st.obj, st.trials), _arr(st.obj0, st.trials), **sc)
+        obj, obj0, sc = head_of(st, INT_KEYS + FLOAT_KEYS)
+        return cls(cones, obj, obj0, **sc)
 
 
 def read_rounding(path):
     """Parse a rounding file (Session.write_rounding / lorads --roundFile) into a Rounding (signs and scalars only)."""
-    with open(path) as f:
-        lines = f.read().split("\n")
-    if lines[0] != "lorads-rounding 1":
-        raise ValueError("%s: not a lorads rounding file" % path)
-    pos = 1
-    sc = {}
-    for key in INT_KEYS + FLOAT_KEYS:
-        t = lines[pos].split()
-        pos += 1
-        if len(t) != 2 or t[0] != key:
-            raise ValueError("%s: expected %s, found %r" % (path, key, t))
-        sc[key] = int(t[1]) if key in INT_KEYS else float(t[1])
+    lines, pos, sc = read_head(path, "lorads-rounding 1", "rounding", INT_KEYS)
     cones = []
     while pos < len(lines) and lines[pos].strip():
         t = lines[pos].split()

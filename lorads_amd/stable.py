@@ -11,9 +11,10 @@ import ctypes as C
 
 import numpy as np
 
-INT_KEYS = ("trials", "seed", "max_rounds", "rounds", "src", "best", "best0", "lp_columns", "lp_negative")
-FLOAT_KEYS = ("scale", "f_best", "f_best0", "by", "bound", "gap", "tol")
-_STRUCT_NAME = {"lp_columns": "nlp", "lp_negative": "lp_neg"}
+from . import _rounded
+from ._rounded import FLOAT_KEYS, RoundHeadStruct, _arr, fill_head, head_of, read_head
+
+INT_KEYS = _rounded.INT_KEYS + ("lp_columns", "lp_negative")
 
 
 class StableConeStruct(C.Structure):
@@ -24,16 +25,8 @@ class StableConeStruct(C.Structure):
 
 class StableStruct(C.Structure):
     """lrd_stable (csrc/host/lorads_host.h)"""
-    _fields_ = [("nblk", C.c_int), ("trials", C.c_int), ("max_rounds", C.c_int), ("rounds", C.c_int),
-                ("src", C.c_int), ("seed", C.c_uint64), ("scale", C.c_double), ("best", C.c_int), ("best0", C.c_int),
-                ("f_best", C.c_double), ("f_best0", C.c_double), ("obj", C.POINTER(C.c_double)), ("obj0", C.POINTER(C.c_double)),
-                ("nlp", C.c_int), ("lp_neg", C.c_int), ("lp_upper", C.POINTER(C.c_double)),
-                ("by", C.c_double), ("bound", C.c_double), ("gap", C.c_double), ("tol", C.c_double),
+    _fields_ = [("head", RoundHeadStruct), ("nblk", C.c_int), ("nlp", C.c_int), ("lp_neg", C.c_int), ("lp_upper", C.POINTER(C.c_double)),
                 ("cone", C.POINTER(StableConeStruct))]
-
-
-def _arr(ptr, n, dtype=np.float64):
-    return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n > 0 and ptr else np.zeros(0, dtype=dtype)
 
 
 class StableCone:
@@ -69,20 +62,19 @@ class StableSet:
 
     @classmethod
     def from_struct(cls, st):
-        cones = []
+        cones, K = [], st.head.trials
         for k in range(st.nblk):
             q = st.cone[k]
-            sc = _arr(q.scores, st.trials * q.n).reshape(st.trials, q.n).T.copy() if q.scores else None
-            cones.append(StableCone(q.blk, q.n, q.rank, _arr(q.member, q.size, np.int64), _arr(q.sizes, st.trials, np.int64), q.T,
+            sc = _arr(q.scores, K * q.n).reshape(K, q.n).T.copy() if q.scores else None
+            cones.append(StableCone(q.blk, q.n, q.rank, _arr(q.member, q.size, np.int64), _arr(q.sizes, K, np.int64), q.T,
                                     q.lam_min, sc))
-        sc = {k: getattr(st, _STRUCT_NAME.get(k, k)) for k in INT_KEYS + FLOAT_KEYS}
-        return cls(cones, _arr(st.obj, st.trials), _arr(st.obj0, st.trials), _arr(st.lp_upper, st.nlp), **sc)
+        obj, obj0, sc = head_of(st, INT_KEYS + FLOAT_KEYS)
+        return cls(cones, obj, obj0, _arr(st.lp_upper, st.nlp), **sc)
 
     def to_struct(self):
         """an lrd_stable that holds what the file holds (for lrd_stable_write); keeps its arrays alive on the struct"""
         st = StableStruct()
-        for k in INT_KEYS + FLOAT_KEYS:
-            setattr(st, _STRUCT_NAME.get(k, k), getattr(self, k))
+        fill_head(st, self, INT_KEYS + FLOAT_KEYS)
         st.nblk = len(self.cones)
         arr = (StableConeStruct * max(1, st.nblk))()
         keep = [arr]
@@ -98,18 +90,7 @@ class StableSet:
 
 def read_stable(path):
     """Parse a stable-set file (Session.write_stable / lorads --stableFile) into a StableSet (members and scalars only)."""
-    with open(path) as f:
-        lines = f.read().split("\n")
-    if lines[0] != "lorads-stableset 1":
-        raise ValueError("%s: not a lorads stable-set file" % path)
-    pos = 1
-    sc = {}
-    for key in INT_KEYS + FLOAT_KEYS:
-        t = lines[pos].split()
-        pos += 1
-        if len(t) != 2 or t[0] != key:
-            raise ValueError("%s: expected %s, found %r" % (path, key, t))
-        sc[key] = int(t[1]) if key in INT_KEYS else float(t[1])
+    lines, pos, sc = read_head(path, "lorads-stableset 1", "stable-set", INT_KEYS)
     cones = []
     while pos < len(lines) and lines[pos].strip():
         t = lines[pos].split()

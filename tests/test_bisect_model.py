@@ -155,12 +155,12 @@ def _bisection():
 def _to_struct(x, keep):
     st = BisectionStruct()
     for k in ("trials", "seed", "max_rounds", "rounds", "src", "best", "best0", "scale", "f_best", "f_best0", "by", "bound", "gap", "tol"):
-        setattr(st, k, getattr(x, k))
+        setattr(st.head, k, getattr(x, k))   # (the scalars sit in the struct's lrd_round_head)
     st.nblk = len(x.cones)
     obj, obj0 = (C.c_double * x.trials)(*x.obj), (C.c_double * x.trials)(*x.obj0)
     arr = (BisectionConeStruct * len(x.cones))()
     keep += [obj, obj0, arr]
-    st.obj, st.obj0 = C.cast(obj, C.POINTER(C.c_double)), C.cast(obj0, C.POINTER(C.c_double))
+    st.head.obj, st.head.obj0 = C.cast(obj, C.POINTER(C.c_double)), C.cast(obj0, C.POINTER(C.c_double))
     for q, c in zip(arr, x.cones):
         sig = (C.c_int8 * c.n)(*[int(v) for v in c.sigma])
         keep.append(sig)

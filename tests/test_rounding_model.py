@@ -112,11 +112,12 @@ def test_roundtrip_bit_equal(tmp_path, dims):
         arr[k].sigma = _ptr(s, C.c_int8)
         sig_want.append(s)
     st = RoundingStruct()
-    st.nblk, st.trials, st.max_rounds, st.rounds, st.src = len(dims), 1000, 100, 7, 1
-    st.seed, st.best, st.best0 = (1 << 64) - 5, 917, 3
+    h = st.head   # (the scalars sit in the struct's lrd_round_head)
+    st.nblk, h.trials, h.max_rounds, h.rounds, h.src = len(dims), 1000, 100, 7, 1
+    h.seed, h.best, h.best0 = (1 << 64) - 5, 917, 3
     vals = dict(scale=5.0, f_best=-123.45678901234567, f_best0=1e-310, by=1.0 / 3.0, bound=float("nan"), gap=2.5e-17, tol=1e-8)
     for k, v in vals.items():
-        setattr(st, k, v)
+        setattr(h, k, v)
     st.cone = arr
     lib = host.host_lib()
     lib.lrd_rounding_write.argtypes = [C.c_char_p, C.POINTER(RoundingStruct)]
@@ -125,7 +126,7 @@ def test_roundtrip_bit_equal(tmp_path, dims):
     got = read_rounding(path)
     assert path.read_text().startswith("lorads-rounding 1\n")
     for k in ("trials", "seed", "max_rounds", "rounds", "src", "best", "best0"):
-        assert getattr(got, k) == getattr(st, k), k
+        assert getattr(got, k) == getattr(h, k), k
     for k, v in vals.items():
         g = getattr(got, k)
         assert (np.isnan(g) and np.isnan(v)) or np.float64(g).tobytes() == np.float64(v).tobytes(), k
