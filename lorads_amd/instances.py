@@ -438,9 +438,11 @@ def sdp_lp(n, n_edges, n_extra, seed):
     return dict(m=n, blocks=[n, -d], b=np.ones(n), entries=ent)
 
 
-def coupled_lp(nblk, n_k, m, n_lp, seed):
+def coupled_lp(nblk, n_k, m, n_lp, seed, n_free=0):
     """Coupled SDP cones (every A_i touches every cone) PLUS an LP block whose columns sit in two or three rows each:
-    the general path -- cone-by-cone Gauss-Seidel sweep, then the level-scheduled LP column sweep."""
+    the general path -- cone-by-cone Gauss-Seidel sweep, then the level-scheduled LP column sweep.
+    n_free: that many further columns behind them with a cost and no constraint entry (an empty entry range, ||a||^2 = 0); the
+    first n_lp columns and everything else stay what they are without them."""
     base = coupled_blocks(nblk, n_k, m, seed, n_diag=1, n_off=2, r0=2, c_edges=2 * n_k)
     rng = np.random.default_rng(seed + 5)
     ent = list(base["entries"])
@@ -453,8 +455,10 @@ def coupled_lp(nblk, n_k, m, n_lp, seed):
             a = float(0.2 + 0.8 * rng.random())
             ent.append((i + 1, nblk + 1, j + 1, j + 1, a))
             b[i] += a * x0
+    for j in range(n_lp, n_lp + n_free):
+        ent.append((0, nblk + 1, j + 1, j + 1, -float(0.1 + 0.3 * rng.random())))
     ent.sort(key=lambda e: (e[0], e[1]))
-    return dict(m=m, blocks=list(base["blocks"]) + [-n_lp], b=b, entries=ent)
+    return dict(m=m, blocks=list(base["blocks"]) + [-(n_lp + n_free)], b=b, entries=ent)
 
 
 def coupled_blocks(nblk, n_k, m, seed, n_diag=2, n_off=4, r0=3, c_edges=None):
@@ -550,6 +554,12 @@ NAMED = {
     "sdplp40": lambda: sdp_lp(40, 90, 12, 4001),
     "sdpslack30": lambda: sdp_lp(30, 60, 0, 4002),
     "coupledlp": lambda: coupled_lp(2, 40, 24, 18, 5100),   # coupled cones + LP columns across rows (general path)         # slacks only: every LP column alone in its row (one level)
+    # LP shapes of the ADMM column sweep (tests/test_fixed_count_sweeps.py::test_lp_block): 300 slack columns in one level (the
+    # flat kernel on two workgroups); the same with 12 coupling columns, so that level 0 is longer than a workgroup and levels
+    # follow it; coupledlp with one more column that has a cost and no constraint entry
+    "sdpslack300": lambda: sdp_lp(300, 600, 0, 4003),
+    "sdplp300": lambda: sdp_lp(300, 600, 12, 4004),
+    "coupledlp_free": lambda: coupled_lp(2, 40, 24, 18, 5100, n_free=1),
     # +-1-structured contexts of the rounding and two near misses
     "wmaxcut150": lambda: weighted_maxcut(150, 400, 151),
     "scaledpm1_120": lambda: scaled_pm1(120, 300, 121),

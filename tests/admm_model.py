@@ -12,7 +12,11 @@ and the sweep follows the reference step for step: the right-hand side of LORADS
 when k % 20 == 0 -- k = 0 included --, stop on ||r||_2 / ||b||_1 < tol or at maxit), cones in sequence with U then V and the running
 constraint sum, the LP block column by column in closed form (lorads_admm.c:595-629), the dual update and the evaluation of the fused
 step (pObj, dObj, DIMACS error 1).  The data are what the host hands to the operator table: C = -F0, entries below 1e-12 dropped,
-lower triangle, LP entries keyed by their row.  No summation order of any device kernel is mirrored."""
+lower triangle, LP entries keyed by their row.  No summation order of any device kernel is mirrored.
+
+A sweep's count is the reference's too: a solve that passes on its initial residual adds its cone's stale count (DESIGN.md section 5,
+Q7; run_stage).  stopping_tol finds tolerances at which no solve does that, pattern_tol tolerances at which chosen solves do, and
+solved_state the factors from which they do (tests/test_immediate_exits.py)."""
 import re
 
 import numpy as np
@@ -61,7 +65,8 @@ class _Cone:
 
 
 class AdmmModel:
-    """State: U[k], V[k] (n x r), lam, csum (sum over cones of A(U V^T)), cv[k] (cone k's share of csum).
+    """State: U[k], V[k] (n x r), lam, csum (sum over cones of A(U V^T)), cv[k] (cone k's share of csum), cg_last[k] (the count of
+    cone k's latest solve that iterated: what a solve that passes on its initial residual adds to a sweep's total, see sweep).
     dtype: np.longdouble (the model) or np.float64 (to measure a case's conditioning by the spread between the two)."""
 
     def __init__(self, m, b, dims, entries, dtype=LD):
@@ -91,6 +96,7 @@ class AdmmModel:
         self.lam = np.zeros(m, dtype=dtype)
         self.csum = np.zeros(m, dtype=dtype)
         self.cv = [np.zeros(m, dtype=dtype) for _ in range(self.nb)]
+        self.cg_last = [0] * self.nb  # (CGSolverCreate / CGSolverClear: iter = 0, lorads_cgs.c:27,54)
 
     @classmethod
     def from_file(cls, path, dtype=LD):
@@ -199,8 +205,20 @@ class AdmmModel:
         self.lam = np.asarray(lam, dtype=np.float64).astype(self.dtype)
         self.init_constr()
 
+    def as_dtype(self, dtype):
+        """a copy of the model and its state in another number format (data, factors, multipliers and constraint sums rounded)"""
+        import copy
+        other = copy.deepcopy(self)
+        other.dtype = dtype
+        for cn in other.cones:
+            cn.c_val, cn.a_val = cn.c_val.astype(dtype), cn.a_val.astype(dtype)
+        conv = lambda xs: [None if x is None else x.astype(dtype) for x in xs]  # noqa: E731
+        other.U, other.V, other.cv, other.lp_x = conv(other.U), conv(other.V), conv(other.cv), conv(other.lp_x)
+        other.b, other.lam, other.csum = other.b.astype(dtype), other.lam.astype(dtype), other.csum.astype(dtype)
+        return other
+
     def init_constr(self):
-        self.lp_x = [u[:, 0] * v[:, 0] if cn.is_lp else None for cn, u, v in zip(self.cones, self.U, self.V)]
+        self.lp_x =[u[:, 0] * v[:, 0] if cn.is_lp else None for cn, u, v in zip(self.cones, self.U, self.V)]
         self.cv = [self.cone_auv(k, self.U[k], self.V[k]) for k in range(self.nb)]
         self.csum = np.sum(self.cv, axis=0) if self.nb else np.zeros(self.m, dtype=self.dtype)
 
@@ -211,22 +229,44 @@ class AdmmModel:
             cn.c_val = cn.c_val * s
         self.lam = self.lam * s
 
-    def sweep(self, rho, tol, maxit):
-        """admm_update_var: returns (CG iterations over all solves, [(cone, half, iterations, history), ...])"""
-        rho = self.dtype(rho)
-        tot, log = 0, []
+    def stages(self):
+        """the sweep's stages in order: (cone, half) per CG solve, (cone, None) for the LP block"""
+        out = []
         for k, cn in enumerate(self.cones):
-            if cn.is_lp:
-                self._lp_sweep(k, rho)
-                continue
-            for half in range(2):
-                x, F = (self.U[k], self.V[k]) if half == 0 else (self.V[k], self.U[k])
-                it, hist = self.cg(k, F, x, self.rhs(k, F, rho), tol, maxit)
-                tot += it
-                log.append((k, half, it, hist))
-                self.csum -= self.cv[k]
-                self.cv[k] = self.cone_auv(k, self.U[k], self.V[k])
-                self.csum += self.cv[k]
+            out += [(k, None)] if cn.is_lp else [(k, 0), (k, 1)]
+        return out
+
+    def run_stage(self, k, half, rho, tol, maxit):
+        """one stage of the sweep.  A solve returns (iterations, history, count added to the sweep's total); the LP block None.
+
+        The count is the reference's, not the solve's: every cone has one CGLinsys whose `iter` CGSolve sets to 0 only behind
+        the test of the initial residual (lorads_cgs.c:157-160 return before line 173), and LORADSUpdateSDPVarOne adds that field
+        to cgIter after every solve (lorads_admm.c:477,532).  A solve that passes on its initial residual therefore adds the count
+        of the cone's latest solve that iterated -- of its U- or its V-solve, whichever came last; 0 before the first -- and leaves
+        it as it is.  The LP columns are closed forms without a CGLinsys (lorads_admm.c:595-629) and add nothing."""
+        rho = self.dtype(rho)
+        if half is None:
+            self._lp_sweep(k, rho)
+            return None
+        x, F = (self.U[k], self.V[k]) if half == 0 else (self.V[k], self.U[k])
+        it, hist = self.cg(k, F, x, self.rhs(k, F, rho), tol, maxit)
+        if not passed_at_once(it, hist, tol):
+            self.cg_last[k] = it
+        self.csum -= self.cv[k]
+        self.cv[k] = self.cone_auv(k, self.U[k], self.V[k])
+        self.csum += self.cv[k]
+        return it, hist, self.cg_last[k]
+
+    def sweep(self, rho, tol, maxit):
+        """admm_update_var: returns (the reference's CG count of the sweep, [(cone, half, iterations, history), ...]).  The log
+        holds what each solve did (0 iterations for one that passed on its initial residual); the count is cgIter's increment,
+        which for such a solve is the cone's stale count (see run_stage)."""
+        tot, log = 0, []
+        for k, half in self.stages():
+            res = self.run_stage(k, half, rho, tol, maxit)
+            if res is not None:
+                tot += res[2]
+                log.append((k, half, res[0], res[1]))
         return tot, log
 
     def update_dual(self, rho):
@@ -254,6 +294,11 @@ class AdmmModel:
         return its, p, d, e, log
 
 
+def passed_at_once(it, hist, tol):
+    """did the solve with this count and residual history leave on its initial residual (CGSolve's first exit)?"""
+    return it == 0 and hist[0] < tol
+
+
 def stopping_tol(model, rho, js, maxit, ratio=1.5, margin=1.05, probe_maxit=None):
     """A tolerance that stops some solve of the next sweep after exactly j iterations, for the first j of `js` that has one: the
     geometric mean of that solve's smallest residual before iteration j and its residual after iteration j, taken only where they
@@ -278,3 +323,121 @@ def stopping_tol(model, rho, js, maxit, ratio=1.5, margin=1.05, probe_maxit=None
                     probe_maxit is None or all(h[-1] < tol for _, _, _, h in log2)):
                 return tol, j, idx
     return None
+
+
+RUN = "run"
+
+
+def _pattern_shown(model, rho, tol, maxit, pattern, stop, margin, clear):
+    """the per-solve counts of the model's next sweep at `tol` if it shows the pattern with the margins of pattern_tol, else None"""
+    import copy
+    _, log = copy.deepcopy(model).sweep(rho, tol, maxit)
+    _, log64 = model.as_dtype(np.float64).sweep(rho, tol, maxit)
+    if len(log) != len(pattern) or [e[2] for e in log64] != [e[2] for e in log]:
+        return None
+    for want, (_, _, it, h), (_, _, _, h64) in zip(pattern, log, log64):
+        gone = passed_at_once(it, h, tol)
+        if any(tol / margin < x < tol * margin for x in h + h64) or (gone and not h[0] + clear * abs(h64[0] - h[0]) < tol / margin):
+            return None
+        if want is None:
+            continue
+        if (want == 0) != gone or (want != 0 and it < 1) or (want not in (0, RUN) and not (it == want and h[-1] < tol)):
+            return None
+    if stop is not None and not any(w == RUN and it == stop and h[-1] < tol for w, (_, _, it, h) in zip(pattern, log)):
+        return None
+    return tuple(e[2] for e in log)
+
+
+def pattern_tol(model, rho, maxit, pattern, stop=None, margin=1.05, clear=100.0, top=1.0, budget=120):
+    """A tolerance below `top` at which the model's next sweep shows a wanted pattern of immediate exits, or None.
+
+    pattern: one entry per CG solve of the sweep, in sweep order (cone by cone, U then V; the LP block has none): 0 -- the solve
+    passes on its initial residual and does nothing; RUN -- it iterates at least once; an integer j >= 1 -- the tolerance stops it
+    after exactly j iterations; None -- whatever the model says.  stop: some solve marked RUN is stopped by the tolerance after
+    exactly that many iterations.
+
+    Conditions, all decided by the model alone (the same kind as stopping_tol's): the sweep at the returned tolerance shows exactly
+    that pattern; no residual of any history lies within the factor `margin` of the tolerance; the model in float64 -- the format
+    the device forms its residuals in -- runs the same counts with the same margin; and every solve that passes still passes, by
+    that margin, with `clear` times the distance between the two formats' initial residuals added to its own.  Where a solve starts
+    at its solution (solved_state) its residual is rounding alone -- some 1e-18 ||b||_1 in the model, 1e-16 in float64 and on the
+    device, which sums in another order again -- and the condition reads: the float64 residual is below tol / `clear`.  Where the
+    residual is a property of the state (a V-solve that passes at 0.06 under a tolerance of 0.1 while a U-solve iterates), the
+    two formats agree to 1e-16 and the margin decides, as for every other residual.  Returns (tol, counts per solve).
+
+    The search walks the sweep solve by solve and keeps the interval of tolerances that is still open: a solve's residual history
+    (at tolerance 0, from the state the earlier solves leave) splits it into "passes at once", "stops after j" for every j, and
+    "runs to maxit"; each admissible part is followed depth first, at most `budget` solves in all."""
+    import copy
+    stages = model.stages()
+    left = [budget]
+
+    def walk(mdl, si, pi, lo, hi, have):
+        while si < len(stages) and stages[si][1] is None:
+            mdl.run_stage(stages[si][0], None, rho, 0.0, maxit)
+            si += 1
+        if si == len(stages):
+            if stop is not None and not have:
+                return None
+            tol = float(np.sqrt(lo * hi)) if lo > 0 else hi / 2
+            counts = _pattern_shown(model, rho, tol, maxit, pattern, stop, margin, clear)
+            return None if counts is None else (tol, counts)
+        if left[0] <= 0:
+            return None
+        left[0] -= 1
+        k, half = stages[si]
+        want = pattern[pi]
+        _, h, _ = copy.deepcopy(mdl).run_stage(k, half, rho, 0.0, maxit)
+        parts = []  # (iterations to run: None = passes at once, lo, hi, stops at the wanted `stop`)
+        if want in (0, None):
+            parts.append((None, max(lo, h[0] * margin), hi, False))
+        if want != 0:
+            for j in range(1, len(h)):
+                if want in (RUN, None, j):
+                    parts.append((j, max(lo, h[j] * margin), min(hi, min(h[:j]) / margin), want == RUN and j == stop))
+            if want in (RUN, None) and len(h) > 1:
+                parts.append((len(h) - 1, lo, min(hi, min(h) / margin), False))
+        parts = [p for p in parts if p[1] < p[2]]
+        parts.sort(key=lambda p: not (p[3] and not have))  # (stable: the wanted stop first while none is taken)
+        for j, plo, phi, st in parts:
+            nxt = copy.deepcopy(mdl)
+            nxt.run_stage(k, half, rho, np.inf if j is None else 0.0, j or 0)
+            found = walk(nxt, si + 1, pi + 1, plo, phi, have or st)
+            if found:
+                return found
+        return None
+
+    return walk(copy.deepcopy(model), 0, 0, 0.0, float(top), False)
+
+
+def solved_state(model, rho, cones=None, half=0, iters=200):
+    """(U, V) in float64 with the chosen cones' U (half 0; 1: V) replaced by the converged solve for the other factor as the model
+    holds it: the model's cg at tolerance 0 over `iters` iterations, cone by cone in sweep order (a later cone's right-hand side
+    sees the constraint values of an earlier cone's solution), rounded to float64.  cones: None = every cone with a CG.  In a sweep
+    from the returned state such a solve starts at its solution (initial residual near 1e-16 ||b||_1 in double) as long as no
+    earlier solve of the sweep has moved what its right-hand side reads; the model decides that (pattern_tol)."""
+    import copy
+    probe = copy.deepcopy(model)
+    for k, h in probe.stages():
+        if h is not None and h == half and (cones is None or k in cones):
+            probe.run_stage(k, half, rho, 0.0, iters)
+    U = [np.asarray(u, dtype=np.float64) for u in probe.U]
+    V = [np.asarray(v, dtype=np.float64) for v in probe.V]
+    assert all(np.all(np.isfinite(x)) for x in U + V)
+    return U, V
+
+
+def lp_levels(model, k):
+    """column counts per level of LP block k's level schedule, from the model's data: level(j) = 1 + the largest level among the
+    earlier columns that share a constraint row with j (columns of one level do not see each other; a column without an entry
+    is in level 0)"""
+    cn = model.cones[k]
+    row_lvl, sizes = {}, []
+    for col in range(cn.n):
+        rows = [int(g) for g in cn.a_con[cn.a_row == col]]
+        lvl = max([row_lvl.get(g, 0) for g in rows], default=0)
+        for g in rows:
+            row_lvl[g] = lvl + 1
+        sizes += [0] * (lvl + 1 - len(sizes))
+        sizes[lvl] += 1
+    return sizes
