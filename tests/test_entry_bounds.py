@@ -1,8 +1,11 @@
 """Separation of entry bounds on the GPU (lorads_hip_entry_bounds, Session.entry_bounds, Session.write_bounded, --boundsMax) against
 the numpy model (tests/bounds_model.py): exact counts, the selection in its total order with any number of ties, determinism,
-read-only continuation, refusals, and the bounded Hamming-graph theta problem solved on the device."""
+read-only continuation, refusals, the tile groups of the grid's second dimension (n > 512), and the bounded Hamming-graph theta
+problem solved on the device."""
 import os
+import re
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -112,6 +115,194 @@ def test_massive_ties(signed):
             assert a.tobytes() == b.tobytes()
     finally:
         s.close()
+
+
+# ------------------------------------------------------------------ past one tile group
+# A workgroup of k_bnd_enum walks at most BND_ITERS tiles J from J0 = I + BND_ITERS blockIdx.y, so from 17 row tiles on (n > 512) the
+# grid has a second dimension: J0 of a later group, the early return J0 >= nt and J1 clipped inside a later group.
+
+
+def _bounds_inc(name):
+    text = open(os.path.join(common.ROOT, "lorads_amd", "csrc", "hip", "bounds.inc")).read()
+    return int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text).group(1))
+
+
+BND_T, BND_ITERS, BND_LDS_COLS = (_bounds_inc(k) for k in ("BND_T", "BND_ITERS", "BND_LDS_COLS"))
+
+
+def tile_groups(n):
+    """(row tiles, the second dimension of bnd_launch's grid), restated"""
+    nt = -(-n // BND_T)
+    return nt, -(-nt // BND_ITERS)
+
+
+GROUPS = {512: (16, 1), 513: (17, 2), 545: (18, 2), 1025: (33, 3)}   # 545 and 1025: a ragged last tile of one row
+
+
+def test_the_restated_groups():
+    assert (BND_T, BND_ITERS, BND_LDS_COLS) == (TILE, 16, 128)
+    for n, want in GROUPS.items():
+        assert tile_groups(n) == want, n
+
+
+def _far(p, q):
+    """the pairs a later group than the first enumerates"""
+    return np.asarray(q) // BND_T - np.asarray(p) // BND_T >= BND_ITERS
+
+
+def _tail_bounds(F, lo=0.01, up=0.995):
+    """bounds at the 1 % and 99.5 % quantiles of the off-diagonal entries of X (numpy, from the factor): the count stays in the
+    thousands -- about 1.5 % of n (n - 1) / 2 -- and the model's loops stay short.  Where a later group has so few entries that
+    none of them may lie that far out (n = 513: the 32 of tile pair (0, 16)), the bound moves in to 0.01 inside the most extreme
+    of them (ten times the threshold), so that each class has a violation there (at n = 513 and rank 5 that is a third of the
+    pairs, 45186 items with both bounds on: the case still takes 0.2 s)."""
+    p, q = np.triu_indices(F.shape[0], 1)
+    x = (F @ F.T)[p, q]
+    lower, upper = np.quantile(x, [lo, up])
+    far = x[_far(p, q)]
+    if len(far):
+        lower, upper = max(lower, far.min() + 0.01), min(upper, far.max() - 0.01)
+    return float(lower), float(upper)
+
+
+@pytest.mark.parametrize("r", [6, 5])
+@pytest.mark.parametrize("n", sorted(GROUPS))
+def test_synthetic_factors_against_model_past_one_group(n, r):
+    """test_synthetic_factors_against_model's inputs and checks at 16 tiles (still one group), 17, 18 with a ragged last tile and 33
+    (three groups, the last of one tile).  Cheap: one context of n <= 1025 rows, one Scan of the model per case (0.14 s at 1025)."""
+    t0 = time.perf_counter()
+    nt, groups = tile_groups(n)
+    assert (nt, groups) == GROUPS[n] and (groups > 1) == (n > 512)
+    rng = np.random.default_rng(1000 * n + r)
+    F = rng.standard_normal((n, r)) / np.sqrt(r)
+    lo, up = _tail_bounds(F)
+    minv = 1e-3
+    s = _maxcut_session(n, r)
+    try:
+        _load(s, F)
+        for lower, upper in [(lo, INF), (-INF, up), (lo, up)]:   # lower only, upper only, both: CASES at these bounds
+            cnt0, *_rest, passes0 = _call(s, lower, upper, minv, 0)
+            assert all(len(x) == 0 for x in _rest) and passes0 == 1 and cnt0 > 0
+            sc = bm.Scan(F, lower, upper, minv)
+            far = int(np.count_nonzero(_far(sc.p, sc.q)))
+            print("n %d r %d [%g, %g]: count %d, the model has %d, %d of them in later groups" % (n, r, lower, upper, cnt0, len(sc.v), far))
+            assert (far > 0) == (groups > 1)   # (without one the case says nothing about the groups)
+            for K in (1, 100, cnt0 + 7):
+                cnt, p, q, cl, v, passes = _call(s, lower, upper, minv, K)
+                assert cnt == cnt0 and passes >= 2
+                bm.check_against_model([F], lower, upper, minv, K, [cnt], np.zeros(len(p)), p, q, cl, v, scans=[sc])
+                if K > cnt0 and sc.count_hi == sc.count_lo:   # (no item at the threshold: the whole list is the model's,
+                    assert int(np.count_nonzero(_far(p, q))) == far   #  every later group's pairs in it)
+                if upper == INF:
+                    assert (cl == 0).all()
+                if lower == -INF:
+                    assert (cl == 1).all()
+                again = _call(s, lower, upper, minv, K)
+                assert again[0] == cnt and again[5] == passes
+                for a, b in zip(again[1:5], (p, q, cl, v)):
+                    assert a.tobytes() == b.tobytes()
+    finally:
+        s.close()
+    print("n %d r %d: %.2f s" % (n, r, time.perf_counter() - t0))
+
+
+# rows that share a column of the planted factor, per n; every row of a set carries +-1 in the set's column (the sign is the row's
+# parity) and zeros elsewhere, so X_pq = +-1 inside a set and 0 everywhere else, exactly.  Tile distances J - I inside the sets: 15
+# (the last tile group 0 walks), 16 (the first of group 1), 31 (the last of group 1 at I = 0) and 32 (group 2, clipped to one tile);
+# row n - 1 is alone in the ragged last tile.
+PLANTED = {
+    1025: [[2, 16 * 32 + 9, 1024],            # tiles 0, 16, 32: distances 16, 32 (group 2, J1 clipped, the ragged tile), 16
+           [31, 15 * 32, 30 * 32 + 31],       # tiles 0, 15, 30: 15, 30, 15 at the tiles' first and last rows
+           [0, 16 * 32],                      # 16, first rows
+           [63, 16 * 32 + 31],                # tiles 1, 16: 15, last rows
+           [10, 31 * 32 + 31],                # 31: the last J of group 1
+           [37, 17 * 32 + 3],                 # tiles 1, 17: 16
+           [100, 20 * 32 + 1]],               # tiles 3, 20: 17
+    545: [[3, 544],                           # tiles 0, 17: 17, group 1 clipped to two tiles, the ragged one its last
+          [33, 16 * 32 + 31],                 # tiles 1, 16: 15
+          [0, 16 * 32],                       # 16
+          [31, 15 * 32],                      # 15
+          [35, 16 * 32 + 1]],                 # tiles 1, 16: 15
+}
+
+
+def _planted_factor(n, r):
+    """(F, the planted pairs).  Columns past the sets' hold one row each (decoys next to the planted rows: X = 0 with everything)."""
+    sets = PLANTED[n]
+    F = np.zeros((n, r))
+    pairs = []
+    for c, rows in enumerate(sets):
+        for i in rows:
+            F[i, c] = -1.0 if i % 2 else 1.0
+        pairs += [(a, b) for x, a in enumerate(rows) for b in rows[x + 1:]]
+    used = {i for rows in sets for i in rows}
+    assert len(used) == sum(len(rows) for rows in sets)
+    decoys = [i + d for rows in sets for i in rows for d in (1, -1) if 0 <= i + d < n and i + d not in used]
+    for c, i in zip(range(len(sets), r), dict.fromkeys(decoys)):
+        F[i, c] = -1.0 if i % 2 else 1.0
+    return F, sorted(pairs)
+
+
+@pytest.mark.parametrize("n", sorted(PLANTED))
+def test_planted_violations_in_later_groups_are_exact(n):
+    """entries of X that are exactly 0 or +-1 against the bounds [-0.5, 0.5]: the violations are the planted pairs alone, all at
+    v = 0.5 exactly, and every one lies in a tile pair with J - I >= 15 -- the count is the planted number and the list the model's
+    bit for bit.  Cheap: n <= 1025, a handful of pairs."""
+    t0 = time.perf_counter()
+    r = 32
+    F, pairs = _planted_factor(n, r)
+    X = F @ F.T
+    assert set(np.unique(X).tolist()) <= {-1.0, 0.0, 1.0}
+    assert sorted(zip(*np.nonzero(np.triu(X, 1)))) == pairs   # (the planted pairs and no other)
+    dist = sorted({q // BND_T - p // BND_T for p, q in pairs})
+    nt, groups = tile_groups(n)
+    assert dist[0] == BND_ITERS - 1 and BND_ITERS in dist and any(q == n - 1 for _, q in pairs) and n - 1 == (nt - 1) * BND_T
+    assert dist[-1] == nt - 1   # (the last, clipped group)
+    planted = {1025: 11, 545: 5}[n]
+    assert len(pairs) == planted
+    lower, upper, minv = -0.5, 0.5, 0.25
+    sc = bm.Scan(F, lower, upper, minv)
+    assert len(sc.v) == planted and (sc.v == 0.5).all() and {0, 1} == set(sc.c.tolist())
+    s = _maxcut_session(n, r)
+    try:
+        _load(s, F)
+        for K in (0, 1, planted + 7):
+            cnt, p, q, cl, v, passes = _call(s, lower, upper, minv, K)
+            print("planted, n %d, max_cuts %d: count %d, kept %d, passes %d" % (n, K, cnt, len(p), passes))
+            assert cnt == planted
+            kept = min(K, planted)
+            assert np.array_equal(p, sc.p[:kept]) and np.array_equal(q, sc.q[:kept]) and np.array_equal(cl, sc.c[:kept])
+            assert v.tobytes() == sc.v[:kept].astype(np.float64).tobytes()
+            again = _call(s, lower, upper, minv, K)
+            assert again[0] == cnt and again[5] == passes
+            for a, b in zip(again[1:5], (p, q, cl, v)):
+                assert a.tobytes() == b.tobytes()
+    finally:
+        s.close()
+    print("planted, n %d: %.2f s" % (n, time.perf_counter() - t0))
+
+
+def test_wide_factor_past_one_group():
+    """rl4 = 132 > BND_LDS_COLS at 18 row tiles: the strip-from-memory operands in a second, clipped group and on the ragged tile"""
+    t0 = time.perf_counter()
+    n, r = 545, 131
+    assert tile_groups(n) == (18, 2) and ((r + 3) & ~3) > BND_LDS_COLS
+    rng = np.random.default_rng(11)
+    F = rng.standard_normal((n, r)) / np.sqrt(r)
+    lower, upper = _tail_bounds(F)
+    sc = bm.Scan(F, lower, upper, 1e-3)
+    far = int(np.count_nonzero(_far(sc.p, sc.q)))
+    assert far > 0
+    s = _maxcut_session(n, r)
+    try:
+        _load(s, F)
+        for K in (0, 100, len(sc.v) + 7):
+            cnt, p, q, cl, v, _ = _call(s, lower, upper, 1e-3, K)
+            bm.check_against_model([F], lower, upper, 1e-3, K, [cnt], np.zeros(len(p)), p, q, cl, v, scans=[sc])
+        assert cnt > 100 and (sc.count_hi != sc.count_lo or int(np.count_nonzero(_far(p, q))) == far)
+    finally:
+        s.close()
+    print("wide factor, n %d r %d: count %d, %d in the later group; %.2f s" % (n, r, cnt, far, time.perf_counter() - t0))
 
 
 def _quantile_bounds(F):

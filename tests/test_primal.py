@@ -5,19 +5,23 @@ u = 2^-53.  F is numpy's (U + V) / 2 or R of the read-back factors (the average 
   entries     |val - F_i . F_j| <= 2 rl u sum_c |F_ic F_jc|                      (the dot-product bound gamma_rl, any order, FMA included)
   apply       |T - F^T B| <= 2 n u (|F^T| |B|),  |Y - F (F^T B)| <= 2 (n + rl) u (|F| |F^T| |B|), elementwise
   statistics  stats[2] bit-equal to max |val - ref|; stats[0], [1], [3] within 2 (count + 4) u of their own value
-The longdouble references carry 2^-64: below 2^-10 of the bounds.  Every test prints the worst achieved ratio to its bound."""
+The longdouble references carry 2^-64: below 2^-10 of the bounds.  Every test prints the worst achieved ratio to its bound.
+The size splits of primal_apply (row strips past 256 rows, row panels past 65536) have cases of their own at the end of the file, on
+integer data and exact."""
 import ctypes as C
 import os
 import re
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
-from lorads_amd import host, primal
+from lorads_amd import host, instances, primal
 from lorads_amd.solution import read_solution
 from tests import common
 from tests.admm_model import read_sdpa
+from tests.test_triangle_cuts import _maxcut_session
 
 pytestmark = pytest.mark.gpu
 
@@ -210,7 +214,7 @@ def _apply_check(s, src, k, B, tag, X=None):
         ex = np.abs(X.astype(LD) @ Bl - Y.astype(LD))
         assert np.all(ex <= bx), (tag, "X @ B")
         rx = float(np.max(ex / np.maximum(bx, tiny)))
-    print("%s block %d (n %d, rl %d, %d columns): worst ratios T %.3f, Y %.3f, X @ B %.3f" % (tag, k, n, rl, Bl.shape[1], rt, ry, rx))
+    print("%s block %d (n %d, rl %d, %d columns): worst ratios T %.3g, Y %.3g, X @ B %.3g" % (tag, k, n, rl, Bl.shape[1], rt, ry, rx))
     return Y, T
 
 
@@ -535,3 +539,204 @@ def test_cli(built, tmp_path):
     bad.write_text("1 1 31\n1 2\n")
     p = subprocess.run([exe, path, "--entriesFile", str(bad)], capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and "line 2" in p.stderr and "End Program" not in p.stdout
+
+
+# ------------------------------------------------------------------ the size splits of lorads_hip_primal_apply
+# Past 256 rows a row panel has more than one strip (k_primal_ftb's blockIdx.x, the partial's address, k_primal_ftb_sum's loop);
+# past PRIMAL_ROWS there is a second row panel (first = 0 in the sum, the r0 offsets of the factor, of B and of Y, k_primal_lp
+# again).  The cases below are exact: factors in [-3, 3] and B in [-4, 4] are integers, U = F + D and V = F - D with an integer D give
+# (U + V) / 2 = F exactly, every product and partial sum is an integer below 2^53, so T = F^T B and Y = F T have ONE correct bit
+# pattern whatever the order of the sums -- numpy's float64 product is the reference and nothing is tolerated.  They are cheap: a few
+# launches and at most 66000 x 20 numbers each way; the contexts above 65535 rows are opened once for the module.
+
+
+def _inc_int(text, name):
+    m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*(\d+)(?:\s*<<\s*(\d+))?\s*;" % name, text)
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+def _primal_inc_consts():
+    text = open(os.path.join(common.ROOT, "lorads_amd", "csrc", "hip", "primal.inc")).read()
+    return tuple(_inc_int(text, k) for k in ("PRIMAL_ROWS", "PRIMAL_MAX_STRIPS", "PRIMAL_PW"))
+
+
+PRIMAL_ROWS, PRIMAL_MAX_STRIPS, PRIMAL_PW = _primal_inc_consts()
+
+
+def row_strips(rows, smax):
+    """(strips, rows_per_strip) of postsolve.inc's row_strips, restated"""
+    s = max(1, min(smax, -(-rows // 256)))
+    rps = max(64, (-(-rows // s) + 63) & ~63)
+    return max(1, -(-rows // rps)), rps
+
+
+def apply_plan(n):
+    """[(first row, rows, strips, rows_per_strip)] of the row panels lorads_hip_primal_apply walks, restated"""
+    return [(r0, min(PRIMAL_ROWS, n - r0)) + row_strips(min(PRIMAL_ROWS, n - r0), PRIMAL_MAX_STRIPS) for r0 in range(0, n, PRIMAL_ROWS)]
+
+
+# n -> the panels (strips, rows_per_strip) the case is there for
+PLAN = {256: [(1, 256)], 257: [(2, 192)], 1000: [(4, 256)], 4097: [(17, 256)], 65536: [(256, 256)], 65537: [(256, 256), (1, 64)],
+        66000: [(256, 256), (2, 256)]}
+
+
+def test_the_restated_plan():
+    assert (PRIMAL_ROWS, PRIMAL_MAX_STRIPS, PRIMAL_PW) == (65536, 256, 16)
+    for n, want in PLAN.items():
+        assert [p[2:] for p in apply_plan(n)] == want, n
+    assert [p[:2] for p in apply_plan(66000)] == [(0, 65536), (65536, 464)]
+
+
+_BIG = {}
+
+
+def _big(n, r):
+    """a context of one SDP cone of n rows at rank r, kept for the module (n = 66000: the SDP + LP instance, an LP block of 66000
+    columns beside the cone); the rank only grows, so a case that asks for a lower one than the kept context has opens it anew"""
+    s = _BIG.get(n)
+    if s is not None and s.block_shape(0)[1] > r:
+        _BIG.pop(n).close()
+        s = None
+    if s is None:
+        if n == 66000:
+            s = common.hip_session(common.generated_instance("primal_sdplp66000", lambda: instances.sdp_lp(66000, 132000, 0, 66)), timesLogRank=1e-3)
+            assert [s.block_shape(k) for k in range(s.nblk)] == [(66000, 1), (66000, 1)] and s._lp_blocks() == [False, True]
+        else:
+            s = _maxcut_session(n, 1)
+        _BIG[n] = s
+    if s.block_shape(0)[1] != r:
+        s.be.resize_rank([r] + [1] * (s.nblk - 1))
+    assert s.block_shape(0) == (n, r)
+    return s
+
+
+def teardown_module(module):
+    for s in _BIG.values():
+        s.close()
+    _BIG.clear()
+
+
+def _load_integers(s, k, seed):
+    """integer factors into block k: R, and U = F + D, V = F - D around another F.  Returns {src: F}."""
+    n, r = s.block_shape(k)
+    rng = np.random.default_rng(seed)
+    R, F, D = (rng.integers(-a, a + 1, (n, r)).astype(np.float64) for a in (3, 3, 5))
+    s.be.set_mat(host.MAT_R, k, R)
+    s.be.set_mat(host.MAT_U, k, F + D)
+    s.be.set_mat(host.MAT_V, k, F - D)
+    return {host.PAIR_RR: R, host.PAIR_UV: F}
+
+
+def _indicator_rows(n):
+    """the rows whose unit vectors ride in B: both ends of the cone, of the first strip, of the first row panel"""
+    rps = apply_plan(n)[0][3]
+    return sorted({i for i in (0, rps - 1, rps, PRIMAL_ROWS - 1, PRIMAL_ROWS, n - 1) if 0 <= i < n})
+
+
+def _integer_b(rng, n, nc, rows):
+    """B (n, nc) of integers in [-4, 4] whose last columns are the unit vectors of `rows` (column 0 stays random).  Returns
+    (B, {column: row})."""
+    B = rng.integers(-4, 5, (n, nc)).astype(np.float64)
+    take = rows[len(rows) - min(len(rows), nc - 1):]
+    at = {}
+    for j, i in zip(range(nc - len(take), nc), take):
+        B[:, j] = 0.0
+        B[i, j] = 1.0
+        at[j] = i
+    return B, at
+
+
+def _same(got, want, tag):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (tag, got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    if len(bad):
+        print("%s: %d of %d values differ, first at %s (got %r, want %r), last at %s" % (tag, len(bad), got.size, bad[0].tolist(), got[tuple(bad[0])],
+                                                                                         want[tuple(bad[0])], bad[-1].tolist()))
+    assert len(bad) == 0, tag
+
+
+def _exact_apply(s, src, k, F, nc, seed, tag, entries):
+    """one call with integer data against numpy's exact product; with `entries`, column i of X is asked of primal_entries too"""
+    n = F.shape[0]
+    lp = s._lp_blocks()[k]
+    B, at = _integer_b(np.random.default_rng(seed), n, nc, _indicator_rows(n))
+    rc, Y, T = s.be.primal_apply(src, k, B, want_t=not lp)
+    assert rc == 0, _last_error(s)
+    if lp:
+        _same(Y, (F[:, :1] * F[:, :1]) * B, tag + " Y")
+    else:
+        Tw = F.T @ B
+        assert np.abs(F @ Tw).max() < 2.0 ** 53
+        _same(T, Tw, tag + " T")
+        _same(Y, F @ Tw, tag + " Y")
+    for j, i in at.items():
+        if lp:
+            xi = np.zeros(n)
+            xi[i] = F[i, 0] * F[i, 0]
+        else:
+            xi = F @ F[i]
+            _same(T[:, j], F[i], "%s T of e_%d" % (tag, i))     # row i of F
+        _same(Y[:, j], xi, "%s Y of e_%d" % (tag, i))           # column i of X
+        if entries:
+            rc, val, _ = s.be.primal_entries(src, k, np.arange(n, dtype=np.int32), np.full(n, i, dtype=np.int32))
+            assert rc == 0, _last_error(s)
+            _same(val, xi, "%s entries of column %d" % (tag, i))
+    return len(at)
+
+
+def _exact_block(s, k, seed, columns, tag):
+    t0 = time.perf_counter()
+    Fs = _load_integers(s, k, seed)
+    seen = 0
+    for src, what in ((host.PAIR_RR, "RR"), (host.PAIR_UV, "UV")):
+        for nc in columns:
+            seen += _exact_apply(s, src, k, Fs[src], nc, seed + nc, "%s %s, %d columns" % (tag, what, nc), entries=nc == max(columns))
+    print("%s: bit-equal to numpy on both sources, columns %s, %d unit vectors; %.2f s" % (tag, list(columns), seen, time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("r", [5, 20])
+@pytest.mark.parametrize("n", [256, 257, 1000, 4097])
+def test_apply_is_exact_on_integers_past_one_strip(built, n, r):
+    """1, 2, 4 and 17 row strips (257: strips of 192 rows, a wavefront's quarter of 48), an odd padded rank and two rank tiles, one
+    column, a full column panel and one column more"""
+    (plan,) = apply_plan(n)
+    assert plan[2:] == PLAN[n][0] and (plan[2] > 1) == (n > 256)
+    s = _maxcut_session(n, r)
+    try:
+        _exact_block(s, 0, 7000 + n + r, (1, 16, 17), "n %d r %d (%d strips of %d rows)" % ((n, r) + plan[2:]))
+    finally:
+        s.close()
+
+
+@pytest.mark.parametrize("n,r", [(65536, 5), (65536, 20), (65537, 5), (65537, 20), (66000, 5), (66000, 20)])
+def test_apply_is_exact_on_integers_past_one_row_panel(built, n, r):
+    """a full first row panel of 256 strips alone (65536), then a second panel of one row and of 464 rows in two strips: T is added
+    to, not overwritten, and every array is read and written at r0 = 65536.  17 columns: two column panels, so T is opened anew for
+    the second one after the first one's second row panel.  Unit vectors at rows 65535, 65536 and n - 1 cross the panel's edge; the
+    entry kernel is asked for the same columns of X with row indices above 65535."""
+    plan = apply_plan(n)
+    assert [p[2:] for p in plan] == PLAN[n] and len(plan) == (2 if n > PRIMAL_ROWS else 1) and plan[0][2] == PRIMAL_MAX_STRIPS
+    _exact_block(_big(n, r), 0, 9000 + n + r, (17,), "n %d r %d (%d row panels)" % (n, r, len(plan)))
+
+
+def test_lp_block_is_exact_on_integers_past_one_row_panel(built):
+    """Y = diag(f^2) B on an LP block of 66000 columns: k_primal_lp on a second panel; T is refused as on any LP block"""
+    s = _big(66000, 5)
+    assert len(apply_plan(s.block_shape(1)[0])) == 2
+    _exact_block(s, 1, 9100, (1, 17), "LP block of 66000")
+    rc = s.be.primal_apply(host.PAIR_UV, 1, np.zeros((66000, 2)), want_t=True)[0]
+    assert rc not in (0, 3) and "LP block" in _last_error(s)
+
+
+def test_apply_random_values_past_one_row_panel(built):
+    """the longdouble route of _apply_check at two row panels.  Its bounds grow with n (2 n u |F^T| |B| for T): at n = 66000 they are
+    wide, and the exact cases above carry the weight; this one shows that non-integer data takes the same path to the same bounds."""
+    t0 = time.perf_counter()
+    s = _big(66000, 20)
+    assert len(apply_plan(66000)) == 2
+    _random_state(s, 66)
+    for k in range(s.nblk):
+        n = s.block_shape(k)[0]
+        _apply_check(s, host.PAIR_UV, k, np.random.default_rng(660 + k).standard_normal((n, 17)), "sdplp66000 random")
+    print("sdplp66000 random: %.2f s" % (time.perf_counter() - t0))

@@ -1,12 +1,15 @@
 """Spectrum and rank reduction of the solution factors on the GPU (lorads_amd/csrc/hip/spectral.inc) against
 numpy on the read-back factors: eigenvalues and eigenvectors, every rank shape, the pure rotation, truncation and the ADMM steps
-after it, phase 1, read-only / deterministic / owned, the one-launch paths after a reduction, the command line.
+after it, phase 1, read-only / deterministic / owned, the one-launch paths after a reduction, the command line, and the two caps
+of the Gram's row strips (n > 65536; a large rank).
 
 u = 2^-53.  bound1 = 2 (n + 8 sweeps) rl u lambda_1: a dot of length n carries at most n u lambda_1, an eigenvalue moves by at most
 rl max|dG|, numpy's own Gram carries the same, and the Jacobi part is 8 sweeps m u lambda_1 (tests/test_spectral_model.py)."""
 import ctypes as C
 import os
+import re
 import subprocess
+import time
 
 import numpy as np
 import pytest
@@ -175,6 +178,121 @@ def test_headline_size(built):
             s.close()
     finally:
         os.remove(d)
+
+
+# ------------------------------------------------------------------ the two caps of the Gram's row strips
+# Up to n = 65536 a strip has 256 rows.  Above it the cap of SPEC_MAX_STRIPS strips makes them 320, 384, ... rows: a wavefront's quarter
+# of 80 and more no longer starts on a 64-row boundary.  At a large rank SPEC_PART_CAP (the doubles of Gram partials) allows fewer
+# strips than that, and the strips grow at a far smaller n.
+
+
+def _spec_inc(name):
+    text = open(os.path.join(common.ROOT, "lorads_amd", "csrc", "hip", "spectral.inc")).read()
+    m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*(?:\(size_t\))?\s*(\d+)(?:\s*<<\s*(\d+))?\s*;" % name, text)
+    return int(m.group(1)) << int(m.group(2) or 0)
+
+
+SPEC_MAX_STRIPS, SPEC_PART_CAP, SPEC_MAXR = (_spec_inc(k) for k in ("SPEC_MAX_STRIPS", "SPEC_PART_CAP", "SPEC_MAXR"))
+
+
+def gram_strips(n, rl):
+    """(strip cap by SPEC_PART_CAP, strips, rows_per_strip) of spec_run and postsolve.inc's row_strips, restated"""
+    T = -(-rl // 16)
+    npairs = T * (T + 1) // 2
+    cap = SPEC_PART_CAP // (npairs * 256)
+    s = max(1, min(SPEC_MAX_STRIPS, cap, -(-n // 256)))
+    rps = max(64, (-(-n // s) + 63) & ~63)
+    return cap, max(1, -(-n // rps)), rps
+
+
+def test_the_restated_strips():
+    assert (SPEC_MAX_STRIPS, SPEC_PART_CAP, SPEC_MAXR) == (256, 4 << 20, 512)
+    assert gram_strips(20000, 40)[1:] == (79, 256) and gram_strips(65536, 20)[1:] == (256, 256)
+    assert gram_strips(66000, 20) == (SPEC_PART_CAP // (3 * 256), 207, 320)
+    assert gram_strips(40, 258)[0] == 107 and gram_strips(7937, 497) == (31, 25, 320)
+
+
+_BIG = {}
+
+
+def _sdplp66000(r):
+    """the context of one SDP cone of 66000 rows at rank r (and an LP block of 66000 columns), kept for the module"""
+    s = _BIG.get(r)
+    if s is None:
+        path = common.generated_instance("spec_sdplp66000", lambda: instances.sdp_lp(66000, 132000, 0, 66))
+        s = _BIG[r] = common.hip_session(path, timesLogRank=1e-3)
+        assert s.block_shape(0) == (66000, 1)
+        s.be.resize_rank([r, 1])
+    assert s.block_shape(0) == (66000, r) and _lp(s) == [False, True]
+    return s
+
+
+def teardown_module(module):
+    for s in _BIG.values():
+        s.close()
+    _BIG.clear()
+
+
+def test_strips_of_320_rows(built):
+    """n = 66000: 207 strips of 320 rows.  A random state through check_spectrum as it stands, then a factor whose columns have
+    disjoint supports and entries +-1: every partial Gram is a diagonal of integer counts, no rotation is due, and the eigenvalues
+    must be the column counts exactly.  Cheap: two Grams of 66000 x 20 and an eigen-solve of order 20."""
+    t0 = time.perf_counter()
+    n, r = 66000, 20
+    assert gram_strips(n, r)[1:] == (207, 320) and n > 256 * SPEC_MAX_STRIPS
+    s = _sdplp66000(r)
+    _random_state(s, 66)
+    worst = check_spectrum(s, host.PAIR_UV, "sdplp66000 r=%d" % r)
+    print("sdplp66000 r=%d: worst ratios %.3g, %.3g, %.3g" % ((r,) + tuple(worst)))
+    rng = np.random.default_rng(67)
+    col = rng.permutation(np.repeat(np.arange(r), np.arange(1, r + 1)))[np.arange(n) % (r * (r + 1) // 2)]   # column j: ~ (j + 1) / 210 of the rows
+    F = np.zeros((n, r))
+    F[np.arange(n), col] = rng.choice([-1.0, 1.0], n)
+    D = rng.integers(-5, 6, (n, r)).astype(np.float64)
+    s.be.set_mat(host.MAT_U, 0, F + D)
+    s.be.set_mat(host.MAT_V, 0, F - D)
+    counts = np.bincount(col, minlength=r).astype(np.float64)
+    assert counts.sum() == n and len(set(counts.tolist())) == r
+    rc, lam, sweeps, Q = s.be.spectrum(host.PAIR_UV, vectors=True)
+    assert rc == 0
+    print("sdplp66000 disjoint columns: %d sweeps, eigenvalues %s" % (sweeps[0], lam[0][:4]))
+    assert sweeps[0] == 1   # (a diagonal Gram: the first sweep rotates nothing)
+    assert np.array_equal(lam[0], np.sort(counts)[::-1])
+    order = np.argsort(-counts, kind="stable")
+    assert np.array_equal(Q[0], np.eye(r)[:, order])   # (and the vectors are the unit vectors of those columns)
+    print("sdplp66000: %.2f s" % (time.perf_counter() - t0))
+
+
+def _smallest_part_cap_case():
+    """the smallest n, and the smallest rank at it, at which SPEC_PART_CAP and not SPEC_MAX_STRIPS sets the number of strips"""
+    best = None
+    for rl in range(1, SPEC_MAXR + 1):
+        cap = gram_strips(1, rl)[0]
+        if cap >= SPEC_MAX_STRIPS:
+            continue
+        n = 256 * cap + 1   # the smallest n with ceil(n / 256) > cap
+        if best is None or n < best[0]:
+            best = (n, rl)
+    return best
+
+
+def test_strips_capped_by_the_partials(built):
+    """rank 497 (32 rank tiles, 528 tile pairs) leaves 31 strips; n = 7937 asks for 32.  Cheap for its size: a factor of 3.9 M
+    numbers and one eigen-solve of order 498 in the scratch."""
+    t0 = time.perf_counter()
+    n, r = _smallest_part_cap_case()
+    cap, strips, rps = gram_strips(n, r)
+    print("SPEC_PART_CAP binds first at n %d, rank %d: at most %d strips, %d of %d rows" % (n, r, cap, strips, rps))
+    assert (n, r) == (7937, 497)
+    assert min(SPEC_MAX_STRIPS, cap) < -(-n // 256) and cap < SPEC_MAX_STRIPS and rps > 256
+    path = common.generated_instance("spec_maxcut%d" % n, lambda: instances.maxcut(n, 2 * n, n))
+    s = _open_at_ranks(path, [r])
+    try:
+        _random_state(s, r)
+        worst = check_spectrum(s, host.PAIR_UV, "maxcut%d r=%d" % (n, r))
+        print("maxcut%d r=%d: worst ratios %.3g, %.3g, %.3g; %.2f s" % ((n, r) + tuple(worst) + (time.perf_counter() - t0,)))
+    finally:
+        s.close()
 
 
 def _rotation_bound(sweeps, rl):
