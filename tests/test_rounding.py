@@ -1,26 +1,63 @@
 """Hyperplane rounding and 1-flip local search on the GPU (Session.round_pm1) against the numpy model (tests/rounding_model.py):
-hyperplanes, signs, f before and after the search, the best trial, the dual bound, determinism, read-only continuation, refusals
-and the command line's --roundTrials / --roundFile."""
+hyperplanes, signs, f before and after the search, the best trial, cones past 1024 rows on a seeded factor, the dual bound,
+determinism, read-only continuation, refusals and the command line's --roundTrials / --roundFile."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from lorads_amd import host
+from lorads_amd import host, instances
 from lorads_amd.rounding import read_rounding
 from tests import common
 from tests import rounding_model as rm
 
 pytestmark = pytest.mark.gpu
 
-UNIT = {"maxcut100", "maxcut800", "blk4x60", "blkmix5", "densemaxcut120", "maxcut100odd"}
+UNIT = {"maxcut100", "maxcut800", "blk4x60", "blkmix5", "densemaxcut120", "maxcut100odd", "big2100", "densebig1100", "mixbig"}
 GOLDEN = {"maxcut100", "maxcut800", "blk4x60", "theta30", "rand120", "sdplp40", "mix4"}
+
+
+# Cones past 1024 rows, rounded from a seeded factor in the phase-1 state (source R).  One trip of the field pass covers FIELD_TRIP
+# rows: RND_STRIPS = 256 strips of TPB / 64 = 4 wavefronts, one row each (csrc/hip/rounding.inc).  The evaluation always launches the
+# 256 strips; a colour-class pass of the search launches min(256, ceil(rows / 4)).  Unit weights: C holds multiples of 1/4.
+BIG = {
+    "big2100": lambda: instances.maxcut(2100, 2100, 3000),               # sparse C; the first colour class alone has more than 1024 rows
+    "densebig1100": lambda: instances.dense_maxcut(1100, 70000, 1101),   # C kept dense (Cfull, stride npad)
+    "mixbig": lambda: instances.block_diag([instances.maxcut(90, 140, 71), instances.maxcut(2100, 2100, 3000),
+                                            instances.maxcut(120, 250, 72)]),   # a small cone before and after a large one
+}
+FIELD_TRIP = 1024
+BIG_SEED = 20261
+
+
+def field_trips(nrows, search):
+    """trips of the field pass's row loop over nrows rows, from the launch rule restated: the evaluation launches 256 strips, a
+    colour-class pass of the search min(256, ceil(nrows / 4)); a strip holds 4 wavefronts, each with one row per trip"""
+    strips = max(1, min(256, -(-nrows // 4))) if search else 256
+    return -(-nrows // (4 * strips))
+
+
+def seeded_session(name):
+    """(context of the generated instance `name` in its phase-1 state with R of every cone drawn from a fixed generator, R per cone
+    as the device holds it)"""
+    s = common.hip_session(_path(name))
+    rng = np.random.default_rng(BIG_SEED)
+    for k in range(s.nblk):
+        s.be.set_mat(host.MAT_R, k, rng.standard_normal(s.block_shape(k)))
+    return s, [s.be.get_mat(host.MAT_R, k) for k in range(s.nblk)]
+
+
+def class_sizes(adj):
+    """rows per colour class of one cone (the model's greedy colouring)"""
+    return np.bincount(rm.colouring(adj))
 
 
 def _path(name):
     if name == "maxcut100odd":
         name = "maxcut100"
+    if name in BIG:
+        return common.generated_instance(name, BIG[name])
     return common.instance_path(name) if name in GOLDEN else common.generated_instance(name)
 
 
@@ -56,7 +93,13 @@ _STATES = {}
 
 
 def _state(name):
-    """(session, model problem, R per cone, scale) after phase 1 and three ADMM steps, kept for the module"""
+    """(session, model problem, R per cone, scale) after phase 1 and three ADMM steps -- a name of BIG: in the phase-1 state with a
+    seeded R -- kept for the module"""
+    if name not in _STATES and name in BIG:
+        s, R = seeded_session(name)
+        P = rm.Pm1Problem.read(_path(name))
+        assert P.ok
+        _STATES[name] = (s, P, R, s.results()["scale_obj_his"])
     if name not in _STATES:
         kw = _odd_rank_params() if name == "maxcut100odd" else {}
         s, _, _ = _phase2(_path(name), **kw)
@@ -110,13 +153,9 @@ def test_hyperplanes_match_model(name):
 NAMES = ["maxcut100", "maxcut800", "blk4x60", "blkmix5", "wmaxcut150", "scaledpm1_120", "densemaxcut120", "maxcut100odd"]
 
 
-@pytest.mark.parametrize("K", [1, 63, 64, 1000])
-@pytest.mark.parametrize("name", NAMES)
-def test_rounding_without_local_search(name, K):
+def _check_start(name, K, seed):
     s, P, R, scale = _state(name)
-    if name == "maxcut100odd":
-        assert R[0].shape[1] % 2 == 1
-    r = s.round_pm1(trials=K, seed=K + 3, local_search_rounds=0, tol=0, hyperplanes=True)
+    r = s.round_pm1(trials=K, seed=seed, local_search_rounds=0, tol=0, hyperplanes=True)
     assert r.rounds == 0 and np.array_equal(r.obj, r.obj0) and r.best == r.best0
     sig, near = _model_start(P, R, r, K)
     keep = ~near
@@ -129,13 +168,20 @@ def test_rounding_without_local_search(name, K):
         assert np.array_equal(c.x, c.sigma * c.t)
         if keep[r.best]:
             assert np.array_equal(c.sigma, sig[k][:, r.best])
+    return near
 
 
-@pytest.mark.parametrize("name", ["maxcut100", "maxcut800", "blk4x60", "blkmix5", "densemaxcut120", "wmaxcut150", "scaledpm1_120"])
-def test_local_search(name):
+@pytest.mark.parametrize("K", [1, 63, 64, 1000])
+@pytest.mark.parametrize("name", NAMES)
+def test_rounding_without_local_search(name, K):
+    if name == "maxcut100odd":
+        assert _state(name)[2][0].shape[1] % 2 == 1
+    _check_start(name, K, seed=K + 3)
+
+
+def _check_search(name, K, seed):
     s, P, R, scale = _state(name)
-    K = 256
-    r = s.round_pm1(trials=K, seed=99, local_search_rounds=100, tol=0, hyperplanes=True)
+    r = s.round_pm1(trials=K, seed=seed, local_search_rounds=100, tol=0, hyperplanes=True)
     sig0, near = _model_start(P, R, r, K)
     keep = ~near
     assert np.all(r.obj <= r.obj0 + 1e-13 * np.maximum(1.0, np.abs(r.obj0)))
@@ -157,6 +203,60 @@ def test_local_search(name):
         f += float(c.x @ P.C[k] @ c.x)
     assert abs(f - r.f_best) <= 1e-13 * max(1.0, abs(f))
     assert r.rounds >= 1
+    return r, near
+
+
+@pytest.mark.parametrize("name", ["maxcut100", "maxcut800", "blk4x60", "blkmix5", "densemaxcut120", "wmaxcut150", "scaledpm1_120"])
+def test_local_search(name):
+    _check_search(name, 256, seed=99)
+
+
+def big_facts(name, s, scale, cones):
+    """what a case past 1024 rows rests on, asserted from the model (cones: (C, t, adj, R) per cone) and the device's image of the
+    cone: a cone whose evaluation takes a second trip; on the sparse ones a colour class whose search pass takes a second trip; on
+    the dense one C kept dense; every product C_pq t_p t_q a multiple of 1/4 and the objective unscaled"""
+    assert scale == 1.0
+    dims = [len(t) for _, t, _, _ in cones]
+    k = int(np.argmax(dims))
+    n, cls = dims[k], class_sizes(cones[k][2])
+    assert n > FIELD_TRIP and field_trips(n, search=False) >= 2
+    if name == "densebig1100":
+        assert s.hip_block_image(k)["dense_c"] == 1
+    else:
+        assert s.hip_block_image(k)["dense_c"] == 0
+        assert cls.max() > FIELD_TRIP and field_trips(int(cls.max()), search=True) == 2
+    if name == "mixbig":   # the large cone between two that leave most strips without a row
+        assert dims == [90, 2100, 120] and k == 1
+    assert all(np.array_equal(4 * C, np.round(4 * C)) and np.all(t == 1.0) for C, t, _, _ in cones)
+    print("%s: cone %d of %d rows (rank %d), classes %s: trips %d (evaluation), %d (search, largest class)"
+          % (name, k, n, cones[k][3].shape[1], cls.tolist() if len(cls) <= 8 else "%d of up to %d rows" % (len(cls), cls.max()),
+             field_trips(n, search=False), field_trips(int(cls.max()), search=True)))
+
+
+def _big_facts(name):
+    s, P, R, scale = _state(name)
+    big_facts(name, s, scale, [(P.C[k], P.t[k], P.adj[k], R[k]) for k in range(len(P.dims))])
+
+
+BIG_K = 65   # two sign words per row, the second with one live lane
+
+
+@pytest.mark.parametrize("name", sorted(BIG))
+def test_big_cones_without_local_search(name):
+    """cones past 1024 rows: the evaluation's row loop carries its partial sum over a second trip (and a third on 2100 rows)"""
+    _big_facts(name)
+    near = _check_start(name, BIG_K, seed=BIG_K + 3)
+    assert not near.any()   # (every trial is compared, the best one's signs among them)
+
+
+@pytest.mark.parametrize("name", sorted(BIG))
+def test_big_cones_local_search(name):
+    """the search on the same cones: on the sparse ones the first colour class is a row list of more than 1024 entries, read on a
+    second trip; f after the search, the rounds and the best trial's signs are the model's"""
+    _big_facts(name)
+    r, near = _check_search(name, BIG_K, seed=99)
+    assert not near.any()   # (so the rounds and the best trial's signs were compared)
+    print("%s: %d rounds" % (name, r.rounds))
 
 
 @pytest.mark.parametrize("name", ["maxcut100", "scaledpm1_120", "blk4x60"])

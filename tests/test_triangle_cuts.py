@@ -1,6 +1,7 @@
 """Separation of the triangle inequalities on the GPU (lorads_hip_triangle_cuts, Session.triangle_cuts, Session.write_tightened,
 --cutsMax) against the numpy model (tests/triangle_model.py): exact counts, the selection in its total order with any number of
-ties, determinism, read-only continuation, refusals, and the tightened problem solved on the device."""
+ties, packed indices past 32 bits and a wide rank on planted factors, determinism, read-only continuation, refusals, and the
+tightened problem solved on the device."""
 import ctypes as C
 import os
 import subprocess
@@ -156,6 +157,159 @@ def test_massive_ties():
         assert again[0] == cnt
         for a, b in zip(again[1:6], (p, q, s_, cl, v)):
             assert a.tobytes() == b.tobytes()
+    finally:
+        s.close()
+
+
+# ---- past 1024 rows: packed indices ((p n + q) n + s) 4 + class above 2^32, tiles I dealt by the cap of CUT_ITERS = 16 per workgroup, and
+# a rank as wide as maxcut20000's.  Planted integer factors (tests/triangle_model.py: plant_rows) make every v exact and give the
+# counts in closed form (checked against the full enumeration in test_triangle_model.py), so nothing is enumerated on the host.
+
+BIG_N = 1430
+
+
+def _deal(n):
+    """cut_launch's deal of the tiles I over blockIdx.y restated: (row tiles nt, the cap's term ceil(nt / 16), the small-cone term
+    min(nt, ceil(2048 / pairs)), tiles I the longest workgroup walks)"""
+    nt = -(-n // TILE)
+    npairs = nt * (nt + 1) // 2
+    cap, fill = -(-nt // 16), min(nt, -(-2048 // npairs))
+    return nt, cap, fill, -(-nt // max(cap, fill))
+
+
+def _assert_big_deal(n):
+    nt, cap, fill, walk = _deal(n)
+    assert (nt, n - (nt - 1) * TILE) == (45, 22)     # a ragged last tile of 22 rows
+    assert (cap, fill) == (3, 2) and cap > fill      # the cap's term decides the deal, as from n = 1409 on ...
+    assert walk == 15                                # ... and a workgroup walks up to 15 tiles I
+    assert 4 * n ** 3 > 1 << 32
+    assert all(_deal(m)[1] <= _deal(m)[2] for m in SIZES + [800])   # (in every other case the small-cone term decides)
+
+
+def _packed(n, p, q, s, cl):
+    return ((p.astype(np.int64) * n + q) * n + s) * 4 + cl
+
+
+def _same_bytes(a, b):
+    assert a[0] == b[0] and a[6] == b[6]
+    for x, y in zip(a[1:6], b[1:6]):
+        assert x.tobytes() == y.tobytes()
+
+
+def test_planted_directions_past_1024_rows():
+    """plant A: row p = D[p % 3].  477 477 476 pairs share v = 2, the same bits, and their indices run to 34 bits: the selection closes
+    on the index digits of the low word alone"""
+    n = BIG_N
+    _assert_big_deal(n)
+    hi, lo = tm.plant_counts(n)
+    assert np.bincount(np.arange(n) % 3).tolist() == [477, 477, 476] and hi == 477 * 477 * 476
+    s = _maxcut_session(n, 3)
+    try:
+        _load(s, tm.plant_rows(n))
+        assert _call(s, 1.5, 0)[0] == hi
+        assert _call(s, 0.5, 0)[0] == lo
+        got = _call(s, 1.5, 100)
+        cnt, p, q, s_, cl, v, passes = got
+        print("plant A: n %d, count %d above 1.5, %d above 0.5, kept %d, passes %d" % (n, cnt, lo, len(p), passes))
+        assert cnt == hi and len(p) == 100
+        assert (v == 2.0).all() and (cl == 0).all()
+        assert list(zip(p.tolist(), q.tolist(), s_.tolist())) == tm.first_distinct_triples(list(range(n)), 100)
+        # no digit above bit 34 tells two keys apart (v's 64 bits and the complement's leading ones): the first pass, seven that
+        # cannot narrow (shifts 104 .. 32 of 12 bits each; the last one sees bits 32 and 33), at least the emit
+        assert passes >= 9
+        _same_bytes(_call(s, 1.5, 100), got)
+    finally:
+        s.close()
+
+
+def test_planted_tail_has_every_index_above_2_32():
+    """plant B: zero rows but the last 96.  Every kept triple starts at p >= n - 96: its packed index does not fit 32 bits"""
+    n, live = BIG_N, 96
+    _assert_big_deal(n)
+    hi, lo = tm.plant_counts(n, live)
+    assert hi == 32 ** 3
+    s = _maxcut_session(n, 3)
+    try:
+        _load(s, tm.plant_rows(n, live))
+        assert _call(s, 0.5, 0)[0] == lo
+        got = _call(s, 1.5, 100)
+        cnt, p, q, s_, cl, v, passes = got
+        print("plant B: n %d, count %d, kept %d, passes %d, smallest packed index 2^%.2f" % (n, cnt, len(p), passes,
+                                                                                           np.log2(float(_packed(n, p, q, s_, cl).min()))))
+        assert cnt == hi and len(p) == 100
+        assert (v == 2.0).all() and (cl == 0).all()
+        assert (p >= n - live).all() and (_packed(n, p, q, s_, cl) > 1 << 32).all()
+        assert list(zip(p.tolist(), q.tolist(), s_.tolist())) == tm.first_distinct_triples(list(range(n - live, n)), 100)
+        _same_bytes(_call(s, 1.5, 100), got)
+    finally:
+        s.close()
+
+
+def test_scattered_support_past_1024_rows():
+    """200 unit rows of rank 6 at scattered positions of 1430, zero rows between them.  A triple with a zero row has two rho = 0 and
+    |third| <= 1: v <= 0.  So the list is the 200-row problem's with its rows renumbered -- the positions ascend, so the total order
+    carries over -- and its v are the bits the 200-row context gives (a rho depends on its two rows alone)"""
+    n, m, r, minv = BIG_N, 200, 6, 0.4
+    _assert_big_deal(n)
+    rng = np.random.default_rng(1430200)
+    fixed = np.array([0, 1023, 1024, 1408, 1429])
+    pos = np.sort(np.concatenate([fixed, rng.choice(np.setdiff1d(np.arange(n), fixed), m - len(fixed), replace=False)]))
+    assert len(np.unique(pos)) == m and set(fixed.tolist()) <= set(pos.tolist())
+    t = np.ones(m)
+    Fs = _sphere_rows(rng, m, r, t)
+    F = np.zeros((n, r))
+    F[pos] = Fs
+    back = np.full(n, -1)
+    back[pos] = np.arange(m)
+    big, small = _maxcut_session(n, r), _maxcut_session(m, r)
+    try:
+        _load(big, F)
+        _load(small, Fs)
+        cnt0 = _call(big, minv, 0)[0]
+        assert 100 < cnt0 and cnt0 + 7 <= 1 << 20
+        scans = None
+        for K in (1, 100, cnt0 + 7):
+            cnt, p, q, s_, cl, v, passes = _call(big, minv, K)
+            assert cnt == cnt0
+            mp, mq, ms = back[p], back[q], back[s_]
+            assert (mp >= 0).all() and (mq >= 0).all() and (ms >= 0).all()   # no triple with a zero row
+            scans = tm.check_against_model([(Fs, t)], minv, K, [cnt], np.zeros(len(p)), mp, mq, ms, cl, v,
+                                           scans=scans or [tm.Scan(Fs, t, minv, cnt0 + 8)])
+            c2, p2, q2, s2, cl2, v2, _ = _call(small, minv, K)
+            assert c2 == cnt and v2.tobytes() == v.tobytes() and cl2.tobytes() == cl.tobytes()
+            assert np.array_equal(p2, mp) and np.array_equal(q2, mq) and np.array_equal(s2, ms)
+        print("scattered support: count %d, %d of the kept triples reach past row 1024, largest packed index 2^%.2f"
+              % (cnt0, int((s_ >= 1024).sum()), np.log2(float(_packed(n, p, q, s_, cl).max()))))
+        assert (_packed(n, p, q, s_, cl) > 1 << 32).any() and (p == 0).any() and (s_ == n - 1).any()
+    finally:
+        big.close()
+        small.close()
+
+
+def test_wide_odd_rank_is_exact_on_integer_rows():
+    """rank 41 (padded to 44: 11 steps of the matrix cores, as maxcut20000's rank 40) on rows of integers in [-2, 2]: every product and
+    sum is exact, so the count and the kept values are the enumeration's with no tolerance, in the total order"""
+    n, r, minv = 200, 41, 50.5   # (v is an integer: none sits on the threshold)
+    F = np.random.default_rng(41200).integers(-2, 3, (n, r)).astype(np.float64)
+    t = np.ones(n)
+    P, Q, S, Cl, V = tm.enumerate_all(F, t)
+    assert np.array_equal(V, np.round(V)) and np.abs(V).max() < 2.0 ** 20
+    m = V > minv
+    o = tm.order(V[m], P[m], Q[m], S[m], Cl[m])
+    want = [x[m][o] for x in (P, Q, S, Cl, V)]
+    s = _maxcut_session(n, r)
+    try:
+        assert (r + 3) // 4 == 11
+        _load(s, F)
+        assert _call(s, minv, 0)[0] == int(m.sum()) > 100
+        for K in (100, int(m.sum()) + 7):
+            cnt, p, q, s_, cl, v, passes = _call(s, minv, K)
+            kept = min(K, int(m.sum()))
+            print("wide rank: n %d, r %d, count %d, kept %d, passes %d, v in [%g, %g]" % (n, r, cnt, len(p), passes, v.min(), v.max()))
+            assert cnt == int(m.sum()) and len(p) == kept
+            assert np.array_equal(v, tm.exact_values(F, t, p, q, s_, cl).astype(np.float64))
+            for got, w in zip((p, q, s_, cl, v), want):
+                assert np.array_equal(got, w[:kept])
     finally:
         s.close()
 

@@ -47,6 +47,26 @@ def test_model_against_triple_loop(n, r):
     assert keys == sorted(keys)
 
 
+@pytest.mark.parametrize("n,live", [(7, None), (12, None), (20, None), (35, None), (40, None), (20, 6), (37, 12), (40, 11), (40, 40)])
+def test_planted_counts_against_full_enumeration(n, live):
+    """the closed forms the separation's cases past 1024 rows rest on (plant_counts: all rows planted, and zero rows above the last
+    `live`), the values a planted triple takes and the kept list's first triples, against the stored enumeration"""
+    F, t = tm.plant_rows(n, live), np.ones(n)
+    assert np.array_equal(F[-1], tm.PLANT_D[(n - 1) % 3]) and (live is None or live == n or not F[0].any())
+    P, Q, S, Cl, V = tm.enumerate_all(F, t)
+    assert np.array_equal(V, tm.exact_values(F, t, P, Q, S, Cl).astype(np.float64))   # (small integers: exact in both)
+    assert set(V.tolist()) <= {2.0, 1.0, 0.0, -1.0, -2.0, -3.0, -5.0, -7.0}
+    hi, lo = tm.plant_counts(n, live)
+    assert int(np.count_nonzero(V > 1.5)) == hi and int(np.count_nonzero(V > 0.5)) == lo
+    top = V > 1.5
+    assert (V[top] == 2.0).all() and (Cl[top] == 0).all()
+    o = tm.order(V[top], P[top], Q[top], S[top], Cl[top])
+    rows = list(range(0 if live is None else n - live, n))
+    want = tm.first_distinct_triples(rows, 100)
+    assert len(want) == min(100, hi)
+    assert list(zip(P[top][o].tolist(), Q[top][o].tolist(), S[top][o].tolist()))[:100] == want
+
+
 @pytest.mark.parametrize("n,r,minv,K", [(30, 4, 0.05, 50), (41, 7, 1e-3, 10 ** 6), (25, 1, 0.0, 7), (33, 6, 0.3, 1)])
 def test_scan_against_full_enumeration(n, r, minv, K):
     """the streamed scan returns what the stored longdouble enumeration gives: counts at minv -+ eps and the top of the list"""

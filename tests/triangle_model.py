@@ -16,7 +16,11 @@ mantissa: its own error is 2^-11 of that) stands for the exact value.
                   min_violation, and the running top K -- re-evaluated in longdouble: exact counts at min_violation -+ eps and the
                   exact top of the list at sizes where nothing can be stored
   tightened       the tightened problem as a generator dict (lorads_amd.instances.write_sdpa writes it)
+  plant_rows      planted integer factors whose counts have closed forms (plant_counts) and whose kept list is known in advance
+                  (first_distinct_triples), at sizes where nothing can be enumerated on the host
 """
+from math import comb
+
 import numpy as np
 
 from lorads_amd.cuts import SIGNS
@@ -209,6 +213,48 @@ def check_against_model(cones, min_violation, max_cuts, counts, cone, p, q, s, c
         print("triangle cuts: max (v_unlisted - tau) / eps = %.3f" % float(np.max((mv[un] - tau) / me[un])))
         assert (mv[un] <= tau + me[un]).all()
     return scans
+
+
+PLANT_D = np.array([[1.0, -1.0, 0.0], [0.0, 1.0, -1.0], [-1.0, 0.0, 1.0]])   # norm^2 2 each, every pairwise dot -1
+
+
+def plant_rows(n, live=None):
+    """F (n x 3) with row p = PLANT_D[p % 3] on the last `live` rows (None: all of them) and zero above.  With t = 1 every rho is one of
+    2 (the same direction), -1 (two directions) and 0 (a zero row), so every v is a small integer, exact in any order:
+      three directions              v = 2 in class 0, -2 in the others
+      two rows of one direction     v = 1 in two classes, -1 and -5 in the others
+      one direction                 v = 1 in three classes, -7 in class 0
+      a zero row                    v <= -1 + |rho of the other two| <= 1"""
+    F = PLANT_D[np.arange(n) % 3]
+    if live is not None:
+        F[:n - live] = 0.0
+    return F
+
+
+def plant_counts(n, live=None):
+    """(pairs with v > 1.5, pairs with v > 0.5) of plant_rows(n, live) with t = 1, in closed form: c0 c1 c2 triples of three directions
+    give one pair each above 1.5; above 0.5 a triple of live rows with exactly two equal directions gives two more, one of a single
+    direction three, and a triple with one zero row and two live rows of one direction (rho = 0, 0, 2) two"""
+    live = n if live is None else live
+    c = np.bincount(np.arange(n - live, n) % 3, minlength=3).tolist()
+    distinct = c[0] * c[1] * c[2]
+    all_same = sum(comb(x, 3) for x in c)
+    two_same = comb(live, 3) - distinct - all_same
+    zero_and_pair = (n - live) * sum(comb(x, 2) for x in c)
+    return distinct, distinct + 2 * two_same + 3 * all_same + 2 * zero_and_pair
+
+
+def first_distinct_triples(rows, want):
+    """the first `want` triples p < q < s of the ascending row numbers `rows` with three different p % 3, in (p, q, s) order"""
+    out = []
+    for i, a in enumerate(rows):
+        for j in range(i + 1, len(rows)):
+            for c in rows[j + 1:]:
+                if len({a % 3, rows[j] % 3, c % 3}) == 3:
+                    out.append((a, rows[j], c))
+                    if len(out) == want:
+                        return out
+    return out
 
 
 def c5_problem():
