@@ -161,8 +161,11 @@ int lorads_hip_get_slack(lorads_hip_ctx *ctx, int32_t blk, int64_t *nnz, int32_t
  *   sign [sum_k n_k]        the best trial's signs (+1 / -1), cone after cone (may be NULL)
  *   rounds                  local-search rounds run (may be NULL)
  *   hyperplanes             per cone rank_k x trials (row-major: column j of cone k, then trial), cone after cone (may be NULL)
+ * Also qualifies (the rule: lorads_cut_rows.h): the cut-tightened form of such a context -- one LP block whose
+ * columns are all slacks of triangle rows (what lrd_session_write_tightened writes and its positive multiples).  The LP block has no
+ * signs (zeros in `sign`) and no hyperplanes; the local search colours the union pattern, cut positions included.
  * trials = 0 checks applicability only.  1 <= trials <= 65536.  Returns 2 when the context does not qualify (lorads_hip_last_error
- * names the first offending constraint or cone), 3 when it is sharded. */
+ * names the first offending constraint, cone or LP column), 3 when it is sharded. */
 int lorads_hip_round_pm1(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds, double *obj,
                          double *obj0, int32_t *best, int32_t *best0, int8_t *sign, int32_t *rounds, double *hyperplanes);
 
@@ -299,6 +302,8 @@ int lorads_hip_primal_apply(lorads_hip_ctx *ctx, int32_t src, int32_t blk, int32
  *   p, q, s, cls, viol [max_cuts]: the *kept = min(count, max_cuts) largest pairs in the total order "v descending, then p, q, s, class
  *     ascending" (0-based rows), written in that order -- exact with respect to the device's v whatever ties at the cut-off;
  *   max_cuts = 0 counts only (the five arrays and kept may then be NULL); passes (may be NULL): enumeration passes that ran.
+ * On a cut-tightened context the pairs that are rows of the problem already are neither counted nor listed:
+ * count is "violated and not present".
  * Read-only on the solver's state and deterministic (no float atomics; the same state and arguments give the same bits and list).
  * Scratch: the packed factor, max_cuts + 16384 keys rounded up to a power of two, one histogram.
  * Returns 1 on a bad argument (src, blk out of range or the LP block, max_cuts outside [0, 2^20], min_violation negative or not finite,

@@ -16,6 +16,7 @@
 // complement of ((p n + q) n + s) 4 + class -- larger keys come earlier in "v descending, then p, q, s, class ascending", and no two
 // pairs share a key.  The selection is select.inc's radix select on the key (shared with bounds.inc): ties of v are told apart by
 // the digits of the index, so any number of them is handled exactly.  Every pass enumerates anew (v is the same bits every time).
+// On a cut-tightened context (DESIGN.md section 20) the pairs that are rows already are passed over: k_cut_enum<CutArgsPresent>.
 // Read-only on the solver's state: the scratch is the feature's own (CutScratch), launches go straight to the stream (never through
 // LAUNCH).  No float atomics; the integer atomics of the counts, the histograms and the emit cursor commute, and the emitted keys are
 // sorted, so the same state and arguments give the same bits.
@@ -39,6 +40,26 @@ struct CutArgs {
     unsigned long long cap;
 };
 
+// The arguments of the enumeration on a cone of a cut-tightened context (DESIGN.md section 20) that holds cuts: the sorted packed
+// indices of the (triple, class) pairs that are rows of the problem already.  k_cut_enum<CutArgsPresent> passes over them in cut_handle,
+// the dense pass, alone: the gate and the tiles are k_cut_enum<CutArgs>'s, which a cone without cuts launches as it always did.
+struct CutArgsPresent : CutArgs {
+    const unsigned long long *present;
+    int npresent;
+};
+template <typename A> constexpr bool cut_excludes = false;
+template <> constexpr bool cut_excludes<CutArgsPresent> = true;
+
+// is `key` in the ascending list [0, n)?  (a binary search on the whole 64-bit packed index: past 2^32 for n > 1024)
+__device__ __forceinline__ bool cut_listed(const unsigned long long *__restrict__ list, int n, unsigned long long key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (list[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && list[lo] == key;
+}
+
 // out <- the tile rho[A][B] (transposed: out[b][a]): wavefront w forms the 16 x 16 quarter (w >> 1, w & 1) as D = F_A F_B^T in steps of
 // four columns (the operand layout of postsolve.inc's tiles: lane (nn, kk) supplies row nn, column k0 + kk of both and holds
 // D[kk + 4 q][nn]; not mfma_fm_tile itself: both operands are rows of the packed, padded F, with nothing to clamp or mask), then
@@ -61,8 +82,9 @@ __device__ __forceinline__ void cut_tile(const CutArgs &a, int A, int B, double 
 
 // One triple with a violated class, by its code (i << 10) | (j << 5) | sl inside the tiles at hand: the four v again from the same
 // three rho in the same order of operations (the same bits as the gate saw), every class with v > min_violation counted, binned or
-// emitted.
-__device__ __forceinline__ void cut_handle(const CutArgs &a, unsigned code, int I, int J, int K, const double (*pq)[CUT_LD],
+// emitted -- unless the problem holds it as a row already (CutArgsPresent).
+template <typename A>
+__device__ __forceinline__ void cut_handle(const A &a, unsigned code, int I, int J, int K, const double (*pq)[CUT_LD],
                                            const double (*ps)[CUT_LD], const double (*qs)[CUT_LD], unsigned *hist, SelAcc &acc) {
     const int i = code >> 10, j = (code >> 5) & 31, sl = code & 31;
     const double ra = pq[i][j], rb = ps[i][sl], rc = qs[sl][j];
@@ -74,6 +96,8 @@ __device__ __forceinline__ void cut_handle(const CutArgs &a, unsigned code, int 
 #pragma unroll
     for (int cl = 0; cl < 4; ++cl) { // (must match select.inc's select_item)
         if (!(v[cl] > a.minv)) continue;
+        if constexpr (cut_excludes<A>)
+            if (cut_listed(a.present, a.npresent, base + cl)) continue;
         const unsigned long long hi = (unsigned long long)__double_as_longlong(v[cl]), lo = ~(base + cl);
         if (a.mode == 2) {
             if (hi > a.khi || (hi == a.khi && lo >= a.klo)) {
@@ -99,7 +123,8 @@ __device__ __forceinline__ void cut_handle(const CutArgs &a, unsigned code, int 
 // > min_violation -- the same bits as the larger v (rounding is monotone and symmetric) -- into one bit per triple: no branch in the
 // loop.  The few triples that pass are then queued in LDS by their code (one cursor step per thread) and handled by all threads,
 // densely; what the queue cannot hold is handled on the spot.
-__global__ __launch_bounds__(TPB) void k_cut_enum(CutArgs a) {
+template <typename A>
+__global__ __launch_bounds__(TPB) void k_cut_enum(A a) {
     __shared__ double pq[CUT_T][CUT_LD], ps[CUT_T][CUT_LD], qs[CUT_T][CUT_LD]; // rho[p][q], rho[p][s], rho[q][s] as qs[s][q]
     __shared__ unsigned hist[CUT_BINS];
     __shared__ unsigned short queue[CUT_QUEUE];
@@ -173,12 +198,13 @@ __global__ __launch_bounds__(TPB) void k_cut_enum(CutArgs a) {
         if (hist[b]) atomicAdd(a.hist + b, (unsigned long long)hist[b]);
 }
 
-int cut_launch(lorads_hip_ctx *c, const CutArgs &a, int nt) {
+template <typename A>
+int cut_launch(lorads_hip_ctx *c, const A &a, int nt) {
     const long long npairs = (long long)nt * (nt + 1) / 2;
     // tiles I are dealt over blockIdx.y: at most CUT_ITERS per workgroup (the longest workgroups would otherwise run nt of them while
     // the device drains), and enough workgroups for a small cone
     const int split = (int)std::max<long long>(nblocks_for((size_t)nt, CUT_ITERS), std::min<long long>(nt, (2048 + npairs - 1) / npairs));
-    hipLaunchKernelGGL(k_cut_enum, dim3((unsigned)npairs, (unsigned)split), dim3(TPB), 0, c->stream, a);
+    hipLaunchKernelGGL(k_cut_enum<A>, dim3((unsigned)npairs, (unsigned)split), dim3(TPB), 0, c->stream, a);
     HC(hipGetLastError());
     return 0;
 }
@@ -207,14 +233,16 @@ extern "C" int lorads_hip_triangle_cuts(lorads_hip_ctx *c, int32_t src, int32_t 
     if (n > CUT_MAXN) return fail_msg("triangle_cuts: cone dimension above 2^20");
     CutScratch &X = c->cuts;
     const int nt = nblocks_for((size_t)n, CUT_T), npad = nt * CUT_T, rl4 = (B.rl + 3) & ~3;
-    CutArgs a{};
+    CutArgsPresent a{};
     if (X.Fp.grow(X.mem, (size_t)npad * rl4) || X.tp.grow(X.mem, (size_t)npad)) return 1;
     if (select_reserve(X.sel, X.mem, max_cuts, min_violation, a)) return 1;
     if (pack_factor(c, src, blk, npad, c->rnd.t + c->rnd.t_off[blk], X.Fp, X.tp)) return 1;
     a.n = n; a.rl4 = rl4;
     a.Fp = X.Fp; a.tp = X.tp;
+    a.npresent = c->rnd.lpk >= 0 ? c->rnd.npresent[blk] : 0;
+    a.present = a.npresent ? c->rnd.present[blk] : nullptr;
     std::vector<unsigned long long> khi, klo;
-    if (select_largest(c, "triangle_cuts", max_cuts, a, [&] { return cut_launch(c, a, nt); }, count, passes, khi, klo))
+    if (select_largest(c, "triangle_cuts", max_cuts, a, [&] { return a.npresent ? cut_launch(c, a, nt) : cut_launch(c, static_cast<const CutArgs &>(a), nt); }, count, passes, khi, klo))
         return 1;
     const size_t want = khi.size();
     if (want == 0) return 0;

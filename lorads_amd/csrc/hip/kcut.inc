@@ -142,45 +142,8 @@ __global__ __launch_bounds__(TPB) void k_kcut_field(int nrows, const int *__rest
     if (wv == 0 && valid) part[(size_t)t * RND_STRIPS + strip] = ((sh[0][lane] + sh[0][64 + lane]) + sh[0][128 + lane]) + sh[0][192 + lane];
 }
 
-// ---- the constraint data as the applicability checks read it (shared with stable.inc)
-// every stored entry, constraint by constraint: (block, row, column, coefficient); b; the LP block's objective
-struct ConEnt { int k, p, q; double a; };
-struct ConData {
-    std::vector<std::vector<ConEnt>> con;
-    std::vector<double> b, cobj;
-};
-int read_constraints(lorads_hip_ctx *c, ConData &D) {
-    D.con.assign((size_t)c->m, {});
-    D.b.assign((size_t)c->m, 0.0);
-    D.cobj.clear();
-    if (c->m) HC(hipMemcpyAsync(D.b.data(), c->b, sizeof(double) * D.b.size(), hipMemcpyDeviceToHost, c->stream));
-    for (int k = 0; k < c->nb; ++k) {
-        const Block &B = c->blk[k];
-        if (B.is_lp) { // (read_constraint_image below synchronises for this copy too)
-            D.cobj.resize((size_t)B.n);
-            if (B.n) HC(hipMemcpyAsync(D.cobj.data(), B.lp_cobj, sizeof(double) * D.cobj.size(), hipMemcpyDeviceToHost, c->stream));
-        }
-        ConImage m;
-        if (read_constraint_image(c, k, m)) return 1;
-        for (int i = 0; i < B.nrow; ++i)
-            for (int s = m.ap[i]; s < m.ap[i + 1]; ++s) D.con[(size_t)m.ri[i]].push_back({k, m.er[m.ae[s]], m.ec[m.ae[s]], m.av[s]});
-    }
-    return 0;
-}
-// what holds before any constraint is looked at: at most one LP block, a cone, no dense constraint matrices ("" or the reason)
-std::string blocks_admit_bound_rows(const lorads_hip_ctx *c, int *lpk) {
-    char msg[256];
-    int nlp = 0, nsdp = 0;
-    *lpk = -1;
-    for (int k = 0; k < c->nb; ++k) {
-        if (c->blk[k].is_lp) { ++nlp; *lpk = k; } else ++nsdp;
-    }
-    if (nlp > 1) return "more than one LP block";
-    if (nsdp == 0) return "no cone";
-    for (int k = 0; k < c->nb; ++k)
-        if (c->blk[k].dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); return msg; }
-    return "";
-}
+// ---- the constraint data as the applicability checks read it: read_constraints and blocks_admit_bound_rows of rounding.inc (shared
+// with its check of a cut-tightened context and with stable.inc)
 // entries of constraint E in the LP block lpk
 inline int lp_entries(const std::vector<ConEnt> &E, int lpk) {
     int lp = 0;

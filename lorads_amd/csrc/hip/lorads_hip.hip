@@ -76,6 +76,7 @@
 #include <vector>
 
 #include "lorads_hip.h"
+#include "lorads_cut_rows.h"
 #include "lorads_hip_dev.h"
 
 namespace {
@@ -644,6 +645,11 @@ struct RoundScratch : Applies {
     double *t = nullptr;                      // t_p = sqrt(b_i / a_i), cone k at t_off[k]
     std::vector<std::vector<int>> cls_ptr;    // per cone: colour class -> its range of the class-sorted row list
     int *cls_rows = nullptr;                  // class-sorted rows, cone k at t_off[k]
+    // a cut-tightened context (lpk >= 0: its LP block of slacks), left by rnd_check with t:
+    int lpk = -1;
+    std::vector<unsigned long long *> present; // per cone: the packed indices ((p n + q) n + s) 4 + class of its cuts, ascending, on the device
+    std::vector<int> npresent;                // how many (0: present[k] is null)
+    std::vector<double> lp_u;                 // [LP columns] u_j = 4 (-b / c) of the column's triangle row
     TrialScratch trial;                       // (G: the hyperplanes, rank x K per cone)
     DevBuf<unsigned long long> sgn;           // sign words, cone k at t_off[k] * W
     DevPool mem;

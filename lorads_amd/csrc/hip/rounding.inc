@@ -4,7 +4,8 @@
 // A context qualifies when it has no LP block and every constraint is a_i X_k[p,p] = b_i with b_i / a_i > 0, one per diagonal
 // position of every cone.  Then x = sigma o t (t_p = sqrt(b_i / a_i)) is feasible for every sigma in {+-1}^n.  Per cone and trial a
 // Gaussian hyperplane g (counter-based: it depends on (seed, cone, trial, column) alone) gives sigma_p = sign(R_p . g); f = x^T C x;
-// then a deterministic 1-flip local search by colour classes of C's off-diagonal graph.
+// then a deterministic 1-flip local search by colour classes of C's off-diagonal graph.  A context whose one LP block holds the slacks
+// of triangle cuts and nothing else qualifies too (rnd_check_tightened; DESIGN.md section 20): its field pass is k_rnd_field_cuts.
 //
 // Sign words: bit l of word sgn[w * n + p] is trial 64 w + l of row p (1: sigma = +1).  A wavefront works on one word (lane = trial),
 // so the words of a row's neighbours are wave-uniform loads.  Everything is read-only on the solver's state: R is formed on the fly
@@ -80,12 +81,16 @@ __global__ __launch_bounds__(TPB) void k_rnd_sign(int n, int rk, int r, int K, i
 //   eval (rows == null): per-workgroup partials of sum_p x_p (h_p + C_pp x_p), part[t * RND_STRIPS + strip]
 //   local search: the rows of one colour class; flip where Delta_p = -4 x_p h_p < -tau_p, tau_p = 2^-40 4 t_p sum_{q != p} |C_pq| t_q,
 //   and raise *flag (every writer writes 1).  No two rows of a class are adjacent: no row reads a word this launch writes.
-// The off-diagonal slots of a qualifying cone are untouched by constraints, so adj_sval holds their C; C_pp comes from cbase.
-__global__ __launch_bounds__(TPB) void k_rnd_field(int nrows, const int *__restrict__ rows, int n, int K, const int *__restrict__ adj_ptr,
-                                                   const int *__restrict__ adj_col, const int *__restrict__ adj_e,
-                                                   const double *__restrict__ adj_sval, const double *__restrict__ cbase,
-                                                   const double *__restrict__ Cfull, int npad, const double *__restrict__ tv,
-                                                   unsigned long long *__restrict__ sgn, double *__restrict__ part, int *__restrict__ flag) {
+// The off-diagonal slots of a cone without cut rows are untouched by constraints, so adj_sval holds their C; C_pp comes from cbase.
+// CUTS (k_rnd_field_cuts, a cut-tightened context: DESIGN.md section 20): the triangle rows touch off-diagonal slots, where adj_sval
+// is no longer C, so every slot's C comes from cbase[adj_e[.]] as in kcut_walk; a cut position outside C's pattern has C = 0 there and
+// adds a zero product, which changes no sum's bits.
+template <bool CUTS>
+__device__ __forceinline__ void rnd_field(int nrows, const int *__restrict__ rows, int n, int K, const int *__restrict__ adj_ptr,
+                                          const int *__restrict__ adj_col, const int *__restrict__ adj_e,
+                                          const double *__restrict__ adj_sval, const double *__restrict__ cbase,
+                                          const double *__restrict__ Cfull, int npad, const double *__restrict__ tv,
+                                          unsigned long long *__restrict__ sgn, double *__restrict__ part, int *__restrict__ flag) {
     __shared__ double sh[TPB];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int w = blockIdx.y, strip = blockIdx.x;
@@ -109,7 +114,7 @@ __global__ __launch_bounds__(TPB) void k_rnd_field(int nrows, const int *__restr
             for (int k = adj_ptr[p]; k < adj_ptr[p + 1]; ++k) {
                 const int q = adj_col[k];
                 if (q == p) { cpp = cbase[adj_e[k]]; continue; }
-                const double cq = adj_sval[k], tq = tv[q];
+                const double cq = CUTS ? cbase[adj_e[k]] : adj_sval[k], tq = tv[q];
                 h += cq * (((sw[q] >> lane) & 1ull) ? tq : -tq);
                 a += fabs(cq) * tq;
             }
@@ -130,6 +135,18 @@ __global__ __launch_bounds__(TPB) void k_rnd_field(int nrows, const int *__restr
     __syncthreads();
     if (wv == 0 && valid) part[(size_t)t * RND_STRIPS + strip] = ((sh[lane] + sh[64 + lane]) + sh[128 + lane]) + sh[192 + lane];
 }
+#define RND_FIELD_ARGS                                                                                                                  \
+    int nrows, const int *__restrict__ rows, int n, int K, const int *__restrict__ adj_ptr, const int *__restrict__ adj_col,           \
+        const int *__restrict__ adj_e, const double *__restrict__ adj_sval, const double *__restrict__ cbase,                          \
+        const double *__restrict__ Cfull, int npad, const double *__restrict__ tv, unsigned long long *__restrict__ sgn,               \
+        double *__restrict__ part, int *__restrict__ flag
+__global__ __launch_bounds__(TPB) void k_rnd_field(RND_FIELD_ARGS) {
+    rnd_field<false>(nrows, rows, n, K, adj_ptr, adj_col, adj_e, adj_sval, cbase, Cfull, npad, tv, sgn, part, flag);
+}
+__global__ __launch_bounds__(TPB) void k_rnd_field_cuts(RND_FIELD_ARGS) {
+    rnd_field<true>(nrows, rows, n, K, adj_ptr, adj_col, adj_e, adj_sval, cbase, Cfull, npad, tv, sgn, part, flag);
+}
+#undef RND_FIELD_ARGS
 
 // f[t] (= or +=) sum of the strips' partials of trial t, in strip order
 __global__ __launch_bounds__(TPB) void k_rnd_sum(int K, int nstrip, const double *__restrict__ part, double *__restrict__ f, int first) {
@@ -200,6 +217,95 @@ std::string diag_row(int gi, int p, int q, double a, double b, double *t) {
     return "";
 }
 
+// ---- the constraint data as the applicability checks read it (shared with kcut.inc and stable.inc)
+// every stored entry, constraint by constraint: (block, row, column, coefficient); b; the LP block's objective
+struct ConEnt { int k, p, q; double a; };
+struct ConData {
+    std::vector<std::vector<ConEnt>> con;
+    std::vector<double> b, cobj;
+};
+int read_constraints(lorads_hip_ctx *c, ConData &D) {
+    D.con.assign((size_t)c->m, {});
+    D.b.assign((size_t)c->m, 0.0);
+    D.cobj.clear();
+    if (c->m) HC(hipMemcpyAsync(D.b.data(), c->b, sizeof(double) * D.b.size(), hipMemcpyDeviceToHost, c->stream));
+    for (int k = 0; k < c->nb; ++k) {
+        const Block &B = c->blk[k];
+        if (B.is_lp) { // (read_constraint_image below synchronises for this copy too)
+            D.cobj.resize((size_t)B.n);
+            if (B.n) HC(hipMemcpyAsync(D.cobj.data(), B.lp_cobj, sizeof(double) * D.cobj.size(), hipMemcpyDeviceToHost, c->stream));
+        }
+        ConImage m;
+        if (read_constraint_image(c, k, m)) return 1;
+        for (int i = 0; i < B.nrow; ++i)
+            for (int s = m.ap[i]; s < m.ap[i + 1]; ++s) D.con[(size_t)m.ri[i]].push_back({k, m.er[m.ae[s]], m.ec[m.ae[s]], m.av[s]});
+    }
+    return 0;
+}
+// what holds before any constraint is looked at: at most one LP block, a cone, no dense constraint matrices ("" or the reason)
+std::string blocks_admit_bound_rows(const lorads_hip_ctx *c, int *lpk) {
+    char msg[256];
+    int nlp = 0, nsdp = 0;
+    *lpk = -1;
+    for (int k = 0; k < c->nb; ++k) {
+        if (c->blk[k].is_lp) { ++nlp; *lpk = k; } else ++nsdp;
+    }
+    if (nlp > 1) return "more than one LP block";
+    if (nsdp == 0) return "no cone";
+    for (int k = 0; k < c->nb; ++k)
+        if (c->blk[k].dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); return msg; }
+    return "";
+}
+
+// rnd_check on a context with an LP block, lpk: the cut-tightened +-1 structure (DESIGN.md section 20) by the rule the host applies to
+// the problem image (lorads_cut_rows.h: the same text, so the same first reason).  A context that qualifies leaves t, the sorted
+// packed indices of every cone's cuts on the device (a row named twice once) and u_j of the slack columns; one that does not leaves
+// its reason and allocates nothing.
+int rnd_check_tightened(lorads_hip_ctx *c, int lpk, const std::string &blocks) {
+    RoundScratch &X = c->rnd;
+    const std::string lead = "block " + std::to_string(lpk + 1) + " is an LP block";
+    X.checked = true;
+    if (!blocks.empty()) { X.why = lead + ": " + blocks; return 0; }
+    ConData D;
+    if (read_constraints(c, D)) { X.checked = false; return 1; }
+    std::vector<int> dim((size_t)c->nb), ptr((size_t)c->m + 1, 0);
+    std::vector<lrd_cr_entry> ent;
+    for (int k = 0; k < c->nb; ++k) dim[k] = c->blk[k].n;
+    for (int i = 0; i < c->m; ++i) {
+        for (const ConEnt &e : D.con[(size_t)i]) ent.push_back({e.k, e.p, e.q, e.a});
+        ptr[(size_t)i + 1] = (int)ent.size();
+    }
+    std::vector<double> th((size_t)X.t_off[c->nb] + 1, 0.0), u((size_t)dim[lpk] + 1, 0.0);
+    std::vector<lrd_cr_cut> cut((size_t)c->m + 1);
+    int ncut = 0;
+    char why[256];
+    const lrd_cr_problem P{c->m, c->nb, lpk, dim.data(), ptr.data(), ent.data(), D.b.data(), D.cobj.data()};
+    if (lrd_cr_check(&P, X.t_off.data(), th.data(), cut.data(), &ncut, u.data(), why, sizeof why)) {
+        X.why = lead + " whose columns are not all triangle-cut slacks: " + why;
+        return 0;
+    }
+    th.resize((size_t)X.t_off[c->nb]);
+    u.resize((size_t)dim[lpk]);
+    std::vector<std::vector<unsigned long long>> idx((size_t)c->nb);
+    for (int e = 0; e < ncut; ++e) {
+        const unsigned long long n = (unsigned long long)dim[cut[e].cone];
+        idx[cut[e].cone].push_back((((unsigned long long)cut[e].p * n + cut[e].q) * n + cut[e].s) * 4ull + (unsigned long long)cut[e].cls);
+    }
+    X.present.assign((size_t)c->nb, nullptr);
+    X.npresent.assign((size_t)c->nb, 0);
+    for (int k = 0; k < c->nb; ++k) {
+        std::sort(idx[k].begin(), idx[k].end());
+        idx[k].erase(std::unique(idx[k].begin(), idx[k].end()), idx[k].end());
+        X.npresent[k] = (int)idx[k].size();
+        if (!idx[k].empty() && X.mem.upload(&X.present[k], idx[k])) { X.checked = false; return 1; }
+    }
+    if (X.mem.upload(&X.t, th)) { X.checked = false; return 1; }
+    X.lpk = lpk;
+    X.lp_u = u;
+    X.qualifies = true;
+    return 0;
+}
+
 // applicability (once per context: the constraint data never changes); t of every cone to the device
 int rnd_check(lorads_hip_ctx *c) {
     RoundScratch &X = c->rnd;
@@ -208,13 +314,16 @@ int rnd_check(lorads_hip_ctx *c) {
     X.why.clear();
     X.t_off.assign(c->nb + 1, 0);
     for (int k = 0; k < c->nb; ++k) X.t_off[k + 1] = X.t_off[k] + c->blk[k].n;
+    {
+        int lpk = -1;
+        const std::string blocks = blocks_admit_bound_rows(c, &lpk);
+        if (lpk >= 0) return rnd_check_tightened(c, lpk, blocks);
+    }
     std::vector<double> b((size_t)c->m), th((size_t)X.t_off[c->nb], 0.0);
     if (c->m) HC(hipMemcpyAsync(b.data(), c->b, sizeof(double) * b.size(), hipMemcpyDeviceToHost, c->stream));
     HC(hipStreamSynchronize(c->stream));
     std::vector<int> per_con((size_t)c->m, 0);
     char msg[256];
-    for (int k = 0; k < c->nb && X.why.empty(); ++k)
-        if (c->blk[k].is_lp) { snprintf(msg, sizeof msg, "block %d is an LP block", k + 1); X.why = msg; }
     for (int k = 0; k < c->nb && X.why.empty(); ++k) {
         const Block &B = c->blk[k];
         if (B.dense_a) { snprintf(msg, sizeof msg, "cone %d stores dense constraint matrices", k + 1); X.why = msg; break; }
@@ -499,7 +608,7 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
         return 1;
     auto field = [&](int k, const int *rows, int nrows) {
         const Block &B = c->blk[k];
-        hipLaunchKernelGGL(k_rnd_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K,
+        hipLaunchKernelGGL(X.lpk >= 0 ? k_rnd_field_cuts : k_rnd_field, dim3(field_strips(rows, nrows), W), dim3(TPB), 0, c->stream, nrows, rows, B.n, K,
                            (const int *)B.pu.adj_ptr, (const int *)B.pu.adj_col, (const int *)B.pu.adj_e, (const double *)B.pu.adj_sval,
                            (const double *)B.pu.cbase, (const double *)(B.dense_c ? B.Cfull : nullptr), B.npad,
                            (const double *)(X.t + X.t_off[k]), X.sgn + (size_t)X.t_off[k] * W, T.part.p, T.ctl);
@@ -511,6 +620,10 @@ extern "C" int lorads_hip_round_pm1(lorads_hip_ctx *c, int32_t src, int32_t tria
         std::vector<unsigned long long> words;
         for (int k = 0; k < c->nb; ++k) {
             const int n = c->blk[k].n;
+            if (c->blk[k].is_lp) { // (the slacks of a cut-tightened context have no sign: zeros)
+                for (int p = 0; p < n; ++p) sign[X.t_off[k] + p] = 0;
+                continue;
+            }
             words.resize((size_t)n);
             if (n) HC(hipMemcpyAsync(words.data(), X.sgn + (size_t)X.t_off[k] * W + (size_t)w * n, sizeof(unsigned long long) * n,
                                      hipMemcpyDeviceToHost, c->stream));

@@ -373,7 +373,10 @@ typedef struct {
 typedef struct {
     lrd_round_head head;
     int nblk;
-    lrd_rounding_cone *cone; /* [nblk], file order */
+    lrd_rounding_cone *cone; /* [nblk], file order; the LP block of a cut-tightened problem (section 20) is an empty cone, n = 0 */
+    /* a cut-tightened problem: the bound has the k-cut's LP term, d = ... + sum_j u_j min(0, s_j) over the slack columns */
+    int nlp, lp_neg;         /* LP columns; how many of their dual slacks were negative (as lrd_kcut) */
+    double *lp_upper;        /* [nlp] u_j (NULL without an LP block) */
 } lrd_rounding;
 /* trials = 0: applicability alone (*out stays NULL).  Returns 2 when the context does not qualify or the table lacks the slot, 3 when
  * it is sharded.  with_hyperplanes: also fill every cone's G. */
@@ -489,6 +492,29 @@ void lrd_cuts_free(lrd_cuts *c);
  * writes the problem alone.  A pure function of the problem image and the list.  1: cannot write; 2: a cut outside the problem or a
  * problem with an LP block; 3: sharded. */
 int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts);
+/* The cut-tightened +-1 structure (the rule: include/lorads_cut_rows.h, the device check's own).  The cuts a
+ * problem with one LP block holds, in constraint order: triple, class, constraint and LP column (0-based), scale = -b / c (1 as
+ * written: the slack x_j / scale = 1 + sum_w sign_w rho_w), and t of all blocks, stacked (zero on the LP block).  A problem without an
+ * LP block: n = 0, lpk = -1, t NULL. */
+typedef struct {
+    int n, lpk;
+    int *cone, *p, *q, *s, *cls, *row, *col;
+    double *scale, *t;
+} lrd_present;
+/* 0; 2: the LP block's columns are not all triangle-cut slacks (the first reason: lrd_cuts_why()); 3: sharded */
+int lrd_session_present_cuts(lrd_session *s, lrd_present **out);
+void lrd_present_free(lrd_present *c);
+/* the reason of the last refusal (rc 2) of lrd_session_present_cuts and lrd_session_write_tightened_keep */
+const char *lrd_cuts_why(void);
+/* lrd_session_write_tightened that also takes a cut-tightened problem: the new cuts follow as constraints m + 1 ... and as columns of
+ * the LP block behind its own, the block stays where it is.  keep (NULL: all; else [nkeep], nkeep = the present cuts' number, in
+ * lrd_session_present_cuts' order): a present cut with keep[e] = 0 leaves with its constraint and its column, the others are renumbered
+ * in order.  A problem without an LP block takes no mask and gives lrd_session_write_tightened's bytes.  2 as well: a new cut that is
+ * already in the problem or listed twice, an LP block that is not all cut slacks. */
+int lrd_session_write_tightened_keep(lrd_session *s, const char *path, const lrd_cuts *cuts, const unsigned char *keep, int nkeep);
+/* ... with the mask from the session's current point (lrd_session_solution at Lanczos tolerance tol): a present cut leaves when its
+ * slack x_j / scale_j = 1 + sum_w sign_w rho_w exceeds drop_slack.  *dropped (may be NULL): how many left. */
+int lrd_session_write_tightened_drop(lrd_session *s, const char *path, const lrd_cuts *cuts, double drop_slack, double tol, int *dropped);
 
 /* ---- entry bounds on the primal X (bounds.c).  Every pair p < q of an SDP cone has two inequalities: class 0,
  * X_pq >= lower with v = lower - X_pq, and class 1, X_pq <= upper with v = X_pq - upper; v > min_violation is a violation. */

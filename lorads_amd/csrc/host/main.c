@@ -26,6 +26,9 @@ int lrd_session_round(lrd_session *s, int trials, uint64_t seed, int max_rounds,
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s file.dat-s [--option value ...]   (options: the reference's long options)\n", argv[0]);
+        fprintf(stderr, "  --cutsMax K [--cutsMinViolation V] [--cutsFile OUT.dat-s] [--cutsDropSlack S] and --roundTrials T also take a file\n"
+                        "  that --cutsFile wrote: the cuts it holds are passed over, the new ones appended, and with --cutsDropSlack the\n"
+                        "  ones whose slack exceeds S dropped\n");
         return 2;
     }
     lrd_session *s = lrd_session_open(argv[1]);
@@ -49,6 +52,7 @@ int main(int argc, char **argv) {
     double cuts_minv = 1e-3;
     int cuts_minv_given = 0;
     const char *cuts_file = NULL;
+    double cuts_drop = -1.0;          /* --cutsDropSlack S: a present cut of a cut-tightened file leaves when its slack exceeds S (< 0: none) */
     int bounds_max = -1;              /* separation of entry bounds lower <= X_pq <= upper (ours as well) */
     double bounds_lower = 0.0, bounds_upper = HUGE_VAL, bounds_minv = 1e-3;
     const char *bounds_file = NULL, *bounds_other = NULL; /* bounds_other: some --bounds* option other than --boundsMax was given */
@@ -102,6 +106,17 @@ int main(int argc, char **argv) {
             }
             if (is_max) cuts_max = (int)k;
             else { cuts_minv = t; cuts_minv_given = 1; }
+            continue;
+        }
+        if (!strcmp(argv[i], "--cutsDropSlack")) {
+            char *end = NULL;
+            const double t = strtod(argv[i + 1], &end);
+            if (!end || end == argv[i + 1] || *end || !(t >= 0) || !(t < HUGE_VAL)) {
+                fprintf(stderr, "bad value %s of %s\n", argv[i + 1], argv[i]);
+                lrd_session_close(s);
+                return 2;
+            }
+            cuts_drop = t;
             continue;
         }
         if (!strcmp(argv[i], "--boundsFile")) { bounds_other = argv[i]; bounds_file = argv[i + 1]; continue; }
@@ -182,8 +197,8 @@ int main(int argc, char **argv) {
         lrd_session_close(s);
         return 2;
     }
-    if ((cuts_file || cuts_minv_given) && cuts_max < 0) {
-        fprintf(stderr, "%s needs --cutsMax\n", cuts_file ? "--cutsFile" : "--cutsMinViolation");
+    if ((cuts_file || cuts_minv_given || cuts_drop >= 0) && cuts_max < 0) {
+        fprintf(stderr, "%s needs --cutsMax\n", cuts_file ? "--cutsFile" : cuts_minv_given ? "--cutsMinViolation" : "--cutsDropSlack");
         lrd_session_close(s);
         return 2;
     }
@@ -397,7 +412,8 @@ int main(int argc, char **argv) {
     }
     if (cuts_max > 0) {
         lrd_cuts *x = NULL;
-        if (lrd_session_triangle_cuts(s, cuts_minv, cuts_max, &x) || (cuts_file && lrd_session_write_tightened(s, cuts_file, x))) {
+        if (lrd_session_triangle_cuts(s, cuts_minv, cuts_max, &x) || (cuts_file && (cuts_drop >= 0 ? lrd_session_write_tightened_drop(s, cuts_file, x, cuts_drop, 1e-8, NULL)
+                                                                                                : lrd_session_write_tightened(s, cuts_file, x)))) {
             fprintf(stderr, "lorads: the separation failed%s%s\n", cuts_file ? " or cannot write " : "", cuts_file ? cuts_file : "");
             lrd_cuts_free(x);
             lrd_session_close(s);
@@ -456,6 +472,7 @@ int main(int argc, char **argv) {
         printf("\t best trial                      : %d (before the local search: %d)\n", x->head.best, x->head.best0);
         printf("\t f = x^T C x before local search : %.10e\n\t f = x^T C x after local search  : %.10e\n", x->head.f_best0, x->head.f_best);
         printf("\t dual bound d                    : %.10e\n\t gap (f - d) / max(1, |d|)       : %.6e\n", x->head.bound, x->head.gap);
+        if (x->nlp > 0) printf("\t triangle cuts in the problem     : %d (%d with a negative dual slack)\n", x->nlp, x->lp_neg);
         lrd_rounding_free(x);
     }
     if (kcut_parts > 0) {

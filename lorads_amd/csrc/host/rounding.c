@@ -25,6 +25,7 @@ void lrd_rounding_free(lrd_rounding *r) {
         free(q->sigma); free(q->t); free(q->x); free(q->G);
     }
     free(r->cone);
+    free(r->lp_upper);
     lrd_round_head_free(&r->head);
     free(r);
 }
@@ -140,9 +141,18 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
     }
     lrd_round_head_scale(h);
     size_t at = 0, gat = 0;
+    int lpk = -1;
     for (int k = 0; k < p->nblk; ++k) { /* t from the problem: the one constraint on every diagonal (the backend has checked it) */
         const lrd_block *b = &p->blk[k];
         lrd_rounding_cone *q = &r->cone[k];
+        if (b->is_lp) { /* the slacks of a cut-tightened problem: no signs and no hyperplanes, an empty cone of the result */
+            lpk = k;
+            q->sigma = (int8_t *)lrd_zalloc(0, 1);
+            q->t = (double *)lrd_zalloc(0, sizeof(double));
+            q->x = (double *)lrd_zalloc(0, sizeof(double));
+            at += (size_t)b->n;
+            continue;
+        }
         const int n = b->n;
         q->n = n; q->rank = v->rank[k];
         q->sigma = (int8_t *)calloc((size_t)(n > 0 ? n : 1), 1);
@@ -150,6 +160,7 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
         q->x = (double *)calloc((size_t)(n > 0 ? n : 1), sizeof(double));
         for (int i = 0; i < b->nrow; ++i) {
             const int e = b->a_ptr[i];
+            if (b->a_ptr[i + 1] - e != 1 || b->a_row[e] != b->a_col[e]) continue; /* (a triangle row of a cut-tightened problem) */
             q->t[b->a_row[e]] = sqrt(p->b[b->row_idx[i]] / b->a_val[e]);
         }
         q->T = 0.0;
@@ -169,8 +180,26 @@ int lrd_session_round_ex(lrd_session *s, int trials, uint64_t seed, int max_roun
     free(sign); free(g);
     double *T = (double *)calloc(2 * (size_t)(p->nblk > 0 ? p->nblk : 1), sizeof(double)), *lm = T + (p->nblk > 0 ? p->nblk : 1);
     for (int k = 0; k < p->nblk; ++k) T[k] = r->cone[k].T;
-    rc = lrd_round_head_bound(h, be, p->nblk, p->nblk, NULL, T, -1, 0, NULL, NULL, lm);
-    for (int k = 0; k < p->nblk; ++k) r->cone[k].lam_min = lm[k];
+    if (lpk < 0) {
+        rc = lrd_round_head_bound(h, be, p->nblk, p->nblk, NULL, T, -1, 0, NULL, NULL, lm);
+        for (int k = 0; k < p->nblk; ++k) r->cone[k].lam_min = lm[k];
+    } else { /* cut-tightened: the LP term of the k-cut's bound with u_j = 4 scale_j of column j's triangle row (cuts.c) */
+        lrd_present *pc = NULL;
+        rc = lrd_session_present_cuts(s, &pc);
+        int *blk = (int *)lrd_zalloc((size_t)p->nblk, sizeof(int)), nsdp = 0;
+        for (int k = 0; k < p->nblk; ++k)
+            if (k != lpk) { blk[nsdp] = k; T[nsdp++] = r->cone[k].T; }
+        if (!rc) {
+            r->nlp = p->blk[lpk].n;
+            r->lp_upper = (double *)lrd_zalloc((size_t)r->nlp, sizeof(double));
+            for (int e = 0; e < pc->n; ++e) r->lp_upper[pc->col[e]] = 4.0 * pc->scale[e];
+            rc = lrd_round_head_bound(h, be, p->nblk, nsdp, blk, T, lpk, r->nlp, r->lp_upper, &r->lp_neg, lm);
+            r->cone[lpk].lam_min = NAN;
+            for (int i = 0; i < nsdp; ++i) r->cone[blk[i]].lam_min = lm[i];
+        }
+        lrd_present_free(pc);
+        free(blk);
+    }
     free(T);
     if (rc) { lrd_rounding_free(r); return 1; }
     *out = r;

@@ -6,7 +6,9 @@ With rho_xy = X_xy / (t_x t_y) every triple p < q < s of a cone has four inequal
 
 and v = -1 - lhs > 0 is a violation.  The enumeration is the device's (Session.triangle_cuts); here: the struct mirror, the
 result object and a reader of the cut list out of a tightened problem file (Session.write_tightened)."""
+import collections
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -20,6 +22,27 @@ class CutsStruct(C.Structure):
                 ("count", C.POINTER(C.c_int64)), ("kept", C.c_int), ("passes", C.c_int),
                 ("cone", C.POINTER(C.c_int)), ("p", C.POINTER(C.c_int)), ("q", C.POINTER(C.c_int)), ("s", C.POINTER(C.c_int)),
                 ("cls", C.POINTER(C.c_int8)), ("viol", C.POINTER(C.c_double))]
+
+
+class PresentStruct(C.Structure):
+    """lrd_present (csrc/host/lorads_host.h)"""
+    _fields_ = [("n", C.c_int), ("lpk", C.c_int)] + [(f, C.POINTER(C.c_int)) for f in ("cone", "p", "q", "s", "cls", "row", "col")] + \
+               [("scale", C.POINTER(C.c_double)), ("t", C.POINTER(C.c_double))]
+
+
+class PresentCut(collections.namedtuple("PresentCut", "cone p q s cls row column scale")):
+    """A triangle cut that a cut-tightened problem holds as a row (Session.present_cuts): its triple and class, its constraint and its
+    LP column (all 0-based), and scale = -b / c of the row (1 as written).  Compares as the tuple (cone, p, q, s, cls, row, column)."""
+    __slots__ = ()
+
+    def __eq__(self, other):
+        return tuple(self[:7]) == tuple(other[:7])
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(tuple(self[:7]))
 
 
 class Cuts:
@@ -101,3 +124,44 @@ def read_tightened(path, m_original):
             raise ValueError("constraint %d has the signs of no class" % e)
         out.append((k - 1, p - 1, q - 1, s - 1, cl[0]))
     return out
+
+
+CutRound = collections.namedtuple("CutRound", "path pObj d f_best gap present added dropped count")
+
+
+def cut_loop(path, workdir, rounds, max_cuts=1000, min_violation=1e-3, drop_slack=None, trials=1024, seed=0, local_search_rounds=100,
+             tol=1e-8, **solve_options):
+    """Rounds of solve, round, separate and tighten on a +-1-structured problem file.  Round i opens its file
+    (round 0: `path`), solves it (solve_options: Session.set_params), rounds the point (Session.round_pm1), separates the triangle
+    inequalities that are not rows yet (Session.triangle_cuts) and writes the next file, workdir/round<i + 1>.dat-s
+    (Session.write_tightened with drop_slack), one context at a time.  It stops after `rounds` rounds, or as soon as nothing is
+    violated.  Returns (history, f_best, sign): per round a CutRound (the file it solved, pObj, the dual bound d, the round's own
+    f_best and gap, the cuts the file held, the cuts added to and dropped from the next, the violated count), and the best +-1 point
+    of all rounds.  Every round's d bounds every round's f: the cuts hold at every +-1 point."""
+    from .host import Session
+    os.makedirs(workdir, exist_ok=True)
+    history, best_f, best_sign = [], np.inf, None
+    for i in range(int(rounds)):
+        s = Session.open(path)
+        try:
+            s.set_params(**dict(dict(verbose=0), **solve_options))
+            s.prepare(1, 0)
+            s.attach_hip(lbfgs_len=int(solve_options.get("lbfgsListLength", 2)))
+            res = s.solve()
+            present = len(s.present_cuts())
+            r = s.round_pm1(trials=trials, seed=seed, local_search_rounds=local_search_rounds, tol=tol)
+            if r.f_best < best_f:
+                best_f, best_sign = r.f_best, r.sign.copy()
+            cuts = s.triangle_cuts(max_cuts=max_cuts, min_violation=min_violation)
+            count, added, dropped, nxt = int(cuts.count.sum()), 0, 0, None
+            if count > 0 and i + 1 < int(rounds):
+                nxt = os.path.join(workdir, "round%d.dat-s" % (i + 1))
+                dropped = s.write_tightened(nxt, cuts, drop_slack=drop_slack if present else None)
+                added = len(cuts)
+            history.append(CutRound(path, res["pObj"], r.bound, r.f_best, r.gap, present, added, dropped, count))
+        finally:
+            s.close()
+        if nxt is None:
+            break
+        path = nxt
+    return history, best_f, best_sign

@@ -1136,7 +1136,8 @@ class Session:
         """Goemans-Williamson hyperplane rounding of the current point with a 1-flip local search, on the device
         (lorads_amd.rounding.Rounding, file units): per trial f = x^T C x before and after the search, the best trial's signs and
         x = sigma o t per cone, and the dual bound d = b.y + sum_k T_k min(0, lambda_min(S_k)) at Lanczos tolerance tol (tol <= 0:
-        NaN).  trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
+        NaN).  On a cut-tightened problem (what write_tightened wrote) d also has the slacks' term sum_j u_j min(0, s_j), u_j = 4.
+        trials = 0 checks applicability alone (None).  Read-only on the solver's state."""
         return self._rounded("pm1", None, trials, seed, local_search_rounds, tol, hyperplanes)
 
     def write_rounding(self, path, trials=1024, seed=0, local_search_rounds=100, tol=1e-8):
@@ -1184,7 +1185,8 @@ class Session:
         """Separation of the triangle inequalities of a +-1-structured problem at the current point, on the device
         (lorads_amd.cuts.Cuts): with rho_xy = X_xy / (t_x t_y) all 4 C(n, 3) inequalities of every cone are enumerated (X is never
         formed), the ones violated by more than min_violation counted exactly, and the max_cuts most violated returned, ordered by
-        (violation descending, cone, p, q, s, cls ascending).  Read-only on the solver's state, deterministic."""
+        (violation descending, cone, p, q, s, cls ascending).  On a cut-tightened problem (what write_tightened wrote) the
+        inequalities that are rows already are neither counted nor returned.  Read-only on the solver's state, deterministic."""
         from .cuts import Cuts, CutsStruct
         ptr = C.POINTER(CutsStruct)()
         self.lib.lrd_session_triangle_cuts.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.POINTER(CutsStruct))]
@@ -1199,16 +1201,61 @@ class Session:
         finally:
             self.lib.lrd_cuts_free(ptr)
 
-    def write_tightened(self, path, cuts):
-        """The problem as it was read plus one constraint and one slack column (a new last LP block) per cut, in SDPA sparse format
-        (the command line's --cutsFile: the same C writer, the same bytes).  cuts: a lorads_amd.cuts.Cuts or None."""
-        from .cuts import CutsStruct
-        self.lib.lrd_session_write_tightened.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct)]
-        st = cuts.to_struct() if cuts is not None else None
-        rc = self.lib.lrd_session_write_tightened(self.h, os.fsencode(path), C.byref(st) if st is not None else None)
+    def _cuts_why(self):
+        self.lib.lrd_cuts_why.restype = C.c_char_p
+        return (self.lib.lrd_cuts_why() or b"").decode()
+
+    def present_cuts(self):
+        """The triangle cuts a cut-tightened problem holds, read off the problem as it was opened: a list of
+        lorads_amd.cuts.PresentCut (cone, p, q, s, cls, row, column; 0-based, in constraint order).  [] without an LP block;
+        ValueError with the first reason when the LP block's columns are not all triangle-cut slacks (the device's rule and words)."""
+        from .cuts import PresentCut, PresentStruct
+        ptr = C.POINTER(PresentStruct)()
+        self.lib.lrd_session_present_cuts.argtypes = [C.c_void_p, C.POINTER(C.POINTER(PresentStruct))]
+        self.lib.lrd_present_free.argtypes, self.lib.lrd_present_free.restype = [C.POINTER(PresentStruct)], None
+        rc = self.lib.lrd_session_present_cuts(self.h, C.byref(ptr))
         if rc == 2:
-            raise ValueError("a cut lies outside the problem, names a row no constraint fixes, or the problem has an LP block")
+            raise ValueError(self._cuts_why())
+        if rc == 3:
+            raise NotImplementedError("the cuts of a sharded deal (world > 1) are not supported")
+        _check(rc, "present_cuts")
+        try:
+            st = ptr.contents
+            return [PresentCut(st.cone[e], st.p[e], st.q[e], st.s[e], st.cls[e], st.row[e], st.col[e], st.scale[e]) for e in range(st.n)]
+        finally:
+            self.lib.lrd_present_free(ptr)
+
+    def write_tightened(self, path, cuts, drop_slack=None, keep=None):
+        """The problem as it was read plus one constraint and one slack column per cut, in SDPA sparse format (the command line's
+        --cutsFile: the same C writer, the same bytes).  cuts: a lorads_amd.cuts.Cuts or None.  The slacks are a new last LP block, or,
+        on a cut-tightened problem, new columns behind its own.  There, drop_slack: a present cut leaves (its row and column with
+        it, the others renumbered in order) when its slack in the row's rho units, x_j / scale_j = 1 + sum sign rho at the current
+        point, exceeds it (the command line's --cutsDropSlack); keep: the mask itself, one flag per present_cuts() entry.
+        Returns how many present cuts left."""
+        from .cuts import CutsStruct
+        st = cuts.to_struct() if cuts is not None else None
+        cp = C.byref(st) if st is not None else None
+        dropped = C.c_int(0)
+        if keep is not None:
+            if drop_slack is not None:
+                raise ValueError("write_tightened: drop_slack and keep exclude each other")
+            mask = np.ascontiguousarray(np.asarray(keep, dtype=bool), dtype=np.uint8)
+            self.lib.lrd_session_write_tightened_keep.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct), C.c_void_p, C.c_int]
+            rc = self.lib.lrd_session_write_tightened_keep(self.h, os.fsencode(path), cp, mask.ctypes.data_as(C.c_void_p), len(mask))
+            dropped.value = int(len(mask) - mask.sum())
+        elif drop_slack is not None:
+            self.lib.lrd_session_write_tightened_drop.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct), C.c_double, C.c_double,
+                                                                  C.POINTER(C.c_int)]
+            rc = self.lib.lrd_session_write_tightened_drop(self.h, os.fsencode(path), cp, float(drop_slack), 1e-8, C.byref(dropped))
+        else:
+            self.lib.lrd_session_write_tightened.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct)]
+            rc = self.lib.lrd_session_write_tightened(self.h, os.fsencode(path), cp)
+        if rc == 2:
+            why = self._cuts_why()
+            raise ValueError("a cut lies outside the problem, names a row no constraint fixes, or the problem has an LP block that "
+                             "is not all cut slacks" + (": " + why if why else ""))
         _check(rc, "write_tightened")
+        return dropped.value
 
     def entry_bounds(self, max_cuts=1000, lower=0.0, upper=None, min_violation=1e-3):
         """Separation of the entry bounds lower <= X_pq <= upper (p < q) of every SDP cone at the current point, on the device
