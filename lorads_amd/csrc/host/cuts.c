@@ -1,8 +1,8 @@
 /* cuts.c -- separation of the triangle inequalities of a +-1-structured problem and the tightened problem file (DESIGN.md
- * section 14).  The enumeration is the backend's (lrd_backend.triangle_cuts); here: the session-level driver that merges the cones'
- * lists (lrd_merge_runs, shared with bounds.c like lrd_write_problem_as_read), and the writer of the problem with one constraint and one slack column per cut, a pure function of the problem image and
- * the cut list (so the format can be checked without a GPU).  A tightened problem can be tightened again: the
- * recogniser of the cuts it holds (lrd_session_present_cuts) and the writer that appends to and drops from them. */
+ * section 14).  The enumeration is the backend's (lrd_backend.triangle_cuts) and the session-level driver separation.c's; here: the
+ * list, its order and its slot call, and the tightened problem -- the validation of a cut list and the rows it becomes, one constraint
+ * and one slack column per cut, handed to separation.c's writer.  A tightened problem can be tightened again:
+ * the recogniser of the cuts it holds (lrd_session_present_cuts), the duplicate check and the mask of the cuts that leave. */
 #include "lorads_host.h"
 #include "lorads_cut_rows.h"
 
@@ -20,39 +20,6 @@ void lrd_cuts_free(lrd_cuts *c) {
     free(c);
 }
 
-int lrd_merge_runs(const void *list, int (*before)(const void *list, int a, int b), const lrd_column *col, int ncol, int at, int got,
-                   int max_cuts) {
-    const int tot = at + got, keep = tot < max_cuts ? tot : max_cuts;
-    size_t wide = 1;
-    for (int w = 0; w < ncol; ++w) wide = col[w].size > wide ? col[w].size : wide;
-    int *order = (int *)malloc((size_t)(keep > 0 ? keep : 1) * sizeof(int));
-    char *tmp = (char *)malloc((size_t)(keep > 0 ? keep : 1) * wide);
-    for (int i = 0, j = at, n = 0; n < keep;) {
-        if (j >= tot || (i < at && before(list, i, j))) order[n++] = i++;
-        else order[n++] = j++;
-    }
-    for (int w = 0; w < ncol; ++w) {
-        const size_t sz = col[w].size;
-        for (int e = 0; e < keep; ++e) memcpy(tmp + (size_t)e * sz, (const char *)col[w].base + (size_t)order[e] * sz, sz);
-        memcpy(col[w].base, tmp, (size_t)keep * sz);
-    }
-    free(order); free(tmp);
-    return keep;
-}
-
-void lrd_write_problem_as_read(FILE *f, const lrd_problem *pr) {
-    for (int k = 0; k < pr->nblk; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
-    }
-    for (int k = 0; k < pr->nblk; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int i = 0; i < b->nrow; ++i)
-            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1]; ++e)
-                fprintf(f, "%d %d %d %d %.17g\n", b->row_idx[i] + 1, k + 1, b->a_col[e] + 1, b->a_row[e] + 1, b->a_val[e]);
-    }
-}
-
 /* is a before b in (v descending, cone, p, q, s, class ascending)? */
 static int cut_before(const void *list, int a, int b) {
     const lrd_cuts *c = (const lrd_cuts *)list;
@@ -64,44 +31,25 @@ static int cut_before(const void *list, int a, int b) {
     return c->cls[a] < c->cls[b];
 }
 
+static int cut_cone(lrd_backend *be, void *list, int src, int k, int at, int64_t *count, int *got, int *np) {
+    lrd_cuts *c = (lrd_cuts *)list;
+    return be->triangle_cuts(be->ctx, src, k, c->min_violation, c->max_cuts, count, c->p + at, c->q + at, c->s + at, c->cls + at,
+                             c->viol + at, got, np);
+}
+
 int lrd_session_triangle_cuts(lrd_session *s, double min_violation, int max_cuts, lrd_cuts **out) {
-    *out = NULL;
     lrd_backend *be = lrd_session_backend(s);
-    int src;
-    const int refused = lrd_session_postsolve(s, be && be->triangle_cuts, "separate triangle inequalities",
-                                              "the separation of a sharded deal (world > 1) is", NULL, NULL, &src);
-    if (refused) return refused;
-    const int nb = lrd_session_problem(s)->nblk, cap = max_cuts > 0 ? max_cuts : 1;
     lrd_cuts *c = (lrd_cuts *)calloc(1, sizeof *c);
-    c->nblk = nb;
-    c->src = src;
     c->min_violation = min_violation;
     c->max_cuts = max_cuts;
-    c->count = (int64_t *)calloc((size_t)(nb > 0 ? nb : 1), sizeof(int64_t));
-    /* room for the merged list and one cone's list behind it */
-    c->cone = (int *)calloc(2 * (size_t)cap, sizeof(int));
-    c->p = (int *)calloc(2 * (size_t)cap, sizeof(int));
-    c->q = (int *)calloc(2 * (size_t)cap, sizeof(int));
-    c->s = (int *)calloc(2 * (size_t)cap, sizeof(int));
-    c->cls = (int8_t *)calloc(2 * (size_t)cap, sizeof(int8_t));
-    c->viol = (double *)calloc(2 * (size_t)cap, sizeof(double));
-    const lrd_column col[6] = {{c->cone, sizeof(int)}, {c->p, sizeof(int)}, {c->q, sizeof(int)}, {c->s, sizeof(int)},
-                               {c->cls, sizeof(int8_t)}, {c->viol, sizeof(double)}};
-    int rc = 0;
-    for (int k = 0; k < nb && !rc; ++k) {
-        if (lrd_session_problem(s)->blk[k].is_lp && nb > 1) continue; /* (the slacks of a cut-tightened problem: count 0) */
-        const int at = c->kept;
-        int got = 0, np = 0;
-        rc = be->triangle_cuts(be->ctx, c->src, k, min_violation, max_cuts, &c->count[k], c->p + at, c->q + at, c->s + at, c->cls + at,
-                               c->viol + at, &got, &np);
-        if (rc) break;
-        c->passes += np;
-        for (int e = 0; e < got; ++e) c->cone[at + e] = k;
-        c->kept = lrd_merge_runs(c, cut_before, col, 6, at, got, max_cuts);
-    }
-    if (rc) { lrd_cuts_free(c); return rc; }
-    *out = c;
-    return 0;
+    const lrd_separation sp = {c, cut_before, cut_cone, &c->nblk, &c->src, &c->kept, &c->passes, &c->count, 6,
+                               {{&c->cone, sizeof(int)}, {&c->p, sizeof(int)}, {&c->q, sizeof(int)}, {&c->s, sizeof(int)},
+                                {&c->cls, sizeof(int8_t)}, {&c->viol, sizeof(double)}}};
+    /* (an LP block beside the cones holds the slacks of a cut-tightened problem and is passed over: count 0) */
+    const int rc = lrd_session_separate(s, be && be->triangle_cuts, "separate triangle inequalities", 1, max_cuts, &sp);
+    *out = rc ? NULL : c;
+    if (rc) lrd_cuts_free(c);
+    return rc;
 }
 
 /* t_p = sqrt(b_i / a_i) of the one constraint a_i X[p,p] = b_i on diagonal p of cone k; 0 where no such constraint is found */
@@ -205,150 +153,89 @@ static int key_cmp(const void *a, const void *b) {
     return 0;
 }
 
-/* The tightened problem of a cut-tightened one: the present cuts with keep[e] == 0 leave with their rows and columns, the others are
- * renumbered in order, the new cuts follow as rows and as columns of the LP block, which stays where it is. */
-static int write_appended(const lrd_problem *pr, const char *path, const lrd_cuts *cuts, const unsigned char *keep, int nkeep) {
-    lrd_present *P = NULL;
-    if (present_cuts(pr, &P)) {
-        fprintf(stderr, "lorads: a problem with an LP block cannot take cuts: %s\n", cuts_why);
-        return 2;
-    }
-    const int ncut = cuts ? cuts->kept : 0, nb = pr->nblk, lpk = P->lpk, m = pr->m, nl = pr->blk[lpk].n;
-    int rc = 0, ndrop = 0;
-    if (keep && nkeep != P->n) {
-        snprintf(cuts_why, sizeof cuts_why, "the keep mask has %d entries, the problem %d cuts", nkeep, P->n);
-        rc = 2;
-    }
-    int t_off = 0, *toff = (int *)calloc((size_t)nb + 1, sizeof(int));
-    for (int k = 0; k < nb; ++k) { toff[k] = t_off; t_off += pr->blk[k].n; }
-    int *key = (int *)lrd_zalloc((size_t)(P->n + ncut), 6 * sizeof(int));
-    int nkey = 0;
-    for (int e = 0; e < P->n && !rc; ++e) {
-        if (keep && !keep[e]) { ++ndrop; continue; }
-        int *x = key + 6 * (size_t)nkey++;
-        x[0] = P->cone[e]; x[1] = P->p[e]; x[2] = P->q[e]; x[3] = P->s[e]; x[4] = P->cls[e]; x[5] = 0;
-    }
-    for (int e = 0; e < ncut && !rc; ++e) {
-        const int k = cuts->cone[e], p = cuts->p[e], q = cuts->q[e], r = cuts->s[e];
-        if (k < 0 || k >= nb || k == lpk || !(0 <= p && p < q && q < r && r < pr->blk[k].n) || cuts->cls[e] < 0 || cuts->cls[e] > 3) {
-            snprintf(cuts_why, sizeof cuts_why, "a cut is outside the problem");
-            rc = 2;
-            break;
-        }
-        int *x = key + 6 * (size_t)nkey++;
-        x[0] = k; x[1] = p; x[2] = q; x[3] = r; x[4] = cuts->cls[e]; x[5] = 1;
-    }
-    if (!rc) {
-        qsort(key, (size_t)nkey, 6 * sizeof(int), key_cmp);
-        for (int e = 1; e < nkey && !rc; ++e)
-            if (key_cmp(key + 6 * (size_t)e, key + 6 * (size_t)(e - 1)) == 0 && (key[6 * (size_t)e + 5] || key[6 * (size_t)(e - 1) + 5])) {
-                const int *x = key + 6 * (size_t)e;
-                snprintf(cuts_why, sizeof cuts_why, "a cut is already in the problem: cone %d, (%d, %d, %d), class %d", x[0] + 1, x[1] + 1,
-                         x[2] + 1, x[3] + 1, x[4]);
-                rc = 2;
-            }
-    }
-    free(key);
-    FILE *f = rc ? NULL : fopen(path, "w");
-    if (!f) {
-        if (rc) fprintf(stderr, "lorads: %s\n", cuts_why);
-        free(toff);
-        lrd_present_free(P);
-        return rc ? rc : 1;
-    }
-    int *rowmap = (int *)lrd_zalloc((size_t)m, sizeof(int)), *colmap = (int *)lrd_zalloc((size_t)nl, sizeof(int));
-    for (int e = 0; e < P->n; ++e)
-        if (keep && !keep[e]) { rowmap[P->row[e]] = -1; colmap[P->col[e]] = -1; }
-    for (int i = 0, at = 0; i < m; ++i) rowmap[i] = rowmap[i] < 0 ? -1 : at++;
-    for (int j = 0, at = 0; j < nl; ++j) colmap[j] = colmap[j] < 0 ? -1 : at++;
-    const int m2 = m - ndrop, nl2 = nl - ndrop;
-    fprintf(f, "%d\n%d\n", m2 + ncut, nb);
-    for (int k = 0; k < nb; ++k) fprintf(f, "%s%d", k ? " " : "", k == lpk ? -(nl2 + ncut) : pr->blk[k].n);
-    fputc('\n', f);
-    for (int i = 0, first = 1; i < m; ++i)
-        if (rowmap[i] >= 0) { fprintf(f, "%s%.17g", first ? "" : " ", pr->b[i]); first = 0; }
-    for (int e = 0; e < ncut; ++e) fprintf(f, "%s-1", m2 + e ? " " : "");
-    fputc('\n', f);
-    for (int k = 0; k < nb; ++k) { /* (the LP block of a recognised problem has no objective) */
-        const lrd_block *b = &pr->blk[k];
-        for (int e = 0; e < b->c_nnz; ++e) fprintf(f, "0 %d %d %d %.17g\n", k + 1, b->c_col[e] + 1, b->c_row[e] + 1, -b->c_val[e]);
-    }
-    for (int k = 0; k < nb; ++k) {
-        const lrd_block *b = &pr->blk[k];
-        for (int i = 0; i < b->nrow; ++i)
-            for (int e = b->a_ptr[i]; e < b->a_ptr[i + 1] && rowmap[b->row_idx[i]] >= 0; ++e) {
-                const int col = k == lpk ? colmap[b->a_col[e]] : b->a_col[e], row = k == lpk ? colmap[b->a_row[e]] : b->a_row[e];
-                fprintf(f, "%d %d %d %d %.17g\n", rowmap[b->row_idx[i]] + 1, k + 1, col + 1, row + 1, b->a_val[e]);
-            }
-    }
-    for (int e = 0; e < ncut; ++e) {
-        const int k = cuts->cone[e], x[3] = {cuts->p[e], cuts->q[e], cuts->s[e]};
-        const int *sg = cut_sign[cuts->cls[e]];
-        const int pair[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-        const double *t = P->t + toff[k];
-        for (int w = 0; w < 3; ++w) {
-            const int a = x[pair[w][0]], c = x[pair[w][1]];
-            fprintf(f, "%d %d %d %d %.17g\n", m2 + e + 1, k + 1, a + 1, c + 1, (double)sg[w] / (2.0 * (t[a] * t[c])));
-        }
-        fprintf(f, "%d %d %d %d -1\n", m2 + e + 1, lpk + 1, nl2 + e + 1, nl2 + e + 1);
-    }
-    free(rowmap); free(colmap); free(toff);
-    lrd_present_free(P);
-    return fclose(f) ? 1 : 0;
-}
-
-int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts) {
-    return lrd_session_write_tightened_keep(s, path, cuts, NULL, 0);
-}
-
 int lrd_session_write_tightened_keep(lrd_session *s, const char *path, const lrd_cuts *cuts, const unsigned char *keep, int nkeep) {
     const lrd_problem *pr = lrd_session_problem(s);
     if (!pr || !path) return 1;
     if (pr->separable || pr->nblk != pr->nblk_global) return 3;
     const int ncut = cuts ? cuts->kept : 0, nb = pr->nblk;
-    for (int k = 0; k < nb && (ncut > 0 || keep); ++k)
-        if (pr->blk[k].is_lp) return write_appended(pr, path, cuts, keep, nkeep);
-    if (keep && nkeep != 0) {
-        fprintf(stderr, "lorads: a keep mask for a problem without cuts\n");
+    int has_lp = 0;
+    for (int k = 0; k < nb; ++k) has_lp |= pr->blk[k].is_lp;
+    lrd_present *P = NULL; /* the cuts the problem holds, where there is something to append to them or to drop from them */
+    if (has_lp && (ncut > 0 || keep) && present_cuts(pr, &P)) {
+        fprintf(stderr, "lorads: a problem with an LP block cannot take cuts: %s\n", cuts_why);
         return 2;
     }
-    double **t = (double **)calloc((size_t)(nb > 0 ? nb : 1), sizeof(double *));
-    int bad = 0;
-    for (int e = 0; e < ncut && !bad; ++e) {
+    const int npres = P ? P->n : 0;
+    char why[sizeof cuts_why] = "";
+    if (keep && nkeep != npres) {
+        if (P) snprintf(why, sizeof why, "the keep mask has %d entries, the problem %d cuts", nkeep, npres);
+        else snprintf(why, sizeof why, "a keep mask for a problem without cuts");
+    }
+    double **t = (double **)lrd_zalloc((size_t)nb, sizeof(double *));
+    for (int e = 0; e < ncut && !why[0]; ++e) {
         const int k = cuts->cone[e], p = cuts->p[e], q = cuts->q[e], r = cuts->s[e];
-        if (k < 0 || k >= nb || !(0 <= p && p < q && q < r && r < pr->blk[k].n) || cuts->cls[e] < 0 || cuts->cls[e] > 3) { bad = 1; break; }
-        if (!t[k]) t[k] = cone_t(pr, k);
-        if (!(t[k][p] > 0) || !(t[k][q] > 0) || !(t[k][r] > 0)) bad = 2;
-    }
-    FILE *f = bad ? NULL : fopen(path, "w");
-    if (!f) {
-        if (bad) fprintf(stderr, bad == 1 ? "lorads: a cut is outside the problem\n" : "lorads: a cut names a row whose diagonal no constraint fixes\n");
-        for (int k = 0; k < nb; ++k) free(t[k]);
-        free(t);
-        return bad ? 2 : 1;
-    }
-    fprintf(f, "%d\n%d\n", pr->m + ncut, nb + (ncut > 0 ? 1 : 0));
-    for (int k = 0; k < nb; ++k) fprintf(f, "%s%d", k ? " " : "", pr->blk[k].is_lp ? -pr->blk[k].n : pr->blk[k].n);
-    if (ncut > 0) fprintf(f, " %d", -ncut);
-    fputc('\n', f);
-    for (int i = 0; i < pr->m; ++i) fprintf(f, "%s%.17g", i ? " " : "", pr->b[i]);
-    for (int e = 0; e < ncut; ++e) fprintf(f, "%s-1", pr->m + e ? " " : "");
-    fputc('\n', f);
-    lrd_write_problem_as_read(f, pr);
-    /* the cuts: sum of sign_xy X_xy / (t_x t_y) - slack = -1; an off-diagonal entry counts twice in <A, X> */
-    for (int e = 0; e < ncut; ++e) {
-        const int k = cuts->cone[e], x[3] = {cuts->p[e], cuts->q[e], cuts->s[e]};
-        const int *sg = cut_sign[cuts->cls[e]];
-        const int pair[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-        for (int w = 0; w < 3; ++w) {
-            const int a = x[pair[w][0]], c = x[pair[w][1]];
-            fprintf(f, "%d %d %d %d %.17g\n", pr->m + e + 1, k + 1, a + 1, c + 1, (double)sg[w] / (2.0 * (t[k][a] * t[k][c])));
+        if (k < 0 || k >= nb || pr->blk[k].is_lp || !(0 <= p && p < q && q < r && r < pr->blk[k].n) || cuts->cls[e] < 0 || cuts->cls[e] > 3) {
+            snprintf(why, sizeof why, "a cut is outside the problem");
+            break;
         }
-        fprintf(f, "%d %d %d %d -1\n", pr->m + e + 1, nb + 1, e + 1, e + 1);
+        if (!t[k]) t[k] = cone_t(pr, k);
+        if (!(t[k][p] > 0) || !(t[k][q] > 0) || !(t[k][r] > 0)) snprintf(why, sizeof why, "a cut names a row whose diagonal no constraint fixes");
+    }
+    if (P && !why[0]) { /* a new cut that the problem keeps, or that is listed twice (x[5]: new) */
+        int *key = (int *)lrd_zalloc((size_t)(npres + ncut), 6 * sizeof(int)), nkey = 0;
+        for (int e = 0; e < npres; ++e) {
+            if (keep && !keep[e]) continue;
+            int *x = key + 6 * (size_t)nkey++;
+            x[0] = P->cone[e]; x[1] = P->p[e]; x[2] = P->q[e]; x[3] = P->s[e]; x[4] = P->cls[e]; x[5] = 0;
+        }
+        for (int e = 0; e < ncut; ++e) {
+            int *x = key + 6 * (size_t)nkey++;
+            x[0] = cuts->cone[e]; x[1] = cuts->p[e]; x[2] = cuts->q[e]; x[3] = cuts->s[e]; x[4] = cuts->cls[e]; x[5] = 1;
+        }
+        qsort(key, (size_t)nkey, 6 * sizeof(int), key_cmp);
+        for (int e = 1; e < nkey && !why[0]; ++e) {
+            const int *x = key + 6 * (size_t)e;
+            if (key_cmp(x, x - 6) == 0 && (x[5] || x[-1]))
+                snprintf(why, sizeof why, "a cut is already in the problem: cone %d, (%d, %d, %d), class %d", x[0] + 1, x[1] + 1, x[2] + 1,
+                         x[3] + 1, x[4]);
+        }
+        free(key);
+    }
+    int rc = 2;
+    if (why[0]) {
+        fprintf(stderr, "lorads: %s\n", why);
+        if (P) memcpy(cuts_why, why, sizeof why); /* (lrd_cuts_why() speaks of cut-tightened problems alone) */
+    } else {
+        /* the cuts: sum of sign_xy X_xy / (t_x t_y) - slack = -1; the present cuts with keep[e] == 0 leave with their rows and columns */
+        lrd_new_row *row = (lrd_new_row *)lrd_zalloc((size_t)ncut, sizeof *row);
+        for (int e = 0; e < ncut; ++e) {
+            const int k = cuts->cone[e], x[3] = {cuts->p[e], cuts->q[e], cuts->s[e]};
+            const int *sg = cut_sign[cuts->cls[e]];
+            const int pair[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+            row[e].rhs = row[e].slack = -1.0;
+            row[e].nent = 3;
+            for (int w = 0; w < 3; ++w) {
+                const int a = x[pair[w][0]], c = x[pair[w][1]];
+                row[e].ent[w].cone = k; row[e].ent[w].i = a; row[e].ent[w].j = c;
+                row[e].ent[w].value = (double)sg[w] / (2.0 * (t[k][a] * t[k][c]));
+            }
+        }
+        unsigned char *drop_row = P ? (unsigned char *)lrd_zalloc((size_t)pr->m, 1) : NULL;
+        unsigned char *drop_col = P ? (unsigned char *)lrd_zalloc((size_t)pr->blk[P->lpk].n, 1) : NULL;
+        for (int e = 0; e < npres && keep; ++e)
+            if (!keep[e]) drop_row[P->row[e]] = drop_col[P->col[e]] = 1;
+        const lrd_extension ext = {ncut, row, drop_row, drop_col};
+        rc = lrd_write_extended(path, pr, &ext);
+        free(row); free(drop_row); free(drop_col);
     }
     for (int k = 0; k < nb; ++k) free(t[k]);
     free(t);
-    return fclose(f) ? 1 : 0;
+    lrd_present_free(P);
+    return rc;
+}
+
+int lrd_session_write_tightened(lrd_session *s, const char *path, const lrd_cuts *cuts) {
+    return lrd_session_write_tightened_keep(s, path, cuts, NULL, 0);
 }
 
 int lrd_session_write_tightened_drop(lrd_session *s, const char *path, const lrd_cuts *cuts, double drop_slack, double tol, int *dropped) {

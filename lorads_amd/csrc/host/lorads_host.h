@@ -628,14 +628,44 @@ void lrd_bisection_free(lrd_bisection *r);
 int lrd_bisection_write(const char *path, const lrd_bisection *r);
 
 /* ---- internal: what the post-solve drivers and writers above share (not part of the interface)
- * Two adjacent runs [0, at) and [at, at + got) of a list kept as ncol parallel columns, each sorted by `before(list, a, b)` (is entry a
- * before entry b?): merged in place, the first min(at + got, max_cuts) entries kept; returns how many (cuts.c). */
-typedef struct { void *base; size_t size; } lrd_column;
+ * A list of cuts is kept as ncol parallel columns; a column names the list's own pointer field (`field`: its address) and the size of
+ * an element.  Two adjacent runs [0, at) and [at, at + got) of the list, each sorted by `before(list, a, b)` (is entry a before entry
+ * b?): merged in place, the first min(at + got, max_cuts) entries kept; returns how many (separation.c). */
+typedef struct { void *field; size_t size; } lrd_column;
 int lrd_merge_runs(const void *list, int (*before)(const void *list, int a, int b), const lrd_column *col, int ncol, int at, int got,
                    int max_cuts);
-/* the objective and constraint entries of the problem as it was read, in SDPA sparse format: lower triangle inside, upper triangle
- * (i <= j) in the file; F0 = -C (cuts.c) */
-void lrd_write_problem_as_read(FILE *f, const lrd_problem *pr);
+/* One separation of the current point (separation.c): the post-solve gate in the feature's words (have_slot, cannot), nblk, src and a
+ * zeroed count [nblk] into the list, 2 max_cuts elements per column (the merged list and one cone's list behind it), then `cone` once
+ * per SDP cone k -- the feature's table slot with the columns from `at` on, *count, *got and *np as the slot gives them -- col[0] (the
+ * cone, int) filled in and the runs merged by `before` into kept, passes summed.  lone_lp: an LP block that is the problem's only
+ * block gets the call too.  Non-zero: the gate's or the slot's code; the caller frees its list. */
+typedef struct {
+    void *list;
+    int (*before)(const void *list, int a, int b);
+    int (*cone)(lrd_backend *be, void *list, int src, int k, int at, int64_t *count, int *got, int *np);
+    int *nblk, *src, *kept, *passes;
+    int64_t **count;
+    int ncol;
+    lrd_column col[6];
+} lrd_separation;
+int lrd_session_separate(lrd_session *s, int have_slot, const char *cannot, int lone_lp, int max_cuts, const lrd_separation *sp);
+/* The problem image in SDPA sparse format (m, blocks, b, every stored entry; doubles %.17g; lower triangle inside, upper triangle
+ * i <= j in the file; F0 = -C), extended by x (NULL: as it was read): the rows with drop_row[i] != 0 (may be NULL, else [m]) and the
+ * columns with drop_col[j] != 0 of the LP block (likewise) leave and the others are renumbered in order; new row e follows as
+ * constraint (rows that stay) + 1 + e with right-hand side rhs, its entries value at (i, j), i <= j, of SDP cone `cone` as given
+ * (0-based), and `slack` in a column of its own: behind the LP block's columns that stay, or in a new last LP block where the problem
+ * has none.  Opens path first: the caller has validated.  1: cannot write (separation.c). */
+typedef struct {
+    double rhs, slack;
+    int nent;
+    struct { int cone, i, j; double value; } ent[3];
+} lrd_new_row;
+typedef struct {
+    int nrow;
+    const lrd_new_row *row;
+    const unsigned char *drop_row, *drop_col;
+} lrd_extension;
+int lrd_write_extended(const char *path, const lrd_problem *pr, const lrd_extension *x);
 /* The dual bound of a rounding, d = b.y + sum_i T_i min(0, lambda_min(S_blk[i])) + sum_j u_j min(0, s_j), from the certificate's y and
  * eigenvalues at Lanczos tolerance tol and the dual slack of the LP block lpk (-1: none, no third sum); sc: scaleObjHis.  Fills *out
  * (gap = (f_best - d) / max(1, |d|); lp_neg: how many s_j < 0) and lam_min [ncone]; all NaN / 0 when tol <= 0 or the table lacks the

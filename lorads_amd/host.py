@@ -1188,18 +1188,31 @@ class Session:
         (violation descending, cone, p, q, s, cls ascending).  On a cut-tightened problem (what write_tightened wrote) the
         inequalities that are rows already are neither counted nor returned.  Read-only on the solver's state, deterministic."""
         from .cuts import Cuts, CutsStruct
-        ptr = C.POINTER(CutsStruct)()
-        self.lib.lrd_session_triangle_cuts.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.POINTER(CutsStruct))]
-        self.lib.lrd_cuts_free.argtypes = [C.POINTER(CutsStruct)]
-        self.lib.lrd_cuts_free.restype = None
-        rc = self.lib.lrd_session_triangle_cuts(self.h, float(min_violation), int(max_cuts), C.byref(ptr))
-        self._refused(rc, "triangle inequalities cannot be separated: the problem is not +-1-structured or the %s backend "
-                      "cannot separate%s", "the separation of a sharded deal (world > 1) is not supported")
-        _check(rc, "triangle_cuts")
+        return self._separated(CutsStruct, Cuts, "lrd_session_triangle_cuts", "lrd_cuts_free", [min_violation], max_cuts,
+                               "triangle inequalities cannot be separated: the problem is not +-1-structured or the %s backend "
+                               "cannot separate%s")
+
+    def _separated(self, struct, result, run, free, lead, max_cuts, what_rc2):
+        """One separation of the current point: the entry point `run` with the doubles `lead`, max_cuts and the list's address, the
+        refusals (what_rc2 as _refused takes it), and `result` of the list, which `free` releases."""
+        run, free = getattr(self.lib, run), getattr(self.lib, free)
+        run.argtypes = [C.c_void_p] + [C.c_double] * len(lead) + [C.c_int, C.POINTER(C.POINTER(struct))]
+        free.argtypes, free.restype = [C.POINTER(struct)], None
+        ptr = C.POINTER(struct)()
+        rc = run(self.h, *(float(x) for x in lead), int(max_cuts), C.byref(ptr))
+        self._refused(rc, what_rc2, "the separation of a sharded deal (world > 1) is not supported")
+        _check(rc, run.__name__[len("lrd_session_"):])
         try:
-            return Cuts.from_struct(ptr.contents)
+            return result.from_struct(ptr.contents)
         finally:
-            self.lib.lrd_cuts_free(ptr)
+            free(ptr)
+
+    def _written(self, write, path, struct, lst, argtypes=(), args=()):
+        """the return code of the writer `write` for the session, path, the list (an object with to_struct, or None) and `args`"""
+        write = getattr(self.lib, write)
+        write.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(struct)] + list(argtypes)
+        st = lst.to_struct() if lst is not None else None
+        return write(self.h, os.fsencode(path), C.byref(st) if st is not None else None, *args)
 
     def _cuts_why(self):
         self.lib.lrd_cuts_why.restype = C.c_char_p
@@ -1233,23 +1246,19 @@ class Session:
         point, exceeds it (the command line's --cutsDropSlack); keep: the mask itself, one flag per present_cuts() entry.
         Returns how many present cuts left."""
         from .cuts import CutsStruct
-        st = cuts.to_struct() if cuts is not None else None
-        cp = C.byref(st) if st is not None else None
         dropped = C.c_int(0)
         if keep is not None:
             if drop_slack is not None:
                 raise ValueError("write_tightened: drop_slack and keep exclude each other")
             mask = np.ascontiguousarray(np.asarray(keep, dtype=bool), dtype=np.uint8)
-            self.lib.lrd_session_write_tightened_keep.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct), C.c_void_p, C.c_int]
-            rc = self.lib.lrd_session_write_tightened_keep(self.h, os.fsencode(path), cp, mask.ctypes.data_as(C.c_void_p), len(mask))
+            rc = self._written("lrd_session_write_tightened_keep", path, CutsStruct, cuts, [C.c_void_p, C.c_int],
+                               [mask.ctypes.data_as(C.c_void_p), len(mask)])
             dropped.value = int(len(mask) - mask.sum())
         elif drop_slack is not None:
-            self.lib.lrd_session_write_tightened_drop.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct), C.c_double, C.c_double,
-                                                                  C.POINTER(C.c_int)]
-            rc = self.lib.lrd_session_write_tightened_drop(self.h, os.fsencode(path), cp, float(drop_slack), 1e-8, C.byref(dropped))
+            rc = self._written("lrd_session_write_tightened_drop", path, CutsStruct, cuts, [C.c_double, C.c_double, C.POINTER(C.c_int)],
+                               [float(drop_slack), 1e-8, C.byref(dropped)])
         else:
-            self.lib.lrd_session_write_tightened.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(CutsStruct)]
-            rc = self.lib.lrd_session_write_tightened(self.h, os.fsencode(path), cp)
+            rc = self._written("lrd_session_write_tightened", path, CutsStruct, cuts)
         if rc == 2:
             why = self._cuts_why()
             raise ValueError("a cut lies outside the problem, names a row no constraint fixes, or the problem has an LP block that "
@@ -1263,33 +1272,16 @@ class Session:
         more than min_violation counted exactly, and the max_cuts most violated returned, ordered by (violation descending, cone, p,
         q, cls ascending).  lower=None / upper=None: no such bound.  Any problem; read-only on the solver's state, deterministic."""
         from .bounds import Bounds, BoundsStruct
-        ptr = C.POINTER(BoundsStruct)()
-        self.lib.lrd_session_entry_bounds.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
-                                                      C.POINTER(C.POINTER(BoundsStruct))]
-        self.lib.lrd_bounds_free.argtypes = [C.POINTER(BoundsStruct)]
-        self.lib.lrd_bounds_free.restype = None
-        lo = -np.inf if lower is None else float(lower)
-        up = np.inf if upper is None else float(upper)
-        rc = self.lib.lrd_session_entry_bounds(self.h, lo, up, float(min_violation), int(max_cuts), C.byref(ptr))
-        if rc == 2:
-            raise NotImplementedError("entry bounds cannot be separated: the %s backend has no such slot"
-                                      % (self.be.name if self.be else "attached"))
-        if rc == 3:
-            raise NotImplementedError("the separation of a sharded deal (world > 1) is not supported")
-        _check(rc, "entry_bounds")
-        try:
-            return Bounds.from_struct(ptr.contents)
-        finally:
-            self.lib.lrd_bounds_free(ptr)
+        lead = [-np.inf if lower is None else lower, np.inf if upper is None else upper, min_violation]
+        return self._separated(BoundsStruct, Bounds, "lrd_session_entry_bounds", "lrd_bounds_free", lead, max_cuts,
+                               "entry bounds cannot be separated: the %s backend has no such slot%.0s")   # (without the backend's reason)
 
     def write_bounded(self, path, bounds):
         """The problem as it was read plus one constraint and one slack column per bound cut, in SDPA sparse format (the command
         line's --boundsFile: the same C writer, the same bytes).  The slack columns join the problem's LP block, or form a new last
         one.  bounds: a lorads_amd.bounds.Bounds or None."""
         from .bounds import BoundsStruct
-        self.lib.lrd_session_write_bounded.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(BoundsStruct)]
-        st = bounds.to_struct() if bounds is not None else None
-        rc = self.lib.lrd_session_write_bounded(self.h, os.fsencode(path), C.byref(st) if st is not None else None)
+        rc = self._written("lrd_session_write_bounded", path, BoundsStruct, bounds)
         if rc == 2:
             raise ValueError("a bound cut lies outside the problem, or the problem has more than one LP block")
         if rc == 3:
