@@ -145,15 +145,33 @@ def _with_sum_row(prob, diff):
     return dict(m=m + 1, blocks=[n], b=np.concatenate([prob["b"], [float(diff * diff)]]), entries=ent)
 
 
-def bisection(n, n_edges, seed, diff=0, weights=None):
-    """min <L/4, X> s.t. X_ii = 1, <11^T, X> = diff^2: the relaxation of the smallest cut with parts of (n + diff) / 2 and
-    (n - diff) / 2 vertices (diff = 0: Min-Bisection).  F0 = -L/4 (=> C = L/4, x^T C x the cut's weight for x in {+-1}^n), F_i = e_i e_i^T
-    with b = 1, and the sum row last.  diff must have n's parity."""
+def bisection_graph(n, edges, w, diff=0, t=1.0, a=1.0):
+    """min <L/4, X> s.t. (1/t) X_ii = t, a <11^T, X> = a t^2 diff^2 on the graph with the edges `edges` (0-based pairs i < j, each
+    once) of weights `w`, signed or not: the relaxation of the smallest cut with parts of (n + diff) / 2 and (n - diff) / 2 vertices
+    (diff = 0: Min-Bisection) in a scaled form, x = t sigma.  F0 = -L/4 (=> C = L/4, x^T C x = t^2 times the cut's weight), the n
+    diagonal rows, and the sum row last: every position of the upper triangle with the value a.  diff must have n's parity."""
     if not 0 <= diff <= n or (n - diff) % 2:
         raise ValueError("diff must lie in [0, n] and have n's parity")
-    p = maxcut(n, n_edges, seed, weights)
-    ent = [(mat, blk, i, j, -v if mat == 0 else v) for mat, blk, i, j, v in p["entries"]]
-    return _with_sum_row(dict(m=n, blocks=[n], b=p["b"], entries=ent), diff)
+    edges = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    w = np.asarray(w, dtype=np.float64)
+    deg = np.zeros(n)
+    np.add.at(deg, edges[:, 0], w)
+    np.add.at(deg, edges[:, 1], w)
+    ent = [(0, 1, i + 1, i + 1, -(deg[i] / 4.0)) for i in range(n) if deg[i] != 0.0]
+    ent += [(0, 1, i + 1, j + 1, wij / 4.0) for (i, j), wij in zip(edges.tolist(), w.tolist())]
+    ent += [(i + 1, 1, i + 1, i + 1, 1.0 / t) for i in range(n)]
+    ent += [(n + 1, 1, i + 1, j + 1, float(a)) for i in range(n) for j in range(i, n)]
+    return dict(m=n + 1, blocks=[n], b=np.concatenate([np.full(n, float(t)), [float(a * t * t * diff * diff)]]), entries=ent)
+
+
+def bisection(n, n_edges, seed, diff=0, weights=None):
+    """bisection_graph with t = a = 1 on a seeded random graph: min <L/4, X> s.t. X_ii = 1, <11^T, X> = diff^2.  F0 = -L/4 (=> C =
+    L/4, x^T C x the cut's weight for x in {+-1}^n), F_i = e_i e_i^T with b = 1, and the sum row last.  diff must have n's parity."""
+    if not 0 <= diff <= n or (n - diff) % 2:
+        raise ValueError("diff must lie in [0, n] and have n's parity")
+    rng = np.random.default_rng(seed)
+    edges = _rand_edges(n, n_edges, rng)
+    return bisection_graph(n, edges, np.ones(len(edges)) if weights is None else weights(rng, len(edges)), diff)
 
 
 def clique_pair(m, seed):

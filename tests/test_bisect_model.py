@@ -1,16 +1,20 @@
 """The bisection rounding without a GPU: the numpy model (tests/bisect_model.py) against brute force, the generators and the structure
-check, the bisection file through the C writer, the command line's refusals, the oracle table and the table's layout."""
+check, the bisection file through the C writer, the command line's refusals, the oracle table and the table's layout; the model on
+signed dyadic weights with t = 2 and a != 1, and the seeds of the long-row cases (tests/bisect_cases.py)."""
 import ctypes as C
 import os
 import subprocess
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from lorads_amd import host, instances
 from lorads_amd.bisection import Bisection, BisectionCone, BisectionConeStruct, BisectionStruct, read_bisection
+from tests import bisect_cases as bc
 from tests import bisect_model as bm
 from tests import common
+from tests import rounding_model as rm
 
 
 def _graph_c(rng, n, quarter_weights):
@@ -243,3 +247,132 @@ def test_oracle_backend_has_no_slot_and_the_table_mirror_places_it():
     assert hasattr(hip, "lorads_hip_round_bisect") and hasattr(hip, "lorads_hip_bisect_trial")
     hdr = open(os.path.join(common.ROOT, "include", "lorads_hip.h")).read()
     assert "int lorads_hip_round_bisect(lorads_hip_ctx *ctx, int32_t src, int32_t trials, uint64_t seed, int32_t max_rounds" in hdr
+
+
+# ---- the model on the data of the long-row cases (tests/bisect_cases.py): signed dyadic weights, t = 2, a != 1 ----
+
+def test_bisection_graph_generalises_bisection():
+    """bisection() is bisection_graph with t = a = 1 on the seeded graph: the entries and b of the construction it replaced (Max-Cut
+    with F0 negated plus _with_sum_row), value for value and in the same order; and the scaled form's rows"""
+    for args, kw in (((24, 80, 241), {}), ((40, 160, 401), dict(diff=4)), ((65, 300, 651), dict(diff=1)), ((300, 1200, 3001), {}),
+                     ((150, 400, 1501), dict(weights=lambda rng, k: rng.uniform(0.5, 2.0, k)))):
+        n, diff = args[0], kw.get("diff", 0)
+        p = instances.maxcut(*args, weights=kw.get("weights"))
+        old = instances._with_sum_row(dict(m=n, blocks=[n], b=p["b"], entries=[e[:4] + (-e[4] if e[0] == 0 else e[4],) for e in p["entries"]]), diff)
+        new = instances.bisection(*args, **kw)
+        assert new["m"] == old["m"] and new["blocks"] == old["blocks"] and np.array_equal(new["b"], old["b"])
+        assert [tuple(float(v) for v in e) for e in new["entries"]] == [tuple(float(v) for v in e) for e in old["entries"]]
+    prob = instances.bisection_graph(4, [(0, 1), (1, 3)], [0.5, -0.25], diff=2, t=2.0, a=-3.0)
+    assert prob["m"] == 5 and np.array_equal(prob["b"], [2.0, 2.0, 2.0, 2.0, -48.0])
+    assert [e for e in prob["entries"] if e[0] == 0] == [(0, 1, 1, 1, -0.125), (0, 1, 2, 2, -0.0625), (0, 1, 4, 4, 0.0625),
+                                                        (0, 1, 1, 2, 0.125), (0, 1, 2, 4, -0.0625)]
+    assert [e for e in prob["entries"] if 0 < e[0] < 5] == [(i, 1, i, i, 0.5) for i in range(1, 5)]
+    assert [e for e in prob["entries"] if e[0] == 5] == [(5, 1, i, j, -3.0) for i in range(1, 5) for j in range(i, 5)]
+    with pytest.raises(ValueError):
+        instances.bisection_graph(4, [(0, 1)], [1.0], diff=1)
+
+
+def _exact_f(Cq, t, sig):
+    x = [Fraction(t) * int(s) for s in sig]
+    return sum(x[p] * Cq[p][q] * x[q] for p in range(len(x)) for q in range(len(x)))
+
+
+@pytest.mark.parametrize("n", range(2, 13))
+def test_model_with_t2_and_signed_dyadic_weights(n):
+    """t = 2, a = -3, weights from the nonzero j / 16 with j in [-8, 32] and every admissible d: the structure check finds t and d, C
+    holds multiples of 1/64, the model's result is balanced and never below the brute-force optimum, `objective` is x^T C x in
+    rational arithmetic, and every logged Delta is the exact change of f"""
+    rng = np.random.default_rng(200 + n)
+    edges = [(p, q) for p in range(n) for q in range(p + 1, n) if rng.random() < 0.6]
+    w = bc.dyadic(rng, len(edges))
+    assert np.all(w != 0) and np.array_equal(w * 16, np.rint(w * 16)) and w.min(initial=0) >= -0.5 and w.max(initial=0) <= 2.0
+    for d in range(n % 2, n + 1, 2):
+        P = bm.BisectProblem.from_instance(instances.bisection_graph(n, edges, w, diff=d, t=2.0, a=-3.0))
+        assert P.ok and P.t == [2.0] and P.d == [d], P.why
+        assert bc.c64_is_integral(P)
+        C_ = P.C[0]
+        Cq = [[Fraction(float(v)) for v in row] for row in C_]
+        opt = bm.brute_force(C_, 2.0, d)
+        for trial in range(3):
+            s0 = np.where(rng.random(n) < 0.5, 1, -1)
+            log = []
+            r = bm.run(C_, 2.0, d, s0, 1000, log)
+            assert abs(int(r["sigma0"].sum())) == d and int(r["sigma"].sum()) == int(r["sigma0"].sum())
+            assert r["f"] >= opt and r["f"] <= r["f0"]
+            assert Fraction(r["f"]) == _exact_f(Cq, 2.0, r["sigma"]) and Fraction(r["f0"]) == _exact_f(Cq, 2.0, r["sigma0"])
+            sig = s0.astype(np.int64).copy()
+            f = _exact_f(Cq, 2.0, sig)
+            for e in log:
+                for v in e[1:-1]:
+                    sig[v] = -sig[v]
+                g = _exact_f(Cq, 2.0, sig)
+                assert g - f == Fraction(e[-1]), (e, g - f)
+                f = g
+            assert np.array_equal(sig, r["sigma"])
+
+
+def test_structure_check_on_a_scaled_sum_row():
+    """-3 <11^T, X> = -12 d^2 beside 0.5 X_pp = 2: t = 2 and d from b / (a t^2); the same problem with b off a square is refused"""
+    rng = np.random.default_rng(7)
+    edges = instances._rand_edges(10, 20, rng)
+    for d in (0, 2, 10):
+        prob = instances.bisection_graph(10, edges, bc.dyadic(rng, 20), diff=d, t=2.0, a=-3.0)
+        assert prob["b"][-1] == -12.0 * d * d and all(e[4] == -3.0 for e in prob["entries"] if e[0] == 11)
+        P = bm.BisectProblem.from_instance(prob)
+        assert P.ok and P.t == [2.0] and P.d == [d] and P.T(0) == 40.0
+        b = prob["b"].copy()
+        b[-1] -= 12.0    # b / (a t^2) = d^2 + 1: no square but for d = 0, where d = 1 has the wrong parity
+        Q = bm.BisectProblem.from_instance(dict(prob, b=b))
+        assert not Q.ok and "b / (a t^2) = %r" % float(d * d + 1) in Q.why, Q.why
+        b[-1] = 12.0 * d * d + (12.0 if d == 0 else 0.0)   # the sign of a forgotten: b / (a t^2) < 0
+        assert not bm.BisectProblem.from_instance(dict(prob, b=b)).ok
+
+
+@pytest.mark.parametrize("name", list(bc.LONG))
+def test_seeds_of_the_long_row_cases(name):
+    """what tests/test_bisection.py relies on in its long-row cases, checked here with the model's own hyperplanes at the ranks the
+    contexts have: the storage rules give the row lists their length, no projection is anywhere near zero, the searches run for
+    tens of rounds and are cut at 5, the hub is a swap's p and a swap's q, and the planted factor makes the hub the first flip from
+    an excess on either side"""
+    P = bm.BisectProblem.read(common.generated_instance("bis_long_" + name, bc.LONG[name][0]))
+    assert P.ok and bc.c64_is_integral(P), P.why
+    s = host.Session.open(common.generated_instance("bis_long_" + name))
+    try:
+        s.set_params(verbose=0)
+        s.prepare(1, 0, separable=False)
+        shapes = [s.block_shape(k) for k in range(s.nblk)]
+    finally:
+        s.close()
+    assert shapes == [(n, bc.RANKS[n]) for n in P.dims]
+    want = {"hub300": ([1.0], [2], [False]), "hubneg300": ([2.0], [2], [False]), "densec300": ([2.0], [0], [True]),
+            "nodense300": ([1.0], [0], [False]), "mixed": ([2.0, 1.0], [2, 4], [False, True])}[name]
+    dense_c = [np.count_nonzero(np.tril(C_)) > 0.1 * len(C_) * (len(C_) + 1) / 2 for C_ in P.C]
+    assert (P.t, P.d, dense_c) == want
+    sparse_row = [n < 32 or "LORADS_NO_DENSE_A" in bc.LONG[name][1] for n in P.dims]
+    assert bc.row_lists(P.C[0], dense_c[0], sparse_row[0]).max() == 300 > bc.TPB
+    if name.startswith("hub"):
+        rows = bc.row_lists(P.C[0], False, False)
+        assert rows[bc.HUB] == 300 and np.delete(rows, bc.HUB).max() < 16
+    R = bc.case_factors(name, P, shapes)
+    G = [rm.hyperplanes(bc.SEEDS[name], k, r, bc.K) for k, (_, r) in enumerate(shapes)]
+    margin = min(float((np.abs(R[k] @ G[k]) / (np.linalg.norm(R[k], axis=1)[:, None] * np.linalg.norm(G[k], axis=0)[None, :])).min())
+                 for k in range(len(shapes)))
+    assert margin > 1e-6    # (the device's hyperplanes are the model's within 1e-14)
+    M = bc.model_trials(P, R, G, 1000)
+    cut = bc.model_trials(P, R, G, 5)
+    rounds = [m["rounds"] for m, _ in M[0]]
+    print("%s: margin %.1e, rounds %s, hub (p, q) in %s trials" % (name, margin, rounds, bc.hub_roles(M[0])))
+    assert max(rounds) < 1000 and max(rounds) > 20
+    assert [m["rounds"] for m, _ in cut[0]] == [min(r, 5) for r in rounds] and sum(r > 5 for r in rounds) >= 4
+    if name.startswith("hub"):
+        p, q = bc.hub_roles(M[0])
+        assert p >= 1 and q >= 1
+    if name == "hubneg300":
+        R = bc.planted(bc.PLANT, shapes)
+        G = [rm.hyperplanes(bc.PLANT, 0, shapes[0][1], bc.K)]
+        M = bc.model_trials(P, R, G, 1000)
+        D = [m["imbalance"] for m, _ in M[0]]
+        assert set(D) == {300, -300}
+        for m, log in M[0]:
+            flips = [e for e in log if e[0] == "flip"]
+            assert len(flips) == 149 and flips[0][1] == bc.HUB and flips[0][2] == -4.0 * 4.0 * 299 / 8.0

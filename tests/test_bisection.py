@@ -2,15 +2,18 @@
 imbalance, the signs of every trial after the repair and the swap search, f before and after the search, the best trials and the
 rounds -- exactly on the unit-weight instances --, the invariants on every instance, the same bits from the dense and the sparse
 store, from the LDS and the slab path and from call to call, the dual bound, the read-only continuation, the refusals and the
-command line's --bisectTrials / --bisectFile."""
+command line's --bisectTrials / --bisectFile.  The long-row cases (tests/bisect_cases.py): row lists longer than the workgroup in
+either store of C, signed dyadic weights, t = 2 and a sum row with a != 1, exactly the model's on seeded factors."""
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
 from lorads_amd import host, instances
 from lorads_amd.bisection import read_bisection
+from tests import bisect_cases as bc
 from tests import bisect_model as bm
 from tests import common
 from tests import rounding_model as rm
@@ -41,6 +44,8 @@ UNIT = [n for n in INST if n != "w150"]
 
 
 def _path(name):
+    if name in bc.LONG:
+        return common.generated_instance("bis_long_" + name, bc.LONG[name][0])
     return common.generated_instance("bis_" + name.replace("nodense", "d"), INST[name][0]) if name in INST else (
         common.instance_path(name) if name in ("maxcut100", "theta30", "sdplp40", "blk4x60") else common.generated_instance(name))
 
@@ -65,10 +70,10 @@ _STATES = {}
 def _state(name):
     """(session, model problem, R per cone) after phase 1 and three ADMM steps, kept for the module"""
     if name not in _STATES:
-        s, _, _ = _phase2(_path(name), INST[name][1])
+        s, _, _ = _phase2(_path(name), (INST.get(name) or bc.LONG[name])[1])
         P = bm.BisectProblem.read(_path(name))
         assert P.ok, P.why
-        if name in UNIT:
+        if name in UNIT or name in bc.LONG:
             assert s.results()["scale_obj_his"] == 1.0
         _STATES[name] = (s, P, [c.R for c in s.solution(tol=0).cones])
     return _STATES[name]
@@ -198,6 +203,148 @@ def test_long_searches_rebuild_the_field_and_match_the_model():
         s.close()
 
 
+_PROBLEMS = {}
+
+
+def _long_context(name, env=None):
+    """a fresh context of bc.LONG[name] (`env` on top of its own), no solve: (session, model problem, (n, rank) per cone).  Its
+    size facts are asserted from the rules restated here: C is stored dense where its nc stored entries exceed 0.1 n (n + 1) / 2;
+    the sum row sits in the dense store from n = 32 up unless LORADS_NO_DENSE_A is set; the union pattern holds the diagonal (the
+    diagonal rows) and what is not stored dense -- C's positions, every position under the sum row --; the dense stores pad n to
+    a multiple of 64 (read from the dense plan the context reports); the longest row list bis_row deals outgrows the workgroup."""
+    if name not in _PROBLEMS:
+        _PROBLEMS[name] = bm.BisectProblem.read(_path(name))
+    P = _PROBLEMS[name]
+    assert P.ok and bc.c64_is_integral(P), P.why
+    own = bc.LONG[name][1]
+    s = common.hip_session_with_env(_path(name), dict(own, **(env or {})), {})
+    try:
+        assert s.results()["scale_obj_his"] == 1.0
+        shapes = [s.block_shape(k) for k in range(s.nblk)]
+        assert shapes == [(n, bc.RANKS[n]) for n in P.dims]
+        longest = 0
+        for k, C_ in enumerate(P.C):
+            n, im = len(C_), s.hip_block_image(k)
+            nc = int(np.count_nonzero(np.tril(C_)))
+            sparse_row = n < 32 or "LORADS_NO_DENSE_A" in own
+            assert im["n"] == n and im["nc"] == nc
+            assert bool(im["dense_c"]) == (nc > 0.1 * n * (n + 1) / 2)
+            assert im["dense_a"] == (0 if sparse_row else 1)
+            held = np.ones((n, n), dtype=bool) if sparse_row else np.eye(n, dtype=bool) | ((C_ != 0) & (not im["dense_c"]))
+            assert im["pattern_union"] == np.count_nonzero(np.tril(held))
+            assert s.hip_dense_plan(k)["npad"] == ((n + 63) // 64 * 64 if im["dense_c"] or im["dense_a"] else 0)
+            longest = max(longest, int(bc.row_lists(C_, bool(im["dense_c"]), sparse_row).max()))
+        assert longest == 300 > bc.TPB
+        if name == "densec300":
+            assert s.hip_block_image(0)["dense_c"] == 1 and s.hip_dense_plan(0)["npad"] == 320 != P.dims[0]
+        else:
+            assert s.hip_block_image(0)["dense_c"] == 0
+    except BaseException:
+        s.close()
+        raise
+    return s, P, shapes
+
+
+def _against_the_model(s, P, R, seed, rounds):
+    """one call of bc.K trials on the factors R (set already) against the model fed the device's hyperplanes, no trial excluded
+    (model_trials asserts that no projection is near zero): t and d, the imbalance, every trial's signs, obj0 and obj bit for bit,
+    best, best0 and rounds.  Returns (the call's dict, the model's (dict, log) per cone and trial)."""
+    rc, o = s.be.round_bisect(host.PAIR_RR, bc.K, seed, rounds, want_hyperplanes=True)
+    assert rc == 0
+    assert list(o["t"]) == P.t and list(o["diff"]) == P.d
+    M = bc.model_trials(P, R, o["hyperplanes"], rounds)
+    got = _trial_signs(s, P, bc.K)
+    for k in range(len(P.dims)):
+        assert np.array_equal(o["imbalance"][k], [m["imbalance"] for m, _ in M[k]]), k
+        want = np.stack([m["sigma"] for m, _ in M[k]], axis=1)
+        bad = [t for t in range(bc.K) if not np.array_equal(got[k][:, t], want[:, t])]
+        assert not bad, (k, bad)
+    f0 = np.sum([[m["f0"] for m, _ in Mk] for Mk in M], axis=0)
+    f = np.sum([[m["f"] for m, _ in Mk] for Mk in M], axis=0)
+    assert np.array_equal(o["obj0"], f0), (o["obj0"], f0)
+    assert np.array_equal(o["obj"], f), (o["obj"], f)
+    assert o["best"] == int(np.argmin(f)) and o["best0"] == int(np.argmin(f0))
+    assert o["rounds"] == max(m["rounds"] for Mk in M for m, _ in Mk)
+    assert np.array_equal(o["sign"], np.concatenate([g[:, o["best"]] for g in got]))
+    return o, M
+
+
+@pytest.mark.parametrize("name", list(bc.LONG))
+def test_long_rows_weights_and_scaled_rows_match_the_model_exactly(name):
+    """Row lists of 300 slots -- a second trip of bis_row's stride over the adjacency or over a row of Cfull, with a remainder --,
+    signed dyadic weights, t = 2 and a = -3.  The premise of tests/bisect_cases.py makes every sum exact (C * 64 is integral, t in
+    {1, 2}, n <= 300), so the comparison is bit for bit whatever the order of summation.  Seeded factors, no solve; the full search
+    and a search cut short at 5 rounds.  On the hub graphs the model's log shows the hub as a swap's p and as a swap's q."""
+    t0 = time.perf_counter()
+    s, P, shapes = _long_context(name)
+    try:
+        R = bc.case_factors(name, P, shapes)
+        for k, Rk in enumerate(R):
+            s.be.set_mat(host.MAT_R, k, Rk)
+        for rounds in (L, 5):
+            o, M = _against_the_model(s, P, R, bc.SEEDS[name], rounds)
+            per = [m["rounds"] for m, _ in M[0]]
+            print("%s, max_rounds %d: rounds per trial %s" % (name, rounds, per) +
+                  (", the hub a swap's (p, q) in %s trials" % (bc.hub_roles(M[0]),) if name.startswith("hub") else ""))
+            if rounds == L:   # (the test's own inputs)
+                assert 20 < o["rounds"] < L
+                if name.startswith("hub"):
+                    p, q = bc.hub_roles(M[0])
+                    assert p >= 1 and q >= 1
+            else:
+                assert o["rounds"] == 5 and sum(r == 5 for r in per) >= 4
+    finally:
+        s.close()
+    print("%s: %.2f s" % (name, time.perf_counter() - t0))
+
+
+def test_the_repair_flips_the_hub_from_either_side():
+    """hubneg300 with factors whose rows are all equal: every trial starts from D = +-n, the hub's Delta = -4 t^2 sum_q C_hq = -598
+    is the least, so the first of the 149 flips of every trial is the hub -- bis_flip over a list of 300 slots -- and the other 148
+    update h_hub through their own short lists"""
+    t0 = time.perf_counter()
+    s, P, shapes = _long_context("hubneg300")
+    try:
+        R = bc.planted(bc.PLANT, shapes)
+        s.be.set_mat(host.MAT_R, 0, R[0])
+        for rounds in (L, 0):
+            o, M = _against_the_model(s, P, R, bc.PLANT, rounds)
+            D = [m["imbalance"] for m, _ in M[0]]
+            print("planted hubneg300, max_rounds %d: D %s, rounds %s" % (rounds, D, [m["rounds"] for m, _ in M[0]]))
+            assert set(D) == {300, -300} and np.array_equal(o["imbalance"][0], D)
+            for m, log in M[0]:
+                flips = [e for e in log if e[0] == "flip"]
+                assert len(flips) == 149 and flips[0][1] == bc.HUB and flips[0][2] == -598.0
+    finally:
+        s.close()
+    print("planted hubneg300: %.2f s" % (time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("name", ["hubneg300", "densec300", "mixed"])
+def test_long_rows_same_bits_on_the_slab_path(name):
+    """LORADS_BISECT_LDS=0: h on the slab at hs + blockIdx.x * n with n above the workgroup's 256 threads, the sign bytes in the
+    trial's place of the store; against the LDS context that the exact test pins to the model, same factors and seed"""
+    t0 = time.perf_counter()
+    runs = []
+    for env in ({}, {"LORADS_BISECT_LDS": "0"}):
+        s, P, shapes = _long_context(name, env)
+        try:
+            assert shapes[0][0] > bc.TPB
+            for k, Rk in enumerate(bc.case_factors(name, P, shapes)):
+                s.be.set_mat(host.MAT_R, k, Rk)
+            rc, o = s.be.round_bisect(host.PAIR_RR, bc.K, bc.SEEDS[name], L, want_hyperplanes=True)
+            assert rc == 0
+            runs.append((o, np.stack([s.be.bisect_trial(t) for t in range(bc.K)], axis=1)))
+        finally:
+            s.close()
+    (a, sa), (b, sb) = runs
+    for key in ("obj", "obj0", "best", "best0", "sign", "imbalance", "rounds", "t", "diff"):
+        assert np.array_equal(a[key], b[key]), key
+    assert all(np.array_equal(x, y) for x, y in zip(a["hyperplanes"], b["hyperplanes"]))
+    assert np.array_equal(sa, sb) and a["rounds"] > 20 and np.all(a["obj"] < a["obj0"])
+    print("%s, slab against LDS: %.2f s" % (name, time.perf_counter() - t0))
+
+
 def _raw(s, K, seed, rounds=L):
     rc, o = s.be.round_bisect(host.PAIR_RR, K, seed, rounds)
     assert rc == 0
@@ -244,9 +391,12 @@ def test_determinism_and_trial_independence():
     assert not np.array_equal(d.cones[0].G, c.cones[0].G)
 
 
-@pytest.mark.parametrize("name", ["d40", "two"])
+@pytest.mark.parametrize("name", ["d40", "two", "mixed"])
 def test_dual_bound(name):
+    """mixed: T_k = n_k t_k^2 is 1200 for the first cone (t = 2) and 24 for the second"""
     s, P, R = _state(name)
+    if name == "mixed":
+        assert [P.T(k) for k in range(2)] == [1200.0, 24.0]
     r = s.round_bisection(trials=64, seed=1, local_search_rounds=10, tol=1e-8)
     sol = s.solution(tol=1e-8)
     lam = []
