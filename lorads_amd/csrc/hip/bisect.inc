@@ -318,7 +318,7 @@ int bis_check(lorads_hip_ctx *c) {
 }
 
 // does a trial's state of a cone of n rows live in the LDS (LORADS_BISECT_LDS=0 at creation: never, the slab path at every size)
-inline bool bis_in_lds(const lorads_hip_ctx *c, int n) { return c->opt_bisect_lds && (size_t)BIS_RED * 8 + 9 * (size_t)n <= BIS_LDS_BYTES; }
+inline bool bis_in_lds(const lorads_hip_ctx *c, int n) { return c->opt.bisect_lds && (size_t)BIS_RED * 8 + 9 * (size_t)n <= BIS_LDS_BYTES; }
 
 const RoundFeature FT_BISECT{"round_bisect", "bisection-structured", bis_check, false};
 

@@ -139,7 +139,7 @@ int build_gram(DevPool &M, Block &B, const lorads_hip_block &hb, const std::vect
 struct StageTimer {
     bool on;
     std::chrono::steady_clock::time_point t0;
-    StageTimer() : on(getenv("LORADS_HIP_VERBOSE") && getenv("LORADS_HIP_VERBOSE")[0] == '2'), t0(std::chrono::steady_clock::now()) {}
+    StageTimer() : on(opt_verbose() == 2), t0(std::chrono::steady_clock::now()) {}
     void lap(const char *what) {
         if (!on) return;
         const auto t1 = std::chrono::steady_clock::now();
@@ -153,7 +153,7 @@ struct StageTimer {
 int make_pattern(lorads_hip_ctx *c, const std::vector<std::pair<int, int>> &pos, int dim, int nrow, const int *a_ptr, int na,
                  const double *a_val, std::vector<std::pair<int, int>> &uniq, std::vector<int> &index, HostPattern &hp, StageTimer &tm,
                  const char *what) {
-    bool dev = c->opt_dev_presolve && pos.size() >= c->dev_presolve_min && dim > 0 && pos.size() <= (size_t)INT32_MAX / 2;
+    bool dev = c->opt.dev_presolve && pos.size() >= c->opt.dev_presolve_min && dim > 0 && pos.size() <= (size_t)INT32_MAX / 2;
     if (dev) {
         if (dev_pattern(c, pos, dim, nrow, a_ptr, na, a_val, uniq, index, hp)) {
             // (no room for the sorts' scratch next to a problem that fills the HBM, or a failed launch: the host builds the same arrays)
@@ -165,7 +165,7 @@ int make_pattern(lorads_hip_ctx *c, const std::vector<std::pair<int, int>> &pos,
         } else {
             c->n_dev_patterns++;
             tm.lap((std::string(what) + " (device: unique, adjacency, transpose)").c_str());
-            if (!c->opt_presolve_check) return 0;
+            if (!c->opt.presolve_check) return 0;
         }
     }
     std::vector<std::pair<int, int>> uniq_h;
@@ -206,7 +206,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
         const double npad_d = (double)((hb_in.n + 63) / 64 * 64);
         if ((double)dcon.size() * npad_d * npad_d * 8.0 > 8e9) dcon.clear();
     }
-    if (!dcon.empty() && !getenv("LORADS_NO_DENSE_A")) {
+    if (!dcon.empty() && c->opt.dense_a) {
         const int npad = (hb_in.n + 63) / 64 * 64;
         std::vector<double> ad((size_t)dcon.size() * npad * npad, 0.0);
         std::vector<char> isd((size_t)hb_in.nrow, 0);
@@ -349,7 +349,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
             }
         }
     }
-    bool single_entry = !diag && B.nrow > 0 && !B.dense_a && !getenv("LORADS_NO_OP_ENTRY");
+    bool single_entry = !diag && B.nrow > 0 && !B.dense_a;
     for (int i = 0; i < hb.nrow && single_entry; ++i) single_entry = hb.a_ptr[i + 1] - hb.a_ptr[i] == 1;
     if (single_entry) {
         std::vector<double> gev((size_t)B.pa.ne, 0.0);
@@ -375,7 +375,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                 }
             }
         }
-        if (bip && !getenv("LORADS_NO_ENTRY_BIP_DATA")) {
+        if (bip) {
             std::vector<int> rows[2];
             for (int p = 0; p < B.n; ++p) rows[colour[p]].push_back(p);
             if (!rows[1].empty()) {
@@ -393,9 +393,8 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
     {
         int maxsz = 0;
         for (int i = 0; i < hb.nrow; ++i) maxsz = std::max(maxsz, hb.a_ptr[i + 1] - hb.a_ptr[i]);
-        const char *force = getenv("LORADS_OP_CW"); // "1" force on, "0" force off (tests / comparisons)
         bool want = !diag && !B.entry_only && hb.nrow >= 256 && maxsz <= 512;
-        if (force && !diag && !B.entry_only && hb.nrow > 0) want = force[0] == '1';
+        if (c->opt.op_cw >= 0 && !diag && !B.entry_only && hb.nrow > 0) want = c->opt.op_cw == 1; // (forced: tests / comparisons)
         if (B.dense_a) want = false;
         if (want) {
             std::vector<int> deg(B.n + 1, 0);
@@ -422,7 +421,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
             }
             std::vector<int> car(hb.a_row, hb.a_row + B.na), cac(hb.a_col, hb.a_col + B.na);
             std::vector<double> cav(hb.a_val, hb.a_val + B.na);
-            if (maxsz <= 32 && (double)hb.nrow * maxsz <= 1.5 * (double)B.na && !getenv("LORADS_NO_ELL")) {
+            if (maxsz <= 32 && (double)hb.nrow * maxsz <= 1.5 * (double)B.na && c->opt.ell) {
                 // constraints of (nearly) equal size: fixed-width layout, padding = (row 0, row 0, 0.0)
                 B.ca_ell = maxsz;
                 car.assign((size_t)hb.nrow * maxsz, 0); cac.assign((size_t)hb.nrow * maxsz, 0); cav.assign((size_t)hb.nrow * maxsz, 0.0);
@@ -433,7 +432,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                     }
             }
             // fixed-width image of the slot list for k_spmm_ell: 8 slots per row when (almost) every row fits, else 16
-            if (!getenv("LORADS_NO_SLOT_ELL")) {
+            if (c->opt.slot_ell) {
                 long over8 = 0;
                 for (int i = 0; i < B.n; ++i) over8 += (ptr[i + 1] - ptr[i]) > 8;
                 const int ew = (double)over8 <= 0.005 * (double)B.n ? 8 : 16;
@@ -450,7 +449,7 @@ int build_block(lorads_hip_ctx *c, Block &B, const lorads_hip_block &hb_in) {
                 B.cell_w = ew;
             }
             for (int i = 0; i < B.n; ++i) B.cell_over += (ptr[i + 1] - ptr[i]) > B.cell_w;
-            if (B.cell_w && !B.dense_c && !getenv("LORADS_NO_FRONT_CW_DATA")) {
+            if (B.cell_w && !B.dense_c) {
                 // k_front_cw: the objective's own adjacency (both orientations, duplicates summed, neighbours ascending) ...
                 std::vector<std::pair<int, int>> posC(B.nc), uniqC;
                 for (int t = 0; t < B.nc; ++t) posC[t] = {hb.c_row[t], hb.c_col[t]};
@@ -555,7 +554,7 @@ inline int pad_rows(int n) { return (n + 31) & ~31; }
 // mechanism of the odd ranks' padding column; the caller sees the cone's own rank: Block::rl).  data/lorads_solver.c:290-319,
 // 806-906 keep per-cone ranks; what is computed on the extra columns is exact zeros.  LORADS_COMMON_RANK=0: each cone its own.
 void common_rank(lorads_hip_ctx *c) {
-    if (!c->merged_ok || c->nb < 2 || !env_on("LORADS_COMMON_RANK")) return;
+    if (!c->merged_ok || c->nb < 2 || !opt_common_rank()) return;
     int rmax = 0;
     for (auto &B : c->blk) rmax = std::max(rmax, B.r);
     for (auto &B : c->blk) B.r = rmax;
@@ -604,7 +603,7 @@ Block *solo(lorads_hip_ctx *c) {
 // launches of one cone instead of nb.  The CG solves keep their per-cone launches (per-cone alpha, beta, stopping).
 int build_merged(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     c->merged_ok = c->has_merged = false;
-    if (c->nb < 2 || getenv("LORADS_NO_MERGE")) return 0;
+    if (c->nb < 2 || !c->opt.merge) return 0;
     for (int k = 0; k < c->nb; ++k)
         if (prob->blocks[k].is_lp) return 0; // the LP block has its own update; no merged view with one present
     std::vector<char> seen((size_t)std::max(c->m, 1), 0);

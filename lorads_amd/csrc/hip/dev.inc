@@ -64,7 +64,7 @@ int lorads_hip_ubench(lorads_hip_ctx *c, int32_t which, int32_t reps, double *ms
             A.csum = c->csum; A.b = c->b; A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_op;
             A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = 1.0; A.wmode = W_ADMM;
             A.contrib = (which == 30 || which == 33) ? B.w_contrib : (double *)nullptr;
-            A.wt = c->opt_wt_stores;
+            A.wt = c->opt.wt_stores;
             const size_t lds = sizeof(double2) * 32 * 4 * 3 * 8;
 #define UB_FRONT(EWV, FCV) LAUNCH_LDS((k_front_cw<3, EWV, 4, false, FCV>), rd.grid, lds, B.n, rd.rpw, A, V, B.r, U, r, rhs, part_slot(c, 0), part_slot(c, 1), NOGUARD, Deferred{})
             if (which < 33) { if (B.cell_w == 8) UB_FRONT(8, 0); else UB_FRONT(16, 0); }

@@ -86,8 +86,8 @@ void snap_key(const lorads_hip_ctx *c, const MutSnap &s, std::vector<uint64_t> &
 // 0.1048 vs 0.1044 ms at n = 10000) and capturing a chain costs a short run more than it can give back (the driver's 20-step window at
 // the headline: 0.128 ms per step with replay, 0.124-0.125 without).
 bool graph_ok(const lorads_hip_ctx *c) {
-    if (!c->opt_graph || !c->use_publish || (c->prof && c->prof_every < (1 << 20)) || c->ar) return false;
-    return c->opt_graph_forced || c->all_elem <= ((size_t)1 << 18);
+    if (!c->opt.graph || c->graph_capture_failed || (c->prof && c->prof_every < (1 << 20)) || c->ar) return false;
+    return c->opt.graph_forced || c->all_elem <= ((size_t)1 << 18);
 }
 
 // the step parameters on the device (see DS): one tiny launch, and only for the words that changed
@@ -153,11 +153,11 @@ int graph_step(lorads_hip_ctx *c, std::vector<uint64_t> &key, F &&enqueue) {
     auto give_up = [&](hipGraph_t g) { // capture is not available for this chain: launch by launch from now on
         if (g) hipGraphDestroy(g);
         (void)hipGetLastError();
-        c->opt_graph = false;
+        c->graph_capture_failed = true;
         snap_put(c, before);
         c->n_matvec = mv0;
         c->pub_seq = seq0;
-        if (getenv("LORADS_HIP_VERBOSE")) fprintf(stderr, "lorads_hip: graph capture failed, launching step by step\n");
+        if (opt_verbose()) fprintf(stderr, "lorads_hip: graph capture failed, launching step by step\n");
         return enqueue();
     };
     if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return give_up(nullptr);

@@ -46,8 +46,6 @@ struct Slice {
 // what orders the store against the loads of the same bytes is its data, which is computed from them -- NO KERNEL LOADS, IN THE SAME
 // LAUNCH, BYTES IT STORED THIS WAY: k_front_cw writes out / rhs_out / contrib and reads none of them; the CG0 form of k_spmm_ell
 // reads its rows of x and r before it forms what it stores there, and R is written only; the plain form writes `out` only.
-enum { WT_R0 = 1, WT_RHS = 2, WT_CONTRIB = 4, WT_CG0 = 8, WT_AVG = 16, WT_OUT = 32, WT_ALL = 63,
-       WT_DEFAULT = WT_R0 | WT_RHS | WT_CG0 | WT_AVG }; // (measured at the headline: profiles/r08_write_through_ab.txt)
 __device__ __forceinline__ void store16(double *p, size_t off, double a, double b, bool wt) {
     if (wt) {
         typedef double d2v __attribute__((ext_vector_type(2)));
@@ -1110,7 +1108,6 @@ struct FrontCwHoArgs : FrontCwArgs { HandoverArgs ho; };
 //            epilogue, so every sum gets the same +0.0 from it as before
 //   FC_LATE  the row's own operands (X_p, xin_p: nothing reads them before the epilogue) are requested behind the first slot batch
 //            and arrive under the waits of the batches that follow -- 8 NS registers free while the objective is walked
-enum { FC_RAW = 1, FC_LATE = 2, FC_ALL = 3, FC_DEFAULT = FC_ALL }; // (measured at the headline: profiles/r11_front_chain_ab.txt)
 template <int NB, class SL, bool RAW = false, int NS, int W>
 __device__ __forceinline__ void front_gather(const double *__restrict__ X, int r, int lane, int q, int u0, double (&v)[NB][NS][W]) {
 #pragma unroll

@@ -339,7 +339,7 @@ extern "C" int lorads_hip_dual_infeasibility(lorads_hip_ctx *c, double tol, int3
     // SDP cones: independent eigen-solves.  Several cones -> a few host threads, each with its own stream, pull cones
     // from a shared counter: the small kernels of different cones overlap on the device and so do the host waits.
     int nthr = (int)std::min<size_t>(cones.size(), 8);
-    if (const char *e = getenv("LORADS_LANCZOS_THREADS")) nthr = std::max(1, std::min(nthr, atoi(e)));
+    nthr = opt_lanczos_threads(nthr);
     const bool pin_ok = (size_t)2 * (std::min<int>(ncv, 1 << 20) + 1) + 2 <= LZ_PINNED;
     while ((int)c->lz_workers.size() < nthr) { // worker streams + pinned read-back buffers are created once and kept
         const bool own_stream = !c->lz_workers.empty() || nthr > 1;

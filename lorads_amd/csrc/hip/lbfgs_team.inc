@@ -489,7 +489,7 @@ int lteam_build(lorads_hip_ctx *c) {
     // all-reduces, which grow with the team (rand20000: 131 workgroups 114.8 us per inner iteration, 782: 119.9; matcomp50000: 489
     // workgroups 221.6 us, 977: 227.3; profiles/r04_lteam_np.txt); small vectors: one pair per thread
     const int cand[7] = {12, 8, 6, 4, 3, 2, 1};
-    const int force_np = getenv("LORADS_LBFGS_TEAM_NP") ? atoi(getenv("LORADS_LBFGS_TEAM_NP")) : 0; // (measurements)
+    const int force_np = opt_lbfgs_team_np(); // (measurements)
     for (int ci = 0; ci < 7 && !P.valid; ++ci) {
         const int np = cand[ci];
         if (force_np && np != force_np) continue;
@@ -526,7 +526,7 @@ int lteam_build(lorads_hip_ctx *c) {
     HC(hipMemset(P.abort_flag, 0, sizeof(int)));
     if (P.mem.upload(&P.d_map, map)) return 1;
     P.tag = 0;
-    if (getenv("LORADS_HIP_VERBOSE"))
+    if (opt_verbose())
         fprintf(stderr, "lorads_hip: one-launch L-BFGS direction: %d workgroups, %d pairs of doubles per thread and vector\n", P.grid, P.np);
     return 0;
 }
@@ -544,7 +544,7 @@ int lteam_scratch(lorads_hip_ctx *c, size_t ne) {
 
 // may this inner iteration's history update + next direction run as the one launch?
 bool lteam_ready(lorads_hip_ctx *c, int next_inner) {
-    if (!c->lteam || !c->opt_lbfgs_team || c->ar || c->L > 2 || next_inner < 1) return false;
+    if (!c->lteam || !c->opt.lbfgs_team || c->ar || c->L > 2 || next_inner < 1) return false;
     LTeamPlan &P = *c->lteam;
     if ((P.valid || P.failed) && P.len != c->all_elem) { P.release(); P.failed = false; }
     if (P.failed) return false;
@@ -569,7 +569,7 @@ int launch_lbfgs_team(lorads_hip_ctx *c, double tau, int next_inner) {
     A.wg_map = P.d_map;
     A.slA = P.gran + P.offA; A.slF = P.gran + P.offF; A.slX = P.gran + P.offX; A.slB = P.gran + P.offB;
     A.G_team = P.grid; A.nsub = P.nsub; A.tag0 = P.tag; A.abort_flag = P.abort_flag;
-    A.allow_l2 = c->opt_persist_l2 ? 1 : 0;
+    A.allow_l2 = c->opt.persist_l2 ? 1 : 0;
     A.abort_out = c->scal + 7;
     P.tag += 16;
     P.launches++;

@@ -19,7 +19,8 @@
 //   * C u A "union pattern" (PU) with transpose + adjacency, used by the RHS / gradient weighted-sum
 //     products (C + sum_i w_i A_i) X.
 //
-// Source layout: this file = context + the C ABI; kernels.inc = every kernel; build.inc = a cone's device image
+// Source layout: this file = context + the C ABI; options.inc = every environment switch; kernels.inc = every kernel;
+// build.inc = a cone's device image
 // (patterns, adjacency, Gram, operator variants, merged block-diagonal cone, LP block); sweep.inc = launch helpers,
 // the CG operator, speculative solves, the cone-by-cone and lockstep sweeps, the evaluation, result hand-over;
 // lanczos.inc = dual infeasibility; dev_pool.inc = DevPool, the owner of every device and pinned allocation (the fields that
@@ -79,6 +80,8 @@
 #include "lorads_cut_rows.h"
 #include "lorads_hip_dev.h"
 
+#include "options.inc"
+
 namespace {
 
 constexpr int TPB = 256;
@@ -96,9 +99,6 @@ int fail_msg(const std::string &m) {
     g_err = m;
     return 1;
 }
-// switches read from the environment at creation: on unless the value starts with '0' / off unless it starts with '1'
-inline bool env_on(const char *name) { const char *v = getenv(name); return !(v && v[0] == '0'); }
-inline bool env_set(const char *name) { const char *v = getenv(name); return v && v[0] == '1'; }
 #define HC(call)                                        \
     do {                                                \
         hipError_t e__ = (call);                        \
@@ -765,6 +765,7 @@ struct TopkScratch {
 };
 
 struct lorads_hip_ctx {
+    Options opt;              // the environment's switches as ctx_init read them (options.inc); nothing writes them afterwards
     int m = 0, nb = 0, L = 2;
     double b_nrm1 = 0;
     hipStream_t stream = nullptr;
@@ -792,7 +793,6 @@ struct lorads_hip_ctx {
     int spec_b[2] = {1, 1};                   // speculated lockstep iterations of the U and V phase
     int spec_b_hist[2][8] = {{1, 1, 1, 1, 1, 1, 1, 1}, {1, 1, 1, 1, 1, 1, 1, 1}};
     int spec_b_pos = 0;
-    int spec_window = 4;                      // sweeps looked back at (LORADS_SPEC_WINDOW, 1 = the previous sweep's count alone)
     bool merged_ok = false;   // structure allows it (separable constraints, no dense C); ranks decide has_merged
     size_t all_elem = 0;
     double *R = nullptr, *U = nullptr, *V = nullptr, *G = nullptr;   // flat factors
@@ -801,7 +801,6 @@ struct lorads_hip_ctx {
     double *cstage = nullptr; // m+2 (+ objective partials): [local constrValSum | objective part | miss flag | partials] on its way through the all-reduce
     bool stage_clean = false; // cstage[0..m) is known to be zero (left so by k_commit_eval)
     int ar_fast_all = -1;     // every rank holds one cone that can send its objective partials through the all-reduce (-1: not yet agreed)
-    bool opt_ar_fast = true;
     double *b = nullptr, *lambda = nullptr, *csum = nullptr, *q12 = nullptr; // csum: m+2, q12: 2m+2
     double *part = nullptr;   // NSLOT x maxpart partial sums
     int maxpart = MINPART;    // capacity of one slot: one partial per workgroup of the widest row kernel of the largest cone (4 rows per
@@ -821,63 +820,22 @@ struct lorads_hip_ctx {
     bool par_changed_last = false;           // the previous step's parameters differed from the step's before it (see graph_this_step)
     double par_req[3] = {0, 0, 0};           // {rho, tolerance, iteration limit} the previous step asked for
     bool par_req_valid = false;
-    bool opt_graph = true;                   // LORADS_GRAPH=0: every iteration enqueued launch by launch
-    bool opt_graph_batched = false;          // LORADS_GRAPH=2: the lockstep sweep of a merged cone is replayed too
-    bool opt_graph_forced = false;           // LORADS_GRAPH=1 or 2: replay whatever the size (default: small cones only, see graph_ok)
     GraphCache *graphs = nullptr;            // captured launch chains by shape (graph.inc)
+    bool graph_capture_failed = false;       // capture is not available for a chain of this context: launch by launch from then on (graph_step)
     PersistPlan *persist = nullptr;          // teams of resident workgroups, one launch per ADMM iteration (persist.inc; LORADS_PERSIST=0: off)
-    bool opt_persist = true;                 // (read at creation)
     int shared_gpu_fd = -1;                  // LORADS_SHARED_GPU=1: lock file of the device (several processes on one card take turns, see run_sweep_persist)
-    bool opt_persist_carry = true;           // the evaluation leaves (C V) for the next iteration's U front (LORADS_PERSIST_CARRY=0: every front gathers)
-    bool opt_persist_l2 = true;              // granules / rows of workgroups verified to share an XCD go through its L2 (LORADS_PERSIST_L2=0: always written through)
-    int opt_persist_rows = 0;                // LORADS_PERSIST_ROWS=1|2|4: only that many rows per lane group (0: the first that fits; read at creation)
-    bool opt_persist_linear = false;         // LORADS_PERSIST_MAP=linear: blocks dealt team by team even where every team fits one XCD (read at creation)
     bool persist_stamps = false;             // team 0's leader leaves its phase times (lorads_hip_persist_stamps)
     long long n_persist = 0;                 // ADMM iterations run that way
     long long n_launch = 0;                  // kernels enqueued through LAUNCH / the one-launch forms (lorads_hip_launch_count: bench.py's launches per step)
     LTeamPlan *lteam = nullptr;              // phase 1: setlbfgsHisTwo + LBFGSDirection as one launch of resident workgroups (lbfgs_team.inc)
-    bool opt_lbfgs_team = true;              // (LORADS_LBFGS_TEAM=0: launch by launch)
-    bool opt_alm_sval_direct = true;         // ... and k_alm_update writes the entries' coefficients where Block::sv_direct holds (LORADS_ALM_SVAL_DIRECT=0: k_sval)
-    bool opt_alm_fold_cv = true;             // ... where every constraint has one entry the pattern pass does the constraint pass's work (LORADS_ALM_FOLD_CV=0)
-    bool opt_alm_fused_tail = true;          // ... and, behind it, shared passes for A(R R^T), q1, q2 and one closing workgroup (LORADS_ALM_FUSED_TAIL=0)
-    bool use_publish = true;
     Pending pend;             // the scalar steps that wait for a carrier kernel: the only owner of that state
     double *lambda_alt = nullptr; // a front that carries the waiting dual update stores the new multipliers here, then the two vectors swap
     bool virt_refresh = false; // the V-solve's front forms its weights as if the refresh after the U-solve had been stored (see enqueue_sweep)
-    bool opt_entry_bip = true; // single-entry cones with a bipartite entry graph: k_op_entry_bip x 2 (LORADS_ENTRY_BIP=0: k_op_entry)
-    bool opt_fuse_dir = true; // Max-Cut-type cones: the direction update inside the operator kernel (LORADS_FUSE_DIR=0: k_cg_dir)
-    bool opt_cw_quad = true;  // k_cw with 4 lanes per entry where it applies (LORADS_CW_QUAD=0: 8 lanes)
-    bool opt_fuse_eval = true; // single cone on the k_cw path: constraint values and objective partials in one launch (LORADS_FUSE_EVAL=0)
-    bool opt_dense_rem = true; // dense GEMM: 1..4 columns beyond the full tiles on plain FMAs instead of a tile of their own (LORADS_DENSE_REM=0)
-    bool opt_pad_rank = true; // odd ranks run as the next even rank with a zero column (LORADS_PAD_ODD_RANK=0: as they are)
-    bool opt_dev_presolve = true;   // pattern work of the pre-solve on the device (presolve.inc; LORADS_DEV_PRESOLVE=0: host)
-    bool opt_presolve_check = false; // LORADS_PRESOLVE_CHECK=1: build every device pattern on the host too and compare
-    size_t dev_presolve_min = (size_t)1 << 15; // stored entries below which a pattern is built on the host (LORADS_DEV_PRESOLVE_MIN)
     long long n_dev_patterns = 0, n_checked_patterns = 0;
-    int opt_trial_chunk = 0;     // stable-set and bisection rounding: at most this many trials per chunk (LORADS_TRIAL_CHUNK=n, tests only: the chunk loop at sizes a test can afford; 0: the chunk rule alone)
-    bool opt_bisect_lds = true;  // bisection rounding: a trial's state in the LDS where it fits (LORADS_BISECT_LDS=0: the device-memory slab at every size, the path of cones too large for the LDS)
-    bool opt_dense_cache = true; // dense constraint matrices: A_j V kept for the length of a CG solve (LORADS_DENSE_CACHE=0: nd + 1 GEMMs per application)
-    bool opt_front_diag = true; // Max-Cut-type cones: the front forms its diagonal coefficients itself, no k_sval (LORADS_FRONT_DIAG=0)
-    bool opt_eval_diag = true; // Max-Cut-type cones: k_eval_diag instead of k_average + k_pairdots + k_cv_res (LORADS_EVAL_DIAG=0)
-    bool opt_fold_avg = true; // the sweep's last k_cg_update also forms R = (U + V) / 2 (LORADS_FOLD_AVG=0: k_average)
-    bool opt_tile_update = true; // Max-Cut-type cones: k_cg_update on the row tiles of k_op_diag (LORADS_TILE_UPDATE=0: grid-stride over the flat vector)
-    bool avg_folded = false;  // ... and has done so for the evaluation that is enqueued next
-    bool opt_front_lds = true; // k_front_cw parks the first four slot rows in LDS for its second visit (LORADS_FRONT_LDS=0: gathered again)
-    bool opt_front_cw = true; // k_front_cw + k_wsum instead of k_sval + k_spmm2<FRONT> + iteration 0's k_cw (LORADS_FRONT_CW=0: the latter)
-    bool opt_fuse_cg0 = true; // CG iteration 0 of a front_cw_ok cone: the update inside k_spmm_ell (LORADS_FUSE_CG0=0: k_cg_update)
-    // rows per workgroup of k_front_cw and k_spmm_ell (row_deal; LORADS_ROW_DEAL, read at creation): -1 the rule, 0 always 32 (the
-    // launches as they were), 1..32 that many for every cone (tests).  row_deal_cus: the compute units the rule deals over (the
-    // device's; LORADS_ROW_DEAL_CUS pretends another count, tests only)
-    int opt_row_deal = -1, row_deal_cus = 0;
-    // which row outputs of those two kernels are stored through the L2 (WT_* bits, store16 in kernels.inc; LORADS_WT_STORES, read at
-    // creation: a bit mask, 0 = plain stores everywhere)
-    int opt_wt_stores = WT_DEFAULT;
-    // the cuts in the solve front's chain of dependent loads (FC_* bits, k_front_cw; LORADS_FRONT_CHAIN, read at creation: a bit
-    // mask, 0 = the front without them)
-    int opt_front_chain = FC_DEFAULT;
+    bool avg_folded = false;  // the sweep's last k_cg_update has formed R = (U + V) / 2 for the evaluation that is enqueued next (Options::fold_avg)
+    int row_deal_cus = 0;     // the compute units row_deal deals over: the device's, or what Options::pretend_cus pretends
     // The U front of the NEXT ADMM step, enqueued behind this step's hand-over while the host still waits for it (sweep.inc:
-    // spec_front_enqueue / spec_front_adopt).  LORADS_SPEC_FRONT=0: off (read at creation)
-    bool opt_spec_front = true;
+    // spec_front_enqueue / spec_front_adopt; Options::spec_front)
     struct SpecFront {
         bool live = false;        // a front is enqueued and its step finished in its first pass: the next admm_step may take it
         bool dual_seen = false;   // update_dual_var has been called since (once: see there)
@@ -889,30 +847,20 @@ struct lorads_hip_ctx {
     } spec;
     unsigned long long spec_epoch = 0; // bumped by spec_touch: every C-ABI entry but update_dual_var, admm_step and the statistics' own
     long long n_spec_enq = 0, n_spec_adopt = 0, n_spec_discard = 0, n_spec_blocked = 0;
-    // ... and that front's launch carries the step's hand-over as one more workgroup instead of following k_publish_final (sweep.inc:
-    // enqueue_publish; k_front_cw's hand-over form).  LORADS_HANDOVER_ON_FRONT=0: two launches (read at creation)
-    bool opt_handover_on_front = true;
     long long n_handover_front = 0, n_handover_alone = 0; // hand-overs carried on a front / launched as kernels of their own
-    bool opt_exact_refresh = false, opt_split_front = false; // test knobs (read at creation): see constr_by_recurrence, fused_front
     bool final_pending = false;              // an evaluation's closing sums wait for the next hand-over (k_publish_final)
     EvalFinalArgs final_args;
     double *scal = nullptr;   // 64 device scalars
     CGState *st = nullptr;    // one per (cone, half)
     CGState *st_shadow = nullptr; // state before a pending convergence test (see Deferred)
-    bool opt_lazy_scalars = true; // LORADS_LAZY_SCALARS=0: every scalar step as its own launch
-    bool opt_seg_carry_init = true; // (LORADS_SEG_CARRY_INIT=0: k_cg_init_seg as a launch of its own)
     // separable shards: the evaluation's four scalars summed by the ranks' hosts after the hand-over (lorads_hip_set_scalar_exchange)
     lorads_hip_scalar_exchange_fn sx = nullptr;
     void *sx_user = nullptr;
     bool sx_pending = false; // the local sums are on their way to the mirror (scal[SX_WORD..+4)); the next wait_publish exchanges them
     int sx_with_obj = 0;
     long long n_sx = 0;
-    bool opt_seg_virt = true; // lockstep sweep, Max-Cut-type merged cone, evaluation at the end: the refresh after the U-solves is not stored, the V front forms its weights from U_p.V_p itself (LORADS_SEG_VIRT=0: k_pairdots + k_cv)
-    bool opt_seg_carry_dual = true; // lockstep sweep: a waiting dual update rides on the U front of the merged cone (LORADS_SEG_CARRY_DUAL=0: k_dual_update)
-    bool opt_seg_carry_restart = true; // lockstep sweep: the k % 20 == 0 restart's test and scalars ride on its two operator kernels (LORADS_SEG_CARRY_RESTART=0)
     double *seg_rr_alt = nullptr; // second slot of every stage's r.r (see SegArgs)
     int *seg_tile_info = nullptr; // int4 per row tile of the merged cone (see DirArgs.seg_info)
-    bool opt_seg_carry = true;    // LORADS_SEG_CARRY=0: k_cg_check_seg after every update of the lockstep sweep
     int *seg_tile_cone = nullptr;             // row tile (workgroup of a row kernel) -> cone, merged cone
     CGState *h_st = nullptr;  // pinned mirror
     double *h_scal = nullptr; // pinned mirror of scalars
@@ -926,8 +874,6 @@ struct lorads_hip_ctx {
     double *sepbuf = nullptr; // 32: scalars on their way through the all-reduce in that mode
     SepExtra sep_extra{};     // scalars the next evaluation's all-reduce also carries (set by the caller, taken by enqueue_eval)
     double *gram = nullptr;   // 128: [0..66) products V_a.V_b of the Gram-form L-BFGS direction, [80..91) the coefficients of D
-    bool opt_gram = true;     // LORADS_LBFGS_GRAM=0: sharded direction by the sequential recursion, one collective per dot
-    bool opt_gram_single = false; // LORADS_LBFGS_GRAM=2: the Gram-form direction on a single GPU as well
     // profiling
     int prof = 0, prof_every = 8;
     int prof_target = 0;      // what a profiling window times: 0 = CG operator applications, 1 = solve fronts (lorads_hip_profile_target)
@@ -979,7 +925,7 @@ double *part_slot(lorads_hip_ctx *c, int k) { return c->part + (size_t)k * c->ma
 // (lorads_hip_set_separable) hold their own constraints: only scalars are summed (c->ar && c->sep).
 inline bool shard_vec(const lorads_hip_ctx *c) { return c->ar && !c->sep; }
 // the rank the kernels run at (see Block::rl): odd ranks take a zero column along; the LP block's "rank" 1 is not a factor width
-inline int dev_rank(const lorads_hip_ctx *c, int r, bool is_lp) { return (c->opt_pad_rank && !is_lp && (r & 1) && r < 512) ? r + 1 : r; }
+inline int dev_rank(const lorads_hip_ctx *c, int r, bool is_lp) { return (c->opt.pad_rank && !is_lp && (r & 1) && r < 512) ? r + 1 : r; }
 
 // whatever a front enqueued ahead of its step has guessed or left in scratch no longer holds: the next step launches its own
 inline void spec_touch(lorads_hip_ctx *c) {
@@ -1008,17 +954,14 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
         if (need > ((size_t)1 << 27)) return fail_msg("cone dimension beyond 2^29 rows");
         c->maxpart = (int)std::max<size_t>((size_t)MINPART, (need + 255) & ~(size_t)255);
     }
-    c->opt_pad_rank = env_on("LORADS_PAD_ODD_RANK");
-    c->opt_dev_presolve = env_on("LORADS_DEV_PRESOLVE");
-    c->opt_presolve_check = env_set("LORADS_PRESOLVE_CHECK");
-    if (getenv("LORADS_DEV_PRESOLVE_MIN")) c->dev_presolve_min = (size_t)std::max(0ll, atoll(getenv("LORADS_DEV_PRESOLVE_MIN")));
+    c->opt = read_options();
     c->blk.resize(c->nb);
     for (int k = 0; k < c->nb; ++k)
         if (build_block(c, c->blk[k], prob->blocks[k])) return 1;
     if (build_merged(c, prob)) return 1;
     common_rank(c);
     refresh_merged(c);
-    if (getenv("LORADS_HIP_VERBOSE"))
+    if (opt_verbose())
         fprintf(stderr, "lorads_hip: %d cone(s), merged view %s\n", c->nb, c->has_merged ? "on" : (c->merged_ok ? "off (ranks differ)" : "not applicable"));
     if (alloc_factors(c)) return 1;
     std::vector<double> hb(prob->b, prob->b + c->m);
@@ -1031,55 +974,18 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
         return 1;
     HC(hipMemset(c->par, 0, sizeof(double) * 8));
     HC(hipMemset(c->seq_dev, 0, sizeof(unsigned long long) * 2));
-    c->opt_graph = env_on("LORADS_GRAPH");
-    c->opt_graph_batched = getenv("LORADS_GRAPH") && getenv("LORADS_GRAPH")[0] == '2';
-    c->opt_graph_forced = getenv("LORADS_GRAPH") && (getenv("LORADS_GRAPH")[0] == '1' || getenv("LORADS_GRAPH")[0] == '2');
     if (M.alloc_pinned(&c->h_ctrl, 64 * sizeof(double) + sizeof(CGState) * (size_t)std::max(2 * c->nb, 1), hipHostMallocMapped) ||
         M.alloc_pinned(&c->h_flag, 64 / sizeof(*c->h_flag), hipHostMallocMapped))
         return 1;
     *c->h_flag = 0;
     HC(hipHostGetDevicePointer((void **)&c->h_ctrl_dev, c->h_ctrl, 0));
     HC(hipHostGetDevicePointer((void **)&c->h_flag_dev, c->h_flag, 0));
-    c->use_publish = !getenv("LORADS_NO_PUBLISH");
-    c->opt_lazy_scalars = env_on("LORADS_LAZY_SCALARS");
-    c->opt_ar_fast = !env_set("LORADS_AR_PLAIN");
-    c->opt_gram = env_on("LORADS_LBFGS_GRAM");
-    c->opt_gram_single = getenv("LORADS_LBFGS_GRAM") && getenv("LORADS_LBFGS_GRAM")[0] == '2';
-    c->opt_fuse_dir = env_on("LORADS_FUSE_DIR");
-    c->opt_entry_bip = env_on("LORADS_ENTRY_BIP");
-    c->opt_seg_carry = env_on("LORADS_SEG_CARRY");
-    c->opt_seg_carry_init = env_on("LORADS_SEG_CARRY_INIT");
-    c->opt_seg_virt = env_on("LORADS_SEG_VIRT");
-    c->opt_seg_carry_dual = env_on("LORADS_SEG_CARRY_DUAL");
-    c->opt_seg_carry_restart = env_on("LORADS_SEG_CARRY_RESTART");
-    c->opt_cw_quad = env_on("LORADS_CW_QUAD");
-    c->opt_front_cw = env_on("LORADS_FRONT_CW");
-    c->opt_fuse_cg0 = env_on("LORADS_FUSE_CG0");
-    c->opt_front_lds = env_on("LORADS_FRONT_LDS");
     {
-        const char *v = getenv("LORADS_ROW_DEAL");
-        c->opt_row_deal = (!v || !v[0] || v[0] == 'a') ? -1 : std::max(0, std::min(32, atoi(v)));
         int dev = 0;
         HC(hipGetDevice(&dev));
         HC(hipDeviceGetAttribute(&c->row_deal_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (getenv("LORADS_ROW_DEAL_CUS")) c->row_deal_cus = std::max(1, atoi(getenv("LORADS_ROW_DEAL_CUS")));
+        if (c->opt.pretend_cus) c->row_deal_cus = c->opt.pretend_cus;
     }
-    if (getenv("LORADS_WT_STORES") && getenv("LORADS_WT_STORES")[0]) c->opt_wt_stores = atoi(getenv("LORADS_WT_STORES")) & WT_ALL;
-    if (getenv("LORADS_FRONT_CHAIN") && getenv("LORADS_FRONT_CHAIN")[0]) c->opt_front_chain = atoi(getenv("LORADS_FRONT_CHAIN")) & FC_ALL;
-    c->opt_spec_front = env_on("LORADS_SPEC_FRONT");
-    c->opt_handover_on_front = env_on("LORADS_HANDOVER_ON_FRONT");
-    if (getenv("LORADS_SPEC_WINDOW")) c->spec_window = std::max(1, std::min(8, atoi(getenv("LORADS_SPEC_WINDOW"))));
-    c->opt_fold_avg = env_on("LORADS_FOLD_AVG");
-    c->opt_tile_update = env_on("LORADS_TILE_UPDATE");
-    c->opt_eval_diag = env_on("LORADS_EVAL_DIAG");
-    c->opt_front_diag = env_on("LORADS_FRONT_DIAG");
-    c->opt_dense_cache = env_on("LORADS_DENSE_CACHE");
-    c->opt_bisect_lds = env_on("LORADS_BISECT_LDS");
-    if (getenv("LORADS_TRIAL_CHUNK")) c->opt_trial_chunk = std::max(0, atoi(getenv("LORADS_TRIAL_CHUNK")));
-    c->opt_fuse_eval = env_on("LORADS_FUSE_EVAL");
-    c->opt_dense_rem = env_on("LORADS_DENSE_REM");
-    c->opt_exact_refresh = env_set("LORADS_EXACT_REFRESH");
-    c->opt_split_front = env_set("LORADS_SPLIT_FRONT");
     c->scal = (double *)c->ctrl;
     c->st = (CGState *)(c->ctrl + 64 * sizeof(double));
     c->h_scal = (double *)c->h_ctrl;
@@ -1093,17 +999,8 @@ int ctx_init(lorads_hip_ctx *c, const lorads_hip_problem *prob) {
     if (M.alloc(&c->st_shadow, (size_t)std::max(2 * c->nb, 1))) return 1;
     HC(hipMemset(c->st_shadow, 0, sizeof(CGState) * (size_t)std::max(2 * c->nb, 1)));
     c->persist = new PersistPlan();
-    c->opt_persist = env_on("LORADS_PERSIST");
-    c->opt_persist_l2 = env_on("LORADS_PERSIST_L2");
-    c->opt_persist_carry = env_on("LORADS_PERSIST_CARRY");
-    c->opt_persist_rows = getenv("LORADS_PERSIST_ROWS") ? atoi(getenv("LORADS_PERSIST_ROWS")) : 0; // (measurements and tests)
-    c->opt_persist_linear = getenv("LORADS_PERSIST_MAP") && getenv("LORADS_PERSIST_MAP")[0] == 'l';
     c->lteam = new LTeamPlan();
-    c->opt_lbfgs_team = env_on("LORADS_LBFGS_TEAM");
-    c->opt_alm_fused_tail = env_on("LORADS_ALM_FUSED_TAIL");
-    c->opt_alm_fold_cv = env_on("LORADS_ALM_FOLD_CV");
-    c->opt_alm_sval_direct = env_on("LORADS_ALM_SVAL_DIRECT");
-    if (env_set("LORADS_SHARED_GPU")) {
+    if (c->opt.shared_gpu) {
         int dev = 0;
         char bus[64] = "0";
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetPCIBusId(bus, sizeof(bus), dev);
@@ -1269,7 +1166,7 @@ int lorads_hip_lbfgs_direction(lorads_hip_ctx *c, int32_t inner) {
     // (LORADS_LBFGS_GRAM=2: the Gram form on one GPU too -- two passes over the vectors instead of five.  Its dots are combinations of
     // the 15 products and round differently from the recursion's (1e-16 of scale): on hard instances whole solves then take other
     // iteration counts than the reference's (theta30 at phase1Tol 1e-3: 3608 inner iterations against 2991), so the default is the recursion)
-    if (!c->ar && !(c->opt_gram_single && c->L <= 5)) { // single rank: one kernel per stage of the recursion (5 + 1 launches for history 2)
+    if (!c->ar && !(c->opt.gram_single && c->L <= 5)) { // single rank: one kernel per stage of the recursion (5 + 1 launches for history 2)
         double *pp[2] = {part_slot(c, 3), part_slot(c, 5)};
         int cur = 0;
         if (inner == 0) {
@@ -1301,7 +1198,7 @@ int lorads_hip_lbfgs_direction(lorads_hip_ctx *c, int32_t inner) {
         LAUNCH(k_use_grad_p, gv, n, pp[cur], gv, c->G, D);
         return 0;
     }
-    if (c->opt_gram && c->L <= 5) { // sharded cones: ONE collective for the whole direction (see k_gram)
+    if (c->opt.gram && c->L <= 5) { // sharded cones: ONE collective for the whole direction (see k_gram)
         if (inner == 0) { // D = -Grad; LBFGSDirUseGrad could only replace it by itself
             LAUNCH(k_scale_copy, gv, n, -1.0, c->G, D);
             return 0;
@@ -1505,7 +1402,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
         // (the history update and the NEXT direction as one launch of resident workgroups, where that applies: lbfgs_team.inc)
         team = lteam_ready(c, next_inner);
         SvDirect sd{};
-        if (c->opt_alm_sval_direct && B.sv_direct && B.pu.cbase && B.nrow == c->m) {
+        if (c->opt.alm_sval_direct && B.sv_direct && B.pu.cbase && B.nrow == c->m) {
             sd.ptr = B.sv_ptr; sd.e = B.sv_e; sd.a = B.sv_a; sd.cbase = B.pu.cbase; sd.S = B.pu.S; sd.row_idx = B.row_idx; sd.b = c->b; sd.lambda = c->lambda;
             sd.rho = rho; sd.nrow = B.nrow;
         }
@@ -1518,7 +1415,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
         const int glag = spmm(c, B, B.pu, c->R, OP_GRAD, nullptr, nullptr, rho, c->G, part_slot(c, 0), NOGUARD);
         if (team) { if (launch_lbfgs_team(c, tau, next_inner)) return 1; }
         else LAUNCH(k_his_two_dot, gv, c->all_elem, tau, c->U, c->G, h.s, h.y, part_slot(c, 3));
-        if (team && c->use_publish && c->opt_alm_fused_tail && B.nc > 0 && B.pa.ne > 0 && lteam_scratch(c, (size_t)B.pa.ne) == 0) {
+        if (team && c->opt.alm_fused_tail && B.nc > 0 && B.pa.ne > 0 && lteam_scratch(c, (size_t)B.pa.ne) == 0) {
             // the next direction exists already: the step's A(R R^T) and the next line search's q1, q2 share their passes, one
             // workgroup closes the iteration and hands it over (lbfgs_team.inc) -- 3 launches where the forms below take 8
             const Shape sh = shape_for(B.r);
@@ -1527,7 +1424,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
             // cones whose constraints have ONE entry each (Max-Cut type, single-entry): the pattern pass does the constraints' bookkeeping too
             // (up to 2048 workgroups' worth of entries: beyond that the nine block sums per workgroup and their partials cost more than
             // the launch they save -- cfg5, 6250 workgroups: 191.7 -> 195.9 us per inner iteration)
-            const bool fold = c->opt_alm_fold_cv && (B.diag_only || B.entry_only) && B.na == B.nrow && B.pa.e_ptr && g1 <= std::min(c->maxpart, 2048);
+            const bool fold = c->opt.alm_fold_cv && (B.diag_only || B.entry_only) && B.na == B.nrow && B.pa.e_ptr && g1 <= std::min(c->maxpart, 2048);
             CvFold cf{};
             if (fold) {
                 cf.e_ptr = B.pa.e_ptr; cf.e_con = B.pa.e_con; cf.e_val = B.pa.e_val; cf.row_idx = B.row_idx; cf.cv = B.cv; cf.csum = c->csum;
@@ -1575,7 +1472,7 @@ int lorads_hip_alm_step(lorads_hip_ctx *c, double rho, double tau, int32_t next_
         LAUNCH(k_alm_tail, 1, part_slot(c, 0), glag, c->scal + 8, part_slot(c, 3), team ? 0 : gv, c->ring_ab + 2 * c->head + 1, part_slot(c, 8),
                part_slot(c, 9), nres, c->scal);
         c->head = (c->head + 1) % c->L;
-    } else if (c->ar && c->sep && c->opt_gram) {
+    } else if (c->ar && c->sep && c->opt.gram) {
         // separable shards: ||Grad||^2 and y.s of the step are local sums like the evaluation's -- they ride on ITS all-reduce
         // (six doubles, one collective for the whole second half), and 1/(y.s) is formed from the summed value afterwards
         Ring &h = c->ring[c->head];
@@ -1664,9 +1561,9 @@ int lorads_hip_update_dual_var(lorads_hip_ctx *c, double rho) {
     if (c->spec.live) { if (c->spec.dual_seen) spec_touch(c); else c->spec.dual_seen = true; }
     // (see Pending::post_dual; with sharded cones only the one-kernel front can take it: it needs no owner pairs, k_wsum stores all of lambda)
     // (lockstep sweep of a Max-Cut-type merged cone that sees every constraint: its U front takes it, see enqueue_batched)
-    const bool merged_front = c->has_merged && c->opt_seg_carry_dual && c->merged.diag_only && c->merged.rc_w > 0 && c->merged.w_uv &&
-                              c->merged.nrow == c->m && c->opt_front_diag && !c->opt_split_front && !shard_vec(c) && !getenv("LORADS_NO_BATCH");
-    if (c->opt_lazy_scalars && c->lambda_alt && ((c->nb == 1 && (!shard_vec(c) || front_cw_ok(c, c->blk[0]))) || merged_front ||
+    const bool merged_front = c->has_merged && c->opt.seg_carry_dual && c->merged.diag_only && c->merged.rc_w > 0 && c->merged.w_uv &&
+                              c->merged.nrow == c->m && c->opt.front_diag && !c->opt.split_front && !shard_vec(c) && !opt_no_batch();
+    if (c->opt.lazy_scalars && c->lambda_alt && ((c->nb == 1 && (!shard_vec(c) || front_cw_ok(c, c->blk[0]))) || merged_front ||
                                                  (c->persist && !c->persist->failed && persist_eligible(c)))) {
         c->pend.flush(c);
         c->pend.post_dual(rho);
@@ -1918,7 +1815,7 @@ int lorads_hip_operator_kind(lorads_hip_ctx *c, int32_t k, int32_t *kind) {
     const Block &B = c->blk[k];
     *kind = B.diag_only ? 2 : B.entry_only ? 3 : B.use_cw ? 4 : B.has_gram ? 0 : 1;
     if (B.dense_a) *kind += 16; // + dense constraint matrices through the dense GEMM
-    if (B.entry_only && B.bip_rows[0] && c->opt_entry_bip) *kind += 32; // single-entry operator in its two-colour form (k_op_entry_bip x 2)
+    if (B.entry_only && B.bip_rows[0] && c->opt.entry_bip) *kind += 32; // single-entry operator in its two-colour form (k_op_entry_bip x 2)
     return 0;
 }
 
@@ -1972,7 +1869,7 @@ int lorads_hip_persist_plan(lorads_hip_ctx *c, int64_t out[8]) {
     out[4] = ok ? P->ssz_max : 0;
     out[5] = ok ? P->occ : 0;
     out[6] = ok ? P->ncu : 0;
-    out[7] = ok && c->opt_persist_l2 ? 1 : 0;
+    out[7] = ok && c->opt.persist_l2 ? 1 : 0;
     return 0;
 }
 
@@ -2052,17 +1949,17 @@ int lorads_hip_row_deal_stats(lorads_hip_ctx *c, int32_t k, int out[3]) { // (a 
 
 int lorads_hip_wt_stores(lorads_hip_ctx *c, int *mask) { // (a statistics entry: leaves a front in flight alone)
     if (!c || !mask) return fail_msg("wt_stores: bad argument");
-    *mask = c->opt_wt_stores;
+    *mask = c->opt.wt_stores;
     return 0;
 }
 
 int lorads_hip_front_chain(lorads_hip_ctx *c, int *mask, int *eff) { // (a statistics entry: leaves a front in flight alone)
     if (!c || !mask) return fail_msg("front_chain: bad argument");
-    *mask = c->opt_front_chain;
+    *mask = c->opt.front_chain;
     if (eff) { // what launch_front_cw launches: the cuts belong to the form with the LDS park
         *eff = 0;
         for (const Block &B : c->blk)
-            if (B.front_cw && c->opt_front_lds && (B.r + 15) / 16 <= 3) *eff = c->opt_front_chain;
+            if (B.front_cw && c->opt.front_lds && (B.r + 15) / 16 <= 3) *eff = c->opt.front_chain;
     }
     return 0;
 }
@@ -2075,7 +1972,7 @@ int lorads_hip_dense_plan(lorads_hip_ctx *c, int32_t k, int64_t out[16]) { // (a
     if (!B.dense_c && !B.dense_a) return 0;
     out[0] = B.npad; out[1] = B.ksplit_b;
     for (int col0 = 0; col0 < B.r && out[2] < 4; col0 += 128) { // (dense_cx's launch loop; rank <= 512: at most four launches)
-        const DenseTiles tl = dense_tiles(B.r, col0, c->opt_dense_rem);
+        const DenseTiles tl = dense_tiles(B.r, col0, c->opt.dense_rem);
         int64_t *o = out + 3 + 3 * out[2]++;
         o[0] = col0; o[1] = tl.nt; o[2] = tl.rem;
     }

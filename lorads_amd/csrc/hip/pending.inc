@@ -9,7 +9,7 @@ CGState *shadow_of(lorads_hip_ctx *c, CGState *st) { return c->st_shadow + (st -
 #define SEG_LAUNCH(kern, ...) do { c->pend.flush(c); SEG_RAW(kern, __VA_ARGS__); } while (0)
 
 void Pending::post_init(lorads_hip_ctx *c, CGState *st, const double *part_rr, int nrr, const double *part_b, int nb, double tol, Guard front) {
-    if (c->opt_lazy_scalars) { // rides on the first kernel of iteration 0 if that kernel can carry it (k_op_diag, k_cw, k_wsum)
+    if (c->opt.lazy_scalars) { // rides on the first kernel of iteration 0 if that kernel can carry it (k_op_diag, k_cw, k_wsum)
         init = InitArgs{st, shadow_of(c, st), part_rr, part_b, nrr, nb, ds_tol(c, tol)};
         init_g = front;
     } else {
@@ -17,7 +17,7 @@ void Pending::post_init(lorads_hip_ctx *c, CGState *st, const double *part_rr, i
     }
 }
 void Pending::post_check(lorads_hip_ctx *c, CGState *st, const double *part, int np, double tol, int maxit, Guard g) {
-    if (c->opt_lazy_scalars) { // rides on the next kernel if that kernel can carry it
+    if (c->opt.lazy_scalars) { // rides on the next kernel if that kernel can carry it
         chk = Deferred{st, shadow_of(c, st), part, np, ds_maxit(c, maxit), ds_tol(c, tol), g.need};
         chk_g = g;
     } else {

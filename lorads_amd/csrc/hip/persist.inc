@@ -832,7 +832,7 @@ inline size_t pk_lds_bytes(int ns, int rows) { return sizeof(double) * ((size_t)
 
 // may this context's ADMM iteration run as the one-launch form at all?
 bool persist_eligible(const lorads_hip_ctx *c) {
-    if (!c->opt_persist || c->nb < 1 || c->m <= 0 || shard_vec(c) || !c->use_publish) return false;
+    if (!c->opt.persist || c->nb < 1 || c->m <= 0 || shard_vec(c)) return false;
     if (c->nb > 1 && !c->merged_ok) return false; // (merged_ok <=> no LP block, no dense cone, every constraint in exactly one cone)
     long long nrow = 0;
     for (const auto &B : c->blk) {
@@ -854,7 +854,7 @@ int persist_build(lorads_hip_ctx *c) {
     int dev = 0, ncu_dev = 0;
     HC(hipGetDevice(&dev));
     HC(hipDeviceGetAttribute(&ncu_dev, hipDeviceAttributeMultiprocessorCount, dev)); // (hipGetDeviceProperties takes milliseconds)
-    const int force_rows = c->opt_persist_rows; // (LORADS_PERSIST_ROWS: measurements and tests)
+    const int force_rows = c->opt.persist_rows; // (LORADS_PERSIST_ROWS: measurements and tests)
     const int cand[3] = {1, 2, 4};
     for (int ci = 0; ci < 3 && !P.valid; ++ci) {
         const int rows = cand[ci];
@@ -902,7 +902,7 @@ int persist_build(lorads_hip_ctx *c) {
         std::vector<int> order(c->nb), load(8, 0), xcd_of(c->nb, 0);
         for (int k = 0; k < c->nb; ++k) order[k] = k;
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cones[a].G > cones[b].G; });
-        bool ok = !c->opt_persist_linear && P.ncu % 8 == 0;
+        bool ok = !c->opt.persist_linear && P.ncu % 8 == 0;
         for (int k : order) {
             int x = 0;
             for (int y = 1; y < 8; ++y) if (load[y] < load[x]) x = y;
@@ -955,7 +955,7 @@ int persist_build(lorads_hip_ctx *c) {
         offB[k] = words; words += (size_t)2 * 8 * PK_SLOTW;
     }
     if (P.mem.alloc(&P.gran, words) || P.mem.alloc(&P.team_out, (size_t)4 * c->nb) || P.mem.alloc(&P.arrive, 1) || P.mem.alloc(&P.abort_flag, 1) || P.mem.alloc(&P.stamps, 16)) return 1;
-    if (c->opt_persist_carry && P.mem.alloc(&P.cx, c->all_elem)) return 1;
+    if (c->opt.persist_carry && P.mem.alloc(&P.cx, c->all_elem)) return 1;
     P.cx_ok = false;
     P.gran_words = words;
     HC(hipMemset(P.gran, 0, sizeof(unsigned long long) * std::max<size_t>(words, 1)));
@@ -968,7 +968,7 @@ int persist_build(lorads_hip_ctx *c) {
     if (P.mem.upload(&P.d_cones, cones) || P.mem.upload(&P.d_map, map)) return 1;
     P.launches = 0;
     P.tag = 0;
-    if (getenv("LORADS_HIP_VERBOSE"))
+    if (opt_verbose())
         fprintf(stderr, "lorads_hip: one-launch ADMM iteration: %d cone(s), %d workgroups (%s), %d row(s) per lane group, column steps %d, %zu bytes of LDS\n",
                 c->nb, P.grid, P.xcd_map ? "every team on one XCD's blocks" : "dealt team by team", P.rows, P.ns, P.lds);
     return 0;
@@ -1015,7 +1015,7 @@ int run_sweep_persist(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
     A.ctrl_src = (unsigned long long *)c->ctrl; A.ctrl_dst = (unsigned long long *)c->h_ctrl_dev; A.nwords = (int)state_words(c);
     A.flag = c->h_flag_dev; A.seq_dev = c->seq_dev;
     A.stamps = c->persist_stamps ? P.stamps : nullptr;
-    A.allow_l2 = c->opt_persist_l2 ? 1 : 0;
+    A.allow_l2 = c->opt.persist_l2 ? 1 : 0;
     A.CX = P.cx; A.cv_in = (P.cx && P.cx_ok) ? 1 : 0; A.cv_out = (P.cx && with_eval) ? 1 : 0;
     P.cx_ok = false; // (V changes in this launch; true again below once the launch has left the new (C V) behind and has been seen to complete)
     P.tag += PK_TAGS_PER_LAUNCH;

@@ -493,7 +493,7 @@ void round_signs(lorads_hip_ctx *c, int32_t src, int k, int K, int W, const doub
 // to the multiple, where a test sets it.  trial_chunks walks the chunks [t0, t1) of K trials (body: 0, or 1 with the message set).
 inline int trial_chunk(const lorads_hip_ctx *c, int K, int nmax, size_t elems, int multiple) {
     size_t ch = std::max<size_t>(16, elems / nmax / multiple * multiple);
-    if (c->opt_trial_chunk > 0) ch = std::min(ch, ((size_t)c->opt_trial_chunk + multiple - 1) / multiple * multiple);
+    if (c->opt.trial_chunk > 0) ch = std::min(ch, ((size_t)c->opt.trial_chunk + multiple - 1) / multiple * multiple);
     return (int)std::min<size_t>((size_t)K, ch);
 }
 template <typename Body>

@@ -87,13 +87,13 @@ int spmm_front(lorads_hip_ctx *c, const Block &B, const Pattern &P, const double
     return grid;
 }
 // rows per workgroup and grid of k_front_cw and of k_spmm_ell at 8 lanes per row on cone B: fixed for the context's life (see
-// row_deal and lorads_hip_ctx::opt_row_deal).  The merged lockstep cone keeps 32 rows; so does a forced deal whose grid would not
+// row_deal and Options::row_deal).  The merged lockstep cone keeps 32 rows; so does a forced deal whose grid would not
 // fit a partial-sum slot.
 RowDeal row_deal_of(const lorads_hip_ctx *c, const Block &B) {
     const size_t n = (size_t)std::max(B.n, 0);
-    if (c->opt_row_deal == 0 || &B == &c->merged) return RowDeal{32, nblocks_for(n, 32)};
-    if (c->opt_row_deal > 0) {
-        const int rpw = nblocks_for(n, c->opt_row_deal) <= c->maxpart ? c->opt_row_deal : 32;
+    if (c->opt.row_deal == 0 || &B == &c->merged) return RowDeal{32, nblocks_for(n, 32)};
+    if (c->opt.row_deal > 0) {
+        const int rpw = nblocks_for(n, c->opt.row_deal) <= c->maxpart ? c->opt.row_deal : 32;
         return RowDeal{rpw, nblocks_for(n, rpw)};
     }
     return row_deal(n, c->row_deal_cus);
@@ -121,7 +121,7 @@ int spmm_cw(lorads_hip_ctx *c, const Block &B, const double *w, const double *X,
     }
     if (B.cell_w && (mode == OP_CG || mode == OP_RES)) {
         Cg0Args wo{}; // (the plain form reads its store mask from here and nothing else)
-        wo.wt = c->opt_wt_stores;
+        wo.wt = c->opt.wt_stores;
         if (B.cell_w == 8)
             SHAPE_DISPATCH(sh, LAUNCH((k_spmm_ell<LG_, V2_, NS_, 8>), rd.grid, B.n, rd.rpw, B.cadj_ptr, B.cadj_col, B.cadj_con, B.cadj_a, B.cell_col,
                                       B.cell_con, B.cell_a, w, X, B.r, mode, xin, rhs, out, part, g, wo));
@@ -135,7 +135,7 @@ int spmm_cw(lorads_hip_ctx *c, const Block &B, const double *w, const double *X,
     return grid;
 }
 bool cw_quad(lorads_hip_ctx *c, const Block &B) {
-    return c->opt_cw_quad && use_v2(B.r) && B.r <= 48 && B.ca_ell > 8 && B.ca_ell <= 16;
+    return c->opt.cw_quad && use_v2(B.r) && B.r <= 48 && B.ca_ell > 8 && B.ca_ell <= 16;
 }
 // w_i = A_i(sym(X Y^T)) for every constraint of the cone + k_cv's bookkeeping, without the pair-dot array
 int cw(lorads_hip_ctx *c, const Block &B, const double *X, const double *Y, double scale, double *w_out, double *cv, int mode,
@@ -174,7 +174,7 @@ int dense_cx(lorads_hip_ctx *c, const Block &B, const double *X, double *W, Guar
         const int gx = B.npad / 32, ks = B.ksplit_b, krange = B.npad / ks;
         double *dst = ks == 1 ? W : B.Wpart;
         for (int col0 = 0; col0 < B.r; col0 += 128) { // (up to 8 column tiles of 16 per launch)
-            const DenseTiles tl = dense_tiles(B.r, col0, c->opt_dense_rem);
+            const DenseTiles tl = dense_tiles(B.r, col0, c->opt.dense_rem);
             const int nt = tl.nt, rem = tl.rem;
 #define DCXB(NTV, RV) hipLaunchKernelGGL((k_dense_cx_b<NTV, 4, RV>), dim3(gx, ks), dim3(TPB), 0, c->stream, B.n, B.npad, krange, M, X, B.r, dst, g, col0)
 #define DCXR(NTV)                                  \
@@ -210,7 +210,7 @@ int dense_cx(lorads_hip_ctx *c, const Block &B, const double *X, double *W, Guar
 // (which saw these constraints empty) has left in cv / vec
 // W_j = A_j Y for every dense constraint (and C Y for a dense objective), kept while Y -- the fixed factor of a CG solve -- stands
 void dense_cache_fill(lorads_hip_ctx *c, Block &B, const double *Y, Guard g) {
-    if (!B.dense_a || !B.Wj || !c->opt_dense_cache) return;
+    if (!B.dense_a || !B.Wj || !c->opt.dense_cache) return;
     const size_t len = (size_t)B.n * B.r, msz = (size_t)B.npad * B.npad;
     for (int j = 0; j < B.nd; ++j)
         if (dense_cx(c, B, Y, B.Wj + (size_t)j * len, g, B.Adense + (size_t)j * msz)) { c->launch_err = "dense GEMM: no kernel form for this rank"; return; }
@@ -271,7 +271,7 @@ int op_diag(lorads_hip_ctx *c, const Block &B, const double *V, int mode, const 
 int op_entry(lorads_hip_ctx *c, const Block &B, const double *V, int mode, const double *xin, const double *rhs, double *out,
              double *part, Guard g) {
     const Shape sh = shape_for(B.r);
-    if (B.bip_rows[0] && c->opt_entry_bip) { // bipartite entry graph: 3 gathered rows per entry instead of 4 (see k_op_entry_bip)
+    if (B.bip_rows[0] && c->opt.entry_bip) { // bipartite entry graph: 3 gathered rows per entry instead of 4 (see k_op_entry_bip)
         const int g0 = nblocks_for((size_t)B.bip_n[0], TPB / sh.lg), g1 = nblocks_for((size_t)B.bip_n[1], TPB / sh.lg);
         if (g0 + g1 <= c->maxpart) {
             SHAPE_DISPATCH(sh, LAUNCH((k_op_entry_bip<LG_, V2_, NS_, 0>), g0, B.bip_n[0], (const int *)B.bip_rows[0], B.pa.adj_ptr, B.pa.adj_col,
@@ -454,18 +454,18 @@ void drain_events(lorads_hip_ctx *c) {
 // Max-Cut-type cones do the same with row dots: w_uv[p] = U_p . V_p (left exact by every front and every residual on the
 // solve variable), w_op[p] = p_p . V_p from k_op_diag, and constraint i = a_i e_p e_p^T has the value a_i w_uv[p].
 bool constr_by_recurrence(lorads_hip_ctx *c, const Block &B) {
-    return (B.use_cw || (B.diag_only && B.w_uv && B.w_op && B.diag_row)) && !c->opt_exact_refresh && &B != &c->merged;
+    return (B.use_cw || (B.diag_only && B.w_uv && B.w_op && B.diag_row)) && !c->opt.exact_refresh && &B != &c->merged;
 }
 
 // k_cw cones and Max-Cut-type cones with a sparse objective build the right-hand side and the initial residual of a solve in one kernel
 // (LORADS_SPLIT_FRONT=1: the two separate passes, for tests and comparisons)
 bool fused_front(lorads_hip_ctx *c, const Block &B) {
-    return ((B.use_cw && B.pu.S2) || B.diag_only) && !B.dense_c && !B.dense_a && !c->opt_split_front && B.pu.ne > 0;
+    return ((B.use_cw && B.pu.S2) || B.diag_only) && !B.dense_c && !B.dense_a && !c->opt.split_front && B.pu.ne > 0;
 }
 
 // cones on the k_cw path with 16-byte row accesses take the one-kernel front (LORADS_FRONT_CW=0: k_sval + k_spmm2<FRONT>)
 bool front_cw_ok(lorads_hip_ctx *c, const Block &B) {
-    return c->opt_front_cw && B.front_cw && fused_front(c, B) && B.use_cw && B.cell_w && use_v2(B.r) && &B != &c->merged;
+    return c->opt.front_cw && B.front_cw && fused_front(c, B) && B.use_cw && B.cell_w && use_v2(B.r) && &B != &c->merged;
 }
 
 // profiling target 1: the front of a solve (its main kernel) between two events, one front in `prof_every`
@@ -501,7 +501,7 @@ FrontCwArgs front_cw_args(lorads_hip_ctx *c, const Block &B, double rho, int wmo
     A.lambda = c->lambda; A.cv = B.cv; A.w_uv = B.w_uv; A.row_idx = B.row_idx_identity ? nullptr : B.row_idx; A.rho = ds_rho(c, rho);
     A.wmode = wmode;
     A.contrib = B.w_contrib;
-    A.wt = c->opt_wt_stores;
+    A.wt = c->opt.wt_stores;
     return A;
 }
 // ... and its launch for the solve `s` under gate `g`; returns its grid (= the number of partials it leaves in slots 18 and 1)
@@ -521,7 +521,7 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     const int lead = ho ? 1 : 0;
     if (ho) { static_cast<FrontCwArgs &>(AH) = A; AH.ho = *ho; AH.ho.lead = lead; }
     // (LORADS_FRONT_CHAIN: the cuts belong to the form with the LDS park, the one they were measured on -- see k_front_cw)
-    const int fc = c->opt_front_chain & FC_ALL;
+    const int fc = c->opt.front_chain & FC_ALL;
 #define FC_SWITCH(...)                                             \
     do { switch (fc) {                                             \
     case 0: { constexpr int FC_ = 0; __VA_ARGS__; } break;         \
@@ -533,7 +533,7 @@ int launch_front_cw(lorads_hip_ctx *c, const Solve &s, const FrontCwArgs &A, Gua
     // (r <= 48: the first four slot rows are parked in LDS for the second visit, see k_front_cw; 48 KB per workgroup at most)
 #define FCWL(NSV, EWV, HO, AV) FC_SWITCH(LAUNCH_LDS((k_front_cw<NSV, EWV, 4, HO, FC_>), grid + lead, sizeof(double2) * 32 * 4 * NSV * 8, B.n, rd.rpw, AV, s.V, B.r, (const double *)s.x, r, rhs, pA, pB, g, d))
 #define FRONT(HO, AV)                                                                                                    \
-    if (c->opt_front_lds && ns <= 3) {                                                                                   \
+    if (c->opt.front_lds && ns <= 3) {                                                                                   \
         if (B.cell_w == 8) { if (ns == 1) FCWL(1, 8, HO, AV); else if (ns == 2) FCWL(2, 8, HO, AV); else FCWL(3, 8, HO, AV); }     \
         else { if (ns == 1) FCWL(1, 16, HO, AV); else if (ns == 2) FCWL(2, 16, HO, AV); else FCWL(3, 16, HO, AV); }                \
     } else if (B.cell_w == 8) { FCW(8, HO, AV) } else { FCW(16, HO, AV) }
@@ -617,7 +617,7 @@ void solve_front(lorads_hip_ctx *c, const Solve &s, double rho, double tol, CGSt
             econ = B.pu.e_con_own;
         }
         // Max-Cut-type cone with its rows' constraint lists: no coefficient pass, the front forms the diagonal coefficients itself
-        const bool onfly = B.diag_only && B.rc_w > 0 && B.w_uv && c->opt_front_diag && &B != &c->merged; // (with or without a dual update on board)
+        const bool onfly = B.diag_only && B.rc_w > 0 && B.w_uv && c->opt.front_diag && &B != &c->merged; // (with or without a dual update on board)
         DiagOnFly of{};
         if (onfly) {
             of.on = true; of.wa = wa; of.wmode = wmode; of.reset = reset; of.nreset = nreset;
@@ -658,7 +658,7 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     const int nw = !rec ? 0 : B.diag_only ? B.n : B.nrow; // (row dots for Max-Cut-type cones, constraint values otherwise)
     const bool v2 = (s.len & 1) == 0 && (((uintptr_t)s.x | (uintptr_t)r | (uintptr_t)p | (uintptr_t)Q) & 15) == 0;
     // the residual of an iteration whose tail is a restart is recomputed there: summed here, not stored
-    const int store_r = (k % 20 != 0 || !c->opt_lazy_scalars) ? 1 : 0;
+    const int store_r = (k % 20 != 0 || !c->opt.lazy_scalars) ? 1 : 0;
     // R = (U + V) / 2 left by this update when it is the last one enqueued before an evaluation (x = V, the other factor = U)
     const double *avg_other = fold_avg ? s.V : (const double *)nullptr;
     double *avg_out = fold_avg ? c->R + B.off : (double *)nullptr;
@@ -669,9 +669,9 @@ void solve_iter_body(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
     const bool rule0 = k == 0 && B.w0_ready && cg0_rule(c, B);
     double *pW = rule0 ? part_slot(c, 20) : (double *)nullptr;
     const int nww = rule0 ? nblocks_for((size_t)B.nrow, TPB / 8) : 0;
-    const bool fuse0 = rule0 && c->opt_fuse_cg0 && v2_avg;
+    const bool fuse0 = rule0 && c->opt.fuse_cg0 && v2_avg;
     Cg0Args u{};
-    u.wt = c->opt_wt_stores;
+    u.wt = c->opt.wt_stores;
     if (fuse0) {
         u.st = s.st; u.part_ww = pW; u.nww = nww; u.x = s.x; u.r = r; u.store_r = store_r;
         u.w_acc = rec ? B.w_uv : (double *)nullptr; u.w_p = B.w_op; u.nw = nw; u.shadow = shadow_of(c, s.st);
@@ -710,15 +710,15 @@ void solve_iter_tail(lorads_hip_ctx *c, const Solve &s, int k, double tol, int m
         // Harmless when the kept values were valid (they still are); but values that were stale before (resume after a
         // speculation miss) must not be taken for fresh on the strength of a kernel that may have been skipped.
         if (!was_valid && !runs_for_sure) B.t_uv_valid = false;
-        if (c->opt_lazy_scalars && B.diag_only && c->opt_fuse_dir) { // p = 2 r is formed by the next operator application itself
+        if (c->opt.lazy_scalars && B.diag_only && c->opt.fuse_dir) { // p = 2 r is formed by the next operator application itself
             c->pend.post_dir(Pending::Dir{DIR_RESTART, s.st, r, p, s.len, s.gv, pA, nr, g});
-        } else if (c->opt_lazy_scalars) { // the restart's two scalars are written by workgroup 0 of the direction kernel
+        } else if (c->opt.lazy_scalars) { // the restart's two scalars are written by workgroup 0 of the direction kernel
             LAUNCH(k_cg_dir, s.gv, s.len, s.st, (int)DIR_RESTART, r, p, g, Deferred{}, (const double *)pA, nr);
         } else {
             LAUNCH(k_cg_check, 1, s.st, (int)CHK_RESTART, pA, nr, ds_tol(c, tol), ds_maxit(c, maxit), g);
             LAUNCH(k_cg_dir, s.gv, s.len, s.st, (int)DIR_RESTART, r, p, g);
         }
-    } else if (c->opt_lazy_scalars && B.diag_only && c->opt_fuse_dir) {
+    } else if (c->opt.lazy_scalars && B.diag_only && c->opt.fuse_dir) {
         // p = r + beta p is formed by the next operator application itself (and the waiting test rides on it too)
         c->pend.post_dir(Pending::Dir{DIR_BETA, s.st, r, p, s.len, s.gv, nullptr, 0, g});
     } else {
@@ -771,7 +771,7 @@ int enqueue_publish(lorads_hip_ctx *c, size_t word0, size_t nwords, const double
         const HandoverArgs H{c->final_args, (const unsigned long long *)c->ctrl + word0, (unsigned long long *)c->h_ctrl_dev + word0,
                              (int)nwords, c->h_flag_dev, c->seq_dev, 0}; // (lead: set by launch_front_cw with the grid)
         const bool own = (const double *)H.src == H.fa.out; // (as k_publish_final sees it)
-        if (front_rho && c->opt_handover_on_front && own && spec_front_enqueue(c, *front_rho, &H)) {
+        if (front_rho && c->opt.handover_on_front && own && spec_front_enqueue(c, *front_rho, &H)) {
             *front_carried = true;
             c->final_pending = false;
             ++c->n_handover_front;
@@ -812,7 +812,7 @@ int wait_publish(lorads_hip_ctx *c) {
     volatile unsigned long long *f = c->h_flag;
     // wall-clock bound on the wait (LORADS_HANDOVER_TIMEOUT_S, default 300): a collective on the stream that a peer never
     // enters (a rank that left the loop, a dead process) keeps hipStreamQuery at NotReady for ever -- report it instead
-    static const double limit_s = getenv("LORADS_HANDOVER_TIMEOUT_S") ? atof(getenv("LORADS_HANDOVER_TIMEOUT_S")) : 300.0;
+    const double limit_s = opt_handover_timeout_s();
     std::chrono::steady_clock::time_point t0;
     bool timing = false;
     for (unsigned long spins = 0;; ++spins) {
@@ -835,13 +835,6 @@ int wait_publish(lorads_hip_ctx *c) {
 }
 // copy [word0, word0 + nwords) of the control block to its pinned mirror and wait for it
 int publish_and_wait(lorads_hip_ctx *c, size_t word0, size_t nwords) {
-    if (!c->use_publish) {
-        c->pend.flush(c);
-        flush_final(c);
-        HC(hipMemcpyAsync(c->h_ctrl + 8 * word0, c->ctrl + 8 * word0, 8 * nwords, hipMemcpyDeviceToHost, c->stream));
-        HC(hipStreamSynchronize(c->stream));
-        return 0;
-    }
     if (enqueue_publish(c, word0, nwords)) return 1;
     return wait_publish(c);
 }
@@ -858,7 +851,7 @@ Solve make_solve(lorads_hip_ctx *c, int k, int half, const int *need) {
     s.front = Guard{nullptr, need};
     s.len = (size_t)B.n * B.r;
     s.gv = std::min(grid1d(s.len), 512); // (512 workgroups stream fastest: ubench variants 6-9, profiles/r01_ubench.txt; their partials are re-summed by the next kernel)
-    if (B.diag_only && c->opt_tile_update) { // row-local operator: the update works on the operator's row tiles (same workgroup -> same XCD)
+    if (B.diag_only && c->opt.tile_update) { // row-local operator: the update works on the operator's row tiles (same workgroup -> same XCD)
         const int rows = TPB / shape_for(B.r).lg, g = nblocks_for((size_t)B.n, rows);
         if (g <= c->maxpart && rows * B.r >= TPB / 2) { s.gv = g; s.tile = rows * B.r; s.tile_w = rows; }
     }
@@ -873,7 +866,7 @@ Solve make_solve(lorads_hip_ctx *c, int k, int half, const int *need) {
 // lrd_admm_optimize does between two steps: update_dual_var(rho), admm_step(rho).  Anything else (spec_touch) leaves its output unused.
 // May this step, whose sweep and evaluation are about to be enqueued, be followed by such a front?
 bool spec_front_ok(lorads_hip_ctx *c) {
-    if (!c->opt_spec_front || !c->use_publish || c->ar || c->nb != 1 || !c->opt_lazy_scalars || !c->lambda_alt) return false;
+    if (!c->opt.spec_front || c->ar || c->nb != 1 || !c->opt.lazy_scalars || !c->lambda_alt) return false;
     if (c->prof && c->prof_every < (1 << 20)) return false; // (a window that times launches between events: nothing runs differently in it)
     return front_cw_ok(c, c->blk[0]) && !c->blk[0].is_lp;
 }
@@ -901,7 +894,7 @@ bool spec_front_adopt(lorads_hip_ctx *c, const Solve &s, double rho, double tol,
     Block &B = *s.B;
     const bool ok = s.st == c->st && reset && !c->par_mode && c->spec.epoch == c->spec_epoch && memcmp(&rho, &c->spec.rho, sizeof(double)) == 0 &&
                     c->spec.dual_seen && c->pend.dual_owed_at(c->spec.rho_dual) && !c->virt_refresh &&
-                    c->spec.wmode == W_ADMM && front_carries_dual(c, s, W_ADMM) && B.t_uv_valid && c->opt_lazy_scalars &&
+                    c->spec.wmode == W_ADMM && front_carries_dual(c, s, W_ADMM) && B.t_uv_valid && c->opt.lazy_scalars &&
                     B.spec[0] >= 1; // (iteration 0 is enqueued: its k_wsum is the next launch and takes the reset words)
     if (!ok) { ++c->n_spec_discard; return false; }
     ++c->n_spec_adopt;
@@ -960,8 +953,8 @@ void enqueue_sweep(lorads_hip_ctx *c, int first, int resume_iter, double rho, do
             // evaluation's first kernel can carry the convergence test k_average used to carry); LORADS_FOLD_AVG=0: k_average
             // (sharded cones too: the evaluation's first constraint kernel is this cone's k_cw there as well, and whatever comes
             // first sends a waiting test off as its own launch if it cannot carry it)
-            const bool fold = eval_follows && stg == 2 * c->nb - 1 && c->nb == 1 && B.use_cw && c->opt_lazy_scalars &&
-                              c->opt_fold_avg && B.nrow > 0 && nblocks_for((size_t)B.nrow, TPB / 64) <= c->maxpart;
+            const bool fold = eval_follows && stg == 2 * c->nb - 1 && c->nb == 1 && B.use_cw && c->opt.lazy_scalars &&
+                              c->opt.fold_avg && B.nrow > 0 && nblocks_for((size_t)B.nrow, TPB / 64) <= c->maxpart;
             solve_iters(c, s, 0, std::min(B.spec[half], maxit), tol, maxit, fold);
         }
         if (eval_follows && stg == 2 * c->nb - 1) {
@@ -977,7 +970,7 @@ void enqueue_sweep(lorads_hip_ctx *c, int first, int resume_iter, double rho, do
                 pairdots(c, B.pa, c->U + B.off, c->V + B.off, B.r, B.T, Guard{nullptr, &s.st->done});
                 B.t_uv_valid = true;
             }
-        } else if (eval_follows && c->nb == 1 && stg == 0 && c->opt_lazy_scalars && constr_by_recurrence(c, B) && B.t_uv_valid &&
+        } else if (eval_follows && c->nb == 1 && stg == 0 && c->opt.lazy_scalars && constr_by_recurrence(c, B) && B.t_uv_valid &&
                    fused_front(c, B) && (B.use_cw || B.diag_only)) {
             // One cone, evaluation at the end of the sweep: what the refresh after the U-solve would store (constrVal <- w_uv,
             // constrValSum += w_uv - old) has ONE reader, the weights of the V-solve's front -- the evaluation overwrites both
@@ -1014,7 +1007,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
     // (the only cone, or the merged block-diagonal cone of a lockstep sweep: its rows, constraints and constrVal array are the
     // concatenation of the cones')
     Block *Dc = solo(c);
-    Block *D1 = (pair == LORADS_HIP_PAIR_UV && !vec && c->opt_eval_diag && Dc && Dc->diag_only && Dc->rc_w > 0 && Dc->nrow == c->m &&
+    Block *D1 = (pair == LORADS_HIP_PAIR_UV && !vec && c->opt.eval_diag && Dc && Dc->diag_only && Dc->rc_w > 0 && Dc->nrow == c->m &&
                  c->m > 0 && Dc->w_uv && !c->avg_folded && !Dc->dense_c) ? Dc : nullptr;
     if (D1) {
         // (k_eval_diag below carries a waiting test and forms R itself)
@@ -1041,11 +1034,11 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
     else for (auto &B0 : c->blk) cones.push_back(&B0);
     // One local cone (the block-per-GPU layout): the objective partials travel through the all-reduce themselves, behind
     // the two tail words k_obj writes, and k_commit_eval leaves the staged sums zeroed for the next evaluation -- three
-    // launches fewer around the collective (no k_zero, no k_stage_tail; LORADS_AR_PLAIN=1: the general form)
+    // launches fewer around the collective (no k_zero, no k_stage_tail)
     // (the length of the collective must be the same on every rank: the ranks agree once -- one host-side sum through the hook --
     // that each of them holds one such cone; a deal that leaves some rank two cones takes the general form everywhere)
     if (vec && c->ar_fast_all < 0) {
-        double v[2] = {(c->opt_ar_fast && c->nb == 1 && !c->blk[0].dense_c && c->blk[0].nc > 0 && !c->blk[0].is_lp) ? 1.0 : 0.0, 1.0};
+        double v[2] = {(c->nb == 1 && !c->blk[0].dense_c && c->blk[0].nc > 0 && !c->blk[0].is_lp) ? 1.0 : 0.0, 1.0};
         c->pend.flush(c);
         HC(hipStreamSynchronize(c->stream));
         if (c->ar(c->ar_user, v, 2, 0)) return fail_msg("allreduce hook failed");
@@ -1066,7 +1059,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
                                       c->R + B.off, B.r, B.rc_w, (const int *)B.rc_con, (const double *)B.diag_a,
                                       B.row_idx_identity ? (const int *)nullptr : (const int *)B.row_idx, B.cv, c->csum,
                                       (const double *)c->b, (const double *)c->lambda, part_slot(c, 8), part_slot(c, 9), g, d));
-        } else if (fold_res && B.use_cw && with_obj && fold_obj && c->opt_fuse_eval && cw_quad(c, B) && B.nc > 0 && !B.dense_c &&
+        } else if (fold_res && B.use_cw && with_obj && fold_obj && c->opt.fuse_eval && cw_quad(c, B) && B.nc > 0 && !B.dense_c &&
                    nblocks_for((size_t)B.nrow, TPB / 64) <= c->maxpart) {
             // constraint values + residual partials AND the objective partials in one launch (k_eval_cw_obj)
             const Deferred d = c->pend.take_check_behind(g);
@@ -1132,7 +1125,7 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
         // and the number of such ranks in scal[5], where run_sweep looks for it (as after k_commit_eval)
         const SepExtra ex = c->sep_extra; // (phase 1: ||Grad||^2 and y.s of the step ride along, see lorads_hip_alm_step)
         c->sep_extra = SepExtra{};
-        if (c->sx && ex.n == 0 && c->use_publish) {
+        if (c->sx && ex.n == 0) {
             // the ranks' hosts sum them after the hand-over (lorads_hip_set_scalar_exchange): no collective on the stream
             LAUNCH(k_sep_stage_local, 1, part_slot(c, 8), part_slot(c, 9), nres, op, nobj, (const double *)c->scal, g, with_obj ? 1 : 0, c->scal + SX_WORD);
             c->sx_pending = true; c->sx_with_obj = with_obj ? 1 : 0;
@@ -1145,12 +1138,8 @@ int enqueue_eval(lorads_hip_ctx *c, int pair, const int *need, bool with_obj = t
         c->pend.post_sep(with_obj ? 1 : 0, ex);
         return 0;
     }
-    if (c->use_publish) {
-        c->final_args = EvalFinalArgs{part_slot(c, 8), part_slot(c, 9), op, nres, nobj, c->scal, g};
-        c->final_pending = true;
-    } else {
-        LAUNCH(k_eval_final, 1, part_slot(c, 8), part_slot(c, 9), nres, c->scal, g, op, nobj);
-    }
+    c->final_args = EvalFinalArgs{part_slot(c, 8), part_slot(c, 9), op, nres, nobj, c->scal, g};
+    c->final_pending = true;
     return 0;
 }
 
@@ -1190,9 +1179,9 @@ int finish_sweep(lorads_hip_ctx *c, int *iters) {
         // more than was enqueued costs a host round trip (the GPU idles for ~20-30 us); an iteration enqueued in vain costs its
         // kernels' immediate exits (~2 us each).  Where the counts wander by one from sweep to sweep (Max-Cut: 5, 6, 5, 5, 6)
         // the previous count alone missed every few sweeps; where they are constant (the headline: 1) nothing changes.
-        B.spec_hist[stg % 2][B.spec_pos % c->spec_window] = h.done == 2 ? 0 : h.iter;
+        B.spec_hist[stg % 2][B.spec_pos % c->opt.spec_window] = h.done == 2 ? 0 : h.iter;
         int mx = 0;
-        for (int k = 0; k < c->spec_window; ++k) mx = std::max(mx, B.spec_hist[stg % 2][k]);
+        for (int k = 0; k < c->opt.spec_window; ++k) mx = std::max(mx, B.spec_hist[stg % 2][k]);
         B.spec[stg % 2] = mx;
         if (stg % 2 == 1) B.spec_pos++;
         c->n_cg_it += (h.done == 2 ? 0 : h.iter);
@@ -1209,7 +1198,7 @@ int seg_threads(lorads_hip_ctx *c) { return 64 * std::max(1, std::min(c->nb, SEG
 // the lockstep sweep's convergence tests ride on the next operator kernel (Max-Cut-type merged cone with the fused direction update;
 // LORADS_SEG_CARRY=0: k_cg_check_seg after every update)
 bool seg_carry(lorads_hip_ctx *c) {
-    return c->merged.diag_only && c->opt_lazy_scalars && c->opt_fuse_dir && c->seg_tile_cone && c->seg_tile_info && c->opt_seg_carry && c->seg_rr_alt;
+    return c->merged.diag_only && c->opt.lazy_scalars && c->opt.fuse_dir && c->seg_tile_cone && c->seg_tile_info && c->opt.seg_carry && c->seg_rr_alt;
 }
 // k: the lockstep iteration the kernel belongs to (see SegArgs: which slot holds r.r)
 SegArgs seg_args(lorads_hip_ctx *c, int half, int k) {
@@ -1245,7 +1234,7 @@ void batched_tail(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     const Guard g{&c->phase_done[half], half ? &c->phase_done[0] : nullptr};
     const SegArgs sa = seg_args(c, half, k);
     // Max-Cut-type merged cone: the direction update is formed by the operator application that follows (k_op_diag, DirArgs)
-    const bool fuse = M.diag_only && c->opt_lazy_scalars && c->opt_fuse_dir && c->seg_tile_cone;
+    const bool fuse = M.diag_only && c->opt.lazy_scalars && c->opt.fuse_dir && c->seg_tile_cone;
     // (iteration k's waiting test rides along with p = r + beta p -- its tolerance and limit are this call's, batched_iters gives an
     // iteration's body and tail the same -- and a riding restart's two scalars, rs_seg, with p = 2 r)
     auto defer_dir = [&](int kind, const double *rs_seg = nullptr) {
@@ -1256,7 +1245,7 @@ void batched_tail(lorads_hip_ctx *c, int half, int k, double tol, int maxit) {
     if (k % 20 == 0) {
         // (the restart recomputes the residual of the cones that are still running: their test comes first -- on the residual pass
         // itself when the test was waiting for an operator kernel anyway, and the restart's two scalars on the operator that follows)
-        const bool ride = fuse && seg_carry(c) && c->opt_seg_carry_restart && c->seg_row0;
+        const bool ride = fuse && seg_carry(c) && c->opt.seg_carry_restart && c->seg_row0;
         if (!(ride && c->pend.segchk_rides_res(half, k))) c->pend.flush_segchk(c);
         // (riding: the residual's partials go to a slot of their own -- the operator kernel that sums them writes slot 0, p.Ap, itself)
         double *p_res = ride ? part_slot(c, 19) : part_slot(c, 0);
@@ -1288,7 +1277,7 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
     // Max-Cut-type merged cone with an evaluation at the end of the sweep: what the refresh after the U-solves would store (constrVal,
     // constrValSum) has one reader, the weights of the V-solves' front -- the evaluation overwrites both vectors (Q1).  That front
     // forms U_p . V_p itself and its weights as if the refresh had been stored (W_ADMM_VS): no k_pairdots, no k_cv.
-    const bool onfly_front = M.diag_only && M.rc_w > 0 && M.w_uv && c->opt_front_diag && !c->opt_split_front && M.pu.ne > 0;
+    const bool onfly_front = M.diag_only && M.rc_w > 0 && M.w_uv && c->opt.front_diag && !c->opt.split_front && M.pu.ne > 0;
     bool virt = false;
     for (int half = phase; half < 2; ++half) {
         const double *Vfix = half == 0 ? c->V : c->U;
@@ -1304,7 +1293,7 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
             // the start of the cones' solves rides on iteration 0's operator kernel (op_diag) when there is one: its partials of ||r_0||^2
             // then live in a slot of their own -- that kernel writes slot 0 (p.Ap) while its other workgroups still read them
             const int k1 = std::min(std::max(c->spec_b[half], 0), maxit);
-            const bool carry_init = k1 > 0 && M.diag_only && seg_carry(c) && c->opt_seg_carry_init && c->seg_row0;
+            const bool carry_init = k1 > 0 && M.diag_only && seg_carry(c) && c->opt.seg_carry_init && c->seg_row0;
             double *p_rr0 = carry_init ? part_slot(c, 18) : part_slot(c, 0);
             WArgs wa{};
             wa.csum = c->csum; wa.b = c->b; wa.lambda = c->lambda; wa.cv = M.cv; wa.row_idx = M.row_idx_identity ? nullptr : M.row_idx; wa.rho = ds_rho(c, rho);
@@ -1315,7 +1304,7 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
                 of.on = true; of.wa = wa; of.wmode = (half == 1 && virt) ? W_ADMM_VS : W_ADMM;
                 // a dual update that is still waiting rides on the sweep's ungated first kernel, as on a single cone's front (solve_front):
                 // every constraint sits in one row of the merged cone, the updated multipliers go to lambda_alt and the vectors swap
-                const bool carry_dual = c->pend.dual_rides(front, true) && half == 0 && M.nrow == c->m && c->m > 0 && c->lambda_alt && c->opt_seg_carry_dual;
+                const bool carry_dual = c->pend.dual_rides(front, true) && half == 0 && M.nrow == c->m && c->m > 0 && c->lambda_alt && c->opt.seg_carry_dual;
                 if (carry_dual) {
                     of.wa.lambda_out = c->lambda_alt;
                     of.wa.rho_dual = ds_rho_dual(c, c->pend.take_dual());
@@ -1342,7 +1331,7 @@ void enqueue_batched(lorads_hip_ctx *c, int phase, int resume, double rho, doubl
                 pairdots(c, M.pa, c->U, c->V, M.r, M.T, Guard{nullptr, &c->phase_done[half]});
                 M.t_uv_valid = true;
             }
-        } else if (eval_follows && half == 0 && onfly_front && c->opt_seg_virt) {
+        } else if (eval_follows && half == 0 && onfly_front && c->opt.seg_virt) {
             virt = true; // (nothing stored: see above)
         } else {
             constr_val(c, M, c->U, c->V, 1.0, M.cv, CV_DELTA, c->csum, Guard{nullptr, &c->phase_done[half]});
@@ -1362,7 +1351,7 @@ int run_sweep_batched(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
     bool first_pass = true, any_missed = false;
     // (the lockstep sweep's long chains -- ~200 launches per iteration on cfg4 -- run no faster replayed than enqueued while the
     // GPU works, 0.288 against 0.279 ms per iteration: replayed only on request, LORADS_GRAPH=2)
-    const bool graph = c->opt_graph_batched && graph_this_step(c, rho, tol, maxit);
+    const bool graph = c->opt.graph_batched && graph_this_step(c, rho, tol, maxit);
     if (graph && set_step_params(c, rho, tol, maxit)) return 1;
     ParMode pm(c, graph);
     for (;;) {
@@ -1371,7 +1360,7 @@ int run_sweep_batched(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
         auto enq = [&]() -> int {
             enqueue_batched(c, phase, resume, rho, tol, maxit, launched, with_eval);
             if (eval_now && enqueue_eval(c, LORADS_HIP_PAIR_UV, &c->phase_done[1])) return 1;
-            return c->use_publish ? enqueue_publish(c, 0, state_words(c)) : 0;
+            return enqueue_publish(c, 0, state_words(c));
         };
         if (graph && first_pass) {
             std::vector<uint64_t> key{2, (uint64_t)with_eval, (uint64_t)maxit};
@@ -1380,7 +1369,7 @@ int run_sweep_batched(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
             launched[0] = std::min(std::max(c->spec_b[0], 0), maxit);
             launched[1] = std::min(std::max(c->spec_b[1], 0), maxit);
         } else if (enq()) return 1;
-        if (c->use_publish ? wait_publish(c) : read_states(c)) return 1;
+        if (wait_publish(c)) return 1;
         if (eval_now && c->ar) any_missed = c->h_scal[5] > 0.5;
         first_pass = false;
         bool u_done = true, v_done = true;
@@ -1401,9 +1390,9 @@ int run_sweep_batched(lorads_hip_ctx *c, double rho, double tol, int maxit, bool
             const CGState &h = c->h_st[2 * k + half];
             if (h.done != 2) mx = std::max(mx, h.iter);
         }
-        c->spec_b_hist[half][c->spec_b_pos % c->spec_window] = mx;
+        c->spec_b_hist[half][c->spec_b_pos % c->opt.spec_window] = mx;
         int mw = 0;
-        for (int k = 0; k < c->spec_window; ++k) mw = std::max(mw, c->spec_b_hist[half][k]);
+        for (int k = 0; k < c->opt.spec_window; ++k) mw = std::max(mw, c->spec_b_hist[half][k]);
         c->spec_b[half] = mw; // (as in finish_sweep: the largest of the last few sweeps)
         if (half == 1) c->spec_b_pos++;
     }
@@ -1421,7 +1410,7 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
     if (persist_ready(c, maxit)) { spec_touch(c); return run_sweep_persist(c, rho, tol, maxit, with_eval); }
     persist_touch(c);
     // (no cross-rank sum inside the sweep: with sharded cones the lockstep form works unchanged)
-    if (c->has_merged && !getenv("LORADS_NO_BATCH")) { spec_touch(c); return run_sweep_batched(c, rho, tol, maxit, with_eval); }
+    if (c->has_merged && !opt_no_batch()) { spec_touch(c); return run_sweep_batched(c, rho, tol, maxit, with_eval); }
     int first = 0, resume = -1;
     bool first_pass = true, any_missed = false, front_carried = false; // (front_carried: the hand-over went with the next step's U front)
     const bool graph = graph_this_step(c, rho, tol, maxit);
@@ -1442,7 +1431,6 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
             if (first_pass && 2 * c->nb - 1 > TPB) HC(hipMemsetAsync(c->st, 0, sizeof(CGState) * (size_t)(2 * c->nb), c->stream));
             enqueue_sweep(c, first, resume, rho, tol, maxit, with_eval);
             if (eval_now && enqueue_eval(c, LORADS_HIP_PAIR_UV, c->nb ? &c->st[2 * c->nb - 1].done : nullptr)) return 1;
-            if (!c->use_publish) return 0;
             return enqueue_publish(c, 0, state_words(c), spec && first_pass ? &rho : nullptr, &front_carried);
         };
         if (graph && first_pass) {
@@ -1450,7 +1438,7 @@ int run_sweep(lorads_hip_ctx *c, double rho, double tol, int maxit, bool with_ev
             if (graph_step(c, key, enq)) return 1;
         } else if (enq()) return 1;
         if (spec && first_pass && !front_carried) spec_front_enqueue(c, rho);
-        if (c->use_publish ? wait_publish(c) : read_states(c)) return 1;
+        if (wait_publish(c)) return 1;
         if (eval_now && c->ar) any_missed = c->h_scal[5] > 0.5;
         const int stg = first_unfinished(c, first);
         if (first_pass && c->spec.live && stg >= 0) { c->spec.live = false; ++c->n_spec_blocked; } // (its gate was shut: it wrote nothing)

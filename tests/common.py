@@ -2,6 +2,7 @@
 sequence that oracle/ref_driver.c (mode `trace`) ran against the REFERENCE, replayed against any
 operator table (CPU oracle or HIP)."""
 import atexit
+import contextlib
 import ctypes as C
 import json
 import os
@@ -57,19 +58,26 @@ def hip_session(path, world=1, rank=0, separable=None, lbfgs_len=None, **params)
     return s
 
 
-def hip_session_with_env(path, env, params, separable=None):
-    """hip_session with the environment variables `env` set while the context is created (the HIP library reads its switches
-    then), restored afterwards"""
+@contextlib.contextmanager
+def environment(env):
+    """the environment variables `env` set inside the block; what was there before (a value, or nothing) is back after it"""
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:
-        return hip_session(path, separable=separable, **params)
+        yield
     finally:
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def hip_session_with_env(path, env, params, separable=None):
+    """hip_session with the environment variables `env` set while the context is created (the HIP library reads its switches
+    then), restored afterwards"""
+    with environment(env):
+        return hip_session(path, separable=separable, **params)
 
 
 def golden_trace(name):

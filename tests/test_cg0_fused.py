@@ -1,8 +1,6 @@
 """CG iteration 0 folded into the operator kernel on cones of the one-kernel front (k_spmm_ell's CG0 form):
 LORADS_FUSE_CG0=0 restores k_cg_update as a launch of its own, with the same step length (rr / (rr + ||w||^2)) and the same
 per-element arithmetic, so the two forms must agree bit for bit."""
-import os
-
 import numpy as np
 import pytest
 
@@ -13,16 +11,8 @@ from tests import common
 def _run(path, env, steps, **kw):
     """phase 1 + `steps` ADMM iterations (every third one through the separate entry points) under `env`; tolerances that
     change from step to step give speculation misses and solves of one and of many iterations"""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with common.environment(env):
         s = common.hip_session(path, phase1Tol=1e-2, **kw)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     try:
         s.alm()
         s.alm_to_admm()

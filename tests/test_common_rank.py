@@ -2,8 +2,6 @@
 cone's own rank, which the caller never sees) so that cones of unequal rank run as one block-diagonal cone -- the lockstep ADMM sweep, the
 single-cone forms of phase 1 -- instead of cone by cone.  Against per-cone ranks (LORADS_COMMON_RANK=0).  Reference: the ranks are per cone
 (src_semi/data/lorads_solver.c:290-319, AUG_RANK :806-906); what is computed on the extra columns is exact zeros."""
-import os
-
 import numpy as np
 import pytest
 
@@ -24,11 +22,8 @@ def _gen(name):
 
 
 def _session(path, on, **kw):
-    os.environ["LORADS_COMMON_RANK"] = "1" if on else "0"
-    try:
+    with common.environment({"LORADS_COMMON_RANK": "1" if on else "0"}):
         return common.hip_session(path, **kw)
-    finally:
-        os.environ.pop("LORADS_COMMON_RANK", None)
 
 
 @pytest.mark.parametrize("name,params", [("blkmix5", dict(reoptLevel=0, phase1Tol=1e-2)), ("blkmix5", dict(reoptLevel=1, phase1Tol=1e-2, timesLogRank=3.5))])

@@ -19,7 +19,6 @@ the MI355X per group, next to the bounds the rule gave there.
 
 The longdouble model takes about 10 s for the three iterations of rand20000 and of maxcut20000 at r = 40 and 17 s for matcomp50000 at
 r = 22, so all three full-size instances are in the list."""
-import contextlib
 import os
 
 import numpy as np
@@ -65,22 +64,6 @@ def _path(name):
     return common.instance_path(name) if os.path.exists(common.instance_path(name)) else common.generated_instance(name)
 
 
-@contextlib.contextmanager
-def _environment(env):
-    """the case's switches: most are read when the context is created, LORADS_LBFGS_TEAM_NP when the first fused step builds the team,
-    so they stay set for the whole case and are restored after it"""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 _plans = {}
 
 
@@ -110,7 +93,9 @@ def run_case(name, env=None, params=None, schedule=SMALL, hist=2, ranks=None, se
     env, params = env or {}, params or {}
     file = file or _path(name)
     rho = schedule["rho"]
-    with _environment(env):
+    # the case's switches: most are read when the context is created, LORADS_LBFGS_TEAM_NP when the first fused step builds the team,
+    # so they stay set for the whole case and are restored after it
+    with common.environment(env):
         s = common.hip_session(file, separable=separable, lbfgs_len=hist, **params)
         try:
             calls = []

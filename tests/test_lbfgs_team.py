@@ -1,8 +1,6 @@
 """Phase 1's L-BFGS history update + next direction as ONE launch of resident workgroups (lorads_amd/csrc/hip/lbfgs_team.inc) against
 the launch-by-launch form of the same library (LORADS_LBFGS_TEAM=0: k_his_two_dot, 2 nn + 1 k_lbfgs_stage, k_use_grad_p).  Reference:
 setlbfgsHisTwo, LBFGSDirection, LBFGSDirectionUseGrad (src_semi/lorads_alg/lorads_alm.c:230-391,469-489,540-560)."""
-import os
-
 import numpy as np
 import pytest
 
@@ -25,20 +23,15 @@ def _gen(name):
 def _session(path, team, **kw):
     """team: True (the default: the one-launch direction and the shared passes behind it), "direction" (the one launch, then the
     launch-by-launch tail: LORADS_ALM_FUSED_TAIL=0), False (LORADS_LBFGS_TEAM=0: everything launch by launch)"""
-    os.environ["LORADS_LBFGS_TEAM"] = "1" if team else "0"
+    env = {"LORADS_LBFGS_TEAM": "1" if team else "0"}
     if team == "direction":
-        os.environ["LORADS_ALM_FUSED_TAIL"] = "0"
+        env["LORADS_ALM_FUSED_TAIL"] = "0"
     if team == "nofold":   # (the shared passes, but the constraints' bookkeeping as a pass of its own: LORADS_ALM_FOLD_CV=0)
-        os.environ["LORADS_ALM_FOLD_CV"] = "0"
+        env["LORADS_ALM_FOLD_CV"] = "0"
     if team == "sval":     # (the entries' coefficients by k_sval instead of by k_alm_update: LORADS_ALM_SVAL_DIRECT=0)
-        os.environ["LORADS_ALM_SVAL_DIRECT"] = "0"
-    try:
+        env["LORADS_ALM_SVAL_DIRECT"] = "0"
+    with common.environment(env):
         return common.hip_session(path, **kw)
-    finally:
-        os.environ.pop("LORADS_LBFGS_TEAM", None)
-        os.environ.pop("LORADS_ALM_FUSED_TAIL", None)
-        os.environ.pop("LORADS_ALM_FOLD_CV", None)
-        os.environ.pop("LORADS_ALM_SVAL_DIRECT", None)
 
 
 def _steps(path, team, iters, rho=0.7, **kw):
@@ -97,14 +90,11 @@ def test_other_history_lengths(built, hist):
     one launch holds: the stage-by-stage form runs, the switch changes nothing) -- 8 inner iterations on rand120, both settings"""
     out = []
     for team in (True, False):
-        os.environ["LORADS_LBFGS_TEAM"] = "1" if team else "0"
-        try:
+        with common.environment({"LORADS_LBFGS_TEAM": "1" if team else "0"}):
             s = host.Session.open(common.instance_path("rand120"))
             s.set_params(verbose=0, lbfgsListLength=hist)
             s.prepare(1, 0, separable=False)
             s.attach_hip(lbfgs_len=hist)
-        finally:
-            os.environ.pop("LORADS_LBFGS_TEAM", None)
         try:
             be = s.be
             rho = 0.7

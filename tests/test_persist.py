@@ -1,8 +1,6 @@
 """The one-launch ADMM iteration of Max-Cut-type cones (lorads_amd/csrc/hip/persist.inc: teams of resident workgroups, factors in
 registers, in-kernel all-reduces) against the launch-by-launch form of the same library (LORADS_PERSIST=0) and, at full size,
 against the compiled reference.  Reference loops: lorads_alg/lorads_alg_common.c:187-215, linalg/lorads_cgs.c:174-234."""
-import os
-
 import numpy as np
 import pytest
 
@@ -23,11 +21,8 @@ def _gen(name):
 
 
 def _session(path, persist, **kw):
-    os.environ["LORADS_PERSIST"] = "1" if persist else "0"
-    try:
+    with common.environment({"LORADS_PERSIST": "1" if persist else "0"}):
         return common.hip_session(path, **kw)
-    finally:
-        os.environ.pop("LORADS_PERSIST", None)
 
 
 def _run(path, persist, iters, kw, mixed=True):

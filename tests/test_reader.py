@@ -104,15 +104,8 @@ def _digest(path, mode):
     lib = host.host_lib()
     lib.lrd_problem_digest.argtypes = [C.c_void_p]
     lib.lrd_problem_digest.restype = C.c_uint64
-    old = os.environ.get("LORADS_READER")
-    os.environ["LORADS_READER"] = mode
-    try:
+    with common.environment({"LORADS_READER": mode}):
         s = host.Session.open(path)
-    finally:
-        if old is None:
-            os.environ.pop("LORADS_READER")
-        else:
-            os.environ["LORADS_READER"] = old
     try:
         lib.lrd_session_problem.restype = C.c_void_p
         s.set_params(verbose=0)
